@@ -145,6 +145,12 @@ typedef struct {
     int64_t post_onehot_stride;
     int32_t post_draw;             /* 1: categorical draw (exponential race); 0: argmax of the posterior      */
     int32_t reserved_tail2;
+    /* Per-sample Philox keys of the fused reverse step (batches of independent volumes).  NULL: post_philox_seed keys every voxel
+     * and the counter is the voxel index m over the whole batch (the single-key mode).  Set: sample n = m / post_rows_per_sample draws
+     * with key post_philox_seeds[n] and counter row m - n * post_rows_per_sample, so its labels do not depend on its batch slot;
+     * post_rows_per_sample must be Do * Ho * Wo.  At N = 1 with post_philox_seeds[0] == post_philox_seed both modes give the same bits. */
+    const uint64_t *post_philox_seeds;   /* device uint64 [N] or NULL                                             */
+    int64_t post_rows_per_sample;
 } gg_conv_desc;
 
 /* Bytes of the packed weight for a conv with the given logical shape. */
@@ -281,6 +287,13 @@ int gg_ccdm_posterior_sample(const float *head, int32_t head_stride, int32_t hea
                              const float *E, uint64_t philox_seed, const int64_t *philox_offset_dev, int32_t draw,
                              const float *scalars_dev, int32_t K, int64_t M, int32_t *labels_out, float *probs_out,
                              void *onehot_out, int32_t onehot_stride, void *stream);
+/* gg_ccdm_posterior_sample with one Philox key per sample: row m belongs to sample n = m / rows_per_sample (M must be a multiple of it)
+ * and draws with key philox_seeds_dev[n] (device uint64 [M / rows_per_sample]) and counter row m - n * rows_per_sample instead of m.
+ * At one sample with philox_seeds_dev[0] == philox_seed the labels are bit-identical to gg_ccdm_posterior_sample's. */
+int gg_ccdm_posterior_sample_seeds(const float *head, int32_t head_stride, int32_t head_is_logits, const int32_t *xt,
+                                   const float *E, const uint64_t *philox_seeds_dev, int64_t rows_per_sample,
+                                   const int64_t *philox_offset_dev, int32_t draw, const float *scalars_dev, int32_t K, int64_t M,
+                                   int32_t *labels_out, float *probs_out, void *onehot_out, int32_t onehot_stride, void *stream);
 /* labels -> one-hot bf16 CL rows (x_T assembly; evaluator.py:135-136 + unet.py:774-775 concat with zeros). */
 int gg_labels_to_onehot(const int32_t *labels, int64_t M, int32_t K, void *onehot_out, int32_t stride, void *stream);
 
@@ -318,6 +331,20 @@ int gg_minmax_normalise(const float *src, int64_t n, float *dst, float *workspac
 int gg_mask_to_cond_slice(const int32_t *labels, int32_t N, int32_t Dm, int32_t Hm, int32_t Wm, int32_t slice, int32_t D,
                           int32_t H, int32_t W, const float *prev, void *cond_cl, int32_t stride, float *mask_out,
                           void *stream);
+
+/* Batched slice loop of N independent volumes, each with its own slice window.  schedule_dev: device int32 [iterations][N][3] of
+ * (slice, previous slice, active) per sample; iter_dev: device int32[1], the current row (read by both calls, so that one captured graph
+ * serves every iteration); volume: fp32 [D][N][H*W], sample n's slice s at (s * N + n) * H * W.
+ * gg_mask_to_cond_slices: gg_mask_to_cond_slice of every sample n at its own slice, with prev = volume[prev_n][n]; the same index rule,
+ * rot90 and bf16 row, so that each sample's rows are bit-equal to an N = 1 gg_mask_to_cond_slice call (active or not).
+ * gg_minmax_normalise_scatter: src fp32 [N][n_per_sample]; sample n is normalised over its own values, bit-equal to gg_minmax_normalise
+ * on that sample alone, and written to volume[slice_n][n] only where its row is active.  workspace2n >= 2N floats.  advance != 0: then
+ * increments *iter_dev.  A counter outside [0, iterations) makes both calls write nothing. */
+int gg_mask_to_cond_slices(const int32_t *labels, int32_t N, int32_t Dm, int32_t Hm, int32_t Wm, int32_t D, int32_t H, int32_t W,
+                           const int32_t *schedule_dev, int32_t iterations, const int32_t *iter_dev, const float *volume,
+                           void *cond_cl, int32_t stride, void *stream);
+int gg_minmax_normalise_scatter(const float *src, int32_t N, int64_t n_per_sample, float *workspace2n, const int32_t *schedule_dev,
+                                int32_t iterations, int32_t *iter_dev, int32_t advance, int32_t depth, float *volume, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * fp32 VALIDATION mode of the CCDM path (gg_f32.hip): the same network functions on fp32 channels-last tensors with fp32 weights

@@ -29,6 +29,7 @@ class ConvDesc(C.Structure):
         ("pro_eps", f32), ("skip_C1", i32), ("skip_C2", i32), ("reserved_tail", i32), ("skip_src1", vp), ("skip_src2", vp), ("skip_weight", vp),
         ("post_xt", vp), ("post_labels_out", vp), ("post_scalars", vp), ("post_E", vp), ("post_philox_seed", C.c_uint64),
         ("post_philox_offset_dev", vp), ("post_onehot_out", vp), ("post_onehot_stride", i64), ("post_draw", i32), ("reserved_tail2", i32),
+        ("post_philox_seeds", vp), ("post_rows_per_sample", i64),
     ]
 
 
@@ -73,6 +74,7 @@ SIGNATURES = {
     "gg_nchw_f32_to_cl_bf16": (C.c_int, [vp, i32, i32, i64, vp, i32, i32, i32, vp]),
     "gg_cl_to_nchw_f32": (C.c_int, [vp, i32, i32, i32, i64, i32, vp, vp]),
     "gg_ccdm_posterior_sample": (C.c_int, [vp, i32, i32, vp, vp, u64, vp, i32, vp, i32, i64, vp, vp, vp, i32, vp]),
+    "gg_ccdm_posterior_sample_seeds": (C.c_int, [vp, i32, i32, vp, vp, vp, i64, vp, i32, vp, i32, i64, vp, vp, vp, i32, vp]),
     "gg_labels_to_onehot": (C.c_int, [vp, i64, i32, vp, i32, vp]),
     "gg_ddim_step": (C.c_int, [vp, vp, i32, vp, vp, i64, i32, vp, vp, i32, vp]),
     "gg_minmax_normalise": (C.c_int, [vp, i64, vp, vp, vp]),
@@ -82,6 +84,8 @@ SIGNATURES = {
     "gg_groupnorm_f32": (C.c_int, [vp, i32, vp, i32, i32, i64, i32, vp, vp, f32, i32, vp, vp, vp]),
     "gg_attention_forward_f32": (C.c_int, [C.POINTER(AttentionDesc), vp]),
     "gg_mask_to_cond_slice": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp]),
+    "gg_mask_to_cond_slices": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp, i32, vp]),
+    "gg_minmax_normalise_scatter": (C.c_int, [vp, i32, i64, vp, vp, i32, vp, i32, i32, vp, vp]),
     "gg_ubench_mfma_bf16": (C.c_int, [i32, i32, i32, vp, C.POINTER(C.c_double), vp]),
     "gg_ubench_stream_copy": (C.c_int, [vp, vp, i64, vp]),
 }

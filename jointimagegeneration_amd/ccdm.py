@@ -145,8 +145,10 @@ class DenoisingModel(nn.Module):
 
     @torch.no_grad()
     def sample_labels(self, labels: Tensor, condition: Optional[Tensor], init_t: Optional[int] = None, rng_tapes=None,
-                      trace: Optional[list] = None) -> Tuple[Tensor, Tensor]:
-        """labels int32 [N, (D,) H, W] on the GPU -> (final labels int32, final normalised posterior fp32 [M, K])."""
+                      trace: Optional[list] = None, philox_seeds: Optional[Sequence[int]] = None) -> Tuple[Tensor, Tensor]:
+        """labels int32 [N, (D,) H, W] on the GPU -> (final labels int32, final normalised posterior fp32 [M, K]).
+        philox_seeds (N keys): sample n draws with its own Philox key and its own voxel index as the counter, so that its chain does not
+        depend on its batch slot or its neighbours (independent volumes in one batch); None: `self.philox_seed` over the whole batch."""
         dev = labels.device
         K = self.diffusion.num_classes
         unet = self.unet
@@ -170,20 +172,26 @@ class DenoisingModel(nn.Module):
         cur_scal = torch.empty(2, dtype=torch.float32, device=dev)
         cur_off = torch.zeros(1, dtype=torch.int64, device=dev)
         xcl = CL(xin, cin)
+        seeds = None
+        if philox_seeds is not None:
+            if len(philox_seeds) != N:
+                raise ValueError(f"sample_labels: {len(philox_seeds)} philox_seeds for a batch of {N}")
+            seeds = ops.philox_seed_tensor(philox_seeds, dev)
 
         def step(draw: bool, E=None, want_probs=False):
             bf16_in = xin.dtype == torch.bfloat16
             # softmax + posterior + draw as the head conv's epilogue where the kernel can (ops.conv `post`): the fp32 logits (128 B per
             # voxel) are then never written; steps that return the posterior itself (the last one, traces) take the sampler kernel
             post = dict(xt=lab, scalars=cur_scal, K=K, E=E, philox_seed=self.philox_seed, philox_offset=cur_off, draw=draw, labels_out=lab,
-                        onehot_out=xin.view(M, -1)) if (bf16_in and not want_probs) else None
+                        onehot_out=xin.view(M, -1), philox_seeds=seeds) if (bf16_in and not want_probs) else None
             head = unet.forward_cl(xcl, cur_bias, head_out=logits, head_post=post)
             self.last_step_fused = head.fused_post
             if head.fused_post:
                 return
             ops.ccdm_posterior_sample(logits.view(M, -1), True, lab, cur_scal, K, E=E, philox_seed=self.philox_seed,
                                       philox_offset=cur_off, draw=draw, labels_out=lab,
-                                      probs_out=probs if want_probs else None, onehot_out=xin.view(M, -1) if bf16_in else None)
+                                      probs_out=probs if want_probs else None, onehot_out=xin.view(M, -1) if bf16_in else None,
+                                      philox_seeds=seeds)
             if not bf16_in:                                           # fp32 validation mode: the one-hot input is refreshed by an index scatter
                 ops.labels_to_onehot(lab, K, xin.view(M, -1))
 

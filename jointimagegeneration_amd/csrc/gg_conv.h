@@ -40,6 +40,8 @@ struct ConvParams {
     bf16_t *post_onehot_out;
     long long post_onehot_stride;
     int post_draw;
+    const unsigned long long *post_seeds;     // per-sample Philox keys [N] or nullptr (post_seed for every sample)
+    long long post_rows_per_sample;
 };
 
 // fixed-point scales of the GroupNorm accumulators: |sum| < 2^35, sumsq < 2^43 per channel and sample

@@ -735,6 +735,7 @@ static void fill_params(const gg_conv_desc *d, ConvParams &p)
     p.post_xt = d->post_xt; p.post_labels_out = d->post_labels_out; p.post_scalars = d->post_scalars; p.post_E = d->post_E;
     p.post_seed = d->post_philox_seed; p.post_offset_dev = (const long long *)d->post_philox_offset_dev;
     p.post_onehot_out = (bf16_t *)d->post_onehot_out; p.post_onehot_stride = d->post_onehot_stride; p.post_draw = d->post_draw;
+    p.post_seeds = (const unsigned long long *)d->post_philox_seeds; p.post_rows_per_sample = d->post_rows_per_sample;
     p.mg_osp = gg_magic_u32(p.M, d->Do * d->Ho * d->Wo); p.mg_ohw = gg_magic_u32(p.M, d->Ho * d->Wo); p.mg_wo = gg_magic_u32(p.M, d->Wo);
 }
 
@@ -850,6 +851,9 @@ extern "C" int gg_conv_forward(const gg_conv_desc *d, void *stream_)
         if (!d->post_labels_out || !d->post_scalars) GG_FAIL(GG_ERR_BAD_SHAPE, "conv: fused CCDM reverse step needs labels_out and scalars");
         if (d->post_onehot_out && (d->post_onehot_stride < d->Cout || (d->post_onehot_stride & 1) || ((uintptr_t)d->post_onehot_out & 3)))
             GG_FAIL(GG_ERR_BAD_SHAPE, "conv: fused CCDM reverse step: one-hot rows must be 4-byte aligned (even stride >= K)");
+        if (d->post_philox_seeds && d->post_rows_per_sample != (int64_t)d->Do * d->Ho * d->Wo)
+            GG_FAIL(GG_ERR_BAD_SHAPE, "conv: fused CCDM reverse step: post_rows_per_sample %lld must be Do*Ho*Wo = %lld",
+                    (long long)d->post_rows_per_sample, (long long)d->Do * d->Ho * d->Wo);
     }
     const bool pro_acc = d->prologue_act && !d->gn_scale && !d->gn_shift && d->pro_acc1;
     if (pro_acc) {
@@ -910,6 +914,8 @@ extern "C" int gg_conv_forward(const gg_conv_desc *d, void *stream_)
     p.ws = nullptr;
 #endif
     if (rc != GG_ERR_UNSUPPORTED) return rc;
+    // the fused CCDM reverse step exists on the halo-tile kernel only: the kernels below would ignore post_xt and leave the labels stale
+    if (d->post_xt) GG_FAIL(GG_ERR_UNSUPPORTED, "conv: the halo-tile kernel did not take this shape, and no other kernel runs the fused CCDM reverse step");
 #ifdef GG_BOX_STAMPS
     if (d->path_hint == 98) p.ws = (float *)d->workspace;      // diagnostic build: phase stamps of the box kernel
 #endif

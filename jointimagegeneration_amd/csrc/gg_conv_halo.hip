@@ -296,6 +296,10 @@ __global__ __launch_bounds__((GG_HALO_W16(D3, NT, HB) ? 1024 : (NT <= 2 && HB !=
         }
         const float pa = p.post_scalars[0], pabar = p.post_scalars[1];
         const long long poff = (p.post_draw && !p.post_E && p.post_offset_dev) ? p.post_offset_dev[0] : 0;
+        // per-sample key (gg_conv_desc.post_philox_seeds): a box never straddles two samples (the tiles of sample n are workgroups
+        // [n * tiles_d, (n + 1) * tiles_d)), so n is uniform here: one scalar load of the key, and the counter row is m - n * rows
+        const uint64_t pseed = p.post_seeds ? (uint64_t)p.post_seeds[n] : (uint64_t)p.post_seed;
+        const long long mbase = p.post_seeds ? (long long)n * p.post_rows_per_sample : 0;
 #pragma unroll 1
         for (int r = 0; r < TPW * 16 / 64; ++r) {
             const int pp = r * 64 + lane, tt = pp >> 4, pw = pp & 15;
@@ -312,8 +316,8 @@ __global__ __launch_bounds__((GG_HALO_W16(D3, NT, HB) ? 1024 : (NT <= 2 && HB !=
             }
             const float *erow = p.post_E ? p.post_E + m * p.Cout : nullptr;
             int best;
-            if (p.Cout == 14) best = ccdm_posterior_voxel<16, 14>(p0, 1, x, pa, pabar, 14, m, p.post_draw, erow, (uint64_t)p.post_seed, poff, nullptr);
-            else best = ccdm_posterior_voxel<16>(p0, 1, x, pa, pabar, p.Cout, m, p.post_draw, erow, (uint64_t)p.post_seed, poff, nullptr);
+            if (p.Cout == 14) best = ccdm_posterior_voxel<16, 14>(p0, 1, x, pa, pabar, 14, m - mbase, p.post_draw, erow, pseed, poff, nullptr);
+            else best = ccdm_posterior_voxel<16>(p0, 1, x, pa, pabar, p.Cout, m - mbase, p.post_draw, erow, pseed, poff, nullptr);
             p.post_labels_out[m] = best;
             if (p.post_onehot_out) ccdm_onehot_row<16>(p.post_onehot_out + m * p.post_onehot_stride, best, p.Cout);
         }

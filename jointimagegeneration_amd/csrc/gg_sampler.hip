@@ -5,13 +5,16 @@
 // ------------------------------------------------------------------------------------------------------------
 // CCDM reverse step, one voxel per thread (gg_posterior.h holds the arithmetic).
 // ------------------------------------------------------------------------------------------------------------
-template <int KMAX, int KS = 0>
+// PS (per-sample key): row m belongs to sample n = m / rows_per_sample and draws with key seeds[n] and counter row m - n * rows_per_sample,
+// so that a sample's labels do not depend on its slot in the batch; PS == 0 is the single-key mode (key seed, counter m).
+template <int KMAX, int KS = 0, int PS = 0>
 __global__ __launch_bounds__(256) void ccdm_posterior_kernel(const float *__restrict__ head, int head_stride, int is_logits,
                                                              const int *__restrict__ xt, const float *__restrict__ E,
                                                              uint64_t seed, const long long *__restrict__ offset_dev, int draw,
                                                              const float *__restrict__ scalars, int K, long long M,
                                                              int *__restrict__ labels_out, float *__restrict__ probs_out,
-                                                             bf16_t *__restrict__ onehot_out, int onehot_stride)
+                                                             bf16_t *__restrict__ onehot_out, int onehot_stride,
+                                                             const unsigned long long *__restrict__ seeds, long long rows_per_sample)
 {
     const long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (m >= M) return;
@@ -20,10 +23,47 @@ __global__ __launch_bounds__(256) void ccdm_posterior_kernel(const float *__rest
 #pragma unroll
     for (int c = 0; c < KMAX; ++c) p0[c] = (c < (KS > 0 ? KS : K)) ? hp[c] : 0.f;
     const long long off = (draw && !E && offset_dev) ? offset_dev[0] : 0;
-    const int best = ccdm_posterior_voxel<KMAX, KS>(p0, is_logits, xt[m], scalars[0], scalars[1], K, m, draw, E ? E + m * K : nullptr, seed, off,
+    uint64_t key = seed;
+    long long row = m;
+    if constexpr (PS) {
+        const long long n = m / rows_per_sample;
+        key = seeds[n];
+        row = m - n * rows_per_sample;
+    }
+    const int best = ccdm_posterior_voxel<KMAX, KS>(p0, is_logits, xt[m], scalars[0], scalars[1], K, row, draw, E ? E + m * K : nullptr, key, off,
                                                 probs_out ? probs_out + m * K : nullptr);
     labels_out[m] = best;
     if (onehot_out) ccdm_onehot_row<KMAX, KS>(onehot_out + m * onehot_stride, best, K);
+}
+
+template <int PS>
+static int ccdm_posterior_launch(const float *head, int32_t head_stride, int32_t head_is_logits, const int32_t *xt, const float *E,
+                                 uint64_t philox_seed, const int64_t *philox_offset_dev, int32_t draw, const float *scalars_dev, int32_t K,
+                                 int64_t M, int32_t *labels_out, float *probs_out, void *onehot_out, int32_t onehot_stride,
+                                 const uint64_t *seeds, int64_t rows_per_sample, hipStream_t stream)
+{
+    if (!head || !xt || !scalars_dev || !labels_out) GG_FAIL(GG_ERR_BAD_SHAPE, "ccdm_posterior_sample: null pointer");
+    if (K < 2 || K > 32) GG_FAIL(GG_ERR_UNSUPPORTED, "ccdm_posterior_sample: K=%d outside [2, 32]", K);
+    if (head_stride < K) GG_FAIL(GG_ERR_BAD_SHAPE, "ccdm_posterior_sample: head_stride < K");
+    if (onehot_out && onehot_stride < K) GG_FAIL(GG_ERR_BAD_SHAPE, "ccdm_posterior_sample: onehot_stride < K");
+    if (onehot_out && ((onehot_stride & 1) || ((uintptr_t)onehot_out & 3))) GG_FAIL(GG_ERR_BAD_SHAPE, "ccdm_posterior_sample: onehot rows must be 4-byte aligned (even stride)");
+    if (M <= 0) return GG_OK;
+    const unsigned long long *sd = (const unsigned long long *)seeds;
+    dim3 grid((unsigned)((M + 255) / 256));
+    if (K == 14)        // the class count of the shipped configs (13 organs + background), compiled in
+        hipLaunchKernelGGL((ccdm_posterior_kernel<16, 14, PS>), grid, dim3(256), 0, stream, head, head_stride, head_is_logits, xt, E,
+                           philox_seed, (const long long *)philox_offset_dev, draw, scalars_dev, K, (long long)M, labels_out,
+                           probs_out, (bf16_t *)onehot_out, onehot_stride, sd, (long long)rows_per_sample);
+    else if (K <= 16)
+        hipLaunchKernelGGL((ccdm_posterior_kernel<16, 0, PS>), grid, dim3(256), 0, stream, head, head_stride, head_is_logits, xt, E,
+                           philox_seed, (const long long *)philox_offset_dev, draw, scalars_dev, K, (long long)M, labels_out,
+                           probs_out, (bf16_t *)onehot_out, onehot_stride, sd, (long long)rows_per_sample);
+    else
+        hipLaunchKernelGGL((ccdm_posterior_kernel<32, 0, PS>), grid, dim3(256), 0, stream, head, head_stride, head_is_logits, xt, E,
+                           philox_seed, (const long long *)philox_offset_dev, draw, scalars_dev, K, (long long)M, labels_out,
+                           probs_out, (bf16_t *)onehot_out, onehot_stride, sd, (long long)rows_per_sample);
+    GG_CHECK_LAUNCH();
+    return GG_OK;
 }
 
 extern "C" int gg_ccdm_posterior_sample(const float *head, int32_t head_stride, int32_t head_is_logits, const int32_t *xt,
@@ -31,28 +71,20 @@ extern "C" int gg_ccdm_posterior_sample(const float *head, int32_t head_stride, 
                                         const float *scalars_dev, int32_t K, int64_t M, int32_t *labels_out, float *probs_out,
                                         void *onehot_out, int32_t onehot_stride, void *stream_)
 {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (!head || !xt || !scalars_dev || !labels_out) GG_FAIL(GG_ERR_BAD_SHAPE, "ccdm_posterior_sample: null pointer");
-    if (K < 2 || K > 32) GG_FAIL(GG_ERR_UNSUPPORTED, "ccdm_posterior_sample: K=%d outside [2, 32]", K);
-    if (head_stride < K) GG_FAIL(GG_ERR_BAD_SHAPE, "ccdm_posterior_sample: head_stride < K");
-    if (onehot_out && onehot_stride < K) GG_FAIL(GG_ERR_BAD_SHAPE, "ccdm_posterior_sample: onehot_stride < K");
-    if (onehot_out && ((onehot_stride & 1) || ((uintptr_t)onehot_out & 3))) GG_FAIL(GG_ERR_BAD_SHAPE, "ccdm_posterior_sample: onehot rows must be 4-byte aligned (even stride)");
-    if (M <= 0) return GG_OK;
-    dim3 grid((unsigned)((M + 255) / 256));
-    if (K == 14)        // the class count of the shipped configs (13 organs + background), compiled in
-        hipLaunchKernelGGL((ccdm_posterior_kernel<16, 14>), grid, dim3(256), 0, stream, head, head_stride, head_is_logits, xt, E,
-                           philox_seed, (const long long *)philox_offset_dev, draw, scalars_dev, K, (long long)M, labels_out,
-                           probs_out, (bf16_t *)onehot_out, onehot_stride);
-    else if (K <= 16)
-        hipLaunchKernelGGL(ccdm_posterior_kernel<16>, grid, dim3(256), 0, stream, head, head_stride, head_is_logits, xt, E,
-                           philox_seed, (const long long *)philox_offset_dev, draw, scalars_dev, K, (long long)M, labels_out,
-                           probs_out, (bf16_t *)onehot_out, onehot_stride);
-    else
-        hipLaunchKernelGGL(ccdm_posterior_kernel<32>, grid, dim3(256), 0, stream, head, head_stride, head_is_logits, xt, E,
-                           philox_seed, (const long long *)philox_offset_dev, draw, scalars_dev, K, (long long)M, labels_out,
-                           probs_out, (bf16_t *)onehot_out, onehot_stride);
-    GG_CHECK_LAUNCH();
-    return GG_OK;
+    return ccdm_posterior_launch<0>(head, head_stride, head_is_logits, xt, E, philox_seed, philox_offset_dev, draw, scalars_dev, K, M,
+                                    labels_out, probs_out, onehot_out, onehot_stride, nullptr, 0, (hipStream_t)stream_);
+}
+
+extern "C" int gg_ccdm_posterior_sample_seeds(const float *head, int32_t head_stride, int32_t head_is_logits, const int32_t *xt,
+                                              const float *E, const uint64_t *philox_seeds_dev, int64_t rows_per_sample,
+                                              const int64_t *philox_offset_dev, int32_t draw, const float *scalars_dev, int32_t K, int64_t M,
+                                              int32_t *labels_out, float *probs_out, void *onehot_out, int32_t onehot_stride, void *stream_)
+{
+    if (!philox_seeds_dev) GG_FAIL(GG_ERR_BAD_SHAPE, "ccdm_posterior_sample_seeds: null seeds");
+    if (rows_per_sample <= 0 || M % rows_per_sample) GG_FAIL(GG_ERR_BAD_SHAPE, "ccdm_posterior_sample_seeds: M=%lld is not a multiple of rows_per_sample=%lld",
+                                                             (long long)M, (long long)rows_per_sample);
+    return ccdm_posterior_launch<1>(head, head_stride, head_is_logits, xt, E, 0, philox_offset_dev, draw, scalars_dev, K, M, labels_out,
+                                    probs_out, onehot_out, onehot_stride, philox_seeds_dev, rows_per_sample, (hipStream_t)stream_);
 }
 
 __global__ __launch_bounds__(256) void labels_to_onehot_kernel(const int *__restrict__ labels, long long M, int K,
@@ -302,6 +334,123 @@ extern "C" int gg_mask_to_cond_slice(const int32_t *labels, int32_t N, int32_t D
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(mask_to_cond_slice_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, labels, N, Dm, Hm, Wm, slice,
                        D, H, W, zoom0_factor(Dm, D), zoom0_factor(Hm, H), zoom0_factor(Wm, W), prev, (bf16_t *)cond_cl, stride, mask_out);
+    GG_CHECK_LAUNCH();
+    return GG_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// Batched slice loop of independent volumes (GuideGenPipeline.sample_ct_volumes): N volumes, each with its own slice window, run as one
+// batch.  A device schedule int32 [iterations][N][3] = (slice, previous slice, active) and a device iteration counter make the per-slice
+// work graph-capturable: the glue reads row iter_dev[0], the normalise+scatter reads it too and (advance != 0) moves the counter on.
+// volume fp32 [D][N][H*W] (slice-major, sample n's slice s at (s * N + n) * H * W).  Every sample reads and writes only its own rows.
+// ------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void mask_to_cond_slices_kernel(const int *__restrict__ labels, int N, int Dm, int Hm, int Wm, int D, int H,
+                                                                  int W, double zd, double zh, double zw, const int *__restrict__ sched,
+                                                                  int iterations, const int *__restrict__ iter_dev,
+                                                                  const float *__restrict__ volume, bf16_t *__restrict__ cond, int stride)
+{
+    const int it = iter_dev[0];
+    if (it < 0 || it >= iterations) return;                // a schedule overrun writes nothing
+    const long long HW = (long long)H * W, total = (long long)N * HW;
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
+        const int n = (int)(t / HW);
+        const long long r = t - n * HW;
+        const int *row = sched + ((long long)it * N + n) * 3;
+        const int slice = min(max(row[0], 0), D - 1), prev = min(max(row[1], 0), D - 1);
+        const int sd = zoom0_index(slice, zd, Dm);
+        int j = (int)(r % W);
+        int i = (int)(r / W);
+        int y = H - 1 - j, x = i;                         // rot90(k=3), as mask_to_cond_slice_kernel
+        int sy = zoom0_index(y, zh, Hm), sx = zoom0_index(x, zw, Wm);
+        int lab = labels[(((long long)n * Dm + sd) * Hm + sy) * Wm + sx];
+        float mv = (float)lab / 255.0f;
+        float pv = volume[((long long)prev * N + n) * HW + r];
+        bf16_t *crow = cond + t * stride;
+        bf16x8 o = {(bf16_t)pv, (bf16_t)mv, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f};
+        *reinterpret_cast<bf16x8 *>(crow) = o;
+        bf16x8 z = {(bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f};
+        for (int c = 8; c < stride; c += 8) *reinterpret_cast<bf16x8 *>(crow + c) = z;
+    }
+}
+
+extern "C" int gg_mask_to_cond_slices(const int32_t *labels, int32_t N, int32_t Dm, int32_t Hm, int32_t Wm, int32_t D, int32_t H, int32_t W,
+                                      const int32_t *schedule_dev, int32_t iterations, const int32_t *iter_dev, const float *volume,
+                                      void *cond_cl, int32_t stride, void *stream_)
+{
+    if (!labels || !schedule_dev || !iter_dev || !volume || !cond_cl) GG_FAIL(GG_ERR_BAD_SHAPE, "mask_to_cond_slices: null pointer");
+    if (H != W) GG_FAIL(GG_ERR_UNSUPPORTED, "mask_to_cond_slices: rot90 needs H == W");
+    if (stride % 8 || stride < 8) GG_FAIL(GG_ERR_BAD_SHAPE, "mask_to_cond_slices: stride");
+    if (N < 1 || Dm < 1 || Hm < 1 || Wm < 1 || D < 1 || H < 1 || iterations < 1) GG_FAIL(GG_ERR_BAD_SHAPE, "mask_to_cond_slices: empty extent");
+    long long total = (long long)N * H * W;
+    long long blocks = (total + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(mask_to_cond_slices_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, labels, N, Dm, Hm, Wm, D, H, W,
+                       zoom0_factor(Dm, D), zoom0_factor(Hm, H), zoom0_factor(Wm, W), schedule_dev, iterations, iter_dev, volume,
+                       (bf16_t *)cond_cl, stride);
+    GG_CHECK_LAUNCH();
+    return GG_OK;
+}
+
+// Segmented form of gg_minmax_normalise: sample n's min / max over its own n_per values (workspace [N][2], ordered uints), then
+// (src - mn) / den with the same operands and the same rounding, so that each segment is bit-equal to gg_minmax_normalise on that sample
+// alone.  The result goes to volume[slice_n][n] for the samples whose schedule row is active; the others are left untouched.
+__global__ __launch_bounds__(256) void minmax_seg_init_kernel(uint32_t *ws, int N)
+{
+    for (int i = threadIdx.x; i < N; i += blockDim.x) { ws[2 * i] = 0xFFFFFFFFu; ws[2 * i + 1] = 0u; }
+}
+
+__global__ __launch_bounds__(256) void minmax_seg_reduce_kernel(const float *__restrict__ src, long long n_per, uint32_t *ws)
+{
+    const int n = blockIdx.y;
+    const float *s = src + (long long)n * n_per;
+    float mn = INFINITY, mx = -INFINITY;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n_per; i += (long long)gridDim.x * blockDim.x) {
+        float v = s[i];
+        mn = fminf(mn, v);
+        mx = fmaxf(mx, v);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { mn = fminf(mn, __shfl_xor(mn, o)); mx = fmaxf(mx, __shfl_xor(mx, o)); }
+    if ((threadIdx.x & 63) == 0) { atomicMin(&ws[2 * n], f2ord(mn)); atomicMax(&ws[2 * n + 1], f2ord(mx)); }
+}
+
+__global__ __launch_bounds__(256) void minmax_seg_scatter_kernel(const float *__restrict__ src, int N, long long n_per, const uint32_t *ws,
+                                                                 const int *__restrict__ sched, int iterations, const int *__restrict__ iter_dev,
+                                                                 int depth, float *__restrict__ volume)
+{
+#pragma clang fp contract(off)
+    const int n = blockIdx.y;
+    const int it = iter_dev[0];
+    if (it < 0 || it >= iterations) return;
+    const int *row = sched + ((long long)it * N + n) * 3;
+    if (!row[2]) return;
+    const int slice = row[0];
+    if (slice < 0 || slice >= depth) return;
+    const float mn = ord2f(ws[2 * n]), mx = ord2f(ws[2 * n + 1]);
+    const float den = mx - mn;
+    const float *s = src + (long long)n * n_per;
+    float *d = volume + ((long long)slice * N + n) * n_per;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n_per; i += (long long)gridDim.x * blockDim.x)
+        d[i] = (s[i] - mn) / den;
+}
+
+__global__ void schedule_advance_kernel(int *iter_dev) { iter_dev[0] += 1; }
+
+extern "C" int gg_minmax_normalise_scatter(const float *src, int32_t N, int64_t n_per_sample, float *workspace2n, const int32_t *schedule_dev,
+                                           int32_t iterations, int32_t *iter_dev, int32_t advance, int32_t depth, float *volume, void *stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!src || !workspace2n || !schedule_dev || !iter_dev || !volume) GG_FAIL(GG_ERR_BAD_SHAPE, "minmax_normalise_scatter: null pointer");
+    if (N < 1 || N > 65535 || n_per_sample <= 0 || depth < 1 || iterations < 1) GG_FAIL(GG_ERR_BAD_SHAPE, "minmax_normalise_scatter: bad extent");
+    long long bx = (n_per_sample + 255) / 256;
+    long long cap = 2048 / N > 1 ? 2048 / N : 1;           // about gg_minmax_normalise's grid over the whole batch
+    if (bx > cap) bx = cap;
+    hipLaunchKernelGGL(minmax_seg_init_kernel, dim3(1), dim3(256), 0, stream, (uint32_t *)workspace2n, N);
+    hipLaunchKernelGGL(minmax_seg_reduce_kernel, dim3((unsigned)bx, (unsigned)N), dim3(256), 0, stream, src, (long long)n_per_sample,
+                       (uint32_t *)workspace2n);
+    hipLaunchKernelGGL(minmax_seg_scatter_kernel, dim3((unsigned)bx, (unsigned)N), dim3(256), 0, stream, src, N, (long long)n_per_sample,
+                       (const uint32_t *)workspace2n, schedule_dev, iterations, iter_dev, depth, volume);
+    if (advance) hipLaunchKernelGGL(schedule_advance_kernel, dim3(1), dim3(1), 0, stream, iter_dev);
     GG_CHECK_LAUNCH();
     return GG_OK;
 }

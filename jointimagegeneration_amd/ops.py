@@ -448,6 +448,9 @@ def conv(src1: CL, weight: torch.Tensor, bias: Optional[torch.Tensor], cout: int
         d.post_philox_offset_dev = _ptr(post.get("philox_offset"))
         d.post_draw = 1 if post.get("draw", True) else 0
         d.post_onehot_out, d.post_onehot_stride = _ptr(oh), (oh.shape[-1] if oh is not None else 0)
+        seeds = post.get("philox_seeds")
+        if seeds is not None:                   # one Philox key per sample (gg_conv_desc.post_philox_seeds)
+            d.post_philox_seeds, d.post_rows_per_sample = _seeds_ptr(seeds, N), Do * Ho * Wo
         fused_post = True
     check(lib.gg_conv_forward(C.byref(d), _stream()), "gg_conv_forward")
     return CL(out, cout // 2 if geglu else cout, acc=acc, fused_ddim=fused, fused_post=fused_post)
@@ -645,18 +648,41 @@ def timestep_embedding(t: torch.Tensor, dim: int, max_period: float = 10000.0) -
 def ccdm_posterior_sample(head: torch.Tensor, head_is_logits: bool, xt: torch.Tensor, scalars: torch.Tensor, K: int, *,
                           E: Optional[torch.Tensor] = None, philox_seed: int = 0, philox_offset: Optional[torch.Tensor] = None,
                           draw: bool = True, labels_out: Optional[torch.Tensor] = None, probs_out: Optional[torch.Tensor] = None,
-                          onehot_out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """head: fp32 [..., stride] (probs or logits, channels-last); xt int32 [M]; scalars fp32[2] on device."""
+                          onehot_out: Optional[torch.Tensor] = None, philox_seeds: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """head: fp32 [..., stride] (probs or logits, channels-last); xt int32 [M]; scalars fp32[2] on device.
+    philox_seeds: device int64 [N] (bit patterns of the uint64 keys) with M a multiple of N: one Philox key per sample of M / N rows
+    (gg_ccdm_posterior_sample_seeds) instead of `philox_seed` for all."""
     lib = _lib.load()
     stride = head.shape[-1]
     M = head.numel() // stride
     if labels_out is None:
         labels_out = torch.empty(M, dtype=torch.int32, device=head.device)
+    if philox_seeds is not None:
+        Ns = philox_seeds.numel()
+        if Ns < 1 or M % Ns:
+            raise ValueError(f"ccdm_posterior_sample: {M} rows do not split into {Ns} samples")
+        check(lib.gg_ccdm_posterior_sample_seeds(head.data_ptr(), stride, 1 if head_is_logits else 0, xt.data_ptr(), _ptr(E),
+                                                 _seeds_ptr(philox_seeds, Ns), M // Ns, _ptr(philox_offset), 1 if draw else 0,
+                                                 scalars.data_ptr(), K, M, labels_out.data_ptr(), _ptr(probs_out), _ptr(onehot_out),
+                                                 onehot_out.shape[-1] if onehot_out is not None else 0, _stream()),
+              "gg_ccdm_posterior_sample_seeds")
+        return labels_out
     check(lib.gg_ccdm_posterior_sample(head.data_ptr(), stride, 1 if head_is_logits else 0, xt.data_ptr(), _ptr(E), philox_seed,
                                        _ptr(philox_offset), 1 if draw else 0, scalars.data_ptr(), K, M, labels_out.data_ptr(),
                                        _ptr(probs_out), _ptr(onehot_out), onehot_out.shape[-1] if onehot_out is not None else 0,
                                        _stream()), "gg_ccdm_posterior_sample")
     return labels_out
+
+
+def _seeds_ptr(seeds: torch.Tensor, N: int) -> int:
+    if seeds.dtype != torch.int64 or not seeds.is_cuda or not seeds.is_contiguous() or seeds.numel() != N:
+        raise ValueError(f"philox_seeds must be a contiguous device int64 tensor of {N} keys")
+    return seeds.data_ptr()
+
+
+def philox_seed_tensor(seeds: Sequence[int], device) -> torch.Tensor:
+    """Device int64 tensor holding the uint64 Philox keys `seeds` bit for bit (what `philox_seeds` arguments take)."""
+    return torch.tensor([int(s) - (1 << 64) if int(s) >= (1 << 63) else int(s) for s in seeds], dtype=torch.int64, device=device)
 
 
 def labels_to_onehot(labels: torch.Tensor, K: int, out: torch.Tensor) -> None:
@@ -693,6 +719,43 @@ def mask_to_cond_slice(labels: torch.Tensor, slice_idx: int, D: int, H: int, W: 
     N, Dm, Hm, Wm = labels.shape
     check(lib.gg_mask_to_cond_slice(labels.data_ptr(), N, Dm, Hm, Wm, slice_idx, D, H, W, _ptr(prev), cond.data_ptr(), cond.shape[-1],
                                     _ptr(mask_out), _stream()), "gg_mask_to_cond_slice")
+
+
+def mask_to_cond_slices(labels: torch.Tensor, D: int, H: int, W: int, schedule: torch.Tensor, it: torch.Tensor, volume: torch.Tensor,
+                        cond: torch.Tensor) -> None:
+    """Batched glue of independent volumes: sample n's conditioning row from its own schedule row schedule[it[0], n] = (slice, prev,
+    active) (device int32 [iterations, N, 3]; `it` device int32[1]); prev read from volume fp32 [D, N, H, W].  cond bf16 CL [N,1,H,W,stride]."""
+    lib = _lib.load()
+    N, Dm, Hm, Wm = labels.shape
+    _check_schedule(schedule, N, it)
+    if tuple(volume.shape) != (D, N, H, W) or volume.dtype != torch.float32 or not volume.is_contiguous():
+        raise ValueError(f"mask_to_cond_slices: volume must be contiguous fp32 {(D, N, H, W)}")
+    check(lib.gg_mask_to_cond_slices(labels.data_ptr(), N, Dm, Hm, Wm, D, H, W, schedule.data_ptr(), schedule.shape[0], it.data_ptr(),
+                                     volume.data_ptr(), cond.data_ptr(), cond.shape[-1], _stream()), "gg_mask_to_cond_slices")
+
+
+def minmax_normalise_scatter(src: torch.Tensor, schedule: torch.Tensor, it: torch.Tensor, volume: torch.Tensor, advance: bool = True,
+                             workspace: Optional[torch.Tensor] = None) -> None:
+    """src fp32 [N, ...]: each sample min-max normalised over its own values (bit-equal to minmax_normalise on that sample) and written
+    to volume[slice_n, n] (volume fp32 [depth, N, ...]) where its row schedule[it[0], n] is active; advance: then it[0] += 1."""
+    lib = _lib.load()
+    N = src.shape[0]
+    _check_schedule(schedule, N, it)
+    n_per = src.numel() // N
+    if volume.dtype != torch.float32 or not volume.is_contiguous() or volume.shape[1] != N or volume[0, 0].numel() != n_per:
+        raise ValueError(f"minmax_normalise_scatter: volume must be contiguous fp32 [depth, {N}, ...] of {n_per} values per slice")
+    if workspace is None:
+        workspace = torch.empty(2 * N, dtype=torch.float32, device=src.device)
+    check(lib.gg_minmax_normalise_scatter(src.data_ptr(), N, n_per, workspace.data_ptr(), schedule.data_ptr(), schedule.shape[0],
+                                          it.data_ptr(), 1 if advance else 0, volume.shape[0], volume.data_ptr(), _stream()),
+          "gg_minmax_normalise_scatter")
+
+
+def _check_schedule(schedule: torch.Tensor, N: int, it: torch.Tensor) -> None:
+    if schedule.dtype != torch.int32 or schedule.dim() != 3 or schedule.shape[1:] != (N, 3) or not schedule.is_contiguous():
+        raise ValueError(f"schedule must be a contiguous int32 [iterations, {N}, 3] tensor")
+    if it.dtype != torch.int32 or it.numel() != 1:
+        raise ValueError("the iteration counter must be a device int32[1] tensor")
 
 
 def zoom0_index(n_in: int, n_out: int) -> torch.Tensor:

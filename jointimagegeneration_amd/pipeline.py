@@ -7,8 +7,11 @@ Volumes are independent units: multi-GPU runs shard volumes over ranks with no c
 
 CLI (one process per GPU, under torch.distributed.run or alone):
     python -m jointimagegeneration_amd.pipeline --volumes V --out DIR [--mask-size D H W] [--depth 256] [--hw 512] [--ccdm-steps 250] [--ddim-steps 50]
+                                                [--volumes-per-gpu B]
 samples volumes `volume_id mod world_size == rank` and writes `mask_<id>.nii.gz` (uint8 labels) and `ct_<id>.nii.gz` (fp32 in [0, 1])
 per volume; volume id v uses seed `--seed + 1000 v` for the mask chain and `+ 1` for the slice loop, whatever the world size.
+With B > 1 a rank samples its volumes in groups of B independent volumes per batch (GuideGenPipeline.run_volumes; the last group may
+be smaller): same seeds and file names per volume id as at B = 1.
 """
 from __future__ import annotations
 
@@ -16,7 +19,7 @@ import argparse
 import os
 import sys
 import time
-from typing import Dict, Optional, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -59,6 +62,34 @@ def build_ldm(seed: int = 1024, device="cuda", use_ema: bool = False) -> LatentD
     return m.eval().to(device)
 
 
+def slice_window(labels: torch.Tensor, depth: int, max_slices: Optional[int] = None) -> List[int]:
+    """The slice loop of ONE volume (labels [Dm, Hm, Wm] or [1, Dm, Hm, Wm]), exactly as GuideGenPipeline.sample_ct visits it: slices whose
+    order-0 upsampled mask is non-empty (sample_diffusion.py:202), from one before the first (python indexing: -1 is the last slice) to
+    the last; an empty mask visits slice 0 only.  Returns the loop values m (slice m % depth, previous slice max(0, m - 1) % depth)."""
+    lab = labels.reshape((-1,) + tuple(labels.shape[-3:]))
+    assert lab.shape[0] == 1, "slice_window: one volume"
+    Dm = lab.shape[1]
+    nz = (lab != 0).flatten(2).any(-1).any(0).cpu()                                   # [Dm]
+    idx = torch.nonzero(nz[ops.zoom0_index(Dm, depth)]).flatten()
+    start, end = (int(idx[0]), int(idx[-1])) if idx.numel() else (1, 0)
+    todo = list(range(start - 1, end + 1))
+    return todo[:max_slices] if max_slices is not None else todo
+
+
+def volume_schedule(windows: Sequence[Sequence[int]], depth: int) -> Tuple[torch.Tensor, float]:
+    """Static-batch schedule of independent volumes: int32 [iterations, B, 3] of (slice, previous slice, active), iterations = the longest
+    window; volume i is active in its first len(windows[i]) iterations (finished volumes keep computing on row (0, 0, 0), their output is
+    discarded).  Also returns the fraction of batch slots that do discarded work, 1 - sum(len_i) / (B * iterations)."""
+    B = len(windows)
+    iters = max(len(w) for w in windows)
+    sched = torch.zeros((iters, B, 3), dtype=torch.int32)
+    for i, w in enumerate(windows):
+        for it, m in enumerate(w):
+            sched[it, i, 0], sched[it, i, 1], sched[it, i, 2] = m % depth, max(0, m - 1) % depth, 1
+    wasted = 1.0 - sum(len(w) for w in windows) / float(B * iters)
+    return sched, wasted
+
+
 def _log(msg: str) -> None:
     print(f"[guidegen {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
@@ -73,6 +104,7 @@ class GuideGenPipeline:
         self.stats: Dict[str, float] = {}
         self.use_graph = True
         self._slice_graphs: Dict = {}
+        self._volume_graphs: Dict = {}
         # spatial reduction of the first stage: f = 2^(levels-1) (8 for ch_mult [1,2,4,4], ..._ae.yaml:41-67)
         self.latent_factor = 2 ** (ldm.first_stage_model.decoder.num_resolutions - 1)
 
@@ -87,6 +119,18 @@ class GuideGenPipeline:
         self.ccdm.philox_seed = seed
         cond = torch.zeros((N, 1) + tuple(size), device=dev)
         labels, _ = self.ccdm.sample_labels(x_T, cond, init_t)
+        return labels
+
+    @torch.no_grad()
+    def sample_masks(self, seeds: Sequence[int], size: Tuple[int, int, int], init_t: Optional[int] = None) -> torch.Tensor:
+        """Independent volumes in one batch: volume i is sample_mask(1, size, seeds[i]) -- its own x_T generator and its own Philox key
+        (per-sample key of the reverse step), so that it depends on nothing its neighbours hold.  Returns int32 labels [B, D, H, W]."""
+        dev = self.ccdm.diffusion.betas.device
+        K = self.ccdm.diffusion.num_classes
+        x_T = torch.cat([torch.randint(0, K, (1,) + tuple(size), generator=torch.Generator(device=dev).manual_seed(int(s)), device=dev,
+                                       dtype=torch.int32) for s in seeds])
+        cond = torch.zeros((len(seeds), 1) + tuple(size), device=dev)
+        labels, _ = self.ccdm.sample_labels(x_T, cond, init_t, philox_seeds=[int(s) for s in seeds])
         return labels
 
     def _slice_engine(self, N: int, hw: int, dev, st) -> Dict:
@@ -208,6 +252,116 @@ class GuideGenPipeline:
             samples[mm].copy_(sg["ds"])
         return samples.permute(1, 0, 2, 3)
 
+    def _volume_engine(self, B: int, hw: int, depth: int, lab_shape: Tuple[int, ...], dev, st) -> Dict:
+        """Static buffers + the ONE per-slice hipGraph of the batched slice loop of B independent volumes: batched glue (schedule row of the
+        device iteration counter), cond-encode, the S DDIM steps, decode, per-volume normalise + scatter (advances the counter)."""
+        ldm = self.ldm
+        lat, Cz = hw // self.latent_factor, ldm.channels
+        key = (B, hw, depth, tuple(lab_shape), str(dev))
+        token = (id(st), ops.weights_token(ldm.cond_stage_model), ops.weights_token(ldm.first_stage_model))
+        ve = self._volume_graphs.get(key)
+        if ve is not None and ve["token"] == token:
+            return ve
+        ve = dict(token=token, labels=torch.zeros(tuple(lab_shape), dtype=torch.int32, device=dev),
+                  samples=torch.zeros((depth, B, hw, hw), dtype=torch.float32, device=dev),
+                  sched=torch.zeros((depth + 1, B, 3), dtype=torch.int32, device=dev),      # a window has at most depth + 1 iterations
+                  it=torch.zeros(1, dtype=torch.int32, device=dev), ws=torch.empty(2 * B, dtype=torch.float32, device=dev),
+                  cond_in=torch.empty((B, 1, hw, hw, 32), dtype=torch.bfloat16, device=dev),
+                  z=torch.zeros((B, 1, lat, lat, 32), dtype=torch.bfloat16, device=dev),
+                  ds=torch.empty((B, hw, hw), dtype=torch.float32, device=dev), graph=None, warmed=False)
+
+        def glue():
+            ops.mask_to_cond_slices(ve["labels"], depth, hw, hw, ve["sched"], ve["it"], ve["samples"], ve["cond_in"])
+
+        def encode():
+            mom = ldm.cond_stage_model.encode_moments_cl(CL(ve["cond_in"], 2))
+            st["unet_in"][..., Cz:2 * Cz].copy_(mom.t[..., :Cz])
+
+        def decode():
+            ve["z"][..., :Cz].copy_(st["x"] * (1.0 / ldm.scale_factor))
+            dec = ldm.first_stage_model.decode_cl(CL(ve["z"], Cz))
+            ve["ds"].copy_(dec.t[..., 0].reshape(B, hw, hw))
+            ops.minmax_normalise_scatter(ve["ds"], ve["sched"], ve["it"], ve["samples"], advance=True, workspace=ve["ws"])
+
+        ve["glue"], ve["encode"], ve["decode"] = glue, encode, decode
+        self._volume_graphs[key] = ve
+        return ve
+
+    @torch.no_grad()
+    def sample_ct_volumes(self, labels: torch.Tensor, depth: int, hw: int, seeds: Sequence[int], max_slices: Optional[int] = None,
+                          x_T_tapes=None) -> torch.Tensor:
+        """labels int32 [B,Dm,Hm,Wm] of B INDEPENDENT volumes -> CT fp32 [B, depth, hw, hw]: volume i is sample_ct(labels[i:i+1], depth,
+        hw, seeds[i], max_slices) -- its own slice window, its own min-max normalisation, its own x_T generator -- up to the bf16 rounding
+        of batch-size-dependent kernel plans, and bit for bit independent of the other volumes at a fixed B.  The batch is static: a volume
+        whose window has ended keeps computing on a discarded row.  One graph replay per slice iteration; the host's share is one x_T
+        draw per ACTIVE volume (so every volume's generator stream is its solo one).  `x_T_tapes` (parity runs): per volume, one
+        [1, Cz, lat, lat] start latent per generated slice in loop order.  self.stats["wasted_slot_fraction"] reports the discarded work."""
+        ldm, sampler = self.ldm, self.sampler
+        dev = labels.device
+        B = labels.shape[0]
+        if len(seeds) != B or (x_T_tapes is not None and len(x_T_tapes) != B):
+            raise ValueError(f"sample_ct_volumes: {B} volumes need {B} seeds (and {B} tapes)")
+        lat, Cz = hw // self.latent_factor, ldm.channels
+        windows = [slice_window(labels[i], depth, max_slices) for i in range(B)]
+        sched, wasted = volume_schedule(windows, depth)
+        iters = sched.shape[0]
+        self.stats["wasted_slot_fraction"] = wasted
+        gens = [torch.Generator(device=dev).manual_seed(int(s)) for s in seeds]
+        st = sampler.prepare_state(B, Cz, (lat, lat), dev, Cz)
+        ve = self._volume_engine(B, hw, depth, tuple(labels.shape), dev, st)
+        ve["labels"].copy_(labels)
+        ve["samples"].zero_()
+        ve["sched"].zero_()
+        ve["sched"][:iters].copy_(sched)                                               # uploaded once per batch
+        ve["it"].zero_()
+        glue, encode, decode = ve["glue"], ve["encode"], ve["decode"]
+
+        t_last = time.time()
+        for it in range(iters):
+            if time.time() - t_last > self.progress_every_s:
+                _log(f"LDM slice {it}/{iters} (batch of {B})")
+                t_last = time.time()
+            x_T = torch.zeros((B, Cz, lat, lat), dtype=torch.float32, device=dev)
+            for i in range(B):
+                if it < len(windows[i]):                                               # NCHW draw order of sample_ct
+                    x_T[i] = (x_T_tapes[i][it].to(dev).float().reshape(Cz, lat, lat) if x_T_tapes is not None
+                              else torch.randn((1, Cz, lat, lat), generator=gens[i], device=dev)[0])
+            x_T = x_T.permute(0, 2, 3, 1).reshape(B, 1, lat, lat, Cz)
+            st["x"].copy_(x_T)
+            st["unet_in"][..., :Cz].copy_(x_T)
+            if not (self.use_graph and sampler.chain_graphable(st)):
+                glue()
+                encode()
+                sampler.run_steps(st, None, 0.0, None)
+                decode()
+            elif not ve["warmed"]:
+                glue()
+                encode()                                                               # eager once: fills the repack caches
+                sampler.chain(st)
+                decode()
+                ve["warmed"] = True
+            else:
+                if ve["graph"] is None:
+                    ve["graph"] = ops.capture_graph(lambda: (glue(), encode(), sampler.chain(st), decode()))
+                ve["graph"].replay()
+        return ve["samples"].clone().permute(1, 0, 2, 3)
+
+    @torch.no_grad()
+    def run_volumes(self, seeds: Sequence[int], mask_size=(128, 128, 128), depth: int = 256, hw: int = 512,
+                    ccdm_init_t: Optional[int] = None, max_slices: Optional[int] = None):
+        """B independent volumes in one batch: volume i is run_volume(N=1, seed=seeds[i]) (seed for the CCDM stage, seed + 1 for the
+        LDM stage) up to the bf16 rounding of batch-size-dependent kernel plans.  Returns (labels [B, Dm, Hm, Wm], ct [B, depth, hw, hw])."""
+        t0 = time.time()
+        labels = self.sample_masks(seeds, mask_size, ccdm_init_t)
+        torch.cuda.synchronize()
+        t1 = time.time()
+        ct = self.sample_ct_volumes(labels, depth, hw, [int(s) + 1 for s in seeds], max_slices)
+        torch.cuda.synchronize()
+        self.stats.update({"ccdm_s": t1 - t0, "ldm_s": time.time() - t1})
+        _log(f"{len(seeds)} volumes done: CCDM {t1 - t0:.1f}s, LDM {time.time() - t1:.1f}s, "
+             f"wasted slots {self.stats['wasted_slot_fraction']:.3f}")
+        return labels, ct
+
     @torch.no_grad()
     def run_volume(self, N: int = 1, mask_size=(128, 128, 128), depth: int = 256, hw: int = 512, seed: int = 1024,
                    ccdm_init_t: Optional[int] = None, max_slices: Optional[int] = None):
@@ -237,7 +391,10 @@ def main(argv=None) -> None:
     ap.add_argument("--ddim-steps", type=int, default=50)
     ap.add_argument("--seed", type=int, default=1024)
     ap.add_argument("--max-slices", type=int, default=None, help="DEV ONLY: truncate the slice loop")
+    ap.add_argument("--volumes-per-gpu", type=int, default=1, help="independent volumes per batch (groups of a rank's shard)")
     args = ap.parse_args(argv)
+    if args.volumes_per_gpu < 1:
+        ap.error("--volumes-per-gpu must be >= 1")
     rank, local, world = ggd.env_rank_world()
     dry = os.environ.get("GG_PIPELINE_DRY") == "1"          # CPU rehearsal of the sharding (tests): no model, no GPU
     os.makedirs(args.out, exist_ok=True)
@@ -252,15 +409,30 @@ def main(argv=None) -> None:
         ggd.init("nccl", dev)
         pipe = GuideGenPipeline(build_ccdm(args.classes, args.ccdm_steps, 1024, dev), build_ldm(1024, dev), ddim_steps=args.ddim_steps)
     t0 = time.time()
-    for vid in mine:
-        seed = args.seed + 1000 * vid
-        if dry:
-            with open(os.path.join(args.out, f"ct_{vid:04d}.txt"), "w") as f:
-                f.write(f"rank {rank} world {world} seed {seed}\n")
-            continue
-        labels, ct = pipe.run_volume(N=1, mask_size=tuple(args.mask_size), depth=args.depth, hw=args.hw, seed=seed, max_slices=args.max_slices)
-        write_nifti(os.path.join(args.out, f"mask_{vid:04d}.nii.gz"), labels[0].to(torch.uint8).cpu().numpy())
-        write_nifti(os.path.join(args.out, f"ct_{vid:04d}.nii.gz"), ct[0].float().cpu().numpy())
+    B = args.volumes_per_gpu
+    if B == 1:
+        for vid in mine:
+            seed = args.seed + 1000 * vid
+            if dry:
+                with open(os.path.join(args.out, f"ct_{vid:04d}.txt"), "w") as f:
+                    f.write(f"rank {rank} world {world} seed {seed}\n")
+                continue
+            labels, ct = pipe.run_volume(N=1, mask_size=tuple(args.mask_size), depth=args.depth, hw=args.hw, seed=seed, max_slices=args.max_slices)
+            write_nifti(os.path.join(args.out, f"mask_{vid:04d}.nii.gz"), labels[0].to(torch.uint8).cpu().numpy())
+            write_nifti(os.path.join(args.out, f"ct_{vid:04d}.nii.gz"), ct[0].float().cpu().numpy())
+    else:
+        for gi, g0 in enumerate(range(0, len(mine), B)):
+            group = mine[g0:g0 + B]
+            seeds = [args.seed + 1000 * vid for vid in group]
+            if dry:
+                for vid, seed in zip(group, seeds):
+                    with open(os.path.join(args.out, f"ct_{vid:04d}.txt"), "w") as f:
+                        f.write(f"rank {rank} world {world} seed {seed} group {gi} volumes {','.join(str(v) for v in group)}\n")
+                continue
+            labels, ct = pipe.run_volumes(seeds, mask_size=tuple(args.mask_size), depth=args.depth, hw=args.hw, max_slices=args.max_slices)
+            for i, vid in enumerate(group):
+                write_nifti(os.path.join(args.out, f"mask_{vid:04d}.nii.gz"), labels[i].to(torch.uint8).cpu().numpy())
+                write_nifti(os.path.join(args.out, f"ct_{vid:04d}.nii.gz"), ct[i].float().cpu().numpy())
     print(f"[rank {rank}/{world}] volumes {mine} in {time.time() - t0:.1f}s -> {args.out}", file=sys.stderr)
     ggd.finalize()
 
