@@ -223,6 +223,21 @@ int gg_groupnorm_scale_shift_acc(const int64_t *acc1, int32_t stripes1, int32_t 
                                  float *scale_out, float *shift_out, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Resampling / FiLM (gg_resample.hip): the conv-free Upsample / Downsample (conv_resample=False) and the ResBlock up / down steps
+ * (resblock_updown), and the ResBlock's FiLM term (use_scale_shift_norm).  unet.py:85-145,254-257 ; openaimodel.py:93-160,270-274
+ * ------------------------------------------------------------------------------------------------ */
+/* dst = resample(act(src * scale[n, c] + shift[n, c])) on channels-last [N, D, H, W, C_pad] tensors (dtype GG_BF16 or GG_F32, fp32
+ * arithmetic).  mode 0: nearest x2 upsample; mode 1: 2x average pool (odd pooled extents: GG_ERR_UNSUPPORTED).  H and W always, D too
+ * iff resample_d (3-D networks).  scale / shift: optional fp32 [N, C_pad] (both or neither), act 1 = SiLU (only with scale / shift).
+ * dst [N, Do, Ho, Wo, C_pad], channels >= C_logical written as zeros. */
+int gg_resample2x(const void *src, int32_t dtype, int32_t N, int32_t D, int32_t H, int32_t W, int32_t C_pad, int32_t C_logical,
+                  int32_t resample_d, int32_t mode, const float *scale, const float *shift, int32_t act, void *dst, void *stream);
+/* In place, for c < C: scale[n, c] *= 1 + s, shift[n, c] = shift[n, c] * (1 + s) + t with s = film[n, c], t = film[n, C + c]
+ * (scale / shift fp32 rows of coef_stride, film fp32 rows of film_stride >= 2 C).  One launch, no host synchronisation: the per-(n, c)
+ * GroupNorm coefficients of a FiLM out-norm, for every consumer that takes coefficients (conv prologue, gg_groupnorm_apply). */
+int gg_film_fold(float *scale, float *shift, int32_t coef_stride, int32_t N, int32_t C, const float *film, int64_t film_stride, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Attention: out = softmax(scale * Q K^T) V, flash-style (no TxT buffer), MFMA 16x16x32 bf16, fp32 softmax.
  * Replaces QKVAttentionLegacy (unet.py:334-360, openaimodel.py:349-371), CrossAttention
  * (ldm/modules/attention.py:170-193) and AttnBlock2d's bmm/softmax/bmm (model.py:243-257).
@@ -359,6 +374,11 @@ int gg_conv_forward_f32(const gg_conv_desc *desc, void *stream);
 int gg_groupnorm_f32(const float *src1, int32_t C1, const float *src2, int32_t C2, int32_t N, int64_t S, int32_t C_logical,
                      const float *gamma, const float *beta, float eps, int32_t act, float *out, float *workspace, void *stream);
 /* gg_attention_desc with fp32 q / k / v / out (head_dim <= 64): softmax((q a)(k a)^T) v, a = sqrt(scale), all fp32. */
+/* The ResBlock out-norm under use_scale_shift_norm in the reference's order: act(GroupNorm(32)(src) * (1 + s) + t) with s = film[n, c],
+ * t = film[n, C_logical + c] (film fp32, row stride film_stride >= 2 * C_logical), every step rounded to fp32; single source.  out fp32 CL
+ * [N, S, C_pad] (pad lanes zero); workspace: 64 * N floats. */
+int gg_groupnorm_f32_film(const float *src, int32_t C_pad, int32_t N, int64_t S, int32_t C_logical, const float *gamma, const float *beta,
+                          float eps, const float *film, int64_t film_stride, int32_t act, float *out, float *workspace, void *stream);
 int gg_attention_forward_f32(const gg_attention_desc *desc, void *stream);
 
 /* ------------------------------------------------------------------------------------------------

@@ -83,6 +83,9 @@ SIGNATURES = {
     "gg_conv_forward_f32": (C.c_int, [C.POINTER(ConvDesc), vp]),
     "gg_groupnorm_f32": (C.c_int, [vp, i32, vp, i32, i32, i64, i32, vp, vp, f32, i32, vp, vp, vp]),
     "gg_attention_forward_f32": (C.c_int, [C.POINTER(AttentionDesc), vp]),
+    "gg_groupnorm_f32_film": (C.c_int, [vp, i32, i32, i64, i32, vp, vp, f32, vp, i64, i32, vp, vp, vp]),
+    "gg_resample2x": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp]),
+    "gg_film_fold": (C.c_int, [vp, vp, i32, i32, i32, vp, i64, vp]),
     "gg_mask_to_cond_slice": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp]),
     "gg_mask_to_cond_slices": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp, i32, vp]),
     "gg_minmax_normalise_scatter": (C.c_int, [vp, i32, i64, vp, vp, i32, vp, i32, i32, vp, vp]),

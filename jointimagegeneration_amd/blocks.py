@@ -15,6 +15,7 @@ Reference blocks mirrored (file:line relative to the reference tree):
 from __future__ import annotations
 
 import math
+import weakref
 from typing import List, Optional
 
 import torch
@@ -42,18 +43,21 @@ def _k3(w: torch.Tensor):
 
 
 class _Packed:
-    """Cache of kernel-friendly repacks (bf16 MFMA tile order, padded fp32 biases) keyed by parameter version."""
+    """Cache of kernel-friendly repacks (bf16 MFMA tile order, padded fp32 biases) keyed by parameter version.
+    Keys hold id(module), which Python reuses once a module is freed, and a new module's parameters can land on the freed storage with
+    the same version counters: so a hit also requires the cached parameters to be the very same tensor objects (weak references)."""
 
     def __init__(self):
         self.store = {}
 
     def get(self, key, params, build):
-        ver = tuple((p.data_ptr(), p._version) for p in params if p is not None)
+        params = [p for p in params if p is not None]
+        ver = tuple((p.data_ptr(), p._version) for p in params)
         hit = self.store.get(key)
-        if hit is not None and hit[0] == ver:
+        if hit is not None and hit[0] == ver and all(r() is p for r, p in zip(hit[2], params)):
             return hit[1]
         val = build()
-        self.store[key] = (ver, val)
+        self.store[key] = (ver, val, [weakref.ref(p) for p in params])
         return val
 
 
@@ -119,27 +123,34 @@ def gn_silu(h: CL, norm: nn.GroupNorm, act: bool, src2: Optional[CL] = None) -> 
     return ops.groupnorm_apply(h, scale, shift, act, src2)
 
 
-def norm_conv(h: CL, norm: nn.GroupNorm, act: bool, weight, bias, cout, src2: Optional[CL] = None, **conv_kw) -> CL:
-    """conv(act(GroupNorm(cat[h, src2]))).
+def norm_conv(h: CL, norm: nn.GroupNorm, act: bool, weight, bias, cout, src2: Optional[CL] = None, film: Optional[torch.Tensor] = None,
+              **conv_kw) -> CL:
+    """conv(act(GroupNorm(cat[h, src2]))), or with film (fp32 [N, >= 2C] rows [s | t], use_scale_shift_norm)
+    conv(act(GroupNorm(h) * (1 + s) + t)): FiLM takes the coefficient route (statistics or accumulator fold -> gg_film_fold -> fused
+    prologue or gg_groupnorm_apply), never the kernels that compute the coefficients inside another launch.
     Halo-tile convs (3x3(x3), stride 1, large extents): one stats pass, then normalise*affine(+SiLU) and the skip concat are
     fused into the conv's staging pass (applied once per staged element) -- the activation is never re-written to HBM.
     Gather-kernel convs: separate apply pass (measured: SiLU inside the latency-bound gather loop costs 26 vs 16.6 us/conv)."""
+    if ops.is_f32(h.t) and film is not None:  # fp32 validation path of a FiLM norm: the reference's rounding order, nothing folded
+        return ops.conv(ops.groupnorm_f32_film(h, f32(norm.weight), f32(norm.bias), norm.eps, film, act), weight, bias, cout, **conv_kw)
     if ops.is_f32(h.t):                      # fp32 validation path: separate fp32 GroupNorm launch, then the fp32 conv
         return ops.conv(ops.groupnorm_f32(h, f32(norm.weight), f32(norm.bias), norm.eps, act, src2), weight, bias, cout, **conv_kw)
-    if ops.conv_prologue_from_acc(h, cout, act, src2=src2, **conv_kw):
+    if film is None and ops.conv_prologue_from_acc(h, cout, act, src2=src2, **conv_kw):
         # box conv + producers' sums: the conv folds them and normalises its staged box itself -- NO GroupNorm launch of any kind
         return ops.conv(h, weight, bias, cout, src2=src2, prologue_acc=(f32(norm.weight), f32(norm.bias), norm.eps), prologue_silu=act, **conv_kw)
     fused = ops.conv_fuses_prologue(h, cout, src2=src2, **conv_kw)
-    if not fused and ops.groupnorm_fused_ok(h, src2):     # small tensor: statistics + apply in ONE launch
+    if film is None and not fused and ops.groupnorm_fused_ok(h, src2):     # small tensor: statistics + apply in ONE launch
         a = ops.groupnorm_fused(h, f32(norm.weight), f32(norm.bias), norm.eps, act, src2)
         return ops.conv(a, weight, bias, cout, **conv_kw)
-    if not fused and ops.has_stats(h, src2):     # statistics came with the tensor (conv epilogue accumulators)
+    if film is None and not fused and ops.has_stats(h, src2):     # statistics came with the tensor (conv epilogue accumulators)
         a = ops.groupnorm_apply_acc(h, f32(norm.weight), f32(norm.bias), norm.eps, act, src2)
         return ops.conv(a, weight, bias, cout, **conv_kw)
     if ops.has_any_stats(h, src2):     # halo-tile producers: fold their sums instead of re-reading 17..805 MB per norm
         scale, shift = ops.groupnorm_scale_shift_acc(h, f32(norm.weight), f32(norm.bias), norm.eps, src2)
     else:
         scale, shift = ops.groupnorm_stats(h, f32(norm.weight), f32(norm.bias), norm.eps, src2)
+    if film is not None:
+        ops.film_fold(scale, shift, film, h.C)
     if fused:
         return ops.conv(h, weight, bias, cout, src2=src2, prologue=(scale, shift), prologue_silu=act, **conv_kw)
     a = ops.groupnorm_apply(h, scale, shift, act, src2)
@@ -163,11 +174,12 @@ class Upsample(nn.Module):
     def __init__(self, channels, use_conv, dims=2, out_channels=None):
         super().__init__()
         self.channels, self.out_channels, self.use_conv, self.dims = channels, out_channels or channels, use_conv, dims
-        if not use_conv:
-            raise NotImplementedError("Upsample without conv is not on the scoped path (conv_resample=True everywhere)")
-        self.conv = conv_nd(dims, channels, self.out_channels, 3, padding=1)
+        if use_conv:
+            self.conv = conv_nd(dims, channels, self.out_channels, 3, padding=1)
 
     def run(self, h: CL) -> CL:
+        if not self.use_conv:                # nearest x2 (D too for dims == 3, unet.py:104-110): the resample kernel
+            return ops.resample2x(h, True, self.dims == 3)
         pw, pb = packed_conv(self.conv, h.Cpad)
         return ops.conv(h, pw, pb, self.out_channels, k=_k3(self.conv.weight), stride=1, pad=1, upsample=True)
 
@@ -176,11 +188,15 @@ class Downsample(nn.Module):
     def __init__(self, channels, use_conv, dims=2, out_channels=None):
         super().__init__()
         self.channels, self.out_channels, self.use_conv, self.dims = channels, out_channels or channels, use_conv, dims
-        if not use_conv:
-            raise NotImplementedError("avg-pool Downsample is not on the scoped path (conv_resample=True everywhere)")
-        self.op = conv_nd(dims, channels, self.out_channels, 3, stride=2, padding=1)
+        if use_conv:
+            self.op = conv_nd(dims, channels, self.out_channels, 3, stride=2, padding=1)
+        else:
+            assert self.channels == self.out_channels
+            self.op = {1: nn.AvgPool1d, 2: nn.AvgPool2d, 3: nn.AvgPool3d}[dims](2, 2)     # parameter-free container, never called
 
     def run(self, h: CL) -> CL:
+        if not self.use_conv:                # 2x average pool (stride (2, 2, 2) for dims == 3): the resample kernel, no GroupNorm sums
+            return ops.resample2x(h, False, self.dims == 3)
         pw, pb = packed_conv(self.op, h.Cpad)
         # the output is a skip tensor: a decoder GroupNorm over cat[h, skip] takes its statistics from accumulators only if BOTH sources
         # carry them, so leave the sums behind also below ops.GN_ACC_MIN_ELEMS (the 16x16 x 320 tensor of the latent UNet: otherwise
@@ -191,17 +207,27 @@ class Downsample(nn.Module):
 
 class ResBlock(TimestepBlock):
     """GN+SiLU -> conv3 (+timestep bias) -> GN+SiLU -> conv3 (+skip).  The timestep projection
-    `emb_layers` is folded into conv1's per-sample bias (SURVEY.md 2.3 "timestep-embed epilogue")."""
+    `emb_layers` is folded into conv1's per-sample bias (SURVEY.md 2.3 "timestep-embed epilogue").
+    use_scale_shift_norm (FiLM): emb_layers gives per-sample rows [s | t] (2C) instead, conv1 keeps its own bias, and the out-norm is
+    GroupNorm(h) * (1 + s) + t through gg_film_fold on its per-(n, c) coefficients.  up / down (resblock_updown): GN+SiLU -> nearest x2
+    / 2x average pool -> conv1 on the h path, the same resampling of x as the residual (unet.py:238-245)."""
 
     def __init__(self, channels, emb_channels, dropout, out_channels=None, use_conv=False, use_scale_shift_norm=False,
                  dims=2, use_checkpoint=False, up=False, down=False):
         super().__init__()
-        if use_scale_shift_norm or up or down:
-            raise NotImplementedError("use_scale_shift_norm / resblock_updown are not used by any shipped config")
         self.channels, self.emb_channels = channels, emb_channels
         self.out_channels = out_channels or channels
+        self.use_scale_shift_norm, self.dims = use_scale_shift_norm, dims
         self.in_layers = nn.Sequential(normalization(channels), nn.SiLU(), conv_nd(dims, channels, self.out_channels, 3, padding=1))
-        self.emb_layers = nn.Sequential(nn.SiLU(), nn.Linear(emb_channels, self.out_channels))
+        self.updown = up or down
+        if up:
+            self.h_upd, self.x_upd = Upsample(channels, False, dims), Upsample(channels, False, dims)
+        elif down:
+            self.h_upd, self.x_upd = Downsample(channels, False, dims), Downsample(channels, False, dims)
+        else:
+            self.h_upd = self.x_upd = nn.Identity()
+        self.up, self.down = up, down
+        self.emb_layers = nn.Sequential(nn.SiLU(), nn.Linear(emb_channels, 2 * self.out_channels if use_scale_shift_norm else self.out_channels))
         self.out_layers = nn.Sequential(normalization(self.out_channels), nn.SiLU(), nn.Dropout(p=dropout),
                                         zero_module(conv_nd(dims, self.out_channels, self.out_channels, 3, padding=1)))
         if self.out_channels == channels:
@@ -211,15 +237,25 @@ class ResBlock(TimestepBlock):
         else:
             self.skip_connection = conv_nd(dims, channels, self.out_channels, 1)
 
+    @property
+    def time_bias_width(self) -> int:
+        """fp32 columns per sample of this block's time-bias row: Cout_pad, or 2 * Cout_pad of FiLM rows [s | t] (s, t at 0 and Cout)."""
+        return pad32(self.out_channels) * (2 if self.use_scale_shift_norm else 1)
+
     def time_bias(self, emb: torch.Tensor, out: torch.Tensor) -> None:
-        """out[M, Cout_pad] = conv1.bias + Linear(SiLU(emb))  (unet.py:251-260)."""
+        """out[M, Cout_pad] = conv1.bias + Linear(SiLU(emb))  (unet.py:251-260); FiLM: out[M, 2 Cout_pad] = Linear(SiLU(emb)) = [s | t]."""
         lin, c1 = self.emb_layers[1], self.in_layers[2]
+        if self.use_scale_shift_norm:
+            ops.linear_f32(emb, f32(lin.weight), f32(lin.bias), act_in=True, out=out)
+            return
         b = PACKED.get((id(self), "tb"), [lin.bias, c1.bias], lambda: (f32(lin.bias) + f32(c1.bias)))
         ops.linear_f32(emb, f32(lin.weight), b, act_in=True, out=out)
 
     def run(self, h: CL, tbias: torch.Tensor, src2: Optional[CL] = None, want_stats: bool = False) -> CL:
         """want_stats: the consumer of this block's output folds GroupNorm sums itself (an AttentionBlock's norm in front of its box-kernel
         qkv conv, or a tiny-image ResBlock): conv2 leaves them even for tensors below ops.GN_ACC_MIN_ELEMS."""
+        if self.use_scale_shift_norm or self.updown:
+            return self._run_options(h, tbias, src2, want_stats)
         c1, c2 = self.in_layers[2], self.out_layers[3]
         k = _k3(c1.weight)
         cin_pad = h.Cpad + (src2.Cpad if src2 is not None else 0)
@@ -244,14 +280,53 @@ class ResBlock(TimestepBlock):
         assert h1.Cpad == pad32(self.out_channels)
         return norm_conv(h1, self.out_layers[0], True, pw2, pb2, self.out_channels, k=k, residual=res, want_stats=want_stats, **skip_kw)
 
+    def _run_options(self, h: CL, tbias: torch.Tensor, src2: Optional[CL], want_stats: bool) -> CL:
+        """The same block with use_scale_shift_norm and / or up / down (unet.py:238-259)."""
+        c1, c2, n1 = self.in_layers[2], self.out_layers[3], self.in_layers[0]
+        k = _k3(c1.weight)
+        cout = self.out_channels
+        cin_pad = h.Cpad + (src2.Cpad if src2 is not None else 0)
+        film = tbias.view(h.N, -1) if self.use_scale_shift_norm else None     # per-sample rows [s | t]
+        pw1, pb1 = packed_conv(c1, cin_pad)
+        b1, b1_ps = (pb1, False) if film is not None else (tbias, True)       # FiLM: conv1 keeps its own bias
+        pw2, pb2 = packed_conv(c2, pad32(cout))
+        x = h
+        if self.updown:
+            if src2 is not None:
+                raise RuntimeError("an up / down ResBlock takes no skip concat")
+            x = self.x_upd.run(h)                                             # residual source: x_upd(x)
+            if self.up:
+                # nearest x2 commutes with the pointwise GN+SiLU: normalise at low resolution, conv1 upsamples while it gathers
+                h1 = norm_conv(h, n1, True, pw1, b1, cout, k=k, upsample=True, bias_per_sample=b1_ps)
+            else:
+                # avgpool(SiLU(GN(h))) in one resample launch from the per-(n, c) coefficients, then conv1
+                if ops.is_f32(h.t):
+                    a = ops.resample2x(ops.groupnorm_f32(h, f32(n1.weight), f32(n1.bias), n1.eps, True), False, self.dims == 3)
+                else:
+                    if ops.has_any_stats(h):
+                        sc, sh = ops.groupnorm_scale_shift_acc(h, f32(n1.weight), f32(n1.bias), n1.eps)
+                    else:
+                        sc, sh = ops.groupnorm_stats(h, f32(n1.weight), f32(n1.bias), n1.eps)
+                    a = ops.resample2x(h, False, self.dims == 3, prologue=(sc, sh), act=True)
+                h1 = ops.conv(a, pw1, b1, cout, k=k, pad=1, bias_per_sample=b1_ps)
+        else:
+            h1 = norm_conv(h, n1, True, pw1, b1, cout, src2=src2, k=k, bias_per_sample=b1_ps)
+        sk = self.skip_connection
+        if isinstance(sk, nn.Identity):
+            res = x
+        else:
+            pws, pbs = packed_conv(sk, cin_pad)
+            ks = _k3(sk.weight)
+            res = ops.conv(x, pws, pbs, cout, k=ks, pad=ks[-1] // 2, src2=src2 if not self.updown else None)
+        return norm_conv(h1, self.out_layers[0], True, pw2, pb2, cout, k=k, residual=res, want_stats=want_stats, film=film)
+
 
 class AttentionBlock(nn.Module):
     """GN -> qkv 1x1 -> QKVAttentionLegacy -> proj 1x1 + x, with flash attention tiles (no TxT buffer)."""
 
     def __init__(self, channels, num_heads=1, num_head_channels=-1, use_checkpoint=False, use_new_attention_order=False):
         super().__init__()
-        if use_new_attention_order:
-            raise NotImplementedError("use_new_attention_order is not used by any shipped config")
+        self.new_order = use_new_attention_order
         self.channels = channels
         if num_head_channels == -1:
             self.num_heads = num_heads
@@ -268,11 +343,16 @@ class AttentionBlock(nn.Module):
         ch = Cc // nh
         N, T = h.N, h.S
         pw, pb = packed_conv(self.qkv, h.Cpad)
-        qkv = norm_conv(h, self.norm, False, pw, pb, 3 * Cc, k=(1, 1, 1), pad=0)   # legacy order: head-major, q|k|v per head
+        qkv = norm_conv(h, self.norm, False, pw, pb, 3 * Cc, k=(1, 1, 1), pad=0)
         att = torch.empty(tuple(h.t.shape[:4]) + (Cc,), dtype=h.t.dtype, device=h.t.device)
         ld = qkv.Cpad
-        ops.attention(qkv.t, qkv.t, qkv.t, att, N, nh, ch, T, T, (ld, 3 * ch), (ld, 3 * ch), (ld, 3 * ch), (Cc, ch),
-                      1.0 / math.sqrt(ch), q_off=0, k_off=ch, v_off=2 * ch)
+        # (q ch^-1/4)(k ch^-1/4) == scale 1/sqrt(ch) on q k^T in both orders (unet.py:352-354,379-385)
+        if self.new_order:          # QKVAttention: q | k | v blocks of C channels first, then heads of ch inside each block
+            ops.attention(qkv.t, qkv.t, qkv.t, att, N, nh, ch, T, T, (ld, ch), (ld, ch), (ld, ch), (Cc, ch),
+                          1.0 / math.sqrt(ch), q_off=0, k_off=Cc, v_off=2 * Cc)
+        else:                       # legacy order: head-major, q|k|v per head
+            ops.attention(qkv.t, qkv.t, qkv.t, att, N, nh, ch, T, T, (ld, 3 * ch), (ld, 3 * ch), (ld, 3 * ch), (Cc, ch),
+                          1.0 / math.sqrt(ch), q_off=0, k_off=ch, v_off=2 * ch)
         pw2, pb2 = packed_conv(self.proj_out, Cc)
         return ops.conv(CL(att, Cc), pw2, pb2, Cc, k=(1, 1, 1), pad=0, residual=h)
 

@@ -8,6 +8,7 @@
 //   conv_f32_kernel       nn.Conv{1,2,3}d (stride 1 / 2, zero padding 1 or AE (0,1), fused nearest x2 upsample, skip concat as a second
 //                         source, per-sample bias = conv bias + timestep embedding, residual add)   unet.py:188-228,106-139
 //   gn_f32_stats / apply  GroupNorm32 (+ SiLU): statistics in fp64, (x - mean) * rstd * gamma + beta in fp32 as ATen evaluates it
+//   gn_f32_apply_film     the same, then the ResBlock's FiLM term * (1 + s) + t (use_scale_shift_norm)   unet.py:254-257
 //                         nn.py:17-19,93-100
 //   attn_f32_kernel       QKVAttentionLegacy: softmax((q * s)(k * s)^T) v with s = ch^-1/4, fp32   unet.py:334-360
 #include "gg_common.h"
@@ -211,6 +212,56 @@ extern "C" int gg_groupnorm_f32(const float *src1, int32_t C1, const float *src2
     if (blocks > 16384) blocks = 16384;
     hipLaunchKernelGGL(gn_f32_apply_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, src1, C1, src2, C2, (long long)S, C_logical, gamma, beta,
                        (const float *)mean, (const float *)rstd, act, out, total);
+    GG_CHECK_LAUNCH();
+    return GG_OK;
+}
+
+// The ResBlock's out-norm under use_scale_shift_norm (unet.py:254-257): out_norm(h) * (1 + s) + t with the per-sample FiLM row
+// film[n] = [s (C) | t (C)], then SiLU -- every step rounded to fp32 in the reference's order (not folded into the coefficients).
+__global__ __launch_bounds__(256) void gn_f32_apply_film_kernel(const float *__restrict__ s1, int C1, long long S, int C_logical,
+                                                                const float *__restrict__ gamma, const float *__restrict__ beta,
+                                                                const float *__restrict__ mean, const float *__restrict__ rstd,
+                                                                const float *__restrict__ film, long long film_stride, int act,
+                                                                float *__restrict__ out, long long total)
+{
+    const int cpg = C_logical / 32;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const long long row = i / C1;
+        const int c = (int)(i - row * C1);
+        float y = 0.f;
+        if (c < C_logical) {
+            const int n = (int)(row / S), g = c / cpg;
+            const float *f = film + n * film_stride;
+            {
+#pragma clang fp contract(off)
+                y = (s1[i] - mean[n * 32 + g]) * rstd[n * 32 + g];
+                y = y * gamma[c] + beta[c];
+                y = y * (1.0f + f[c]) + f[C_logical + c];
+            }
+            if (act) y = y / (1.0f + expf(-y));
+        }
+        out[i] = y;
+    }
+}
+
+extern "C" int gg_groupnorm_f32_film(const float *src, int32_t C_pad, int32_t N, int64_t S, int32_t C_logical, const float *gamma,
+                                     const float *beta, float eps, const float *film, int64_t film_stride, int32_t act, float *out,
+                                     float *workspace, void *stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    if (C_pad <= 0 || C_pad % 32) GG_FAIL(GG_ERR_BAD_SHAPE, "groupnorm_f32_film: C_pad must be a multiple of 32");
+    if (C_logical <= 0 || C_logical % 32 || C_logical > C_pad) GG_FAIL(GG_ERR_BAD_SHAPE, "groupnorm_f32_film: logical channels %d not divisible into 32 groups", C_logical);
+    if (film_stride < 2LL * C_logical) GG_FAIL(GG_ERR_BAD_SHAPE, "groupnorm_f32_film: film row stride %lld < 2 * %d", (long long)film_stride, C_logical);
+    if (!src || !gamma || !beta || !film || !out || !workspace || N <= 0 || S <= 0) GG_FAIL(GG_ERR_BAD_SHAPE, "groupnorm_f32_film: null pointer / empty");
+    float *mean = workspace, *rstd = workspace + (size_t)N * 32;
+    hipLaunchKernelGGL(gn_f32_stats_kernel, dim3(32, (unsigned)N), dim3(256), 0, stream, src, C_pad, (const float *)nullptr, 0, (long long)S, C_logical,
+                       eps, mean, rstd);
+    GG_CHECK_LAUNCH();
+    const long long total = (long long)N * S * C_pad;
+    long long blocks = (total + 255) / 256;
+    if (blocks > 16384) blocks = 16384;
+    hipLaunchKernelGGL(gn_f32_apply_film_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, src, C_pad, (long long)S, C_logical, gamma, beta,
+                       (const float *)mean, (const float *)rstd, film, (long long)film_stride, act, out, total);
     GG_CHECK_LAUNCH();
     return GG_OK;
 }

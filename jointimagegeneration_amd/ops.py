@@ -527,6 +527,49 @@ def groupnorm_f32(src1: CL, gamma: torch.Tensor, beta: torch.Tensor, eps: float,
     return CL(out, c_log)
 
 
+def groupnorm_f32_film(src: CL, gamma: torch.Tensor, beta: torch.Tensor, eps: float, film: torch.Tensor, act: bool) -> CL:
+    """fp32 validation path of a FiLM out-norm: act(GroupNorm(32)(src) * (1 + s) + t) in the reference's order, with s = film[n, :C] and
+    t = film[n, C:2C] (film fp32 [N, >= 2C], row-strided)."""
+    lib = _lib.load()
+    N, S = src.N, src.S
+    _check_film(film, N, src.C)
+    out = torch.empty_like(src.t)
+    ws = torch.empty(64 * N, dtype=torch.float32, device=src.t.device)
+    check(lib.gg_groupnorm_f32_film(src.t.data_ptr(), src.Cpad, N, S, src.C, gamma.data_ptr(), beta.data_ptr(), eps, film.data_ptr(),
+                                    film.stride(0), 1 if act else 0, out.data_ptr(), ws.data_ptr(), _stream()), "gg_groupnorm_f32_film")
+    return CL(out, src.C)
+
+
+def film_fold(scale: torch.Tensor, shift: torch.Tensor, film: torch.Tensor, C: int) -> None:
+    """In place: per-(n, c) GroupNorm coefficients [N, Ct] of a FiLM out-norm take the per-sample term *(1 + s) + t, s = film[n, :C],
+    t = film[n, C:2C] (gg_film_fold); channels >= C are left as they are."""
+    _check_film(film, scale.shape[0], C)
+    check(_lib.load().gg_film_fold(scale.data_ptr(), shift.data_ptr(), scale.stride(0), scale.shape[0], C, film.data_ptr(), film.stride(0),
+                                   _stream()), "gg_film_fold")
+
+
+def _check_film(film: torch.Tensor, N: int, C: int) -> None:
+    if film.dtype != torch.float32 or film.dim() != 2 or film.shape[0] != N or film.shape[1] < 2 * C or film.stride(1) != 1:
+        raise ValueError(f"film must be fp32 [{N}, >= {2 * C}] rows with unit column stride, got {tuple(film.shape)} {film.dtype}")
+
+
+def resample2x(src: CL, up: bool, resample_d: bool, prologue: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, act: bool = False) -> CL:
+    """Nearest x2 upsample (up) or 2x average pool of a channels-last tensor (bf16, or fp32 in validation mode): H and W, and D too if
+    resample_d.  prologue = per-(n, c) fp32 (scale, shift) [N, Cpad]: every input element becomes act(x * scale + shift) first (the h path
+    of a down ResBlock in one launch).  The output carries no GroupNorm accumulators."""
+    lib = _lib.load()
+    N, D, H, W, cp = src.t.shape
+    Do = (D * 2 if up else D // 2) if resample_d else D
+    out = torch.empty((N, Do, H * 2 if up else H // 2, W * 2 if up else W // 2, cp), dtype=src.t.dtype, device=src.t.device)
+    if prologue is not None and tuple(prologue[0].shape) != (N, cp):
+        raise ValueError(f"resample2x: prologue coefficients must be [{N}, {cp}]")
+    check(lib.gg_resample2x(src.t.data_ptr(), GG_F32 if is_f32(src.t) else GG_BF16, N, D, H, W, cp, src.C, 1 if resample_d else 0,
+                            0 if up else 1, _ptr(prologue[0]) if prologue is not None else None,
+                            _ptr(prologue[1]) if prologue is not None else None, 1 if (act and prologue is not None) else 0,
+                            out.data_ptr(), _stream()), "gg_resample2x")
+    return CL(out, src.C)
+
+
 def groupnorm_apply_acc(src1: CL, gamma: torch.Tensor, beta: torch.Tensor, eps: float, act: bool, src2: Optional[CL] = None) -> CL:
     """act(GroupNorm(32)(cat[src1, src2])) with the statistics taken from the accumulators the producing convs left in CL.acc."""
     lib = _lib.load()

@@ -19,8 +19,13 @@ from .ops import CL, pad32
 
 
 def _layout(self, *, dims, in_channels, model_channels, out_channels, num_res_blocks, attention_resolutions, dropout,
-            channel_mult, conv_resample, num_heads, num_head_channels, num_heads_upsample, make_attention):
-    """Builds time_embed / input_blocks / middle_block / output_blocks with the reference's indices."""
+            channel_mult, conv_resample, num_heads, num_head_channels, num_heads_upsample, make_attention,
+            use_scale_shift_norm=False, resblock_updown=False):
+    """Builds time_embed / input_blocks / middle_block / output_blocks with the reference's indices.  resblock_updown: the steps between
+    levels are ResBlock(down=True) / ResBlock(up=True) instead of Downsample / Upsample; use_scale_shift_norm goes to every ResBlock."""
+    def resblock(cin, cout=None, **kw):
+        return ResBlock(cin, ted, dropout, out_channels=cout, dims=dims, use_scale_shift_norm=use_scale_shift_norm, **kw)
+
     ted = model_channels * 4
     self.time_embed = nn.Sequential(nn.Linear(model_channels, ted), nn.SiLU(), nn.Linear(ted, ted))
     ch = int(channel_mult[0] * model_channels)
@@ -31,28 +36,28 @@ def _layout(self, *, dims, in_channels, model_channels, out_channels, num_res_bl
     ds = 1
     for level, mult in enumerate(channel_mult):
         for _ in range(num_res_blocks):
-            layers = [ResBlock(ch, ted, dropout, out_channels=int(mult * model_channels), dims=dims)]
+            layers = [resblock(ch, int(mult * model_channels))]
             ch = int(mult * model_channels)
             if ds in attention_resolutions:
                 layers.append(make_attention(ch, num_heads))
             self.input_blocks.append(TimestepEmbedSequential(*layers))
             chans.append(ch)
         if level != len(channel_mult) - 1:
-            self.input_blocks.append(TimestepEmbedSequential(Downsample(ch, conv_resample, dims=dims, out_channels=ch)))
+            self.input_blocks.append(TimestepEmbedSequential(resblock(ch, ch, down=True) if resblock_updown else
+                                                             Downsample(ch, conv_resample, dims=dims, out_channels=ch)))
             chans.append(ch)
             ds *= 2
-    self.middle_block = TimestepEmbedSequential(ResBlock(ch, ted, dropout, dims=dims), make_attention(ch, num_heads),
-                                                ResBlock(ch, ted, dropout, dims=dims))
+    self.middle_block = TimestepEmbedSequential(resblock(ch), make_attention(ch, num_heads), resblock(ch))
     self.output_blocks = nn.ModuleList([])
     for level, mult in list(enumerate(channel_mult))[::-1]:
         for i in range(num_res_blocks + 1):
             ich = chans.pop()
-            layers = [ResBlock(ch + ich, ted, dropout, out_channels=int(model_channels * mult), dims=dims)]
+            layers = [resblock(ch + ich, int(model_channels * mult))]
             ch = int(model_channels * mult)
             if ds in attention_resolutions:
                 layers.append(make_attention(ch, num_heads_upsample))
             if level and i == num_res_blocks:
-                layers.append(Upsample(ch, conv_resample, dims=dims, out_channels=ch))
+                layers.append(resblock(ch, ch, up=True) if resblock_updown else Upsample(ch, conv_resample, dims=dims, out_channels=ch))
                 ds //= 2
             self.output_blocks.append(TimestepEmbedSequential(*layers))
     return ch
@@ -66,17 +71,18 @@ class _UNetBase(nn.Module):
         return [m for m in self.modules() if isinstance(m, ResBlock)]
 
     def time_bias_layout(self, N: int):
-        """offsets of every ResBlock's [N, Cout_pad] bias rows inside one flat fp32 row."""
+        """offsets of every ResBlock's [N, width] bias rows inside one flat fp32 row (width = ResBlock.time_bias_width: Cout_pad, or the
+        2 * Cout_pad of FiLM rows)."""
         off, lay = 0, {}
         for rb in self.resblocks():
-            cp = pad32(rb.out_channels)
+            cp = rb.time_bias_width
             lay[id(rb)] = (off, cp)
             off += N * cp
         return lay, off
 
     def time_bias_table(self, timesteps: torch.Tensor, N: int) -> torch.Tensor:
         """timesteps fp32 [S] -> table fp32 [S, total]: for every step the concatenated per-ResBlock biases
-        (conv1.bias + emb_layers(time_embed(sinusoid(t)))), identical for the N samples of a step."""
+        (conv1.bias + emb_layers(time_embed(sinusoid(t))), or the FiLM rows emb_layers(...)), identical for the N samples of a step."""
         S = timesteps.shape[0]
         lay, total = self.time_bias_layout(N)
         dev = timesteps.device
@@ -148,8 +154,7 @@ class CCDMUNetModel(_UNetBase):
                  feature_cond_encoder=None, use_spatial_transformer=False, transformer_depth=None, context_dim=None,
                  disabled_sa=False, use_linear_in_transformer=False):
         super().__init__()
-        if use_scale_shift_norm or resblock_updown or use_new_attention_order or ce_head or num_classes is not None \
-                or use_spatial_transformer:
+        if ce_head or num_classes is not None or use_spatial_transformer:
             raise NotImplementedError("option outside the shipped CCDM configuration (params_eval.yml:58-64)")
         # use_fp16 (unet.py:447,742-756: the reference casts the torso to half precision) is ACCEPTED and has no effect: this engine's
         # torso always runs on bf16 tensors with fp32 accumulation (ops.fp32_validation() is the switch to full precision)
@@ -167,12 +172,13 @@ class CCDMUNetModel(_UNetBase):
         self.feature_condition_idx = []
 
         def make_attention(ch, heads):
-            return AttentionBlock(ch, num_heads=heads, num_head_channels=num_head_channels)
+            return AttentionBlock(ch, num_heads=heads, num_head_channels=num_head_channels, use_new_attention_order=use_new_attention_order)
 
         ch = _layout(self, dims=dims, in_channels=in_channels, model_channels=model_channels, out_channels=out_channels,
                      num_res_blocks=num_res_blocks, attention_resolutions=attention_resolutions, dropout=dropout,
                      channel_mult=channel_mult, conv_resample=conv_resample, num_heads=num_heads,
-                     num_head_channels=num_head_channels, num_heads_upsample=num_heads_upsample, make_attention=make_attention)
+                     num_head_channels=num_head_channels, num_heads_upsample=num_heads_upsample, make_attention=make_attention,
+                     use_scale_shift_norm=use_scale_shift_norm, resblock_updown=resblock_updown)
         input_ch = int(channel_mult[0] * model_channels)
         head = [normalization(ch), nn.SiLU(), zero_module(conv_nd(dims, input_ch, out_channels, 3, padding=1))]
         if softmax_output:
@@ -252,7 +258,7 @@ class UNetModel(_UNetBase):
             assert num_head_channels != -1, "Either num_heads or num_head_channels has to be set"
         if num_head_channels == -1:
             assert num_heads != -1, "Either num_heads or num_head_channels has to be set"
-        if use_scale_shift_norm or resblock_updown or use_new_attention_order or num_classes is not None or n_embed is not None:
+        if num_classes is not None or n_embed is not None:
             raise NotImplementedError("option outside the shipped LDM configurations (configs/latent-diffusion/*.yaml)")
         self.image_size, self.in_channels, self.model_channels, self.out_channels = image_size, in_channels, model_channels, out_channels
         self.num_res_blocks, self.attention_resolutions, self.channel_mult = num_res_blocks, attention_resolutions, channel_mult
@@ -271,12 +277,14 @@ class UNetModel(_UNetBase):
                 dh = ch // nh if use_spatial_transformer else num_head_channels
             if use_spatial_transformer:
                 return SpatialTransformer(ch, nh, dh, depth=transformer_depth, context_dim=context_dim)
-            return AttentionBlock(ch, num_heads=nh if num_head_channels == -1 else heads, num_head_channels=dh)
+            return AttentionBlock(ch, num_heads=nh if num_head_channels == -1 else heads, num_head_channels=dh,
+                                  use_new_attention_order=use_new_attention_order)
 
         ch = _layout(self, dims=dims, in_channels=in_channels, model_channels=model_channels, out_channels=out_channels,
                      num_res_blocks=num_res_blocks, attention_resolutions=attention_resolutions, dropout=dropout,
                      channel_mult=channel_mult, conv_resample=conv_resample, num_heads=num_heads,
-                     num_head_channels=num_head_channels, num_heads_upsample=num_heads_upsample, make_attention=make_attention)
+                     num_head_channels=num_head_channels, num_heads_upsample=num_heads_upsample, make_attention=make_attention,
+                     use_scale_shift_norm=use_scale_shift_norm, resblock_updown=resblock_updown)
         self.out = nn.Sequential(normalization(ch), nn.SiLU(), zero_module(conv_nd(dims, model_channels, out_channels, 3, padding=1)))
 
     def context_cl(self, context: Optional[torch.Tensor]) -> Optional[CL]:
