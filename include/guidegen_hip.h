@@ -328,6 +328,17 @@ int gg_ddim_step(float *x, const float *eps, int32_t eps_stride, const float *no
 int gg_ddpm_step(float *x, const float *eps, int32_t eps_stride, const float *noise, const float *scalars_dev, int64_t M, int32_t C,
                  void *unet_in, int32_t unet_in_stride, void *stream);
 
+/* Inpainting blend of the LDM samplers (ddim.py:144-148, plms.py:147-150, ddpm.py:1212-1214), fp32 elementwise on CL rows [M, C]:
+ *   x <- (s[0]*x0 + s[1]*noise) * mask + (1 - mask) * x      (the q_sample of ddpm.py:275-278, then the blend; mask 1 keeps x0)
+ *   evaluated without contraction in the reference's order: t1 = s0*x0; t2 = s1*n; o = t1 + t2; p = o*m; q = (1 - m)*x; x = p + q.
+ *   scalars device fp32[2] = {sqrt_alphas_cumprod[t], sqrt_one_minus_alphas_cumprod[t]} (a captured chain reads its row in place).
+ *   x, x0, noise fp32 [M, C]; mask fp32 [M, mask_C] with mask_C 1 (broadcast over channels) or C; otherwise GG_ERR_BAD_SHAPE, as for
+ *   NULL operands or unet_in_stride < C.  unet_in optional bf16 CL [M, unet_in_stride]: channels [0, C) are refreshed with bf16(x), the
+ *   pad lanes are not touched.  C == 4 with 16-byte aligned rows (8-byte unet_in rows) runs one row per lane; any other case a
+ *   grid-stride loop per element.  No allocation, no synchronisation. */
+int gg_inpaint_blend(float *x, const float *x0, const float *mask, int32_t mask_C, const float *noise, const float *scalars_dev,
+                     int64_t M, int32_t C, void *unet_in, int32_t unet_in_stride, void *stream);
+
 /* PLMS multistep combination of noise estimates (ldm/models/diffusion/plms.py:218-232), fp32, evaluated left to right:
  *   out = (c0*e0 + c1*e1 + c2*e2 + c3*e3) / denom ; e1..e3 may be NULL (skipped). */
 int gg_lincomb4(const float *e0, const float *e1, const float *e2, const float *e3, float c0, float c1, float c2, float c3,

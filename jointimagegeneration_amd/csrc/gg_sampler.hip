@@ -200,6 +200,97 @@ extern "C" int gg_ddpm_step(float *x, const float *eps, int32_t eps_stride, cons
 }
 
 // ------------------------------------------------------------------------------------------------------------
+// Inpainting blend (ddim.py:144-148, plms.py:147-150, ddpm.py:1212-1214), fp32, the reference's operation order:
+//   o = s[0]*x0 + s[1]*noise  (q_sample, ddpm.py:275-278) ;  x <- o*mask + (1 - mask)*x
+// scalars device fp32[2] = {sqrt_alphas_cumprod[t], sqrt_one_minus_alphas_cumprod[t]}; mask has 1 or C channels.
+// ------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float inpaint_blend_one(float xv, float x0v, float nv, float mv, float a, float b)
+{
+#pragma clang fp contract(off)
+    const float t1 = a * x0v;
+    const float t2 = b * nv;
+    const float o = t1 + t2;
+    const float p = o * mv;
+    const float q = (1.0f - mv) * xv;
+    return p + q;
+}
+
+// C == 4 (the latent channels of every shipped config): one row per lane, 16-byte loads of x / x0 / noise (and of a 4-channel mask),
+// one 8-byte bf16x4 store into the UNet input.  The host checks the alignment these accesses need.
+template <int MC>
+__global__ __launch_bounds__(256) void inpaint_blend_c4_kernel(float *__restrict__ x, const float *__restrict__ x0,
+                                                               const float *__restrict__ mask, const float *__restrict__ noise,
+                                                               const float *__restrict__ sc, long long M, bf16_t *__restrict__ unet_in,
+                                                               int unet_in_stride)
+{
+    const float a = sc[0], b = sc[1];
+    for (long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x; m < M; m += (long long)gridDim.x * blockDim.x) {
+        const f32x4 xv = *reinterpret_cast<const f32x4 *>(x + m * 4);
+        const f32x4 x0v = *reinterpret_cast<const f32x4 *>(x0 + m * 4);
+        const f32x4 nv = *reinterpret_cast<const f32x4 *>(noise + m * 4);
+        f32x4 mv;
+        if constexpr (MC == 4) {
+            mv = *reinterpret_cast<const f32x4 *>(mask + m * 4);
+        } else {
+            const float m1 = mask[m];
+            mv = f32x4{m1, m1, m1, m1};
+        }
+        f32x4 r;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) r[c] = inpaint_blend_one(xv[c], x0v[c], nv[c], mv[c], a, b);
+        *reinterpret_cast<f32x4 *>(x + m * 4) = r;
+        if (unet_in) {
+            bf16x4 o;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) o[c] = (bf16_t)r[c];
+            *reinterpret_cast<bf16x4 *>(unet_in + m * unet_in_stride) = o;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void inpaint_blend_kernel(float *__restrict__ x, const float *__restrict__ x0, const float *__restrict__ mask,
+                                                            int mask_C, const float *__restrict__ noise, const float *__restrict__ sc,
+                                                            long long M, int C, bf16_t *__restrict__ unet_in, int unet_in_stride)
+{
+    const float a = sc[0], b = sc[1];
+    const long long total = M * C;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const long long m = i / C;
+        const int c = (int)(i - m * C);
+        const float r = inpaint_blend_one(x[i], x0[i], noise[i], mask[m * mask_C + (mask_C == 1 ? 0 : c)], a, b);
+        x[i] = r;
+        if (unet_in) unet_in[m * unet_in_stride + c] = (bf16_t)r;
+    }
+}
+
+extern "C" int gg_inpaint_blend(float *x, const float *x0, const float *mask, int32_t mask_C, const float *noise, const float *scalars_dev,
+                                int64_t M, int32_t C, void *unet_in, int32_t unet_in_stride, void *stream_)
+{
+    if (!x || !x0 || !mask || !noise || !scalars_dev) GG_FAIL(GG_ERR_BAD_SHAPE, "inpaint_blend: null pointer");
+    if (C <= 0 || (mask_C != 1 && mask_C != C)) GG_FAIL(GG_ERR_BAD_SHAPE, "inpaint_blend: mask_C=%d must be 1 or C=%d", mask_C, C);
+    if (unet_in && unet_in_stride < C) GG_FAIL(GG_ERR_BAD_SHAPE, "inpaint_blend: unet_in_stride %d < C=%d", unet_in_stride, C);
+    if (M <= 0) return GG_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    const auto al = [](const void *p, uintptr_t n) { return ((uintptr_t)p & (n - 1)) == 0; };
+    const bool vec = C == 4 && al(x, 16) && al(x0, 16) && al(noise, 16) && (mask_C == 1 || al(mask, 16)) &&
+                     (!unet_in || (al(unet_in, 8) && unet_in_stride % 4 == 0));
+    const long long work = vec ? (long long)M : (long long)M * C;
+    long long blocks = (work + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    if (vec && mask_C == 4)
+        hipLaunchKernelGGL(inpaint_blend_c4_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, stream, x, x0, mask, noise, scalars_dev,
+                           (long long)M, (bf16_t *)unet_in, unet_in_stride);
+    else if (vec)
+        hipLaunchKernelGGL(inpaint_blend_c4_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, stream, x, x0, mask, noise, scalars_dev,
+                           (long long)M, (bf16_t *)unet_in, unet_in_stride);
+    else
+        hipLaunchKernelGGL(inpaint_blend_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, x, x0, mask, mask_C, noise, scalars_dev,
+                           (long long)M, C, (bf16_t *)unet_in, unet_in_stride);
+    GG_CHECK_LAUNCH();
+    return GG_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------
 // PLMS noise-estimate combination (ldm/models/diffusion/plms.py:218-232), fp32, same left-to-right order as the reference
 // expression:  out = (c0*e0 + c1*e1 + c2*e2 + c3*e3) / denom   (terms with a NULL pointer are skipped)
 // ------------------------------------------------------------------------------------------------------------

@@ -386,6 +386,25 @@ class LatentDiffusion(nn.Module):
             return z
         return self.first_stage_model.decode(1.0 / self.scale_factor * z)
 
+    @torch.no_grad()
+    def encode_first_stage(self, x):
+        """first_stage_model.encode(x): the reference's path without `split_input_params` (ddpm.py:839-893), which is refused."""
+        if hasattr(self, "split_input_params"):
+            raise NotImplementedError("encode_first_stage: split_input_params (the patch-wise fold/unfold path) is not supported")
+        if self.no_first_stage:
+            return x
+        return self.first_stage_model.encode(x)
+
+    def get_first_stage_encoding(self, encoder_posterior):
+        """scale_factor * (posterior sample | tensor) (ddpm.py:551-558)."""
+        if isinstance(encoder_posterior, DiagonalGaussianDistribution):
+            z = encoder_posterior.sample()
+        elif isinstance(encoder_posterior, torch.Tensor):
+            z = encoder_posterior
+        else:
+            raise NotImplementedError(f"encoder_posterior of type '{type(encoder_posterior)}' not yet implemented")
+        return self.scale_factor * z
+
     def apply_model(self, x_noisy, t, cond, return_ids=False):
         if not isinstance(cond, dict):
             if not isinstance(cond, list):
@@ -397,11 +416,16 @@ class LatentDiffusion(nn.Module):
     @torch.no_grad()
     def p_sample_loop(self, cond, shape, return_intermediates=False, x_T=None, verbose=True, callback=None, timesteps=None,
                       quantize_denoised=False, mask=None, x0=None, img_callback=None, start_T=None, log_every_t=None,
-                      noise_tape=None):
+                      noise_tape=None, mask_noise_tape=None):
         """Vanilla ancestral sampling over all `num_timesteps` (ddpm.py:1179-1227 + p_sample :1092-1120), channels-last on the
-        GPU: per step one UNet forward + one fused `gg_ddpm_step`.  clip_denoised is False for LatentDiffusion (ddpm.py:477)."""
-        if mask is not None or quantize_denoised:
-            raise NotImplementedError("inpainting / quantised denoising are not on the scoped path")
+        GPU: per step one UNet forward + one fused `gg_ddpm_step`.  clip_denoised is False for LatentDiffusion (ddpm.py:477).
+        Inpainting (mask=, x0=; ddpm.py:1201-1218): after each step at timestep t one `gg_inpaint_blend`,
+        x <- q_sample(x0, t) * mask + (1 - mask) * x, so the known region of the result is q_sample(x0, 0).  `mask_noise_tape`
+        (this package's addition, like `noise_tape`): T tensors [N, C, *sp], the q_sample noise of each step; without it every step
+        draws a fresh device `randn`, which matches the reference's `randn_like` in distribution, not in stream (that stream is CPU
+        torch's).  `noise_tape` / `mask_noise_tape` exist so that tests can feed the reference's draws."""
+        if quantize_denoised:
+            raise NotImplementedError("p_sample_loop: quantize_denoised is not supported (it needs a VQ first stage)")
         dev = self.device
         unet = self.model.diffusion_model
         ck = self.model.conditioning_key
@@ -412,6 +436,10 @@ class LatentDiffusion(nn.Module):
         T = self.num_timesteps if timesteps is None else timesteps
         if start_T is not None:
             T = min(T, start_T)
+        if mask is not None and x0 is not None and tuple(x0.shape[2:3]) != tuple(mask.shape[2:3]):
+            raise ValueError(f"p_sample_loop: x0 {tuple(x0.shape)} and mask {tuple(mask.shape)} differ in spatial size "
+                             "(ddpm.py:1200 asserts x0.shape[2:3] == mask.shape[2:3])")
+        ip = inpaint_operands(mask, x0, shape, mask_noise_tape, T)
         c_concat = cond if (cond is not None and ck == "concat" and not isinstance(cond, dict)) else \
             (cond.get("c_concat", [None])[0] if isinstance(cond, dict) else None)
         context = cond if (cond is not None and ck == "crossattn" and not isinstance(cond, dict)) else None
@@ -432,6 +460,10 @@ class LatentDiffusion(nn.Module):
         eps = torch.empty((N,) + sp3 + (pad32(unet.out_channels),), dtype=torch.float32, device=dev)
         M = x.numel() // Cx
         xin = CL(unet_in, Cx + Cc)
+        if ip is not None:
+            x0_cl = ip[0].to(dev).permute(perm).contiguous()
+            mask_cl = ip[1].to(dev).permute(perm).contiguous()
+            qscal = torch.stack([self.sqrt_alphas_cumprod[ts], self.sqrt_one_minus_alphas_cumprod[ts]], 1).contiguous()
         for i in range(T):
             unet.forward_cl(xin, table[i], ctx_cl, head_out=eps)
             if noise_tape is not None:
@@ -439,13 +471,76 @@ class LatentDiffusion(nn.Module):
             else:
                 nz = torch.randn_like(x)
             ops.ddpm_step(x.view(M, Cx), eps.view(M, -1), scal[i], noise=nz.view(M, Cx), unet_in=unet_in.view(M, -1))
+            if ip is not None:
+                nm = mask_noise_tape[i].to(dev).float().permute(perm).contiguous() if mask_noise_tape is not None else torch.randn_like(x)
+                ops.inpaint_blend(x.view(M, Cx), x0_cl.view(M, Cx), mask_cl.view(M, -1), nm.view(M, Cx), qscal[i], unet_in=unet_in.view(M, -1))
         out = x.view((N,) + sp + (Cx,)).permute((0, nd + 1) + tuple(range(1, nd + 1))).contiguous()
         return (out, [img, out]) if return_intermediates else out
+
+    @torch.no_grad()
+    def sample(self, cond, batch_size=16, return_intermediates=False, x_T=None, verbose=True, timesteps=None, quantize_denoised=False,
+               mask=None, x0=None, shape=None, noise_tape=None, mask_noise_tape=None, **kwargs):
+        """Ancestral sampling of `batch_size` samples (ddpm.py:1231-1245): the conditioning is cut to the batch, then p_sample_loop.
+        Default shape: (batch_size, channels) + (image_size,) * dims -- the reference writes `(self.channels,) * self.dims` for the
+        spatial extent there, which no caller of this package reaches with a meaningful result."""
+        if shape is None:
+            shape = (batch_size, self.channels) + (self.image_size if isinstance(self.image_size, tuple) else (self.image_size,) * self.dims)
+        if cond is not None:
+            if isinstance(cond, dict):
+                cond = {key: cond[key][:batch_size] if not isinstance(cond[key], list) else [c[:batch_size] for c in cond[key]] for key in cond}
+            else:
+                cond = [c[:batch_size] for c in cond] if isinstance(cond, list) else cond[:batch_size]
+        return self.p_sample_loop(cond, shape, return_intermediates=return_intermediates, x_T=x_T, verbose=verbose, timesteps=timesteps,
+                                  quantize_denoised=quantize_denoised, mask=mask, x0=x0, noise_tape=noise_tape, mask_noise_tape=mask_noise_tape)
+
+    @torch.no_grad()
+    def sample_log(self, cond, batch_size, ddim, ddim_steps, **kwargs):
+        """DDIM (ddim=True) or ancestral sampling of `batch_size` samples (ddpm.py:1248-1260); kwargs such as mask= / x0= / eta= go through."""
+        if ddim:
+            sampler = DDIMSampler(self)
+            shape = (self.channels,) + (self.image_size if isinstance(self.image_size, tuple) else (self.image_size,) * self.dims)
+            return sampler.sample(ddim_steps, batch_size, shape, cond, verbose=False, **kwargs)
+        return self.sample(cond=cond, batch_size=batch_size, return_intermediates=True, **kwargs)
 
     def q_sample(self, x_start, t, noise=None):
         noise = torch.randn_like(x_start) if noise is None else noise
         sh = (-1,) + (1,) * (x_start.ndim - 1)
         return self.sqrt_alphas_cumprod[t].reshape(sh) * x_start + self.sqrt_one_minus_alphas_cumprod[t].reshape(sh) * noise
+
+
+def inpaint_operands(mask, x0, shape, tape=None, steps=0):
+    """Host-side validation of the inpainting operands of the samplers (ddim.py:144-148, plms.py:147-150, ddpm.py:1201-1218), run
+    before any launch.  Returns None without a mask (x0 alone is ignored, as in the reference); else (x0 fp32 [N, C, *sp],
+    mask fp32 [N, Cm, *sp], Cm) as broadcast views, Cm = the mask's channel extent (1 or C).  Bool / integer masks are cast to fp32.
+    `tape` (optional): at least `steps` q_sample noises of shape [N, C, *sp].  Anything else raises ValueError naming the shapes."""
+    if mask is None:
+        return None
+    if x0 is None:
+        raise ValueError("inpainting: mask= was given without x0= (the latent whose mask = 1 region is kept)")
+    if not isinstance(mask, torch.Tensor) or not isinstance(x0, torch.Tensor):
+        raise ValueError(f"inpainting: mask and x0 must be tensors, got {type(mask).__name__} and {type(x0).__name__}")
+    full = tuple(int(s) for s in shape)
+    N, C = full[:2]
+
+    def fits(t):
+        try:
+            return tuple(torch.broadcast_shapes(tuple(t.shape), full)) == full
+        except RuntimeError:
+            return False
+    if x0.is_complex() or not fits(x0):
+        raise ValueError(f"inpainting: x0 of shape {tuple(x0.shape)} ({x0.dtype}) does not broadcast to the latent shape {full}")
+    if mask.is_complex() or not fits(mask):
+        raise ValueError(f"inpainting: mask of shape {tuple(mask.shape)} ({mask.dtype}) does not broadcast to the latent shape {full}")
+    ch = mask.ndim - (len(full) - 1)                  # the mask's channel axis once right-aligned against [N, C, *sp]
+    Cm = int(mask.shape[ch]) if ch >= 0 else 1
+    m = mask.float().reshape((1,) * (len(full) - mask.ndim) + tuple(mask.shape)).expand((N, Cm) + full[2:])
+    if tape is not None:
+        if len(tape) < steps:
+            raise ValueError(f"inpainting: mask_noise_tape holds {len(tape)} tensors, the schedule has {steps} steps")
+        for i in range(steps):
+            if tuple(tape[i].shape) != full:
+                raise ValueError(f"inpainting: mask_noise_tape[{i}] has shape {tuple(tape[i].shape)}, the latent is {full}")
+    return x0.float().expand(full), m, Cm
 
 
 # ================================================================================================ DDIM
@@ -504,24 +599,42 @@ class DDIMSampler(object):
                          float(self.ddim_sqrt_one_minus_alphas[idx])])
         return torch.tensor(rows, dtype=torch.float32)
 
+    def q_sample_scalar_table(self) -> torch.Tensor:
+        """fp32 [S, 2] rows (sqrt_alphas_cumprod[t], sqrt_one_minus_alphas_cumprod[t]) in SAMPLING order, t = flip(ddim_timesteps)[i]:
+        the model's own fp32 buffers, as the reference's q_sample reads them (ddpm.py:275-278), not values recomputed from ddim_alphas."""
+        ts = torch.as_tensor(np.flip(self.ddim_timesteps).copy(), dtype=torch.long)
+        sa = self.model.sqrt_alphas_cumprod.detach().cpu()
+        s1 = self.model.sqrt_one_minus_alphas_cumprod.detach().cpu()
+        return torch.stack([sa[ts], s1[ts]], 1).float().contiguous()
+
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
                quantize_x0=False, eta=0.0, mask=None, x0=None, temperature=1.0, noise_dropout=0.0, score_corrector=None,
                corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.0,
-               unconditional_conditioning=None, noise_tape: Optional[Sequence[torch.Tensor]] = None, ddim_discretize="uniform", **kwargs):
+               unconditional_conditioning=None, noise_tape: Optional[Sequence[torch.Tensor]] = None, ddim_discretize="uniform",
+               mask_noise_tape: Optional[Sequence[torch.Tensor]] = None, **kwargs):
         """`ddim_discretize` ("uniform" | "quad": make_schedule's argument, ddim.py:24) is this package's addition to the signature: the
         reference's sample() always builds the uniform schedule and reaches "quad" only through make_schedule + ddim_sampling.
-        Classifier-free guidance (ddim.py:175-180) runs as two UNet evaluations per step and one linear combination."""
-        if mask is not None or score_corrector is not None or quantize_x0 or noise_dropout > 0.0 or temperature != 1.0:
-            raise NotImplementedError("inpainting / correctors / quantisation are not on the scoped path (sample_diffusion.py:212-220)")
-        self.make_schedule(ddim_num_steps=S, ddim_discretize=ddim_discretize, ddim_eta=eta, verbose=False)
+        Classifier-free guidance (ddim.py:175-180) runs as two UNet evaluations per step and one linear combination.
+        Inpainting (mask=, x0=; ddim.py:144-148, plms.py:147-150): before each step's UNet evaluation at DDPM timestep t one
+        `gg_inpaint_blend`, x <- q_sample(x0, t) * mask + (1 - mask) * x (mask 1 keeps x0, 0 is generated, soft values blend); the
+        deterministic chain stays one captured graph with the blend inside.  `mask_noise_tape` is this package's addition, like
+        `noise_tape`: S tensors [N, C, *sp], the q_sample noise of each step.  Without it the S noises come from one device `randn`,
+        which matches the reference's per-step `randn_like` in distribution, not in stream (that stream is CPU torch's)."""
+        refused = [name for name, on in (("quantize_x0", quantize_x0), ("score_corrector", score_corrector is not None),
+                                         ("noise_dropout", noise_dropout > 0.0), ("temperature", temperature != 1.0)) if on]
+        if refused:
+            raise NotImplementedError(f"DDIMSampler.sample: {', '.join(refused)} not supported (needs a VQ first stage or a user callback; "
+                                      "no shipped config uses it)")
         size = (batch_size,) + tuple(shape)
+        ip = inpaint_operands(mask, x0, size, mask_noise_tape, S)
+        self.make_schedule(ddim_num_steps=S, ddim_discretize=ddim_discretize, ddim_eta=eta, verbose=False)
         dev = self.model.device
         img = torch.randn(size, device=dev) if x_T is None else x_T.to(dev).float()
         cfg = None
         if unconditional_conditioning is not None and unconditional_guidance_scale != 1.0:
             cfg = (unconditional_conditioning, float(unconditional_guidance_scale))
-        z, pred_x0 = self._sample_cl(img, conditioning, eta, noise_tape, cfg)
+        z, pred_x0 = self._sample_cl(img, conditioning, eta, noise_tape, cfg, ip, mask_noise_tape)
         return z, {"x_inter": [img, z], "pred_x0": [img, pred_x0]}
 
     # ---- channels-last fast path -------------------------------------------------------------------------
@@ -539,7 +652,7 @@ class DDIMSampler(object):
                 context = conditioning
         return c_concat, context
 
-    def _sample_cl(self, x_T: torch.Tensor, conditioning, eta: float, noise_tape, cfg=None):
+    def _sample_cl(self, x_T: torch.Tensor, conditioning, eta: float, noise_tape, cfg=None, inpaint=None, mask_noise_tape=None):
         model = self.model
         unet = model.model.diffusion_model
         ck = model.model.conditioning_key
@@ -549,8 +662,10 @@ class DDIMSampler(object):
         nd = len(sp)
         c_concat, context = self._split_cond(conditioning)
         st = self.prepare_state(N, Cx, sp, dev, c_concat.shape[1] if c_concat is not None else 0,
-                                ctx_shape=tuple(context.shape[1:]) if context is not None else None)
+                                ctx_shape=tuple(context.shape[1:]) if context is not None else None, mask_C=inpaint[2] if inpaint else 0)
         self.load_state(st, x_T, c_concat, context)
+        if inpaint is not None:
+            self.load_inpaint(st, inpaint[0], inpaint[1], mask_noise_tape)
         if cfg is not None:
             self._run_steps_cfg(st, x_T, cfg, eta, noise_tape)
         else:
@@ -560,11 +675,14 @@ class DDIMSampler(object):
         p0 = st["pred_x0"].view((N,) + sp + (Cx,)).permute(perm).contiguous()
         return z, p0
 
-    def prepare_state(self, N, Cx, sp, dev, Cc, ctx_shape=None):
+    def prepare_state(self, N, Cx, sp, dev, Cc, ctx_shape=None, *, mask_C=0):
+        """Static buffers (and the captured graph) of one chain shape.  mask_C > 0: the inpainting state of a mask with mask_C channels --
+        static fp32 CL buffers for x0 [M, Cx], the mask [M, mask_C] and the per-step q_sample noise [S, M, Cx], plus the [S, 2] q_sample
+        scalar table; it lives under its own key, so a mask-free call never sees it."""
         unet = self.model.model.diffusion_model
         sp3 = (1,) * (3 - len(sp)) + tuple(sp)
         S = self.ddim_timesteps.shape[0]
-        key = (N, Cx, sp3, Cc, str(dev), ctx_shape)
+        key = (N, Cx, sp3, Cc, str(dev), ctx_shape) + ((("inpaint", mask_C),) if mask_C else ())
         # everything cached below is a function of the schedule (steps, eta -> sigmas) and of the UNet's weights (time-bias
         # table, packed weights baked into the captured graph): a changed schedule or weight version rebuilds the state
         token = (S, tuple(int(v) for v in self.ddim_timesteps), tuple(float(v) for v in self.ddim_sigmas), ops.weights_token(unet))
@@ -582,6 +700,11 @@ class DDIMSampler(object):
                   ctx=(CL(torch.zeros((N, 1, 1, ctx_shape[0], pad32(ctx_shape[1])), dtype=torch.bfloat16, device=dev), ctx_shape[1])
                        if ctx_shape is not None else None),
                   graph=None, warmed=False)
+        if mask_C:
+            st.update(ip_x0=torch.empty((N,) + sp3 + (Cx,), dtype=torch.float32, device=dev),
+                      ip_mask=torch.empty((N,) + sp3 + (mask_C,), dtype=torch.float32, device=dev),
+                      ip_noise=torch.empty((S, N) + sp3 + (Cx,), dtype=torch.float32, device=dev),
+                      ip_scal=self.q_sample_scalar_table().to(dev))
         self._graphs[key] = st
         return st
 
@@ -596,6 +719,33 @@ class DDIMSampler(object):
         ops.to_cl(x_T, out=st["unet_in"], c_offset=0, zero_fill=False)
         if c_concat is not None:
             ops.to_cl(c_concat.float(), out=st["unet_in"], c_offset=st["Cx"], zero_fill=False)
+
+    def load_inpaint(self, st, x0: torch.Tensor, mask: torch.Tensor, mask_noise_tape=None):
+        """x0 [N, C, *sp] and mask [N, Cm, *sp] (inpaint_operands' views) -> the state's static CL buffers; the S q_sample noises from
+        the tape, or from one device randn [S, N, C, *sp].  Outside any graph: a captured chain reads the buffers in place."""
+        N, Cx, S = st["N"], st["Cx"], st["S"]
+        dev = st["x"].device
+        sp = tuple(x0.shape[2:])
+        nd = len(sp)
+        perm = (0,) + tuple(range(2, nd + 2)) + (1,)
+        st["ip_x0"].view((N,) + sp + (Cx,)).copy_(x0.to(dev).permute(perm))            # plumbing: layout copies
+        st["ip_mask"].view((N,) + sp + (mask.shape[1],)).copy_(mask.to(dev).permute(perm))
+        noise = st["ip_noise"].view((S, N) + sp + (Cx,))
+        if mask_noise_tape is not None:
+            for i in range(S):
+                noise[i].copy_(mask_noise_tape[i].to(dev).float().permute(perm))
+        else:
+            noise.copy_(torch.randn((S, N, Cx) + sp, device=dev).permute((0, 1) + tuple(range(3, nd + 3)) + (2,)))
+
+    def _blend(self, st, i):
+        """Inpainting blend before step i's UNet evaluation (ddim.py:144-148): x and the UNet input's channels [0, Cx) <- q_sample(x0,
+        t_i) * mask + (1 - mask) * x.  No-op (no launch) on a mask-free state."""
+        if "ip_x0" not in st:
+            return
+        Cx = st["Cx"]
+        M = st["x"].numel() // Cx
+        ops.inpaint_blend(st["x"].view(M, Cx), st["ip_x0"].view(M, Cx), st["ip_mask"].view(M, -1), st["ip_noise"][i].view(M, Cx),
+                          st["ip_scal"][i], unet_in=st["unet_in"].view(M, -1))
 
     def _step(self, st, ctx_cl, bias, scal, noise):
         """One reverse step on the state's buffers; `bias` / `scal` are rows of the per-schedule tables (ddim.py:165-205)."""
@@ -638,6 +788,9 @@ class DDIMSampler(object):
                 noise = nt.permute((0,) + tuple(range(2, nd + 2)) + (1,)).contiguous()
             elif eta != 0.0:
                 noise = torch.randn_like(st["x"])
+            if "ip_x0" in st:                   # inpainting: both evaluations see the blended x (ddim.py:144-148 precede :175-180)
+                self._blend(st, i)
+                uin_u[..., :Cx].copy_(st["unet_in"][..., :Cx])
             unet.forward_cl(CL(uin_u, Cx + Cc), st["table"][i], ctx_u, head_out=eps_u)
             unet.forward_cl(CL(st["unet_in"], Cx + Cc), st["table"][i], st["ctx"], head_out=st["eps"])
             ops.lincomb4([eps_u, st["eps"]], [1.0 - scale, scale], 1.0, st["eps"])        # (1 - s) e_u + s e_c
@@ -653,6 +806,7 @@ class DDIMSampler(object):
         """All S deterministic steps back to back, every step reading ITS rows of the time-bias / scalar tables in place: no
         per-step copies, no host decisions, so the whole chain (13 k kernel nodes at S = 50) is one capturable launch sequence."""
         for i in range(st["S"]):
+            self._blend(st, i)
             self._step(st, ctx_cl, st["table"][i], st["scal"][i], None)
 
     def run_steps(self, st, ctx_cl, eta, noise_tape):
@@ -675,6 +829,7 @@ class DDIMSampler(object):
                 noise = nt.permute((0,) + tuple(range(2, nd + 2)) + (1,)).contiguous()
             elif eta != 0.0:
                 noise = torch.randn_like(st["x"])
+            self._blend(st, i)
             self._step(st, ctx_cl, st["table"][i], st["scal"][i], noise)
 
 
@@ -701,6 +856,7 @@ class PLMSSampler(DDIMSampler):
             ops.ddim_step(x, e_cl.view(M, -1), scal, pred_x0_out=st["pred_x0"].view(M, Cx), unet_in=uin)
 
         for i in range(S):
+            self._blend(st, i)                 # inpainting (plms.py:147-150): before the first evaluation, so x_keep holds the blended x
             unet.forward_cl(xin, st["table"][i], ctx_cl, head_out=eps)
             e_t = eps.clone()
             if len(old) == 0:

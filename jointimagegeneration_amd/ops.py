@@ -746,6 +746,20 @@ def ddim_step(x: torch.Tensor, eps: torch.Tensor, scalars: torch.Tensor, noise: 
                            _ptr(unet_in), unet_in.shape[-1] if unet_in is not None else 0, _stream()), "gg_ddim_step")
 
 
+def inpaint_blend(x: torch.Tensor, x0: torch.Tensor, mask: torch.Tensor, noise: torch.Tensor, scalars: torch.Tensor,
+                  unet_in: Optional[torch.Tensor] = None) -> None:
+    """x <- q_sample(x0, t, noise) * mask + (1 - mask) * x in place; x, x0, noise fp32 CL [M, C], mask fp32 CL [M, 1 or C],
+    scalars fp32[2] = (sqrt_alphas_cumprod[t], sqrt_one_minus_alphas_cumprod[t]) on device; unet_in channels [0, C) <- bf16(x)."""
+    lib = _lib.load()
+    Cc = x.shape[-1]
+    M = x.numel() // Cc
+    for name, t, c in (("x", x, Cc), ("x0", x0, Cc), ("noise", noise, Cc), ("mask", mask, mask.shape[-1])):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != M * c:
+            raise ValueError(f"inpaint_blend: {name} must be contiguous fp32 [{M}, {c}], got {t.dtype} {tuple(t.shape)}")
+    check(lib.gg_inpaint_blend(x.data_ptr(), x0.data_ptr(), mask.data_ptr(), mask.shape[-1], noise.data_ptr(), scalars.data_ptr(), M, Cc,
+                               _ptr(unet_in), unet_in.shape[-1] if unet_in is not None else 0, _stream()), "gg_inpaint_blend")
+
+
 def minmax_normalise(src: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     lib = _lib.load()
     if out is None:
