@@ -7,6 +7,7 @@ struct ConvParams {
     int kd, kh, kw, stride, pad, upsample;
     int Do, Ho, Wo, out_dtype, prologue_act;
     int path_hint;            // gg_conv_desc.path_hint (1: tests force the halo kernel below the grid-fill gate)
+                              // (box kernel: GG_BOX_HINT_GENERIC / GG_BOX_HINT_SPEC_ONLY, gg_conv_box_spec.hip)
     int nchunk1, nchunk, ntaps;
     long long M;              // N*Do*Ho*Wo
     long long bias_stride;
@@ -43,6 +44,11 @@ struct ConvParams {
     const unsigned long long *post_seeds;     // per-sample Philox keys [N] or nullptr (post_seed for every sample)
     long long post_rows_per_sample;
 };
+
+// path_hint values of the box kernel (tests, A/B): run the generic kernel even where a shape-specialised one is listed / fail a box conv
+// that has no shape-specialised kernel
+#define GG_BOX_HINT_GENERIC 10
+#define GG_BOX_HINT_SPEC_ONLY 11
 
 // fixed-point scales of the GroupNorm accumulators: |sum| < 2^35, sumsq < 2^43 per channel and sample
 #define GG_ACC_SUM_SCALE 268435456.0f   /* 2^28 */
