@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """GuideGen sampling benchmark on MI355X (contract in the task statement; metric from BASELINE.json).
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 The workload is a stream of complete GuideGen volumes per GPU (config C5 of BASELINE.json, one independent volume per rank):
   CCDM 3-D categorical UNet, 128^3 mask, 14 classes, 250 reverse steps  ->  stage glue  ->
@@ -21,6 +21,12 @@ the seed recipe; timed volume v: seed 1024 + rank + 1000 v, as pipeline.run_volu
 computed at its last step: the current volume's CCDM labels, the CT slice of the last step, and the current volume's CT buffer
 (slices not yet sampled are zero), each cut to a fixed seeded sample when larger than DUMP_MAX_ELEMS, so that two builds can be
 compared output for output.
+
+A plain run does only what the headline needs: it builds the models, runs the capture run, the W warm-up and the K timed steps,
+dumps the outputs if asked and prints the line.  --full adds the legs that take runs of their own, on rank 0: the roofline of the
+judged kernel with the measured MFMA / stream-copy peaks, the captured per-stage times, the configurations off the C5 wall and the
+secondary 8-volumes-per-GPU sample (before the timed region), and the CPU baseline (after it); --no-roofline, --no-extra and
+--no-cpu-baseline leave single legs out of a --full run.
 
 N > 1.  Under a launcher (torch.distributed.run: RANK/LOCAL_RANK/WORLD_SIZE set) each process is one rank.  Started directly
 (`python bench.py --gpus 4`, WORLD_SIZE unset) the process becomes a PARENT that never touches the GPU: it starts N child
@@ -61,10 +67,15 @@ def parse(argv=None):
     ap.add_argument("--slices", type=int, default=256)
     ap.add_argument("--volumes-per-gpu", type=int, default=1, help="independent volumes sampled concurrently per GPU (BASELINE C5 = 1)")
     ap.add_argument("--max-slices", type=int, default=None, help="DEV ONLY: truncate the slice loop (marks the line partial)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary 8-volumes-per-GPU sample")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the roofline, measured-peak, other-configuration, 8-volumes-per-GPU and CPU-baseline legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline and measured-peak legs")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the other configurations and the 8-volumes-per-GPU sample")
+    args = ap.parse_args(argv)
+    if not args.full:                                      # a plain run: the headline only
+        args.no_cpu_baseline = args.no_roofline = args.no_extra = True
+    return args
 
 
 # ------------------------------------------------------------------------------------------------ parent launcher
@@ -537,7 +548,7 @@ def main():
         log("untimed warm-up (weight repack, hipGraph capture)")
         pipe.run_volume(N=args.volumes_per_gpu, mask_size=(128, 128, 128), depth=args.slices, hw=512, seed=7, ccdm_init_t=10005, max_slices=3)
 
-    # ---- roofline legs BEFORE the timed region
+    # ---- --full: roofline and characterisation legs BEFORE the timed region
     line_extra = {}
     if rank == 0 and not dry:
         if not args.no_roofline:
@@ -594,8 +605,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # after the timed region: output dump, stage timings + JSON + teardown, and on rank 0 the CPU-baseline leg (~35 s of host work: it
-    # runs after the last collective, so that the other ranks never wait in a barrier for it)
+    # after the timed region: output dump, stage timings + JSON + teardown, and with --full on rank 0 the CPU-baseline leg (~35 s of host
+    # work: it runs after the last collective, so that the other ranks never wait in a barrier for it)
     dumped = None
     if rank == 0 and args.dump_outputs and not dry:
         labels, samples, mm, _ = last
@@ -619,7 +630,7 @@ def main():
             "value": round(world * args.volumes_per_gpu * (masks * 128 ** 3 + slices * 512 * 512) / elapsed, 1), "unit": "voxels/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 1),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
-            "steps_requested": args.steps, "warmup_requested": args.warmup,
+            "steps_requested": args.steps, "warmup_requested": args.warmup, "full": args.full,
             "step": "one CT slice of the autoregressive loop; the step that begins a volume also samples its 128^3 CCDM mask",
             "timed_masks": masks, "timed_slices": slices,
             "warmup_note": "untimed capture run (5 CCDM steps + 3 slices on the real shapes) + `warmup` steps on a warm-up volume",

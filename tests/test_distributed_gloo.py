@@ -125,6 +125,25 @@ def test_bench_dump_outputs_writes_float32_arrays_and_a_fixed_sample(tmp_path):
     assert sum(4 * min(n, bench.DUMP_MAX_ELEMS) for n in full.values()) <= 64 << 20
 
 
+def test_bench_plain_run_leaves_the_extra_legs_to_full():
+    """A plain run measures the headline only; --full turns the roofline, extra and CPU-baseline legs on, and the --no-* options
+    still leave single legs out of a --full run."""
+    import json
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse(["--steps", "2"])
+    assert not a.full and a.no_roofline and a.no_extra and a.no_cpu_baseline
+    a = bench.parse(["--steps", "2", "--full"])
+    assert a.full and not (a.no_roofline or a.no_extra or a.no_cpu_baseline)
+    a = bench.parse(["--full", "--no-cpu-baseline", "--no-extra"])
+    assert a.no_cpu_baseline and a.no_extra and not a.no_roofline
+    for args, full in (([], False), (["--full"], True)):
+        r = _run_bench(["--gpus", "1", "--steps", "2", "--warmup", "1"] + args, {"GG_BENCH_DRY": "1"})
+        assert r.returncode == 0, r.stderr[-2000:]
+        j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+        assert j["full"] is full and j["steps"] == 2 and j["warmup"] == 1
+
+
 def test_bench_gpus_mismatch_and_failed_rank_are_errors():
     # a launcher that started the wrong number of ranks
     r = _run_bench(["--gpus", "4", "--steps", "1"], {"GG_BENCH_DRY": "1", "WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})

@@ -13,8 +13,8 @@ calls = sum(int(r["Calls"]) for r in h)
 tot = sum(float(r["TotalDurationNs"]) for r in h)
 post = [r for r in h if r["Name"].startswith("void conv_halo_kernel<1, 1, 0, 2, 1>")]
 plain = [r for r in h if r["Name"].startswith("void conv_halo_kernel<1, 1, 0, 2, 0>")]
-d = json.loads(open(bench_json).read().strip().splitlines()[-1])["roofline"]
-out = ["rocprofv3 --kernel-trace --stats of `python3 bench.py --gpus 1 --steps 1 --warmup 0 --ccdm-steps 20 --max-slices 6 --no-cpu-baseline --no-extra` (tools/profile_round.sh pass 1)"]
+d = json.loads(open(bench_json).read().strip().splitlines()[-1])["roofline"]          # the line of a `bench.py --full` run
+out = ["rocprofv3 --kernel-trace --stats of `python3 bench.py --gpus 1 --steps 1 --warmup 0 --ccdm-steps 20 --max-slices 6 --full --no-cpu-baseline --no-extra` (tools/profile_round.sh pass 1)"]
 for r in h:
     out.append(f"  {r['Name'][:60]:60s} calls {r['Calls']:>4s} avg {float(r['AverageNs']) / 1e3:8.1f} us")
 avg = tot / calls / 1e3

@@ -7,7 +7,7 @@ OUT=gpurun_out/${1:-prof}
 mkdir -p $OUT
 export TMPDIR=/tmp
 # 1. the bench command, bounded, hipGraphs ON
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -o bench -- python3 bench.py --gpus 1 --steps 1 --warmup 0 --ccdm-steps 20 --max-slices 6 --no-cpu-baseline --no-extra > $OUT/bench_under_rocprof.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -o bench -- python3 bench.py --gpus 1 --steps 1 --warmup 0 --ccdm-steps 20 --max-slices 6 --full --no-cpu-baseline --no-extra > $OUT/bench_under_rocprof.log 2>&1
 echo "bench pass rc=$?"
 # 2. one eager latent-UNet forward, per-kernel timeline
 GG_NO_GRAPH=1 rocprofv3 --kernel-trace --stats -d $OUT/ldm -o ldm -- python3 tools/perf_probe.py ldm > $OUT/ldm_probe.log 2>&1
