@@ -339,6 +339,29 @@ int gg_ddpm_step(float *x, const float *eps, int32_t eps_stride, const float *no
 int gg_inpaint_blend(float *x, const float *x0, const float *mask, int32_t mask_C, const float *noise, const float *scalars_dev,
                      int64_t M, int32_t C, void *unet_in, int32_t unet_in_stride, void *stream);
 
+/* Vector quantisation of a VQ first stage (taming's VectorQuantizer as ldm/models/autoencoder.py:45 builds it), gg_vq.hip.
+ * gg_vq_nearest: rows fp32 channels-last [M, row_stride] (channels [0, C) are read), codebook fp32 [n_embed, C]:
+ *   d[m,k] = sum_c z[m,c]^2 + sum_c E[k,c]^2 - 2 sum_c z[m,c] E[k,c];  idx[m] = argmin_k d[m,k], the first minimum on a tie.
+ *   All fp32, no contraction: zz, ee and dot are each summed over ascending c (product rounded, then added), d = (zz + ee) - 2*dot.
+ *   idx_out (optional) int32 [M]; st_out (optional) fp32 [M, st_stride]: channels [0, C) <- the straight-through rows
+ *   z + (E[idx] - z), evaluated in that order (not E[idx]: the two differ by a rounding); st_out may be `rows` itself.
+ *   C outside [1, 8]: GG_ERR_UNSUPPORTED; n_embed >= 1 is arbitrary (the codebook is staged through LDS in tiles of 1024 codes, codes
+ *   past n_embed are never read).  No allocation, no host readback, no synchronisation: capturable.
+ * gg_ddim_step_vq: one reverse step with the prediction of x_0 quantised (ddim.py:196-204 with quantize_denoised; ancestral != 0:
+ *   ddpm.py:1073-1083 + p_sample).  x, eps, noise, pred_x0_out, unet_in as in gg_ddim_step; scalars device fp32[5]:
+ *   ancestral == 0: {a_t, a_prev, sigma_t, sqrt(1 - a_t), noise coefficient (sigma_t * temperature)}
+ *     p = (x - s[3]*eps)/sqrt(a_t);  q = quantise(p);  x <- sqrt(a_prev)*q + sqrt(1 - a_prev - sigma_t^2)*eps + s[4]*noise
+ *   ancestral != 0: {sqrt_recip_alphas_cumprod, sqrt_recipm1_alphas_cumprod, posterior_mean_coef1, posterior_mean_coef2, sigma}
+ *     p = s[0]*x - s[1]*eps;          q = quantise(p);  x <- s[2]*q + s[3]*x + s[4]*noise
+ *   each line left to right without contraction, as gg_ddim_step / gg_ddpm_step evaluate theirs.  pred_x0_out receives q (the
+ *   straight-through rows), idx_out (optional) the indices.  codebook NULL (n_embed 0): no quantisation, q = p -- the plain step with a
+ *   noise coefficient of its own (temperature != 1).  Same envelope and guarantees as gg_vq_nearest. */
+int gg_vq_nearest(const float *rows, int32_t row_stride, const float *codebook, int32_t n_embed, int32_t C, int64_t M,
+                  int32_t *idx_out, float *st_out, int32_t st_stride, void *stream);
+int gg_ddim_step_vq(float *x, const float *eps, int32_t eps_stride, const float *noise, const float *scalars_dev, int32_t ancestral,
+                    const float *codebook, int32_t n_embed, int64_t M, int32_t C, int32_t *idx_out, float *pred_x0_out,
+                    void *unet_in, int32_t unet_in_stride, void *stream);
+
 /* PLMS multistep combination of noise estimates (ldm/models/diffusion/plms.py:218-232), fp32, evaluated left to right:
  *   out = (c0*e0 + c1*e1 + c2*e2 + c3*e3) / denom ; e1..e3 may be NULL (skipped). */
 int gg_lincomb4(const float *e0, const float *e1, const float *e2, const float *e3, float c0, float c1, float c2, float c3,

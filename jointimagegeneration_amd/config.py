@@ -19,6 +19,10 @@ import yaml
 TARGET_ALIASES = {
     "ldm.modules.diffusionmodules.openaimodel.UNetModel": "jointimagegeneration_amd.unet.UNetModel",
     "ldm.models.autoencoder.AutoencoderKL": "jointimagegeneration_amd.ldm.AutoencoderKL",
+    "ldm.models.autoencoder.VQModel": "jointimagegeneration_amd.ldm.VQModel",
+    "ldm.models.autoencoder.VQModelInterface": "jointimagegeneration_amd.ldm.VQModelInterface",
+    "ldm.models.autoencoder.IdentityFirstStage": "jointimagegeneration_amd.ldm.IdentityFirstStage",
+    "taming.modules.vqvae.quantize.VectorQuantizer": "jointimagegeneration_amd.ldm.VectorQuantizer",
     "ldm.models.diffusion.ddpm.LatentDiffusion": "jointimagegeneration_amd.ldm.LatentDiffusion",
     "ldm.modules.encoders.modules.IdentityEncoder": "jointimagegeneration_amd.ldm.IdentityEncoder",
     "ldm.models.diffusion.ddim.DDIMSampler": "jointimagegeneration_amd.ldm.DDIMSampler",

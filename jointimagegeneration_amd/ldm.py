@@ -6,7 +6,8 @@ Mirrors the sampling surface of (paths relative to the reference tree, latentdif
   (DDPM/LatentDiffusion/DiffusionWrapper: schedule buffers, apply_model, get_learned_conditioning, decode_first_stage,
   ema_scope), ldm/modules/ema.py (LitEma name mangling), ldm/models/diffusion/ddim.py:11-205 (DDIMSampler),
   ldm/modules/encoders/modules.py:287-289 (IdentityEncoder).
-Training, logging, VQ and the fold/unfold patch path are out of scope.
+VQ first stage: ldm/models/autoencoder.py:18-131,283-301,464-481 (VQModel, VQModelInterface, IdentityFirstStage) with taming's
+VectorQuantizer.  Training, logging and the fold/unfold patch path are out of scope.
 """
 from __future__ import annotations
 
@@ -204,6 +205,187 @@ class AutoencoderKL(nn.Module):
         return ops.from_cl(self.decode_cl(ops.to_cl(z)), 2)
 
 
+class VectorQuantizer(nn.Module):
+    """taming.modules.vqvae.quantize.VectorQuantizer as the reference builds it (autoencoder.py:45: n_e, e_dim, beta=0.25), inference
+    side.  z [N, C, *sp] fp32; rows are the channels-last flattening of z; the nearest codebook row under
+    d = sum z^2 + sum E^2 - 2 z.E (first minimum on a tie) comes from gg_vq_nearest, fp32 in a fixed order (include/guidegen_hip.h).
+    forward returns (quant, loss, (perplexity, min_encodings, min_encoding_indices)) with quant the straight-through expression
+    z + (z_q - z) in fp32 -- not z_q itself, the two differ by a rounding -- and loss, perplexity and min_encodings None (they serve
+    training and logging only); the indices are an int64 tensor [M, 1], M = N * prod(sp).  beta only enters the training loss."""
+
+    def __init__(self, n_e, e_dim, beta=0.25, remap=None, sane_index_shape=False, **unused):
+        super().__init__()
+        for name, on in (("remap", remap is not None), ("sane_index_shape", bool(sane_index_shape))):
+            if on:
+                raise NotImplementedError(f"VectorQuantizer: {name} is not supported (the reference's VQModel does not pass it on, autoencoder.py:45-47)")
+        self.n_e, self.e_dim, self.beta = n_e, e_dim, beta
+        self.embedding = nn.Embedding(n_e, e_dim)
+        self.embedding.weight.data.uniform_(-1.0 / n_e, 1.0 / n_e)
+
+    def codebook(self) -> torch.Tensor:
+        return self.embedding.weight.detach()
+
+    def quantize_rows(self, rows: torch.Tensor, st_out: Optional[torch.Tensor] = None):
+        """Channels-last rows fp32 [..., stride >= e_dim] -> (indices int32 [M], straight-through rows fp32 [M, e_dim] or st_out)."""
+        return ops.vq_nearest(rows, self.codebook(), self.e_dim, st_out=st_out)
+
+    def forward(self, z: torch.Tensor):
+        ops.require_gpu(z, "VectorQuantizer.forward")
+        if z.shape[1] != self.e_dim:
+            raise ValueError(f"VectorQuantizer: z has {z.shape[1]} channels, the codebook has e_dim = {self.e_dim}")
+        nd = z.ndim - 2
+        cl = z.float().permute((0,) + tuple(range(2, nd + 2)) + (1,)).contiguous()                  # plumbing: layout copy
+        idx, st = self.quantize_rows(cl)
+        quant = st.view(cl.shape).permute((0, nd + 1) + tuple(range(1, nd + 1))).contiguous()
+        return quant, None, (None, None, idx.long().view(-1, 1))
+
+    def get_codebook_entry(self, indices, shape):
+        """Codebook rows of `indices`; shape = (batch, height, width, channel) reshapes them to [batch, channel, height, width]."""
+        z_q = self.embedding(indices.reshape(-1).long())
+        if shape is not None:
+            z_q = z_q.view(shape).permute(0, 3, 1, 2).contiguous()
+        return z_q
+
+    def embed_code(self, code_b):
+        """Indices [N, H, W] -> codebook rows as [N, C, H, W] (what VQModel.decode_code feeds to decode)."""
+        return self.get_codebook_entry(code_b, tuple(code_b.shape) + (self.e_dim,))
+
+
+class VQModel(nn.Module):
+    """Sampling side of the reference's VQModel (autoencoder.py:18-131): encoder -> quant_conv -> quantise, post_quant_conv -> decoder,
+    on the Encoder / Decoder channels-last paths; quantisation runs on the fp32 output of quant_conv.  The fork's quant_conv takes
+    2 * z_channels inputs (autoencoder.py:51), so the Encoder is the double_z one."""
+
+    def __init__(self, ddconfig, lossconfig=None, n_embed=None, embed_dim=None, ckpt_path=None, ignore_keys=[], image_key="image",
+                 colorize_nlabels=None, monitor=None, batch_resize_range=None, scheduler_config=None, lr_g_factor=1.0, remap=None,
+                 sane_index_shape=False, use_ema=False, l1_weight=0.5, dims=3):
+        super().__init__()
+        ddconfig = dict(ddconfig)
+        if ddconfig.get("dims", dims) != 2:
+            raise NotImplementedError("the shipped AE configs are 2-D (…_ae.yaml:41-94)")
+        for name, on in (("remap", remap is not None), ("sane_index_shape", bool(sane_index_shape)),
+                         ("batch_resize_range", batch_resize_range is not None), ("use_ema", bool(use_ema))):
+            if on:
+                raise NotImplementedError(f"VQModel: {name} is not supported (training-side or index-remapping option)")
+        if n_embed is None or embed_dim is None:
+            raise TypeError("VQModel: n_embed and embed_dim are required")
+        if not ddconfig.get("double_z", True):
+            raise ValueError("VQModel: quant_conv takes 2 * z_channels inputs (autoencoder.py:51), so ddconfig.double_z must be True")
+        self.embed_dim, self.n_embed, self.image_key = embed_dim, n_embed, image_key
+        self.encoder = Encoder(**ddconfig)
+        self.decoder = Decoder(**ddconfig)
+        self.loss = nn.Identity()                       # training is out of scope
+        self.quantize = VectorQuantizer(n_embed, embed_dim, beta=0.25)
+        self.dims = 2
+        self.quant_conv = nn.Conv2d(2 * ddconfig["z_channels"], embed_dim, 1)
+        self.post_quant_conv = nn.Conv2d(embed_dim, ddconfig["z_channels"], 1)
+        if colorize_nlabels is not None:
+            self.register_buffer("colorize", torch.randn(3, colorize_nlabels, 1, 1))
+        self.use_ema = False
+        if ckpt_path is not None:
+            self.init_from_ckpt(ckpt_path, ignore_keys=ignore_keys)
+
+    init_from_ckpt = AutoencoderKL.init_from_ckpt
+
+    # ---- channels-last paths
+    def prequant_cl(self, x: CL) -> CL:
+        """encoder -> quant_conv, fp32 channels-last output (what the quantiser reads)."""
+        ops.stats_begin(x.t.device)
+        try:
+            h = self.encoder.run(x)
+            pw, pb = packed_conv(self.quant_conv, h.Cpad)
+            return ops.conv(h, pw, pb, self.quant_conv.weight.shape[0], k=(1, 1, 1), pad=0, out_f32=True)
+        finally:
+            ops.stats_end(x.t.device)
+
+    decode_cl = AutoencoderKL.decode_cl
+
+    # ---- reference surface (NCHW fp32)
+    def encode_to_prequant(self, x: torch.Tensor) -> torch.Tensor:
+        ops.require_gpu(x, f"{type(self).__name__}.encode")
+        return ops.from_cl(self.prequant_cl(ops.to_cl(x)), 2)
+
+    def encode(self, x: torch.Tensor):
+        ops.require_gpu(x, "VQModel.encode")
+        h = self.prequant_cl(ops.to_cl(x))
+        N, _, H, W, Cp = h.t.shape
+        idx, st = self.quantize.quantize_rows(h.t.view(-1, Cp))        # the padded fp32 rows are read in place
+        quant = st.view(N, H, W, self.embed_dim).permute(0, 3, 1, 2).contiguous()
+        return quant, None, (None, None, idx.long().view(-1, 1))
+
+    def decode(self, quant: torch.Tensor) -> torch.Tensor:
+        ops.require_gpu(quant, f"{type(self).__name__}.decode")
+        return ops.from_cl(self.decode_cl(ops.to_cl(quant)), 2)
+
+    def decode_code(self, code_b):
+        return self.decode(self.quantize.embed_code(code_b))
+
+    def forward(self, input, return_pred_indices=False):
+        quant, diff, (_, _, ind) = VQModel.encode(self, input)
+        dec = VQModel.decode(self, quant)
+        return (dec, diff, ind) if return_pred_indices else (dec, diff)
+
+
+class VQModelInterface(VQModel):
+    """The first stage of a VQ-regularised latent diffusion model (autoencoder.py:283-301): encode stops before the quantiser, decode
+    goes through it unless force_not_quantize."""
+
+    def __init__(self, embed_dim, *args, **kwargs):
+        super().__init__(embed_dim=embed_dim, *args, **kwargs)
+        self.embed_dim = embed_dim
+
+    def encode(self, x):
+        return self.encode_to_prequant(x)
+
+    def decode(self, h, force_not_quantize=False):
+        ops.require_gpu(h, "VQModelInterface.decode")
+        quant = h if force_not_quantize else self.quantize(h)[0]
+        return super().decode(quant)
+
+
+class IdentityFirstStage(nn.Module):
+    """autoencoder.py:464-481."""
+
+    def __init__(self, *args, vq_interface=False, **kwargs):
+        super().__init__()
+        self.vq_interface = vq_interface
+
+    def encode(self, x, *args, **kwargs):
+        return x
+
+    def decode(self, x, *args, **kwargs):
+        return x
+
+    def quantize(self, x, *args, **kwargs):
+        if self.vq_interface:
+            return x, None, [None, None, None]
+        return x
+
+    def forward(self, x, *args, **kwargs):
+        return x
+
+
+def first_stage_codebook(model, option: str, channels: int) -> torch.Tensor:
+    """The fp32 codebook [n_embed, channels] of `model`'s first stage for `option` (quantize_x0 / quantize_denoised), validated on the
+    host before any launch: the first stage must hold a VectorQuantizer whose width is the latent's channel count.  None for an
+    IdentityFirstStage with vq_interface, whose quantiser changes nothing."""
+    fs = None if getattr(model, "no_first_stage", False) else getattr(model, "first_stage_model", None)
+    if isinstance(fs, IdentityFirstStage) and fs.vq_interface:
+        return None                                     # its quantize() is the identity (autoencoder.py:475-478)
+    q = getattr(fs, "quantize", None)
+    if not isinstance(q, VectorQuantizer):
+        raise NotImplementedError(f"{option} needs a first stage with a `quantize` codebook (VQModelInterface); this model's first stage is "
+                                  f"{type(fs).__name__}, which has none")
+    cb = q.codebook()
+    if cb.shape[1] != channels:
+        raise ValueError(f"{option}: the codebook has e_dim = {cb.shape[1]}, the latent has {channels} channels")
+    if not 1 <= channels <= 8:
+        raise NotImplementedError(f"{option}: gg_ddim_step_vq supports 1..8 latent channels, got {channels}")
+    if cb.dtype != torch.float32 or not cb.is_contiguous():
+        raise ValueError(f"{option}: the codebook must be contiguous fp32, got {cb.dtype}")
+    return cb
+
+
 class IdentityEncoder(nn.Module):
     def encode(self, x):
         return x
@@ -382,9 +564,14 @@ class LatentDiffusion(nn.Module):
 
     @torch.no_grad()
     def decode_first_stage(self, z, predict_cids=False, force_not_quantize=False):
+        if predict_cids:
+            raise NotImplementedError("decode_first_stage: predict_cids is not supported (it needs the UNet's codebook-id head)")
         if self.no_first_stage:
             return z
-        return self.first_stage_model.decode(1.0 / self.scale_factor * z)
+        z = 1.0 / self.scale_factor * z
+        if isinstance(self.first_stage_model, VQModelInterface):
+            return self.first_stage_model.decode(z, force_not_quantize=force_not_quantize)
+        return self.first_stage_model.decode(z)
 
     @torch.no_grad()
     def encode_first_stage(self, x):
@@ -423,9 +610,10 @@ class LatentDiffusion(nn.Module):
         x <- q_sample(x0, t) * mask + (1 - mask) * x, so the known region of the result is q_sample(x0, 0).  `mask_noise_tape`
         (this package's addition, like `noise_tape`): T tensors [N, C, *sp], the q_sample noise of each step; without it every step
         draws a fresh device `randn`, which matches the reference's `randn_like` in distribution, not in stream (that stream is CPU
-        torch's).  `noise_tape` / `mask_noise_tape` exist so that tests can feed the reference's draws."""
-        if quantize_denoised:
-            raise NotImplementedError("p_sample_loop: quantize_denoised is not supported (it needs a VQ first stage)")
+        torch's).  `noise_tape` / `mask_noise_tape` exist so that tests can feed the reference's draws.
+        quantize_denoised (ddpm.py:1081-1082): x_recon goes through the first stage's quantiser before the posterior mean; the step is
+        then one `gg_ddim_step_vq` (ancestral form) in place of `gg_ddpm_step`."""
+        codebook = first_stage_codebook(self, "p_sample_loop: quantize_denoised", shape[1]) if quantize_denoised else None
         dev = self.device
         unet = self.model.diffusion_model
         ck = self.model.conditioning_key
@@ -470,7 +658,11 @@ class LatentDiffusion(nn.Module):
                 nz = noise_tape[i].to(dev).float().permute(perm).contiguous()
             else:
                 nz = torch.randn_like(x)
-            ops.ddpm_step(x.view(M, Cx), eps.view(M, -1), scal[i], noise=nz.view(M, Cx), unet_in=unet_in.view(M, -1))
+            if codebook is not None:
+                ops.ddim_step_vq(x.view(M, Cx), eps.view(M, -1), scal[i], codebook, noise=nz.view(M, Cx), unet_in=unet_in.view(M, -1),
+                                 ancestral=True)
+            else:
+                ops.ddpm_step(x.view(M, Cx), eps.view(M, -1), scal[i], noise=nz.view(M, Cx), unet_in=unet_in.view(M, -1))
             if ip is not None:
                 nm = mask_noise_tape[i].to(dev).float().permute(perm).contiguous() if mask_noise_tape is not None else torch.randn_like(x)
                 ops.inpaint_blend(x.view(M, Cx), x0_cl.view(M, Cx), mask_cl.view(M, -1), nm.view(M, Cx), qscal[i], unet_in=unet_in.view(M, -1))
@@ -620,13 +812,27 @@ class DDIMSampler(object):
         `gg_inpaint_blend`, x <- q_sample(x0, t) * mask + (1 - mask) * x (mask 1 keeps x0, 0 is generated, soft values blend); the
         deterministic chain stays one captured graph with the blend inside.  `mask_noise_tape` is this package's addition, like
         `noise_tape`: S tensors [N, C, *sp], the q_sample noise of each step.  Without it the S noises come from one device `randn`,
-        which matches the reference's per-step `randn_like` in distribution, not in stream (that stream is CPU torch's)."""
-        refused = [name for name, on in (("quantize_x0", quantize_x0), ("score_corrector", score_corrector is not None),
-                                         ("noise_dropout", noise_dropout > 0.0), ("temperature", temperature != 1.0)) if on]
-        if refused:
-            raise NotImplementedError(f"DDIMSampler.sample: {', '.join(refused)} not supported (needs a VQ first stage or a user callback; "
-                                      "no shipped config uses it)")
+        which matches the reference's per-step `randn_like` in distribution, not in stream (that stream is CPU torch's).
+        quantize_x0 (ddim.py:197-198, plms.py:184-185): each step's pred_x0 goes through the first stage's quantiser
+        (`first_stage_model.quantize`, a VectorQuantizer) before x_prev is formed; the step's update is then one `gg_ddim_step_vq`, the
+        head conv's fused DDIM epilogue is not used, and the eta = 0 chain is still one captured graph.  The returned pred_x0 is the
+        quantised one.  temperature (ddim.py:201): the noise term is sigma_t * temperature * noise, the factor sits in the fifth column
+        of the per-step scalar table (rewritten on each call, so temperatures share one state); dir_xt keeps sigma_t unscaled.  noise_dropout (ddim.py:202-203): torch.nn.functional.dropout(p)
+        on each step's noise as it is loaded (the tape's tensor as given, or the device draw), outside any graph; it draws from the
+        device's default generator.  With eta = 0 the noise term is zero whatever the two are.  A call with none of the three takes the
+        state, graph and launches it took before they existed."""
+        if score_corrector is not None:
+            raise NotImplementedError(f"{type(self).__name__}.sample: score_corrector not supported (a user callback inside the step)")
+        if not 0.0 <= float(noise_dropout) < 1.0:
+            raise ValueError(f"{type(self).__name__}.sample: noise_dropout = {noise_dropout} outside [0, 1)")
         size = (batch_size,) + tuple(shape)
+        codebook = first_stage_codebook(self.model, f"{type(self).__name__}.sample: quantize_x0", size[1]) if quantize_x0 else None
+        asked = [name for name, on in (("quantize_x0", quantize_x0), ("noise_dropout", noise_dropout > 0.0),
+                                       ("temperature", temperature != 1.0)) if on]
+        if asked and self.model.device.type != "cuda":
+            # these run in gg_ddim_step_vq / on the device generator only; refused on the host, before any launch
+            raise NotImplementedError(f"{type(self).__name__}.sample: {', '.join(asked)} not supported for a model on {self.model.device} "
+                                      "(the step kernel and the dropout's generator are the GPU's; there is no CPU path)")
         ip = inpaint_operands(mask, x0, size, mask_noise_tape, S)
         self.make_schedule(ddim_num_steps=S, ddim_discretize=ddim_discretize, ddim_eta=eta, verbose=False)
         dev = self.model.device
@@ -634,7 +840,10 @@ class DDIMSampler(object):
         cfg = None
         if unconditional_conditioning is not None and unconditional_guidance_scale != 1.0:
             cfg = (unconditional_conditioning, float(unconditional_guidance_scale))
-        z, pred_x0 = self._sample_cl(img, conditioning, eta, noise_tape, cfg, ip, mask_noise_tape)
+        vq = None
+        if codebook is not None or (float(temperature) != 1.0 and eta != 0.0):        # eta = 0: sigma_t = 0, the temperature has no effect
+            vq = (codebook, float(temperature))
+        z, pred_x0 = self._sample_cl(img, conditioning, eta, noise_tape, cfg, ip, mask_noise_tape, vq=vq, noise_dropout=float(noise_dropout))
         return z, {"x_inter": [img, z], "pred_x0": [img, pred_x0]}
 
     # ---- channels-last fast path -------------------------------------------------------------------------
@@ -652,7 +861,8 @@ class DDIMSampler(object):
                 context = conditioning
         return c_concat, context
 
-    def _sample_cl(self, x_T: torch.Tensor, conditioning, eta: float, noise_tape, cfg=None, inpaint=None, mask_noise_tape=None):
+    def _sample_cl(self, x_T: torch.Tensor, conditioning, eta: float, noise_tape, cfg=None, inpaint=None, mask_noise_tape=None, *, vq=None,
+                   noise_dropout=0.0):
         model = self.model
         unet = model.model.diffusion_model
         ck = model.model.conditioning_key
@@ -662,32 +872,41 @@ class DDIMSampler(object):
         nd = len(sp)
         c_concat, context = self._split_cond(conditioning)
         st = self.prepare_state(N, Cx, sp, dev, c_concat.shape[1] if c_concat is not None else 0,
-                                ctx_shape=tuple(context.shape[1:]) if context is not None else None, mask_C=inpaint[2] if inpaint else 0)
+                                ctx_shape=tuple(context.shape[1:]) if context is not None else None, mask_C=inpaint[2] if inpaint else 0, vq=vq)
         self.load_state(st, x_T, c_concat, context)
         if inpaint is not None:
             self.load_inpaint(st, inpaint[0], inpaint[1], mask_noise_tape)
         if cfg is not None:
-            self._run_steps_cfg(st, x_T, cfg, eta, noise_tape)
+            self._run_steps_cfg(st, x_T, cfg, eta, noise_tape, noise_dropout)
         else:
-            self.run_steps(st, st["ctx"], eta, noise_tape)
+            self.run_steps(st, st["ctx"], eta, noise_tape, noise_dropout)
         perm = (0, nd + 1) + tuple(range(1, nd + 1))
         z = st["x"].view((N,) + sp + (Cx,)).permute(perm).contiguous()
         p0 = st["pred_x0"].view((N,) + sp + (Cx,)).permute(perm).contiguous()
         return z, p0
 
-    def prepare_state(self, N, Cx, sp, dev, Cc, ctx_shape=None, *, mask_C=0):
+    def prepare_state(self, N, Cx, sp, dev, Cc, ctx_shape=None, *, mask_C=0, vq=None):
         """Static buffers (and the captured graph) of one chain shape.  mask_C > 0: the inpainting state of a mask with mask_C channels --
         static fp32 CL buffers for x0 [M, Cx], the mask [M, mask_C] and the per-step q_sample noise [S, M, Cx], plus the [S, 2] q_sample
-        scalar table; it lives under its own key, so a mask-free call never sees it."""
+        scalar table; it lives under its own key, so a mask-free call never sees it.  vq = (codebook or None, temperature): the state of
+        a chain whose update is `gg_ddim_step_vq` -- its scalar table has a fifth column sigma_t * temperature, refreshed here on every
+        call (outside any graph: the steps read their rows in place), and "vq" holds the codebook the steps read in place; also under
+        its own key (quantised or not; the temperature is not part of it), with the codebook's identity in the token."""
         unet = self.model.model.diffusion_model
         sp3 = (1,) * (3 - len(sp)) + tuple(sp)
         S = self.ddim_timesteps.shape[0]
         key = (N, Cx, sp3, Cc, str(dev), ctx_shape) + ((("inpaint", mask_C),) if mask_C else ())
+        if vq is not None:
+            key = key + (("vq", vq[0] is not None),)
         # everything cached below is a function of the schedule (steps, eta -> sigmas) and of the UNet's weights (time-bias
         # table, packed weights baked into the captured graph): a changed schedule or weight version rebuilds the state
         token = (S, tuple(int(v) for v in self.ddim_timesteps), tuple(float(v) for v in self.ddim_sigmas), ops.weights_token(unet))
+        if vq is not None and vq[0] is not None:
+            token = token + ((vq[0].data_ptr(), vq[0]._version, tuple(vq[0].shape)),)
         st = self._graphs.get(key)
         if st is not None and st["token"] == token:
+            if vq is not None:
+                st["scal"][:, 4].copy_(st["scal"][:, 2] * vq[1])
             return st
         steps = torch.tensor(np.flip(self.ddim_timesteps).copy(), dtype=torch.float32, device=dev)
         st = dict(N=N, Cx=Cx, sp3=sp3, Cc=Cc, S=S, token=token,
@@ -705,6 +924,9 @@ class DDIMSampler(object):
                       ip_mask=torch.empty((N,) + sp3 + (mask_C,), dtype=torch.float32, device=dev),
                       ip_noise=torch.empty((S, N) + sp3 + (Cx,), dtype=torch.float32, device=dev),
                       ip_scal=self.q_sample_scalar_table().to(dev))
+        if vq is not None:
+            sc = self.step_scalar_table().to(dev)
+            st.update(vq=vq[0], scal=torch.cat([sc, sc[:, 2:3] * vq[1]], 1).contiguous())          # fp32 product sigma_t * temperature
         self._graphs[key] = st
         return st
 
@@ -747,6 +969,31 @@ class DDIMSampler(object):
         ops.inpaint_blend(st["x"].view(M, Cx), st["ip_x0"].view(M, Cx), st["ip_mask"].view(M, -1), st["ip_noise"][i].view(M, Cx),
                           st["ip_scal"][i], unet_in=st["unet_in"].view(M, -1))
 
+    def _update(self, st, eps, scal, noise=None):
+        """The DDIM update as its own launch on the state's buffers: gg_ddim_step, or gg_ddim_step_vq on a "vq" state (quantised pred_x0
+        and / or a temperature; `scal` is then a row of the five-column table)."""
+        Cx = st["Cx"]
+        M = st["x"].numel() // Cx
+        if "vq" in st:
+            ops.ddim_step_vq(st["x"].view(M, Cx), eps.view(M, -1), scal, st["vq"], noise=noise,
+                             pred_x0_out=st["pred_x0"].view(M, Cx), unet_in=st["unet_in"].view(M, -1))
+        else:
+            ops.ddim_step(st["x"].view(M, Cx), eps.view(M, -1), scal, noise=noise,
+                          pred_x0_out=st["pred_x0"].view(M, Cx), unet_in=st["unet_in"].view(M, -1))
+
+    def _noise(self, st, i, eta, noise_tape, p=0.0):
+        """Step i's noise as a channels-last tensor (None on a deterministic step), after noise_dropout p (ddim.py:202-203)."""
+        if noise_tape is not None:
+            nt = noise_tape[i].to(st["x"].device).float()
+            if p > 0.0:
+                nt = torch.nn.functional.dropout(nt, p=p)
+            nd = nt.ndim - 2
+            return nt.permute((0,) + tuple(range(2, nd + 2)) + (1,)).contiguous()
+        if eta != 0.0:
+            noise = torch.randn_like(st["x"])
+            return torch.nn.functional.dropout(noise, p=p) if p > 0.0 else noise
+        return None
+
     def _step(self, st, ctx_cl, bias, scal, noise):
         """One reverse step on the state's buffers; `bias` / `scal` are rows of the per-schedule tables (ddim.py:165-205)."""
         unet = self.model.model.diffusion_model
@@ -754,14 +1001,13 @@ class DDIMSampler(object):
         M = st["x"].numel() // Cx
         # deterministic steps: the update is the head conv's epilogue where the kernel supports it (Cx == 4 on the box kernel)
         hd = (st["x"].view(M, Cx), scal, st["pred_x0"].view(M, Cx), st["unet_in"].view(M, -1)) \
-            if (noise is None and self.fuse_ddim and Cx == 4) else None
+            if (noise is None and self.fuse_ddim and Cx == 4 and "vq" not in st) else None
         head = unet.forward_cl(CL(st["unet_in"], Cx + Cc), bias, ctx_cl, head_out=st["eps"], head_ddim=hd)
         self.last_step_fused = head.fused_ddim
         if not head.fused_ddim:
-            ops.ddim_step(st["x"].view(M, Cx), st["eps"].view(M, -1), scal, noise=noise,
-                          pred_x0_out=st["pred_x0"].view(M, Cx), unet_in=st["unet_in"].view(M, -1))
+            self._update(st, st["eps"], scal, noise)
 
-    def _run_steps_cfg(self, st, x_T, cfg, eta, noise_tape):
+    def _run_steps_cfg(self, st, x_T, cfg, eta, noise_tape, noise_dropout=0.0):
         """Classifier-free guidance (ddim.py:175-180): e = e_u + s (e_c - e_u).  The reference stacks [uncond, cond] into one batch of 2 N;
         every layer of the UNet is per sample, so two evaluations on the same x with the two conditionings give the same two halves.
         Eager (off the timed path); the update kernel refreshes the conditional UNet input, the unconditional one copies x from it."""
@@ -781,21 +1027,14 @@ class DDIMSampler(object):
             ctx_u = st["ctx"]
         eps_u = torch.empty_like(st["eps"])
         for i in range(st["S"]):
-            noise = None
-            if noise_tape is not None:
-                nt = noise_tape[i].to(st["x"].device).float()
-                nd = nt.ndim - 2
-                noise = nt.permute((0,) + tuple(range(2, nd + 2)) + (1,)).contiguous()
-            elif eta != 0.0:
-                noise = torch.randn_like(st["x"])
+            noise = self._noise(st, i, eta, noise_tape, noise_dropout)
             if "ip_x0" in st:                   # inpainting: both evaluations see the blended x (ddim.py:144-148 precede :175-180)
                 self._blend(st, i)
                 uin_u[..., :Cx].copy_(st["unet_in"][..., :Cx])
             unet.forward_cl(CL(uin_u, Cx + Cc), st["table"][i], ctx_u, head_out=eps_u)
             unet.forward_cl(CL(st["unet_in"], Cx + Cc), st["table"][i], st["ctx"], head_out=st["eps"])
             ops.lincomb4([eps_u, st["eps"]], [1.0 - scale, scale], 1.0, st["eps"])        # (1 - s) e_u + s e_c
-            ops.ddim_step(st["x"].view(M, Cx), st["eps"].view(M, -1), st["scal"][i], noise=noise,
-                          pred_x0_out=st["pred_x0"].view(M, Cx), unet_in=st["unet_in"].view(M, -1))
+            self._update(st, st["eps"], st["scal"][i], noise)
             uin_u[..., :Cx].copy_(st["unet_in"][..., :Cx])
         self.last_step_fused = False
 
@@ -809,7 +1048,7 @@ class DDIMSampler(object):
             self._blend(st, i)
             self._step(st, ctx_cl, st["table"][i], st["scal"][i], None)
 
-    def run_steps(self, st, ctx_cl, eta, noise_tape):
+    def run_steps(self, st, ctx_cl, eta, noise_tape, noise_dropout=0.0):
         S = st["S"]
         if self.chain_graphable(st, ctx_cl, eta, noise_tape):
             # first call: eager (fills the weight-repack caches); afterwards ONE hipGraph replay per chain
@@ -822,13 +1061,7 @@ class DDIMSampler(object):
             st["graph"].replay()
             return
         for i in range(S):
-            noise = None
-            if noise_tape is not None:
-                nt = noise_tape[i].to(st["x"].device).float()
-                nd = nt.ndim - 2
-                noise = nt.permute((0,) + tuple(range(2, nd + 2)) + (1,)).contiguous()
-            elif eta != 0.0:
-                noise = torch.randn_like(st["x"])
+            noise = self._noise(st, i, eta, noise_tape, noise_dropout)
             self._blend(st, i)
             self._step(st, ctx_cl, st["table"][i], st["scal"][i], noise)
 
@@ -843,7 +1076,7 @@ class PLMSSampler(DDIMSampler):
             raise ValueError("ddim_eta must be 0 for PLMS")
         super().make_schedule(ddim_num_steps, ddim_discretize, 0.0, verbose)
 
-    def run_steps(self, st, ctx_cl, eta, noise_tape):
+    def run_steps(self, st, ctx_cl, eta, noise_tape, noise_dropout=0.0):          # eta = 0: no noise, nothing to drop
         unet = self.model.model.diffusion_model
         Cx, Cc, S = st["Cx"], st["Cc"], st["S"]
         xin = CL(st["unet_in"], Cx + Cc)
@@ -853,7 +1086,7 @@ class PLMSSampler(DDIMSampler):
         e_prime = torch.empty_like(eps)
 
         def update(e_cl, scal):
-            ops.ddim_step(x, e_cl.view(M, -1), scal, pred_x0_out=st["pred_x0"].view(M, Cx), unet_in=uin)
+            self._update(st, e_cl, scal)               # quantize_x0 (plms.py:184-185): gg_ddim_step_vq on a "vq" state
 
         for i in range(S):
             self._blend(st, i)                 # inpainting (plms.py:147-150): before the first evaluation, so x_keep holds the blended x

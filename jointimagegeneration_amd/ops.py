@@ -760,6 +760,68 @@ def inpaint_blend(x: torch.Tensor, x0: torch.Tensor, mask: torch.Tensor, noise: 
                                _ptr(unet_in), unet_in.shape[-1] if unet_in is not None else 0, _stream()), "gg_inpaint_blend")
 
 
+def _codebook(codebook: torch.Tensor, what: str) -> Tuple[int, int]:
+    if codebook.dtype != torch.float32 or codebook.dim() != 2 or not codebook.is_contiguous() or not codebook.is_cuda:
+        raise ValueError(f"{what}: the codebook must be a contiguous device fp32 [n_embed, C] tensor, got {codebook.dtype} {tuple(codebook.shape)}")
+    return int(codebook.shape[0]), int(codebook.shape[1])
+
+
+def vq_nearest(rows: torch.Tensor, codebook: torch.Tensor, C: Optional[int] = None, *, idx_out: Optional[torch.Tensor] = None,
+               st_out: Optional[torch.Tensor] = None, want_st: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """Nearest codebook entry of every channels-last row (gg_vq_nearest).  rows fp32 [..., stride] with the channels in [0, C) (C defaults
+    to the codebook's width, stride >= C); codebook fp32 [n_embed, C].  Returns (indices int32 [M], straight-through rows fp32 [M, C] =
+    z + (E[idx] - z), or None with want_st=False).  st_out may be given (fp32 [M, st_stride >= C], or `rows` itself for in place)."""
+    lib = _lib.load()
+    require_gpu(rows, "vq_nearest")
+    n_embed, Ce = _codebook(codebook, "vq_nearest")
+    C = Ce if C is None else C
+    stride = rows.shape[-1]
+    if C != Ce or rows.dtype != torch.float32 or not rows.is_contiguous() or stride < C:
+        raise ValueError(f"vq_nearest: rows must be contiguous fp32 [..., stride >= {Ce}] for a codebook of width {Ce}, got {rows.dtype} "
+                         f"{tuple(rows.shape)} with C={C}")
+    M = rows.numel() // stride
+    if idx_out is None:
+        idx_out = torch.empty(M, dtype=torch.int32, device=rows.device)
+    if st_out is None and want_st:
+        st_out = torch.empty((M, C), dtype=torch.float32, device=rows.device)
+    if idx_out.dtype != torch.int32 or idx_out.numel() != M or not idx_out.is_contiguous():
+        raise ValueError(f"vq_nearest: idx_out must be a contiguous int32 tensor of {M} indices")
+    st_stride = 0
+    if st_out is not None:
+        st_stride = st_out.shape[-1]
+        if st_out.dtype != torch.float32 or not st_out.is_contiguous() or st_stride < C or st_out.numel() != M * st_stride:
+            raise ValueError(f"vq_nearest: st_out must be contiguous fp32 [{M}, stride >= {C}]")
+    check(lib.gg_vq_nearest(rows.data_ptr(), stride, codebook.data_ptr(), n_embed, C, M, idx_out.data_ptr(), _ptr(st_out), st_stride,
+                            _stream()), "gg_vq_nearest")
+    return idx_out, st_out
+
+
+def ddim_step_vq(x: torch.Tensor, eps: torch.Tensor, scalars: torch.Tensor, codebook: Optional[torch.Tensor],
+                 noise: Optional[torch.Tensor] = None, pred_x0_out: Optional[torch.Tensor] = None, unet_in: Optional[torch.Tensor] = None,
+                 idx_out: Optional[torch.Tensor] = None, ancestral: bool = False) -> None:
+    """One reverse step with the prediction of x_0 quantised (gg_ddim_step_vq).  x fp32 CL [M, C] (updated in place); eps fp32 CL
+    [M, stride]; scalars fp32[5] on device: (a_t, a_prev, sigma_t, sqrt(1 - a_t), noise coefficient), or with ancestral=True gg_ddpm_step's
+    five; codebook fp32 [n_embed, C], or None for the step without a quantiser; pred_x0_out receives the quantised prediction."""
+    lib = _lib.load()
+    Cc = x.shape[-1]
+    M = x.numel() // Cc
+    n_embed = 0
+    if codebook is not None:
+        n_embed, Ce = _codebook(codebook, "ddim_step_vq")
+        if Ce != Cc:
+            raise ValueError(f"ddim_step_vq: the codebook has width {Ce}, the state has {Cc} channels")
+    if scalars.numel() < 5 or scalars.dtype != torch.float32 or not scalars.is_contiguous():
+        raise ValueError("ddim_step_vq: scalars must be a contiguous fp32[5] device tensor")
+    for name, t in (("x", x), ("noise", noise), ("pred_x0_out", pred_x0_out)):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != M * Cc):
+            raise ValueError(f"ddim_step_vq: {name} must be contiguous fp32 [{M}, {Cc}], got {t.dtype} {tuple(t.shape)}")
+    if idx_out is not None and (idx_out.dtype != torch.int32 or idx_out.numel() != M or not idx_out.is_contiguous()):
+        raise ValueError(f"ddim_step_vq: idx_out must be a contiguous int32 tensor of {M} indices")
+    check(lib.gg_ddim_step_vq(x.data_ptr(), eps.data_ptr(), eps.shape[-1], _ptr(noise), scalars.data_ptr(), 1 if ancestral else 0,
+                              _ptr(codebook), n_embed, M, Cc, _ptr(idx_out), _ptr(pred_x0_out), _ptr(unet_in),
+                              unet_in.shape[-1] if unet_in is not None else 0, _stream()), "gg_ddim_step_vq")
+
+
 def minmax_normalise(src: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     lib = _lib.load()
     if out is None:

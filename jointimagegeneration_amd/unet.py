@@ -259,7 +259,9 @@ class UNetModel(_UNetBase):
         if num_head_channels == -1:
             assert num_heads != -1, "Either num_heads or num_head_channels has to be set"
         if num_classes is not None or n_embed is not None:
-            raise NotImplementedError("option outside the shipped LDM configurations (configs/latent-diffusion/*.yaml)")
+            named = ", ".join(n for n, v in (("num_classes", num_classes), ("n_embed", n_embed)) if v is not None)
+            raise NotImplementedError(f"option outside the shipped LDM configurations (configs/latent-diffusion/*.yaml): {named}"
+                                      + (" (the predict_codebook_ids head)" if n_embed is not None else ""))
         self.image_size, self.in_channels, self.model_channels, self.out_channels = image_size, in_channels, model_channels, out_channels
         self.num_res_blocks, self.attention_resolutions, self.channel_mult = num_res_blocks, attention_resolutions, channel_mult
         self.dims, self.dtype = dims, torch.float32
