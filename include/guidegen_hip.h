@@ -259,6 +259,10 @@ typedef struct {
 int gg_attention_forward(const gg_attention_desc *desc, void *stream);
 /* Scratch bytes with which gg_attention_forward splits the keys of this shape (0: it never splits it); pointers are not read. */
 int64_t gg_attention_workspace_bytes(const gg_attention_desc *desc);
+/* The launch gg_attention_forward makes for this shape: plan = {keys per K/V tile, key ranges split over workgroups when the
+ * workspace is handed in (1: never), in-workgroup key split 0/1, K/V tiles staged by LDS-DMA 0/1}.  Pointers are not read and
+ * nothing is launched; gg_attention_forward takes its decisions from the same function. */
+int gg_attention_plan(const gg_attention_desc *desc, int32_t plan[4]);
 
 /* LayerNorm over the last dim (nn.LayerNorm eps 1e-5, attention.py:203-205), bf16 rows -> bf16 rows. */
 int gg_layernorm(const void *x, int64_t rows, int32_t C, const float *gamma, const float *beta, float eps,

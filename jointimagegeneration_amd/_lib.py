@@ -66,6 +66,7 @@ SIGNATURES = {
     "gg_groupnorm_scale_shift_acc": (C.c_int, [vp, i32, i32, vp, i32, i32, i32, i64, i32, vp, vp, f32, vp, vp, vp]),
     "gg_attention_forward": (C.c_int, [C.POINTER(AttentionDesc), vp]),
     "gg_attention_workspace_bytes": (i64, [C.POINTER(AttentionDesc)]),
+    "gg_attention_plan": (C.c_int, [C.POINTER(AttentionDesc), C.POINTER(i32)]),
     "gg_layernorm": (C.c_int, [vp, i64, i32, vp, vp, f32, vp, vp]),
     "gg_geglu": (C.c_int, [vp, i64, i32, vp, vp]),
     "gg_add": (C.c_int, [vp, vp, i64, vp, vp]),

@@ -342,11 +342,33 @@ static int attn_ksplit(int D, int KT, long long blocks, int Tkv)
     return s < 2 ? 1 : s;
 }
 
-template <int D, int KT>
-static int launch_attn(AttnParams p, const gg_attention_desc *d, hipStream_t stream)
+// Every host-side decision of one attention launch; gg_attention_plan reports it and launch_attn executes it, so the two cannot drift.
+struct AttnPlan {
+    int KT;          // keys per K/V tile
+    int ksplit;      // cross-workgroup key ranges when the caller hands in the workspace (1: never split)
+    int ws2;         // in-workgroup key split (attn_kernel<D, KT, 2>)
+    int dma;         // K/V tiles staged by LDS-DMA, double buffered
+};
+
+static bool attn_plan(const gg_attention_desc *d, AttnPlan *pl)
 {
-    const long long qtiles = (p.Tq + 63) / 64, blocks = qtiles * p.heads * p.N;
-    int ks = attn_ksplit(D, KT, blocks, p.Tkv);
+    const int D = d->head_dim;
+    if (D != 32 && D != 64 && D != 128 && D != 256 && D != 384 && D != 512) return false;
+    pl->KT = D == 32 ? 256 : D <= 128 ? 64 : 32;
+    pl->dma = D >= 256;
+    const long long blocks = (long long)((d->Tq + 63) / 64) * d->heads * d->N;
+    pl->ksplit = attn_ksplit(D, pl->KT, blocks, d->Tkv);
+    // in-workgroup key split: under-filled grids with at least four K/V tiles per workgroup (the 32x32 attention blocks at batch 1)
+    pl->ws2 = GG_ATTN_WS2 && D < 256 && pl->ksplit == 1 && blocks <= 256 && d->Tkv >= 4 * pl->KT;
+    return true;
+}
+
+template <int D, int KT>
+static int launch_attn(AttnParams p, const gg_attention_desc *d, const AttnPlan &pl, hipStream_t stream)
+{
+    if (pl.KT != KT || pl.dma != (D >= 256) || (pl.ws2 && D >= 256)) GG_FAIL(GG_ERR_UNSUPPORTED, "attention: plan does not match the head_dim %d kernels", D);
+    const long long qtiles = (p.Tq + 63) / 64;
+    int ks = pl.ksplit;
     const long long rows = (long long)p.N * p.heads * ks * p.Tq, need = rows * (D + 2) * 4;
     if (ks > 1 && (!d->workspace || d->workspace_bytes < need)) ks = 1;          // no workspace: the unsplit kernel (slower, same result)
     p.ksplit = ks;
@@ -354,13 +376,10 @@ static int launch_attn(AttnParams p, const gg_attention_desc *d, hipStream_t str
     p.ws_o = (float *)d->workspace;
     p.ws_ml = p.ws_o ? p.ws_o + rows * D : nullptr;
     dim3 grid((unsigned)(qtiles * ks), (unsigned)p.heads, (unsigned)p.N);
-    // in-workgroup key split: under-filled grids with at least four K/V tiles per workgroup (the 32x32 attention blocks at batch 1)
-    bool ws2 = false;
-    if constexpr (D < 256) ws2 = GG_ATTN_WS2 && ks == 1 && blocks <= 256 && p.Tkv >= 4 * KT;
     if constexpr (D < 256) {
-        if (ws2) hipLaunchKernelGGL((attn_kernel<D, KT, 2>), grid, dim3(512), 0, stream, p);
+        if (pl.ws2) hipLaunchKernelGGL((attn_kernel<D, KT, 2>), grid, dim3(512), 0, stream, p);
     }
-    if (!ws2) hipLaunchKernelGGL((attn_kernel<D, KT>), grid, dim3(256), 0, stream, p);
+    if (!pl.ws2) hipLaunchKernelGGL((attn_kernel<D, KT>), grid, dim3(256), 0, stream, p);
     GG_CHECK_LAUNCH();
     if (ks > 1) {
         const long long total = (long long)p.N * p.heads * p.Tq * (D / 4);
@@ -371,13 +390,21 @@ static int launch_attn(AttnParams p, const gg_attention_desc *d, hipStream_t str
     return GG_OK;
 }
 
+extern "C" int gg_attention_plan(const gg_attention_desc *d, int32_t plan[4])
+{
+    AttnPlan pl;
+    if (!d || !plan) GG_FAIL(GG_ERR_BAD_SHAPE, "attention_plan: null pointer");
+    if (d->N <= 0 || d->heads <= 0 || d->Tq <= 0 || d->Tkv <= 0) GG_FAIL(GG_ERR_BAD_SHAPE, "attention_plan: empty extent");
+    if (!attn_plan(d, &pl)) GG_FAIL(GG_ERR_UNSUPPORTED, "attention: head_dim %d not in {32,64,128,256,384,512}", d->head_dim);
+    plan[0] = pl.KT; plan[1] = pl.ksplit; plan[2] = pl.ws2; plan[3] = pl.dma;
+    return GG_OK;
+}
+
 extern "C" int64_t gg_attention_workspace_bytes(const gg_attention_desc *d)
 {
-    if (!d || d->N <= 0 || d->heads <= 0 || d->Tq <= 0 || d->Tkv <= 0) return 0;
-    const int KT = d->head_dim == 32 ? 256 : d->head_dim <= 128 ? 64 : 32;
-    const long long blocks = (long long)((d->Tq + 63) / 64) * d->heads * d->N;
-    const int ks = attn_ksplit(d->head_dim, KT, blocks, d->Tkv);
-    return ks > 1 ? (int64_t)d->N * d->heads * ks * d->Tq * (d->head_dim + 2) * 4 : 0;
+    AttnPlan pl;
+    if (!d || d->N <= 0 || d->heads <= 0 || d->Tq <= 0 || d->Tkv <= 0 || !attn_plan(d, &pl)) return 0;
+    return pl.ksplit > 1 ? (int64_t)d->N * d->heads * pl.ksplit * d->Tq * (d->head_dim + 2) * 4 : 0;
 }
 
 extern "C" int gg_attention_forward(const gg_attention_desc *d, void *stream_)
@@ -394,13 +421,14 @@ extern "C" int gg_attention_forward(const gg_attention_desc *d, void *stream_)
     p.scale_log2 = d->scale * 1.4426950408889634f;
     p.q = (const bf16_t *)d->q; p.k = (const bf16_t *)d->k; p.v = (const bf16_t *)d->v; p.out = (bf16_t *)d->out;
     p.ksplit = 1; p.kchunk = d->Tkv; p.ws_o = nullptr; p.ws_ml = nullptr;
+    AttnPlan pl;
+    if (!attn_plan(d, &pl)) GG_FAIL(GG_ERR_UNSUPPORTED, "attention: head_dim %d not in {32,64,128,256,384,512}", d->head_dim);
     switch (d->head_dim) {
-        case 32: return launch_attn<32, 256>(p, d, stream);
-        case 64: return launch_attn<64, 64>(p, d, stream);
-        case 128: return launch_attn<128, 64>(p, d, stream);
-        case 256: return launch_attn<256, 32>(p, d, stream);
-        case 384: return launch_attn<384, 32>(p, d, stream);
-        case 512: return launch_attn<512, 32>(p, d, stream);
-        default: GG_FAIL(GG_ERR_UNSUPPORTED, "attention: head_dim %d not in {32,64,128,256,384,512}", d->head_dim);
+        case 32: return launch_attn<32, 256>(p, d, pl, stream);
+        case 64: return launch_attn<64, 64>(p, d, pl, stream);
+        case 128: return launch_attn<128, 64>(p, d, pl, stream);
+        case 256: return launch_attn<256, 32>(p, d, pl, stream);
+        case 384: return launch_attn<384, 32>(p, d, pl, stream);
+        default: return launch_attn<512, 32>(p, d, pl, stream);
     }
 }

@@ -94,3 +94,39 @@ def test_dispatch_predicates_are_host_logic_and_follow_the_documented_rules():
     assert lib.gg_conv_runs_halo_tile(ref) == 0
     d, ref = _desc(_lib, 1, 128, 128, 128, 64, 64, (3, 3, 3), stride=2)
     assert lib.gg_conv_runs_halo_tile(ref) == 0
+
+
+def test_attention_plan_is_host_logic_and_pins_the_production_shapes():
+    """gg_attention_plan reads no pointers and launches nothing; gg_attention_forward takes its decisions from the same function.
+    plan = {key tile, key ranges over workgroups given a workspace, in-workgroup key split, LDS-DMA staging}."""
+    import ctypes as C
+    import __graft_entry__ as ge
+    from jointimagegeneration_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        ge.build()
+    lib = _lib.load()
+
+    def plan(N, heads, D, Tq, Tkv):
+        d = _lib.AttentionDesc()
+        d.N, d.heads, d.head_dim, d.Tq, d.Tkv = N, heads, D, Tq, Tkv
+        out = (C.c_int32 * 4)()
+        rc = lib.gg_attention_plan(C.byref(d), out)
+        ws = lib.gg_attention_workspace_bytes(C.byref(d))
+        if rc == 0:                                      # the workspace query is the same decision
+            assert ws == (N * heads * out[1] * Tq * (D + 2) * 4 if out[1] > 1 else 0)
+        return rc, tuple(out)
+
+    # latent UNet, 32x32 level at batch 1 (10 heads of 32 channels, T = 1024): 160 workgroups -> the in-workgroup key split
+    assert plan(1, 10, 32, 1024, 1024) == (0, (256, 1, 1, 0))
+    assert plan(8, 10, 32, 1024, 1024) == (0, (256, 1, 0, 0))           # batch 8 fills the chip: plain kernel
+    assert plan(1, 20, 32, 256, 256) == (0, (256, 1, 0, 0))             # 16x16 level: one key tile
+    # autoencoder mid-block attention: one head of 512 channels over 64x64 tokens: LDS-DMA, keys split four ways
+    assert plan(1, 1, 512, 4096, 4096) == (0, (32, 4, 0, 1))
+    assert plan(4, 1, 512, 4096, 4096) == (0, (32, 1, 0, 1))            # 256 workgroups: no split
+    assert plan(1, 1, 384, 1030, 1030) == (0, (32, 8, 0, 1))
+    assert plan(1, 1, 512, 255, 255) == (0, (32, 1, 0, 1))              # fewer than 8 key tiles: never split
+    # cross attention (SpatialTransformer): Tq != Tkv, a short context
+    assert plan(1, 5, 64, 1024, 77) == (0, (64, 1, 0, 0))
+    assert plan(1, 5, 64, 1024, 256) == (0, (64, 1, 1, 0))
+    assert plan(1, 2, 128, 130, 130) == (0, (64, 1, 0, 0))
+    assert plan(1, 1, 48, 64, 64)[0] < 0 and plan(1, 1, 64, 0, 64)[0] < 0          # unsupported head dim, empty extent
