@@ -366,6 +366,26 @@ int gg_ddim_step_vq(float *x, const float *eps, int32_t eps_stride, const float 
                     const float *codebook, int32_t n_embed, int64_t M, int32_t C, int32_t *idx_out, float *pred_x0_out,
                     void *unet_in, int32_t unet_in_stride, void *stream);
 
+/* Patch-wise evaluation (LatentDiffusion.split_input_params, ddpm.py:573-660), gg_fold.hip.  Geometry of torch.nn.Unfold / Fold with
+ * dilation 1 and padding 0: Ly = (H - kh) / sy + 1, Lx = (W - kw) / sx + 1, crop l = ly * Lx + lx starts at (ly * sy, lx * sx); crop l
+ * of sample n is row l * N + n of the crop batch.
+ * gg_unfold_cl: src channels-last [N, H, W, src_stride] (GG_F32 or GG_BF16, channels [0, C) are read) -> dst channels-last
+ *   [L * N, kh, kw, dst_stride], channels [dst_c_offset, dst_c_offset + C); every other lane of dst is left as it is.  A pure copy;
+ *   fp32 -> bf16 converts with the cast gg_ddim_step uses for its unet_in rows (fp32 -> fp32, fp32 -> bf16, bf16 -> bf16; any other
+ *   pair: GG_ERR_UNSUPPORTED).  Pixels past the last whole crop are not read.
+ * gg_fold_weighted_cl: crops fp32 [L * N, kh, kw, crop_stride] -> out fp32 [N, H, W, out_stride], channels [0, C):
+ *   out = sum_l(o[l] * w[l]) / sum_l(w[l]) over the crops covering a pixel, w[l][ky, kx] = weight[ky * kw + kx] * tie[l] (that product
+ *   rounded to fp32 first; tie NULL: w = weight).  Both sums start from 0.0f and visit the crops in DESCENDING l (descending ly, then
+ *   descending lx); every product is rounded before it is added (no contraction); the last operation is an IEEE fp32 division.  This
+ *   is the order of ATen's CPU col2im, so identical fp32 crops give the reference's fold(o * weighting) / normalization bit for bit.
+ *   A gather (one work item per output pixel and 16-byte channel vector): no atomics, deterministic.  A geometry that leaves a pixel
+ *   uncovered ((H - kh) % sy != 0, (W - kw) % sx != 0, or a stride above the crop extent) is GG_ERR_BAD_SHAPE.  Lanes of out past C
+ *   are not written.  Both: no allocation, no synchronisation, capturable; unaligned rows take an element-wise path. */
+int gg_unfold_cl(const void *src, int32_t src_dtype, int32_t N, int32_t H, int32_t W, int32_t src_stride, int32_t C, void *dst,
+                 int32_t dst_dtype, int32_t dst_stride, int32_t dst_c_offset, int32_t kh, int32_t kw, int32_t sy, int32_t sx, void *stream);
+int gg_fold_weighted_cl(const float *crops, int32_t crop_stride, const float *weight, const float *tie, float *out, int32_t out_stride,
+                        int32_t N, int32_t H, int32_t W, int32_t C, int32_t kh, int32_t kw, int32_t sy, int32_t sx, void *stream);
+
 /* PLMS multistep combination of noise estimates (ldm/models/diffusion/plms.py:218-232), fp32, evaluated left to right:
  *   out = (c0*e0 + c1*e1 + c2*e2 + c3*e3) / denom ; e1..e3 may be NULL (skipped). */
 int gg_lincomb4(const float *e0, const float *e1, const float *e2, const float *e3, float c0, float c1, float c2, float c3,

@@ -7,11 +7,13 @@ Mirrors the sampling surface of (paths relative to the reference tree, latentdif
   ema_scope), ldm/modules/ema.py (LitEma name mangling), ldm/models/diffusion/ddim.py:11-205 (DDIMSampler),
   ldm/modules/encoders/modules.py:287-289 (IdentityEncoder).
 VQ first stage: ldm/models/autoencoder.py:18-131,283-301,464-481 (VQModel, VQModelInterface, IdentityFirstStage) with taming's
-VectorQuantizer.  Training, logging and the fold/unfold patch path are out of scope.
+VectorQuantizer.  Patch-wise evaluation (`split_input_params`, ddpm.py:573-660,718-776,839-876,915-997): SplitPlan / SplitUNet below.
+Training and logging are out of scope.
 """
 from __future__ import annotations
 
 from contextlib import contextmanager
+from dataclasses import dataclass
 from typing import Any, Dict, List, Optional, Sequence
 
 import numpy as np
@@ -442,6 +444,137 @@ class LitEma(nn.Module):
                 p.copy_(c)
 
 
+# ================================================================================================ patch-wise evaluation
+SPLIT_FIRST_STAGE_BATCH = 4          # rows of the crop batch (crop x sample) that go through the first stage in one call
+SPLIT_CONCAT_COND_KEYS = ("image", "LR_image", "segmentation", "bbox_img")      # cond_stage_keys whose conditioning is cut into crops (ddpm.py:930)
+
+
+def delta_border(h: int, w: int) -> torch.Tensor:
+    """Normalised distance to the nearest border, 0 at the border and 0.5 at the centre, fp32 [h, w].  The distance is separable: per
+    axis min(i / (n - 1), 1 - i / (n - 1)) in fp32, then the smaller of the two axes.  min is exact, so the table has the bits of the
+    reference's (ddpm.py:581-593), which takes the same quotients and complements in another order of minima."""
+    def axis(n):
+        f = torch.arange(n, dtype=torch.float32) / float(n - 1)
+        return torch.minimum(f, 1.0 - f)
+    return torch.minimum(axis(h).view(h, 1), axis(w).view(1, w)).contiguous()
+
+
+@dataclass
+class SplitPlan:
+    """Geometry and weight tables of one patch-wise call (what the reference's get_fold_unfold returns as Fold / Unfold modules and two
+    tensors).  Input side: crops kh x kw at stride sy x sx cut from H x W, L = Ly * Lx of them; output side (o*): the extents the crop
+    RESULTS are folded at (x uf for a decode, / df for an encode).  weight fp32 [okh, okw]: the clipped border distance; tie fp32 [L] or
+    None: the clipped border distance of the crop grid (tie_braker).  Both live on the host; `on(device)` caches device copies."""
+    H: int
+    W: int
+    kh: int
+    kw: int
+    sy: int
+    sx: int
+    Ly: int
+    Lx: int
+    oH: int
+    oW: int
+    okh: int
+    okw: int
+    osy: int
+    osx: int
+    weight: torch.Tensor
+    tie: Optional[torch.Tensor]
+
+    @property
+    def L(self) -> int:
+        return self.Ly * self.Lx
+
+    def weighting(self) -> torch.Tensor:
+        """fp32 [okh * okw, L]: the reference's `weighting`, the product rounded to fp32 as get_weighting forms it."""
+        w = self.weight.reshape(1, self.okh * self.okw, 1).repeat(1, 1, self.L)
+        if self.tie is not None:
+            w = w * self.tie.view(1, 1, self.L)
+        return w[0]
+
+    def normalization(self) -> torch.Tensor:
+        """fp32 [oH, oW]: fold(weighting), summed from 0 in descending crop order -- the order of torch's CPU Fold and of
+        gg_fold_weighted_cl."""
+        w = self.weighting().view(self.okh, self.okw, self.L)
+        n = torch.zeros(self.oH, self.oW)
+        for l in range(self.L - 1, -1, -1):
+            y0, x0 = (l // self.Lx) * self.osy, (l % self.Lx) * self.osx
+            n[y0:y0 + self.okh, x0:x0 + self.okw] += w[:, :, l]
+        return n
+
+    def on(self, device):
+        cache = self.__dict__.setdefault("_dev", {})
+        key = str(device)
+        if key not in cache:
+            cache[key] = (self.weight.to(device).contiguous(), self.tie.to(device).contiguous() if self.tie is not None else None)
+        return cache[key]
+
+
+class SplitUNet:
+    """The UNet evaluated on overlapping crops (apply_model with split_input_params, ddpm.py:915-997): per call one gg_unfold_cl of the
+    fp32 state into the crop batch's UNet input (fp32 -> bf16, channels [0, Cx)), ONE UNet forward at batch L * N (crop l of sample n at
+    row l * N + n; every layer is per sample, so this is the reference's loop over crops), one gg_fold_weighted_cl of the head conv's
+    fp32 output into the full-size eps.  Concat conditioning is cut into crops once per `bind`, cross-attention context is repeated per
+    crop.  All buffers are static, so a chain of calls is capturable."""
+
+    def __init__(self, model, N: int, Cx: int, Cc: int, sp: Sequence[int], device):
+        if len(sp) != 2:
+            raise NotImplementedError(f"split_input_params: the patch-wise path is 2-D, the latent has spatial shape {tuple(sp)}")
+        par = model.split_input_params
+        self.plan = model.get_fold_unfold((N, Cx) + tuple(sp), par["ks"], par["stride"])
+        self.N, self.Cx, self.Cc, self.device = N, Cx, Cc, device
+        self.B = self.plan.L * N
+        unet = model.model.diffusion_model
+        p = self.plan
+        self.eps = torch.empty((self.B, 1, p.kh, p.kw, pad32(unet.out_channels)), dtype=torch.float32, device=device)
+        self.inputs: Dict[int, Any] = {}
+        self.contexts: Dict[int, Any] = {}
+
+    def time_bias_table(self, unet, steps: torch.Tensor) -> torch.Tensor:
+        return unet.time_bias_table(steps, self.B)          # the rows of a step are equal for all samples: repeated per crop
+
+    def bind(self, uin: torch.Tensor, ctx: Optional[CL] = None):
+        """(Re)cut the concat conditioning held in channels [Cx, Cx + Cc) of the full-size UNet input `uin` into the crop batch's input
+        buffer, and repeat the context per crop.  Outside any graph; the buffers keep their addresses.  One crop buffer is kept per
+        distinct `uin` (and one repeated context per distinct `ctx`) for as long as this object lives, so a caller that keeps the
+        SplitUNet binds static buffers of its own, never per-call temporaries."""
+        p = self.plan
+        ent = self.inputs.get(id(uin))
+        if ent is None or ent[0] is not uin:
+            ent = (uin, torch.zeros((self.B, 1, p.kh, p.kw, uin.shape[-1]), dtype=uin.dtype, device=uin.device))
+            self.inputs[id(uin)] = ent
+        if self.Cc:
+            src = uin.view(self.N, p.H, p.W, uin.shape[-1])[..., self.Cx:self.Cx + self.Cc]
+            ops.unfold_cl(src, self.Cc, p.kh, p.kw, p.sy, p.sx, out=ent[1].view(self.B, p.kh, p.kw, -1), c_offset=self.Cx)
+        if ctx is not None:
+            c = self.contexts.get(id(ctx.t))
+            if c is None or c[0] is not ctx.t:
+                c = (ctx.t, CL(ctx.t.repeat((p.L,) + (1,) * (ctx.t.dim() - 1)), ctx.C))
+                self.contexts[id(ctx.t)] = c
+            else:
+                c[1].t.copy_(ctx.t.repeat((p.L,) + (1,) * (ctx.t.dim() - 1)))
+
+    def __call__(self, unet, x: torch.Tensor, uin: torch.Tensor, bias_row: torch.Tensor, ctx: Optional[CL], out: torch.Tensor) -> None:
+        p = self.plan
+        buf = self.inputs[id(uin)][1]
+        ops.unfold_cl(x.view(self.N, p.H, p.W, self.Cx), self.Cx, p.kh, p.kw, p.sy, p.sx, out=buf.view(self.B, p.kh, p.kw, -1), c_offset=0)
+        unet.forward_cl(CL(buf, self.Cx + self.Cc), bias_row, self.contexts[id(ctx.t)][1] if ctx is not None else None, head_out=self.eps)
+        w, t = p.on(self.eps.device)
+        ops.fold_weighted_cl(self.eps.view(self.B, p.kh, p.kw, -1), unet.out_channels, w, t, out.view(self.N, p.H, p.W, -1),
+                             p.kh, p.kw, p.sy, p.sx)
+
+
+def unet_eps(unet, split: Optional[SplitUNet], x: torch.Tensor, uin: torch.Tensor, C: int, bias_row: torch.Tensor, ctx: Optional[CL],
+             out: torch.Tensor, head_ddim: Optional[tuple] = None) -> Optional[CL]:
+    """The one place where the samplers obtain eps: the UNet on the full-size input `uin` (returns the head conv's CL, whose epilogue may
+    have applied the DDIM update), or with `split` on crops of the fp32 state `x`, folded into `out` (returns None: no fused update)."""
+    if split is None:
+        return unet.forward_cl(CL(uin, C), bias_row, ctx, head_out=out, head_ddim=head_ddim)
+    split(unet, x, uin, bias_row, ctx, out)
+    return None
+
+
 class DiffusionWrapper(nn.Module):
     def __init__(self, diff_model_config, conditioning_key):
         super().__init__()
@@ -562,22 +695,177 @@ class LatentDiffusion(nn.Module):
             c = getattr(self.cond_stage_model, self.cond_stage_forward)(c)
         return c
 
+    # ---- patch-wise evaluation (split_input_params)
+    def get_weighting(self, h, w, Ly, Lx, device=None):
+        """The reference's weighting tensor fp32 [1, h * w, Ly * Lx] (ddpm.py:595-610): border distance clipped to [clip_min_weight,
+        clip_max_weight], times -- with tie_braker -- the clipped border distance of the crop grid."""
+        weight, tie = self._weight_tables(h, w, Ly, Lx)
+        weighting = weight.view(1, h * w, 1).repeat(1, 1, Ly * Lx)
+        if tie is not None:
+            weighting = weighting * tie.view(1, 1, Ly * Lx)
+        return weighting if device is None else weighting.to(device)
+
+    def _weight_tables(self, h, w, Ly, Lx):
+        par = self.split_input_params
+        if h < 2 or w < 2:
+            raise ValueError(f"split_input_params: crops of extent 1 are not supported (ks -> {h} x {w}: the border distance divides 0 by 0, "
+                             "ddpm.py:588-589)")
+        weight = torch.clip(delta_border(h, w), par["clip_min_weight"], par["clip_max_weight"])
+        tie = None
+        if par.get("tie_braker", False):
+            if Ly < 2 or Lx < 2:
+                raise ValueError(f"split_input_params: tie_braker needs at least 2 crops per axis, got {Ly} x {Lx} (the crop grid's border "
+                                 "distance divides 0 by 0, ddpm.py:602)")
+            tie = torch.clip(delta_border(Ly, Lx), par["clip_min_tie_weight"], par["clip_max_tie_weight"]).reshape(Ly * Lx)
+        return weight.contiguous(), tie
+
+    def get_fold_unfold(self, x, kernel_size, stride, uf=1, df=1) -> SplitPlan:
+        """The plan of one patch-wise call on `x` (a [N, C, H, W] tensor or its shape): the reference's three cases (ddpm.py:612-660),
+        uf > 1 folding the results at ks * uf / stride * uf on H * uf x W * uf (decode), df > 1 at ks // df (encode).  Refused here, on
+        the host: ks of 1, crops larger than the input, a geometry that leaves pixels uncovered (the reference divides 0 by 0 there),
+        and uf / df != 1 with non-square ks (the reference builds its second Fold from ks[0] twice)."""
+        shape = tuple(x.shape) if isinstance(x, torch.Tensor) else tuple(x)
+        if len(shape) != 4:
+            raise NotImplementedError(f"split_input_params: the patch-wise path is 2-D ([N, C, H, W]), got shape {shape}")
+        H, W = int(shape[2]), int(shape[3])
+        kh, kw = (int(v) for v in kernel_size)
+        sy, sx = (int(v) for v in stride)
+        uf, df = int(uf), int(df)
+        if (uf > 1 and df > 1) or uf < 1 or df < 1:
+            raise NotImplementedError(f"split_input_params: uf = {uf} with df = {df} (ddpm.py:659)")
+        if min(sy, sx) < 1 or kh > H or kw > W:
+            raise ValueError(f"split_input_params: ks {(kh, kw)} at stride {(sy, sx)} does not fit the input {H} x {W}")
+        if (H - kh) % sy != 0 or (W - kw) % sx != 0 or ((H > kh) and sy > kh) or ((W > kw) and sx > kw):
+            raise ValueError(f"split_input_params: ks {(kh, kw)} at stride {(sy, sx)} leaves pixels of the {H} x {W} input uncovered "
+                             "(the reference's normalisation is 0 there and it divides 0 by 0): (H - ks) % stride must be 0")
+        if (uf > 1 or df > 1) and kh != kw:
+            raise NotImplementedError(f"split_input_params: vqf = {max(uf, df)} needs square ks, got {(kh, kw)} (the reference builds its "
+                                      "second Fold from ks[0] twice, ddpm.py:635,647)")
+        if df > 1 and any(v % df for v in (kh, kw, sy, sx, H, W)):
+            raise ValueError(f"split_input_params: vqf = {df} does not divide ks {(kh, kw)}, stride {(sy, sx)} and the input {H} x {W}")
+        Ly, Lx = (H - kh) // sy + 1, (W - kw) // sx + 1
+        okh, okw, osy, osx, oH, oW = ((v * uf) // df for v in (kh, kw, sy, sx, H, W))
+        weight, tie = self._weight_tables(okh, okw, Ly, Lx)
+        return SplitPlan(H, W, kh, kw, sy, sx, Ly, Lx, oH, oW, okh, okw, osy, osx, weight, tie)
+
+    def _split_reduced(self, h, w):
+        """ks / stride of split_input_params, reduced to the input as the first-stage paths do (ddpm.py:733-739)."""
+        ks, stride = tuple(self.split_input_params["ks"]), tuple(self.split_input_params["stride"])
+        if ks[0] > h or ks[1] > w:
+            ks = (min(ks[0], h), min(ks[1], w))
+        if stride[0] > h or stride[1] > w:
+            stride = (min(stride[0], h), min(stride[1], w))
+        return ks, stride
+
+    def split_check_cond(self, cond, return_ids=False) -> None:
+        """Host-side refusals of the patch-wise apply_model, by name and before any launch (ddpm.py:915-982)."""
+        if return_ids:
+            raise NotImplementedError("split_input_params: return_ids is not supported (the reference asserts `not return_ids`, ddpm.py:917)")
+        if self.cond_stage_key == "coordinates_bbox":
+            raise NotImplementedError("split_input_params: cond_stage_key 'coordinates_bbox' (per-crop bounding-box tokens) is not supported")
+        ck = self.model.conditioning_key
+        if not isinstance(cond, dict):
+            cond = {("c_concat" if ck == "concat" else "c_crossattn"): cond if isinstance(cond, list) else [cond]}
+        if ck == "hybrid" or len(cond) != 1:
+            raise NotImplementedError(f"split_input_params: hybrid conditioning / more than one conditioning entry is not supported (got "
+                                      f"{sorted(cond)} with conditioning_key '{ck}'; the reference asserts len(cond) == 1, ddpm.py:916)")
+        key, val = next(iter(cond.items()))
+        val = val if isinstance(val, list) else [val]
+        if len(val) != 1:
+            raise NotImplementedError(f"split_input_params: {key} holds {len(val)} tensors, the reference asserts one (ddpm.py:933)")
+        cut = self.cond_stage_key in SPLIT_CONCAT_COND_KEYS and bool(ck)
+        if key == "c_concat" and val[0] is not None and not cut:
+            raise NotImplementedError(f"split_input_params: concat conditioning is cut into crops only for cond_stage_key in "
+                                      f"{list(SPLIT_CONCAT_COND_KEYS)}, got '{self.cond_stage_key}' (the reference passes the full-size tensor "
+                                      "to every crop and fails in torch.cat)")
+        if key == "c_crossattn" and val[0] is not None and cut:
+            raise NotImplementedError(f"split_input_params: cross-attention conditioning under cond_stage_key '{self.cond_stage_key}' is not "
+                                      "supported (the reference unfolds the context as if it were an image)")
+
+    def _first_stage_crops(self, x, plan: SplitPlan, run, C_out: int, what: str, quantizer=None):
+        """x [N, C, H, W] fp32 -> crops -> `run(CL of a chunk of the crop batch)` -> fp32 CL results -> weighted fold -> [N, C_out, oH, oW].
+        run None: an identity first stage, the crops themselves are folded.  quantizer: the crops' fp32 rows go through its
+        quantize_rows before `run` (VQModelInterface.decode).  At most SPLIT_FIRST_STAGE_BATCH rows of the crop batch are inside the
+        first stage at a time, which bounds its activations.  Held for the whole call, and growing with L * N: the crop batch's input
+        `buf` in the first stage's padded rows (pad32(C) lanes per crop pixel) and of each result the C_out logical channels `o`."""
+        ops.require_gpu(x, what)
+        N, C = int(x.shape[0]), int(x.shape[1])
+        dev = x.device
+        B = plan.L * N
+        geom = (plan.kh, plan.kw, plan.sy, plan.sx)
+        x_cl = x.float().permute(0, 2, 3, 1).contiguous()                              # plumbing: layout copy
+        o = torch.empty((B, plan.okh, plan.okw, C_out), dtype=torch.float32, device=dev)
+        if run is None:
+            if (plan.okh, plan.okw) != (plan.kh, plan.kw):
+                raise ValueError(f"{what}: an identity first stage returns {plan.kh} x {plan.kw} crops, vqf asks for {plan.okh} x {plan.okw}")
+            ops.unfold_cl(x_cl, C, *geom, out=o)
+        else:
+            buf = torch.zeros((B, 1, plan.kh, plan.kw, pad32(C)), dtype=torch.float32 if ops.FP32 else torch.bfloat16, device=dev)
+            rows = buf.view(B, plan.kh, plan.kw, -1)
+            if quantizer is None:
+                ops.unfold_cl(x_cl, C, *geom, out=rows)                                 # fp32 -> the first stage's dtype on the way
+            else:
+                crops = ops.unfold_cl(x_cl, C, *geom)                                   # fp32: the quantiser's input and output
+                quantizer.quantize_rows(crops.view(-1, C), st_out=crops.view(-1, C))
+                rows[..., :C].copy_(crops)                                              # plumbing: cast into the padded rows
+            step = max(1, int(SPLIT_FIRST_STAGE_BATCH))
+            for r0 in range(0, B, step):
+                res = run(CL(buf[r0:r0 + step], C))
+                if tuple(res.t.shape[2:4]) != (plan.okh, plan.okw) or res.C != C_out:
+                    raise ValueError(f"{what}: the first stage returned crops {tuple(res.t.shape[2:4])} with {res.C} channels, the fold expects "
+                                     f"{(plan.okh, plan.okw)} with {C_out} (vqf = {self.split_input_params['vqf']})")
+                o[r0:r0 + step].copy_(res.t[:, 0, :, :, :C_out])
+        out = torch.empty((N, plan.oH, plan.oW, C_out), dtype=torch.float32, device=dev)
+        w, t = plan.on(dev)
+        ops.fold_weighted_cl(o, C_out, w, t, out, plan.okh, plan.okw, plan.osy, plan.osx)
+        return out.permute(0, 3, 1, 2).contiguous()
+
+    def _split_first_stage(self) -> bool:
+        return hasattr(self, "split_input_params") and bool(self.split_input_params.get("patch_distributed_vq", False))
+
     @torch.no_grad()
     def decode_first_stage(self, z, predict_cids=False, force_not_quantize=False):
+        """first_stage_model.decode(z / scale_factor); with split_input_params["patch_distributed_vq"] crop by crop (ddpm.py:727-766):
+        z is cut by gg_unfold_cl, the crops are decoded SPLIT_FIRST_STAGE_BATCH at a time and folded at ks * vqf / stride * vqf."""
         if predict_cids:
             raise NotImplementedError("decode_first_stage: predict_cids is not supported (it needs the UNet's codebook-id head)")
         if self.no_first_stage:
             return z
         z = 1.0 / self.scale_factor * z
-        if isinstance(self.first_stage_model, VQModelInterface):
-            return self.first_stage_model.decode(z, force_not_quantize=force_not_quantize)
-        return self.first_stage_model.decode(z)
+        fs = self.first_stage_model
+        if self._split_first_stage():
+            ks, stride = self._split_reduced(z.shape[2], z.shape[3])
+            plan = self.get_fold_unfold(z, ks, stride, uf=self.split_input_params["vqf"])
+            what = "decode_first_stage (split_input_params)"
+            if isinstance(fs, IdentityFirstStage):
+                return self._first_stage_crops(z, plan, None, z.shape[1], what)
+            if not isinstance(fs, (AutoencoderKL, VQModel)):
+                raise NotImplementedError(f"{what}: first stage {type(fs).__name__} has no channels-last decode path")
+            quantizer = fs.quantize if isinstance(fs, VQModelInterface) and not force_not_quantize else None
+            return self._first_stage_crops(z, plan, fs.decode_cl, fs.decoder.conv_out.weight.shape[0], what, quantizer)
+        if isinstance(fs, VQModelInterface):
+            return fs.decode(z, force_not_quantize=force_not_quantize)
+        return fs.decode(z)
 
     @torch.no_grad()
     def encode_first_stage(self, x):
-        """first_stage_model.encode(x): the reference's path without `split_input_params` (ddpm.py:839-893), which is refused."""
-        if hasattr(self, "split_input_params"):
-            raise NotImplementedError("encode_first_stage: split_input_params (the patch-wise fold/unfold path) is not supported")
+        """first_stage_model.encode(x); with split_input_params["patch_distributed_vq"] crop by crop (ddpm.py:839-874) for first stages
+        whose encode returns a tensor: the image is cut at ks / stride, the crops are encoded and folded at ks // vqf / stride // vqf.
+        AutoencoderKL is refused there: its encode returns a distribution per crop, which the reference stacks and fails on."""
+        if self._split_first_stage() and not self.no_first_stage:
+            fs = self.first_stage_model
+            what = "encode_first_stage (split_input_params)"
+            if isinstance(fs, AutoencoderKL):
+                raise NotImplementedError(f"{what}: AutoencoderKL is not supported (its encode returns a DiagonalGaussianDistribution per "
+                                          "crop; the reference stacks them with torch.stack and fails)")
+            if not isinstance(fs, (VQModelInterface, IdentityFirstStage)):
+                raise NotImplementedError(f"{what}: first stage {type(fs).__name__} is not supported (VQModelInterface, IdentityFirstStage)")
+            self.split_input_params["original_image_size"] = x.shape[-2:]
+            ks, stride = self._split_reduced(x.shape[2], x.shape[3])
+            plan = self.get_fold_unfold(x, ks, stride, df=self.split_input_params["vqf"])
+            if isinstance(fs, IdentityFirstStage):
+                return self._first_stage_crops(x, plan, None, x.shape[1], what)
+            return self._first_stage_crops(x, plan, fs.prequant_cl, fs.embed_dim, what)
         if self.no_first_stage:
             return x
         return self.first_stage_model.encode(x)
@@ -598,7 +886,31 @@ class LatentDiffusion(nn.Module):
                 cond = [cond]
             key = "c_concat" if self.model.conditioning_key == "concat" else "c_crossattn"
             cond = {key: cond}
+        if hasattr(self, "split_input_params"):
+            return self._apply_model_split(x_noisy, t, cond, return_ids)
         return self.model(x_noisy, t, **cond)
+
+    @torch.no_grad()
+    def _apply_model_split(self, x_noisy, t, cond, return_ids):
+        """apply_model on overlapping crops (ddpm.py:915-997) through SplitUNet: the same three launches per call as in the samplers."""
+        self.split_check_cond(cond, return_ids)
+        ops.require_gpu(x_noisy, "apply_model (split_input_params)")
+        unet = self.model.diffusion_model
+        N, Cx = int(x_noisy.shape[0]), int(x_noisy.shape[1])
+        cc = cond.get("c_concat", [None])[0]
+        ctx = cond.get("c_crossattn", [None])[0]
+        Cc = int(cc.shape[1]) if cc is not None else 0
+        split = SplitUNet(self, N, Cx, Cc, tuple(x_noisy.shape[2:]), x_noisy.device)
+        xin = ops.to_cl(x_noisy.float(), c_pad=pad32(Cx + Cc))
+        if cc is not None:
+            ops.to_cl(cc.to(x_noisy.device).float(), out=xin.t, c_offset=Cx, zero_fill=False)
+        ctx_cl = unet.context_cl(ctx.to(x_noisy.device)) if ctx is not None else None
+        split.bind(xin.t, ctx_cl)
+        x_cl = x_noisy.float().permute(0, 2, 3, 1).contiguous()                         # plumbing: layout copy
+        out = torch.empty((N, 1) + tuple(x_noisy.shape[2:]) + (pad32(unet.out_channels),), dtype=torch.float32, device=x_noisy.device)
+        bias = unet.time_bias_rows(t.to(x_noisy.device).float().repeat(split.plan.L))
+        split(unet, x_cl, xin.t, bias, ctx_cl, out)
+        return ops.from_cl(CL(out, unet.out_channels), 2)
 
     @torch.no_grad()
     def p_sample_loop(self, cond, shape, return_intermediates=False, x_T=None, verbose=True, callback=None, timesteps=None,
@@ -614,6 +926,9 @@ class LatentDiffusion(nn.Module):
         quantize_denoised (ddpm.py:1081-1082): x_recon goes through the first stage's quantiser before the posterior mean; the step is
         then one `gg_ddim_step_vq` (ancestral form) in place of `gg_ddpm_step`."""
         codebook = first_stage_codebook(self, "p_sample_loop: quantize_denoised", shape[1]) if quantize_denoised else None
+        if hasattr(self, "split_input_params"):                      # refusals of the patch-wise path, before any launch
+            self.split_check_cond(cond)
+            self.get_fold_unfold(tuple(shape), self.split_input_params["ks"], self.split_input_params["stride"])
         dev = self.device
         unet = self.model.diffusion_model
         ck = self.model.conditioning_key
@@ -641,19 +956,22 @@ class LatentDiffusion(nn.Module):
             ops.to_cl(c_concat.float(), out=unet_in, c_offset=Cx, zero_fill=False)
         ctx_cl = unet.context_cl(context) if context is not None else None
         ts = torch.arange(T - 1, -1, -1, device=dev)
-        table = unet.time_bias_table(ts.float(), N)
+        split = None
+        if hasattr(self, "split_input_params"):                      # patch-wise eps (ddpm.py:915-997): crops of x, one UNet forward, fold
+            split = SplitUNet(self, N, Cx, Cc, sp, dev)
+            split.bind(unet_in, ctx_cl)
+        table = unet.time_bias_table(ts.float(), N) if split is None else split.time_bias_table(unet, ts.float())
         sig = torch.exp(0.5 * self.posterior_log_variance_clipped[ts]) * (ts > 0).float()
         scal = torch.stack([self.sqrt_recip_alphas_cumprod[ts], self.sqrt_recipm1_alphas_cumprod[ts], self.posterior_mean_coef1[ts],
                             self.posterior_mean_coef2[ts], sig], 1).float().contiguous()
         eps = torch.empty((N,) + sp3 + (pad32(unet.out_channels),), dtype=torch.float32, device=dev)
         M = x.numel() // Cx
-        xin = CL(unet_in, Cx + Cc)
         if ip is not None:
             x0_cl = ip[0].to(dev).permute(perm).contiguous()
             mask_cl = ip[1].to(dev).permute(perm).contiguous()
             qscal = torch.stack([self.sqrt_alphas_cumprod[ts], self.sqrt_one_minus_alphas_cumprod[ts]], 1).contiguous()
         for i in range(T):
-            unet.forward_cl(xin, table[i], ctx_cl, head_out=eps)
+            unet_eps(unet, split, x, unet_in, Cx + Cc, table[i], ctx_cl, eps)
             if noise_tape is not None:
                 nz = noise_tape[i].to(dev).float().permute(perm).contiguous()
             else:
@@ -833,13 +1151,19 @@ class DDIMSampler(object):
             # these run in gg_ddim_step_vq / on the device generator only; refused on the host, before any launch
             raise NotImplementedError(f"{type(self).__name__}.sample: {', '.join(asked)} not supported for a model on {self.model.device} "
                                       "(the step kernel and the dropout's generator are the GPU's; there is no CPU path)")
+        cfg = None
+        if unconditional_conditioning is not None and unconditional_guidance_scale != 1.0:
+            cfg = (unconditional_conditioning, float(unconditional_guidance_scale))
+        par = getattr(self.model, "split_input_params", None)
+        if par is not None:                                    # refusals of the patch-wise path: conditioning and geometry, before any launch
+            self.model.split_check_cond(conditioning)
+            if cfg is not None:
+                self.model.split_check_cond(cfg[0])
+            self.model.get_fold_unfold(size, par["ks"], par["stride"])
         ip = inpaint_operands(mask, x0, size, mask_noise_tape, S)
         self.make_schedule(ddim_num_steps=S, ddim_discretize=ddim_discretize, ddim_eta=eta, verbose=False)
         dev = self.model.device
         img = torch.randn(size, device=dev) if x_T is None else x_T.to(dev).float()
-        cfg = None
-        if unconditional_conditioning is not None and unconditional_guidance_scale != 1.0:
-            cfg = (unconditional_conditioning, float(unconditional_guidance_scale))
         vq = None
         if codebook is not None or (float(temperature) != 1.0 and eta != 0.0):        # eta = 0: sigma_t = 0, the temperature has no effect
             vq = (codebook, float(temperature))
@@ -898,6 +1222,10 @@ class DDIMSampler(object):
         key = (N, Cx, sp3, Cc, str(dev), ctx_shape) + ((("inpaint", mask_C),) if mask_C else ())
         if vq is not None:
             key = key + (("vq", vq[0] is not None),)
+        par = getattr(self.model, "split_input_params", None)
+        if par is not None:            # patch-wise eps: a state of its own (crop buffers, time-bias rows for L * N), keyed by the geometry
+            key = key + (("split",) + tuple((k, str(par.get(k))) for k in ("ks", "stride", "tie_braker", "clip_min_weight", "clip_max_weight",
+                                                                          "clip_min_tie_weight", "clip_max_tie_weight")),)
         # everything cached below is a function of the schedule (steps, eta -> sigmas) and of the UNet's weights (time-bias
         # table, packed weights baked into the captured graph): a changed schedule or weight version rebuilds the state
         token = (S, tuple(int(v) for v in self.ddim_timesteps), tuple(float(v) for v in self.ddim_sigmas), ops.weights_token(unet))
@@ -909,8 +1237,9 @@ class DDIMSampler(object):
                 st["scal"][:, 4].copy_(st["scal"][:, 2] * vq[1])
             return st
         steps = torch.tensor(np.flip(self.ddim_timesteps).copy(), dtype=torch.float32, device=dev)
+        split = SplitUNet(self.model, N, Cx, Cc, sp, dev) if par is not None else None
         st = dict(N=N, Cx=Cx, sp3=sp3, Cc=Cc, S=S, token=token,
-                  table=unet.time_bias_table(steps, N), scal=self.step_scalar_table().to(dev),
+                  table=unet.time_bias_table(steps, N) if split is None else split.time_bias_table(unet, steps), scal=self.step_scalar_table().to(dev),
                   x=torch.empty((N,) + sp3 + (Cx,), dtype=torch.float32, device=dev),
                   pred_x0=torch.empty((N,) + sp3 + (Cx,), dtype=torch.float32, device=dev),
                   unet_in=torch.zeros((N,) + sp3 + (pad32(Cx + Cc),), dtype=torch.bfloat16, device=dev),
@@ -924,6 +1253,8 @@ class DDIMSampler(object):
                       ip_mask=torch.empty((N,) + sp3 + (mask_C,), dtype=torch.float32, device=dev),
                       ip_noise=torch.empty((S, N) + sp3 + (Cx,), dtype=torch.float32, device=dev),
                       ip_scal=self.q_sample_scalar_table().to(dev))
+        if split is not None:
+            st["split"] = split
         if vq is not None:
             sc = self.step_scalar_table().to(dev)
             st.update(vq=vq[0], scal=torch.cat([sc, sc[:, 2:3] * vq[1]], 1).contiguous())          # fp32 product sigma_t * temperature
@@ -941,6 +1272,12 @@ class DDIMSampler(object):
         ops.to_cl(x_T, out=st["unet_in"], c_offset=0, zero_fill=False)
         if c_concat is not None:
             ops.to_cl(c_concat.float(), out=st["unet_in"], c_offset=st["Cx"], zero_fill=False)
+        if "split" in st:
+            st["split"].bind(st["unet_in"], st["ctx"] if context is not None else None)
+
+    def _eps(self, st, uin, bias, ctx_cl, out, head_ddim=None):
+        """eps of the state's x under the UNet input `uin` (unet_eps: full size, or on crops with a "split" state)."""
+        return unet_eps(self.model.model.diffusion_model, st.get("split"), st["x"], uin, st["Cx"] + st["Cc"], bias, ctx_cl, out, head_ddim)
 
     def load_inpaint(self, st, x0: torch.Tensor, mask: torch.Tensor, mask_noise_tape=None):
         """x0 [N, C, *sp] and mask [N, Cm, *sp] (inpaint_operands' views) -> the state's static CL buffers; the S q_sample noises from
@@ -1001,10 +1338,10 @@ class DDIMSampler(object):
         M = st["x"].numel() // Cx
         # deterministic steps: the update is the head conv's epilogue where the kernel supports it (Cx == 4 on the box kernel)
         hd = (st["x"].view(M, Cx), scal, st["pred_x0"].view(M, Cx), st["unet_in"].view(M, -1)) \
-            if (noise is None and self.fuse_ddim and Cx == 4 and "vq" not in st) else None
-        head = unet.forward_cl(CL(st["unet_in"], Cx + Cc), bias, ctx_cl, head_out=st["eps"], head_ddim=hd)
-        self.last_step_fused = head.fused_ddim
-        if not head.fused_ddim:
+            if (noise is None and self.fuse_ddim and Cx == 4 and "vq" not in st and "split" not in st) else None
+        head = self._eps(st, st["unet_in"], bias, ctx_cl, st["eps"], hd)
+        self.last_step_fused = head is not None and head.fused_ddim
+        if not self.last_step_fused:
             self._update(st, st["eps"], scal, noise)
 
     def _run_steps_cfg(self, st, x_T, cfg, eta, noise_tape, noise_dropout=0.0):
@@ -1016,23 +1353,39 @@ class DDIMSampler(object):
         scale = cfg[1]
         Cx, Cc = st["Cx"], st["Cc"]
         M = st["x"].numel() // Cx
-        uin_u = st["unet_in"].clone()
+        split = st.get("split")
+        if split is None:
+            uin_u = st["unet_in"].clone()
+        else:
+            # patch-wise: SplitUNet.bind keeps crop buffers per UNet input and per context it is given, so the unconditional ones are
+            # members of the state, made on the first guided call and refilled afterwards: a call leaves no memory behind
+            if "cfg_unet_in" not in st:
+                st["cfg_unet_in"] = torch.empty_like(st["unet_in"])
+            uin_u = st["cfg_unet_in"]
+            uin_u.copy_(st["unet_in"])
         if uc_concat is not None:
             ops.to_cl(uc_concat.float(), out=uin_u, c_offset=Cx, zero_fill=False)
         ctx_u = None
         if uc_ctx is not None:
-            ctx_u = CL(torch.zeros_like(st["ctx"].t), st["ctx"].C)
+            if split is None:
+                ctx_u = CL(torch.zeros_like(st["ctx"].t), st["ctx"].C)
+            else:
+                if "cfg_ctx" not in st:
+                    st["cfg_ctx"] = CL(torch.zeros_like(st["ctx"].t), st["ctx"].C)
+                ctx_u = st["cfg_ctx"]
             ops.to_cl(uc_ctx.permute(0, 2, 1).contiguous().float(), out=ctx_u.t, c_offset=0, zero_fill=False)
         elif st["ctx"] is not None:
             ctx_u = st["ctx"]
         eps_u = torch.empty_like(st["eps"])
+        if split is not None:
+            split.bind(uin_u, ctx_u)
         for i in range(st["S"]):
             noise = self._noise(st, i, eta, noise_tape, noise_dropout)
             if "ip_x0" in st:                   # inpainting: both evaluations see the blended x (ddim.py:144-148 precede :175-180)
                 self._blend(st, i)
                 uin_u[..., :Cx].copy_(st["unet_in"][..., :Cx])
-            unet.forward_cl(CL(uin_u, Cx + Cc), st["table"][i], ctx_u, head_out=eps_u)
-            unet.forward_cl(CL(st["unet_in"], Cx + Cc), st["table"][i], st["ctx"], head_out=st["eps"])
+            self._eps(st, uin_u, st["table"][i], ctx_u, eps_u)
+            self._eps(st, st["unet_in"], st["table"][i], st["ctx"], st["eps"])
             ops.lincomb4([eps_u, st["eps"]], [1.0 - scale, scale], 1.0, st["eps"])        # (1 - s) e_u + s e_c
             self._update(st, st["eps"], st["scal"][i], noise)
             uin_u[..., :Cx].copy_(st["unet_in"][..., :Cx])
@@ -1079,7 +1432,6 @@ class PLMSSampler(DDIMSampler):
     def run_steps(self, st, ctx_cl, eta, noise_tape, noise_dropout=0.0):          # eta = 0: no noise, nothing to drop
         unet = self.model.model.diffusion_model
         Cx, Cc, S = st["Cx"], st["Cc"], st["S"]
-        xin = CL(st["unet_in"], Cx + Cc)
         M = st["x"].numel() // Cx
         x, eps, uin = st["x"].view(M, Cx), st["eps"], st["unet_in"].view(M, -1)
         old: List[torch.Tensor] = []
@@ -1090,12 +1442,12 @@ class PLMSSampler(DDIMSampler):
 
         for i in range(S):
             self._blend(st, i)                 # inpainting (plms.py:147-150): before the first evaluation, so x_keep holds the blended x
-            unet.forward_cl(xin, st["table"][i], ctx_cl, head_out=eps)
+            self._eps(st, st["unet_in"], st["table"][i], ctx_cl, eps)
             e_t = eps.clone()
             if len(old) == 0:
                 x_keep, uin_keep = x.clone(), uin.clone()
                 update(e_t, st["scal"][i])                                             # provisional x_prev
-                unet.forward_cl(xin, st["table"][min(i + 1, S - 1)], ctx_cl, head_out=eps)   # e(x_prev, t_next)
+                self._eps(st, st["unet_in"], st["table"][min(i + 1, S - 1)], ctx_cl, eps)    # e(x_prev, t_next)
                 ops.lincomb4([e_t, eps], [1.0, 1.0], 2.0, e_prime)
                 x.copy_(x_keep); uin.copy_(uin_keep)
             elif len(old) == 1:

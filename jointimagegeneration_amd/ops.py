@@ -822,6 +822,73 @@ def ddim_step_vq(x: torch.Tensor, eps: torch.Tensor, scalars: torch.Tensor, code
                               unet_in.shape[-1] if unet_in is not None else 0, _stream()), "gg_ddim_step_vq")
 
 
+def unfold_extent(H: int, W: int, kh: int, kw: int, sy: int, sx: int) -> Tuple[int, int]:
+    """(Ly, Lx) of torch.nn.Unfold with dilation 1 and padding 0."""
+    return (H - kh) // sy + 1, (W - kw) // sx + 1
+
+
+def _cl_dtype(t: torch.Tensor, what: str) -> int:
+    if t.dtype == torch.float32:
+        return GG_F32
+    if t.dtype == torch.bfloat16:
+        return GG_BF16
+    raise ValueError(f"{what}: fp32 or bf16 channels-last tensors, got {t.dtype}")
+
+
+def _rows_dense(t: torch.Tensor) -> bool:
+    """A 4-D channels-last tensor (or view) whose pixel rows lie t.stride(2) elements apart with nothing between the lines."""
+    return (t.dim() == 4 and (t.stride(3) == 1 or t.shape[3] == 1) and (t.shape[1] == 1 or t.stride(1) == t.shape[2] * t.stride(2))
+            and (t.shape[0] == 1 or t.stride(0) == t.shape[1] * t.shape[2] * t.stride(2)) and t.stride(2) >= t.shape[3])
+
+
+def unfold_cl(src: torch.Tensor, C: int, kh: int, kw: int, sy: int, sx: int, out: Optional[torch.Tensor] = None, c_offset: int = 0) -> torch.Tensor:
+    """Crop gather (gg_unfold_cl): src channels-last [N, H, W, stride] (fp32 or bf16; channels [0, C) are read; a view whose rows are
+    `stride` elements apart) -> out [L * N, kh, kw, stride_out], channels [c_offset, c_offset + C), crop l of sample n at row l * N + n.
+    out defaults to a fresh tensor of src's dtype and C channels; a bf16 out of an fp32 src converts on the way.  Other lanes of out
+    are left as they are."""
+    lib = _lib.load()
+    require_gpu(src, "unfold_cl")
+    if not _rows_dense(src):
+        raise ValueError(f"unfold_cl: src must be channels-last [N, H, W, C] with densely packed rows, got {tuple(src.shape)} strides {src.stride()}")
+    N, H, W = (int(v) for v in src.shape[:3])
+    s_stride = int(src.stride(2))
+    if kh > H or kw > W or min(kh, kw, sy, sx) < 1:
+        raise ValueError(f"unfold_cl: crop {kh}x{kw} at stride {sy}x{sx} does not fit {H}x{W}")
+    Ly, Lx = unfold_extent(H, W, kh, kw, sy, sx)
+    if out is None:
+        out = torch.empty((Ly * Lx * N, kh, kw, C), dtype=src.dtype, device=src.device)
+    if out.dim() != 4 or tuple(out.shape[:3]) != (Ly * Lx * N, kh, kw) or not out.is_contiguous():
+        raise ValueError(f"unfold_cl: out must be a contiguous [{Ly * Lx * N}, {kh}, {kw}, stride] tensor, got {tuple(out.shape)}")
+    check(lib.gg_unfold_cl(src.data_ptr(), _cl_dtype(src, "unfold_cl"), N, H, W, s_stride, C, out.data_ptr(), _cl_dtype(out, "unfold_cl"),
+                           out.shape[-1], c_offset, kh, kw, sy, sx, _stream()), "gg_unfold_cl")
+    return out
+
+
+def fold_weighted_cl(crops: torch.Tensor, C: int, weight: torch.Tensor, tie: Optional[torch.Tensor], out: torch.Tensor,
+                     kh: int, kw: int, sy: int, sx: int) -> torch.Tensor:
+    """Weighted overlap-add (gg_fold_weighted_cl): crops fp32 [L * N, kh, kw, stride] -> out fp32 channels-last [N, H, W, stride_out],
+    channels [0, C): sum_l(o[l] * w[l]) / sum_l(w[l]) with w[l][ky, kx] = weight[ky, kx] * tie[l], crops visited in descending l (the
+    order of torch's CPU Fold; include/guidegen_hip.h).  weight fp32 [kh, kw], tie fp32 [L] or None.  crops / out may be views whose
+    rows are `stride` elements apart."""
+    lib = _lib.load()
+    require_gpu(crops, "fold_weighted_cl")
+    if out.dtype != torch.float32 or not _rows_dense(out):
+        raise ValueError(f"fold_weighted_cl: out must be fp32 channels-last [N, H, W, C] with densely packed rows, got {out.dtype} {tuple(out.shape)}")
+    N, H, W = (int(v) for v in out.shape[:3])
+    if kh > H or kw > W or min(kh, kw, sy, sx) < 1:
+        raise ValueError(f"fold_weighted_cl: crop {kh}x{kw} at stride {sy}x{sx} does not fit {H}x{W}")
+    Ly, Lx = unfold_extent(H, W, kh, kw, sy, sx)
+    if crops.dtype != torch.float32 or not _rows_dense(crops) or tuple(crops.shape[:3]) != (Ly * Lx * N, kh, kw):
+        raise ValueError(f"fold_weighted_cl: crops must be fp32 [{Ly * Lx * N}, {kh}, {kw}, C] with densely packed rows, got {crops.dtype} {tuple(crops.shape)}")
+    if weight.dtype != torch.float32 or not weight.is_contiguous() or weight.numel() != kh * kw or weight.device != crops.device:
+        raise ValueError(f"fold_weighted_cl: weight must be a contiguous device fp32 [{kh}, {kw}] table")
+    if tie is not None and (tie.dtype != torch.float32 or not tie.is_contiguous() or tie.numel() != Ly * Lx or tie.device != crops.device):
+        raise ValueError(f"fold_weighted_cl: tie must be a contiguous device fp32 [{Ly * Lx}] table")
+    check(lib.gg_fold_weighted_cl(crops.data_ptr(), int(crops.stride(2)), weight.data_ptr(), _ptr(tie), out.data_ptr(), int(out.stride(2)),
+                                  N, H, W, C, kh, kw, sy, sx, _stream()), "gg_fold_weighted_cl")
+    return out
+
+
 def minmax_normalise(src: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     lib = _lib.load()
     if out is None:

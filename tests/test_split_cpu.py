@@ -1,0 +1,267 @@
+"""CPU suite for the patch-wise path (LatentDiffusion.split_input_params): the weighting and normalisation tables against the reference's
+(tests/golden/split.npz, make_golden_split.py) bit for bit, the descending-order restatement of the fold (tests/split_ref.py) against
+torch.nn.functional.fold at the geometries the GPU suite uses, crop counts and reduced ks / stride, every host-side refusal matched on
+its message, the C-ABI of the two entries, and a model without the attribute staying on the code path it had."""
+import ctypes as C
+import os
+import re
+
+import pytest
+import torch
+
+import split_ref
+from util import AE_SMALL, LDM_SMALL, T, gold
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LOSS = dict(target="torch.nn.Identity")
+SPLIT = dict(ks=(8, 8), stride=(4, 4), vqf=4, patch_distributed_vq=True, tie_braker=False, clip_max_weight=0.5, clip_min_weight=0.01,
+             clip_max_tie_weight=0.5, clip_min_tie_weight=0.01)
+# (H, W, k, s): the geometries of tests/test_split_gpu.py
+GEOMS = [(12, 12, 8, 4), (12, 16, 8, 4), (9, 13, 5, 4), (16, 16, 8, 2), (48, 48, 32, 16)]
+
+
+def ldm(first_stage="kl", cond_stage_key="segmentation", conditioning_key=None, **split):
+    from jointimagegeneration_amd.ldm import LatentDiffusion
+    if first_stage == "kl":
+        fs = dict(target="ldm.models.autoencoder.AutoencoderKL", params=dict(embed_dim=4, dims=2, ddconfig=dict(AE_SMALL), lossconfig=LOSS))
+    elif first_stage == "vq":
+        fs = dict(target="ldm.models.autoencoder.VQModelInterface", params=dict(embed_dim=4, n_embed=64, dims=2, ddconfig=dict(AE_SMALL), lossconfig=LOSS))
+    else:
+        fs = dict(target="ldm.models.autoencoder.IdentityFirstStage")
+    ae2 = dict(target="ldm.models.autoencoder.AutoencoderKL", params=dict(embed_dim=4, dims=2, ddconfig=dict(AE_SMALL, in_channels=2, out_ch=2), lossconfig=LOSS))
+    m = LatentDiffusion(first_stage_config=fs, cond_stage_config=ae2,
+                        unet_config=dict(target="ldm.modules.diffusionmodules.openaimodel.UNetModel", params=dict(LDM_SMALL)),
+                        linear_start=0.0015, linear_end=0.0195, timesteps=1000, image_size=8, channels=4, dims=2, first_stage_key="image",
+                        cond_stage_key=cond_stage_key, conditioning_key=conditioning_key, num_timesteps_cond=1, use_ema=False).eval()
+    m.split_input_params = dict(SPLIT, **split)
+    return m
+
+
+@pytest.fixture(scope="module")
+def g():
+    return gold("split")
+
+
+# ------------------------------------------------------------------------------------------------ tables
+@pytest.mark.parametrize("name,shape,ks,stride,tie,uf,df", [
+    ("t12", (12, 12), (8, 8), (4, 4), False, 1, 1), ("t12x16", (12, 16), (8, 8), (4, 4), False, 1, 1),
+    ("t16tie", (16, 16), (8, 8), (4, 4), True, 1, 1), ("tdec", (12, 12), (8, 8), (4, 4), False, 4, 1),
+    ("tdectie", (16, 16), (8, 8), (4, 4), True, 4, 1), ("tenc", (48, 48), (32, 32), (16, 16), False, 1, 4)])
+def test_tables_equal_the_reference_bit_for_bit(g, name, shape, ks, stride, tie, uf, df):
+    m = ldm(tie_braker=tie)
+    plan = m.get_fold_unfold((1, 1) + shape, ks, stride, uf=uf, df=df)
+    want_w, want_n = T(g["w_" + name]), T(g["n_" + name])
+    assert plan.L == want_w.shape[1] and (plan.oH, plan.oW) == tuple(want_n.shape)
+    assert (plan.okh, plan.okw) == (ks[0] * uf // df, ks[1] * uf // df) and (plan.osy, plan.osx) == (stride[0] * uf // df, stride[1] * uf // df)
+    assert torch.equal(plan.weighting(), want_w)
+    assert torch.equal(plan.normalization(), want_n)
+    assert (plan.tie is not None) == tie
+    # the reference-shaped tensor of get_weighting
+    assert torch.equal(m.get_weighting(plan.okh, plan.okw, plan.Ly, plan.Lx, "cpu")[0], want_w)
+    # the tables the kernel reads reproduce the reference's tensors through the restatement of the kernel's order
+    ones = torch.ones(plan.L, plan.okh, plan.okw, 1)
+    den = split_ref.fold_descending(ones, plan.weight, plan.tie, 1, plan.oH, plan.oW, plan.okh, plan.okw, plan.osy, plan.osx)
+    assert torch.equal(den, torch.ones_like(den))                                 # sum(w) / sum(w)
+
+
+def test_tie_table_is_not_constant_on_a_3x3_crop_grid():
+    plan = ldm(tie_braker=True).get_fold_unfold((1, 4, 16, 16), (8, 8), (4, 4))
+    assert plan.tie.shape == (9,) and float(plan.tie[4]) == 0.5 and float(plan.tie[0]) == pytest.approx(0.01)
+
+
+@pytest.mark.parametrize("H,W,k,s", GEOMS)
+@pytest.mark.parametrize("tie", [False, True], ids=["plain", "tie"])
+def test_descending_restatement_equals_torch_fold_bit_for_bit(H, W, k, s, tie):
+    """Pins the order gg_fold_weighted_cl is held to: the descending-l fp32 loop IS torch's CPU Fold, on random inputs."""
+    Ly, Lx = split_ref.extent(H, W, k, k, s, s)
+    for C_, N in ((1, 1), (3, 3), (4, 2)):
+        gen = torch.Generator().manual_seed(H * 131 + W * 7 + k + C_)
+        crops = torch.randn(Ly * Lx * N, k, k, C_, generator=gen)
+        Wt, Tt = split_ref.weight_tables(k, k, Ly, Lx, tie, seed=H + W)
+        a = split_ref.fold_descending(crops, Wt, Tt, N, H, W, k, k, s, s)
+        assert torch.equal(a, split_ref.fold_reference(crops, Wt, Tt, N, H, W, k, k, s, s))
+
+
+def test_ascending_order_is_a_different_function():
+    """The order matters: the same sums taken in ascending l differ in the last bits somewhere."""
+    H = W = 16; k, s = 8, 2
+    Ly, Lx = split_ref.extent(H, W, k, k, s, s)
+    crops = torch.randn(Ly * Lx, k, k, 4, generator=torch.Generator().manual_seed(3))
+    Wt, Tt = split_ref.weight_tables(k, k, Ly, Lx, True)
+    num = torch.zeros(1, H, W, 4); den = torch.zeros(H, W)
+    for l in range(Ly * Lx):
+        y0, x0 = (l // Lx) * s, (l % Lx) * s
+        w = Wt * Tt[l]
+        num[:, y0:y0 + k, x0:x0 + k] += crops[l:l + 1] * w[None, :, :, None]
+        den[y0:y0 + k, x0:x0 + k] += w
+    assert not torch.equal(num / den[None, :, :, None], split_ref.fold_descending(crops, Wt, Tt, 1, H, W, k, k, s, s))
+
+
+def test_unfold_restatement_and_crop_counts():
+    from jointimagegeneration_amd import ops
+    for H, W, k, s in GEOMS:
+        Ly, Lx = ops.unfold_extent(H, W, k, k, s, s)
+        assert (Ly, Lx) == ((H - k) // s + 1, (W - k) // s + 1) == split_ref.extent(H, W, k, k, s, s)
+    x = torch.arange(2 * 3 * 9 * 13, dtype=torch.float32).view(2, 3, 9, 13)
+    crops = split_ref.unfold_reference(x, 5, 5, 4, 4)
+    assert crops.shape == (2 * 3 * 2, 5, 5, 3)
+    l, n = 4, 1                                           # crop (ly 1, lx 1) of sample 1 starts at (4, 4)
+    assert torch.equal(crops[l * 2 + n], x[n, :, 4:9, 4:9].permute(1, 2, 0))
+    plan = ldm().get_fold_unfold(x, (5, 5), (4, 4))
+    assert (plan.Ly, plan.Lx, plan.L) == (2, 3, 6)
+
+
+def test_ks_and_stride_larger_than_the_input_are_reduced():
+    m = ldm(ks=(128, 128), stride=(64, 64))
+    assert m._split_reduced(12, 16) == ((12, 16), (12, 16))
+    assert m._split_reduced(200, 100) == ((128, 100), (64, 64))        # per axis, as ddpm.py:733-739
+    assert ldm()._split_reduced(12, 16) == ((8, 8), (4, 4))
+    plan = m.get_fold_unfold((1, 4, 12, 12), *m._split_reduced(12, 12), uf=4)
+    assert plan.L == 1 and (plan.oH, plan.okh) == (48, 48)
+
+
+# ------------------------------------------------------------------------------------------------ refusals
+def test_geometry_refusals():
+    m = ldm()
+    with pytest.raises(ValueError, match="crops of extent 1"):
+        m.get_fold_unfold((1, 4, 12, 12), (1, 1), (1, 1))
+    with pytest.raises(ValueError, match="leaves pixels .* uncovered"):
+        m.get_fold_unfold((1, 4, 13, 12), (8, 8), (4, 4))
+    with pytest.raises(ValueError, match="leaves pixels .* uncovered"):
+        m.get_fold_unfold((1, 4, 12, 14), (8, 8), (4, 4))
+    with pytest.raises(ValueError, match="does not fit the input"):
+        m.get_fold_unfold((1, 4, 6, 12), (8, 8), (4, 4))
+    with pytest.raises(NotImplementedError, match="needs square ks"):
+        m.get_fold_unfold((1, 4, 12, 12), (8, 4), (4, 4), uf=4)
+    with pytest.raises(NotImplementedError, match="needs square ks"):
+        m.get_fold_unfold((1, 1, 48, 48), (32, 16), (16, 16), df=4)
+    with pytest.raises(NotImplementedError, match="2-D"):
+        m.get_fold_unfold((1, 4, 4, 12, 12), (8, 8), (4, 4))
+    with pytest.raises(ValueError, match="tie_braker needs at least 2 crops per axis"):
+        ldm(tie_braker=True).get_fold_unfold((1, 4, 8, 12), (8, 8), (4, 4))
+    assert m.get_fold_unfold((1, 4, 12, 16), (8, 4), (4, 4)).L == 2 * 4            # non-square ks is fine without vqf
+
+
+def test_conditioning_refusals_by_name():
+    x, t, c = torch.zeros(1, 4, 12, 12), torch.zeros(1), torch.zeros(1, 4, 12, 12)
+    with pytest.raises(NotImplementedError, match="return_ids"):
+        ldm().apply_model(x, t, c, return_ids=True)
+    with pytest.raises(NotImplementedError, match="coordinates_bbox"):
+        ldm(cond_stage_key="coordinates_bbox", conditioning_key="crossattn").apply_model(x, t, torch.zeros(1, 3, 8))
+    with pytest.raises(NotImplementedError, match="hybrid conditioning / more than one conditioning entry"):
+        ldm(conditioning_key="hybrid").apply_model(x, t, dict(c_concat=[c], c_crossattn=[torch.zeros(1, 3, 8)]))
+    with pytest.raises(NotImplementedError, match="hybrid conditioning / more than one conditioning entry"):
+        ldm().apply_model(x, t, dict(c_concat=[c], c_crossattn=[torch.zeros(1, 3, 8)]))
+    with pytest.raises(NotImplementedError, match="holds 2 tensors"):
+        ldm().apply_model(x, t, dict(c_concat=[c, c]))
+    with pytest.raises(NotImplementedError, match="concat conditioning is cut into crops only for cond_stage_key"):
+        ldm(cond_stage_key="mask").apply_model(x, t, c)
+    with pytest.raises(NotImplementedError, match="cross-attention conditioning under cond_stage_key 'segmentation'"):
+        ldm(conditioning_key="crossattn").apply_model(x, t, torch.zeros(1, 3, 8))
+
+
+@pytest.mark.parametrize("sampler", ["DDIMSampler", "PLMSSampler"])
+def test_samplers_refuse_before_any_launch(sampler, monkeypatch):
+    """With x_T left out the samplers draw it on the model's device, and sample() builds a schedule: neither may come before the
+    refusals, so both are made to fail here."""
+    from jointimagegeneration_amd import ldm as L
+
+    def too_early(*a, **k):
+        raise AssertionError("reached before the refusal")
+    monkeypatch.setattr(torch, "randn", too_early)
+    monkeypatch.setattr(L.DDIMSampler, "make_schedule", too_early)
+    monkeypatch.setattr(L.PLMSSampler, "make_schedule", too_early)
+    c = torch.zeros(1, 4, 12, 12)
+    s = getattr(L, sampler)(ldm(cond_stage_key="mask"))
+    with pytest.raises(NotImplementedError, match="concat conditioning is cut into crops only"):
+        s.sample(S=5, batch_size=1, shape=(4, 12, 12), conditioning=c, verbose=False)
+    s = getattr(L, sampler)(ldm())
+    with pytest.raises(ValueError, match="leaves pixels .* uncovered"):
+        s.sample(S=5, batch_size=1, shape=(4, 14, 12), conditioning=torch.zeros(1, 4, 14, 12), verbose=False)
+    with pytest.raises(NotImplementedError, match="the patch-wise path is 2-D"):
+        s.sample(S=5, batch_size=1, shape=(4, 2, 12, 12), conditioning=torch.zeros(1, 4, 2, 12, 12), verbose=False)
+    with pytest.raises(NotImplementedError, match="hybrid conditioning / more than one conditioning entry"):
+        s.sample(S=5, batch_size=1, shape=(4, 12, 12), conditioning=dict(c_concat=[c], c_crossattn=[torch.zeros(1, 3, 8)]), verbose=False)
+    with pytest.raises(NotImplementedError, match="concat conditioning is cut into crops only"):
+        ldm(cond_stage_key="mask").p_sample_loop(c, (1, 4, 12, 12), verbose=False, timesteps=2)
+
+
+def test_first_stage_refusals():
+    img = torch.zeros(1, 1, 48, 48)
+    with pytest.raises(NotImplementedError, match="AutoencoderKL is not supported"):
+        ldm(ks=(32, 32), stride=(16, 16)).encode_first_stage(img)
+    with pytest.raises(NotImplementedError, match="needs square ks"):
+        ldm("vq", ks=(32, 16), stride=(16, 16)).encode_first_stage(img)
+    with pytest.raises(ValueError, match="leaves pixels .* uncovered"):
+        ldm("vq").decode_first_stage(torch.zeros(1, 4, 13, 12))
+    with pytest.raises(NotImplementedError, match="predict_cids"):
+        ldm("vq").decode_first_stage(torch.zeros(1, 4, 12, 12), predict_cids=True)
+    m = ldm("vq", ks=(32, 32), stride=(16, 16))
+    with pytest.raises(RuntimeError):                      # past the host checks: the engine has no CPU path
+        m.encode_first_stage(img)
+    assert tuple(m.split_input_params["original_image_size"]) == (48, 48)          # set as the reference sets it (ddpm.py:844)
+    # patch_distributed_vq off: the first stage sees the whole tensor, as in the reference
+    m = ldm("identity", patch_distributed_vq=False)
+    z = torch.randn(1, 4, 13, 12)
+    assert torch.equal(m.decode_first_stage(z), z) and m.encode_first_stage(z) is z
+
+
+# ------------------------------------------------------------------------------------------------ C-ABI
+_CT = {"float": C.c_void_p, "void": C.c_void_p, "int32_t": C.c_int32, "int64_t": C.c_int64}
+
+
+@pytest.mark.parametrize("name", ["gg_unfold_cl", "gg_fold_weighted_cl"])
+def test_declarations_match_the_ctypes_signatures(name):
+    from jointimagegeneration_amd import _lib
+    txt = open(os.path.join(ROOT, "include", "guidegen_hip.h")).read()
+    m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", txt)
+    assert m, f"{name} is not declared in guidegen_hip.h"
+    want = []
+    for arg in m.group(1).split(","):
+        toks = arg.replace("const", "").split()
+        want.append(C.c_void_p if "*" in arg else _CT[toks[0]])
+    res, args = _lib.SIGNATURES[name]
+    assert res is C.c_int and args == want
+
+
+def test_entries_reject_bad_arguments_on_the_host():
+    from jointimagegeneration_amd import _lib
+    lib = _lib.load()
+    buf = (C.c_float * 64)()
+    p = C.cast(buf, C.c_void_p)
+    bad_shape, unsupported, F32, BF16 = -1, -3, 1, 0
+    # unfold: (src, src_dtype, N, H, W, src_stride, C, dst, dst_dtype, dst_stride, dst_c_offset, kh, kw, sy, sx, stream)
+    assert lib.gg_unfold_cl(None, F32, 1, 12, 12, 4, 4, p, F32, 4, 0, 8, 8, 4, 4, None) == bad_shape
+    assert lib.gg_unfold_cl(p, F32, 1, 12, 12, 4, 4, None, F32, 4, 0, 8, 8, 4, 4, None) == bad_shape
+    assert lib.gg_unfold_cl(p, F32, 1, 6, 12, 4, 4, p, F32, 4, 0, 8, 8, 4, 4, None) == bad_shape           # crop larger than the input
+    assert lib.gg_unfold_cl(p, F32, 1, 12, 12, 4, 4, p, F32, 4, 0, 8, 8, 0, 4, None) == bad_shape          # stride 0
+    assert lib.gg_unfold_cl(p, F32, 1, 12, 12, 3, 4, p, F32, 4, 0, 8, 8, 4, 4, None) == bad_shape          # src stride < C
+    assert lib.gg_unfold_cl(p, F32, 1, 12, 12, 4, 4, p, BF16, 32, 30, 8, 8, 4, 4, None) == bad_shape       # offset + C past the row
+    assert lib.gg_unfold_cl(p, BF16, 1, 12, 12, 4, 4, p, F32, 4, 0, 8, 8, 4, 4, None) == unsupported       # bf16 -> fp32
+    assert lib.gg_unfold_cl(p, 7, 1, 12, 12, 4, 4, p, F32, 4, 0, 8, 8, 4, 4, None) == unsupported
+    # fold: (crops, crop_stride, weight, tie, out, out_stride, N, H, W, C, kh, kw, sy, sx, stream)
+    assert lib.gg_fold_weighted_cl(None, 4, p, None, p, 4, 1, 12, 12, 4, 8, 8, 4, 4, None) == bad_shape
+    assert lib.gg_fold_weighted_cl(p, 4, None, None, p, 4, 1, 12, 12, 4, 8, 8, 4, 4, None) == bad_shape
+    assert lib.gg_fold_weighted_cl(p, 4, p, None, None, 4, 1, 12, 12, 4, 8, 8, 4, 4, None) == bad_shape
+    assert lib.gg_fold_weighted_cl(p, 3, p, None, p, 4, 1, 12, 12, 4, 8, 8, 4, 4, None) == bad_shape       # crop stride < C
+    assert lib.gg_fold_weighted_cl(p, 4, p, None, p, 4, 1, 13, 12, 4, 8, 8, 4, 4, None) == bad_shape       # a row of pixels uncovered
+    assert b"uncovered" in lib.gg_last_error()
+    assert lib.gg_fold_weighted_cl(p, 4, p, None, p, 4, 1, 12, 12, 4, 2, 2, 5, 5, None) == bad_shape       # gaps between the crops
+    assert lib.gg_fold_weighted_cl(p, 4, p, None, p, 4, 0, 12, 12, 4, 8, 8, 4, 4, None) == bad_shape
+
+
+# ------------------------------------------------------------------------------------------------ the attribute absent
+def test_without_the_attribute_the_old_code_path_runs(monkeypatch):
+    m = ldm("vq")
+    del m.split_input_params
+    seen = []
+    monkeypatch.setattr(m.first_stage_model, "decode", lambda z, force_not_quantize=False: seen.append(("decode", z, force_not_quantize)) or "dec")
+    monkeypatch.setattr(m.first_stage_model, "encode", lambda x: seen.append(("encode", x)) or "enc")
+    monkeypatch.setattr(m.model, "forward", lambda x, t, **cond: seen.append(("unet", x, t, cond)) or "eps")
+    monkeypatch.setattr(m, "get_fold_unfold", lambda *a, **k: pytest.fail("the patch-wise path ran without split_input_params"))
+    z, t, c = torch.randn(1, 4, 13, 11), torch.zeros(1), torch.zeros(1, 4, 13, 11)
+    assert m.decode_first_stage(z, force_not_quantize=True) == "dec" and seen[-1][0] == "decode" and seen[-1][2] is True
+    assert torch.equal(seen[-1][1], 1.0 / m.scale_factor * z)
+    assert m.encode_first_stage(z) == "enc" and seen[-1][1] is z
+    assert m.apply_model(z, t, c) == "eps" and seen[-1][1] is z and list(seen[-1][3]) == ["c_concat"] and seen[-1][3]["c_concat"][0] is c
+    assert m.apply_model(z, t, dict(c_concat=[c], c_crossattn=[c])) == "eps" and sorted(seen[-1][3]) == ["c_concat", "c_crossattn"]
