@@ -9,8 +9,8 @@ Reference blocks mirrored (file:line relative to the reference tree):
       ccdm/ddpm/models/unet_openai/unet.py:70-360, latentdiffusion/ldm/modules/diffusionmodules/openaimodel.py:74-375
   SpatialTransformer / BasicTransformerBlock / CrossAttention / GEGLU
       latentdiffusion/ldm/modules/attention.py:37-64,152-261
-  ResnetBlock / AttnBlock2d / Upsample / Downsample (AE)
-      latentdiffusion/ldm/modules/diffusionmodules/model.py:42-145,209-261
+  ResnetBlock / AttnBlock2d / AttnBlock3d / Upsample / Downsample (AE, dims 2 and 3)
+      latentdiffusion/ldm/modules/diffusionmodules/model.py:42-261
 """
 from __future__ import annotations
 
@@ -490,76 +490,99 @@ def Normalize(in_channels, num_groups=32):
 
 
 class AEUpsample(nn.Module):
+    """nearest x2 then conv3 (model.py:42-58); dims == 3 doubles D as well (the conv's fused upsample with kd == 3)."""
+
     def __init__(self, in_channels, with_conv, dims=2):
         super().__init__()
-        assert with_conv and dims == 2
-        self.with_conv = with_conv
-        self.conv = nn.Conv2d(in_channels, in_channels, kernel_size=3, stride=1, padding=1)
+        if not with_conv:
+            raise NotImplementedError("resamp_with_conv=False is not supported (the conv-free AE resampling is used by no shipped config)")
+        self.with_conv, self.dims = with_conv, dims
+        self.conv = conv_nd(dims, in_channels, in_channels, kernel_size=3, stride=1, padding=1)
 
     def run(self, h: CL) -> CL:
         pw, pb = packed_conv(self.conv, h.Cpad)
-        return ops.conv(h, pw, pb, self.conv.weight.shape[0], k=(1, 3, 3), upsample=True)
+        return ops.conv(h, pw, pb, self.conv.weight.shape[0], k=_k3(self.conv.weight), upsample=True)
 
 
 class AEDownsample(nn.Module):
-    """pad (0,1,0,1) then stride-2 valid conv (model.py:75-79) = conv with leading pad 0, trailing pad 1."""
+    """pad (0,1,0,1[,0,1]) then stride-2 valid conv (model.py:75-79) = conv with leading pad 0, trailing pad 1 on every spatial axis."""
 
     def __init__(self, in_channels, with_conv, dims=2):
         super().__init__()
-        assert with_conv and dims == 2
-        self.with_conv = with_conv
-        self.conv = nn.Conv2d(in_channels, in_channels, kernel_size=3, stride=2, padding=0)
+        if not with_conv:
+            raise NotImplementedError("resamp_with_conv=False is not supported (the conv-free AE resampling is used by no shipped config)")
+        self.with_conv, self.dims = with_conv, dims
+        self.conv = conv_nd(dims, in_channels, in_channels, kernel_size=3, stride=2, padding=0)
 
     def run(self, h: CL) -> CL:
         pw, pb = packed_conv(self.conv, h.Cpad)
-        return ops.conv(h, pw, pb, self.conv.weight.shape[0], k=(1, 3, 3), stride=2, pad=0)
+        return ops.conv(h, pw, pb, self.conv.weight.shape[0], k=_k3(self.conv.weight), stride=2, pad=0)
 
 
 class ResnetBlock(nn.Module):
     def __init__(self, *, in_channels, out_channels=None, conv_shortcut=False, dropout=0.0, temb_channels=0, dims=2):
         super().__init__()
-        assert dims == 2 and temb_channels == 0 and not conv_shortcut
+        assert dims in (2, 3) and temb_channels == 0 and not conv_shortcut
         out_channels = in_channels if out_channels is None else out_channels
-        self.in_channels, self.out_channels = in_channels, out_channels
+        self.in_channels, self.out_channels, self.dims = in_channels, out_channels, dims
         self.norm1 = Normalize(in_channels)
-        self.conv1 = nn.Conv2d(in_channels, out_channels, 3, 1, 1)
+        self.conv1 = conv_nd(dims, in_channels, out_channels, 3, 1, 1)
         self.norm2 = Normalize(out_channels)
         self.dropout = nn.Dropout(dropout)
-        self.conv2 = nn.Conv2d(out_channels, out_channels, 3, 1, 1)
+        self.conv2 = conv_nd(dims, out_channels, out_channels, 3, 1, 1)
         if in_channels != out_channels:
-            self.nin_shortcut = nn.Conv2d(in_channels, out_channels, 1, 1, 0)
+            self.nin_shortcut = conv_nd(dims, in_channels, out_channels, 1, 1, 0)
 
     def run(self, h: CL) -> CL:
+        k = _k3(self.conv1.weight)
         pw1, pb1 = packed_conv(self.conv1, h.Cpad)
-        h1 = norm_conv(h, self.norm1, True, pw1, pb1, self.out_channels, k=(1, 3, 3))
+        h1 = norm_conv(h, self.norm1, True, pw1, pb1, self.out_channels, k=k)
         res = h
         if self.in_channels != self.out_channels:
             pws, pbs = packed_conv(self.nin_shortcut, h.Cpad)
             res = ops.conv(h, pws, pbs, self.out_channels, k=(1, 1, 1), pad=0)
         pw2, pb2 = packed_conv(self.conv2, h1.Cpad)
-        return norm_conv(h1, self.norm2, True, pw2, pb2, self.out_channels, k=(1, 3, 3), residual=res)
+        return norm_conv(h1, self.norm2, True, pw2, pb2, self.out_channels, k=k, residual=res)
+
+
+ATTN_HEAD_DIMS = (32, 64, 128, 256, 384, 512)          # head dims gg_attention_forward has kernels for
 
 
 class AttnBlock2d(nn.Module):
     """Single-head attention over c channels, scale c^-1/2 (model.py:209-261); q|k|v fused into one 1x1 conv."""
+    dims = 2
 
     def __init__(self, in_channels):
         super().__init__()
         self.in_channels = in_channels
         self.norm = Normalize(in_channels)
-        self.q = nn.Conv2d(in_channels, in_channels, 1, 1, 0)
-        self.k = nn.Conv2d(in_channels, in_channels, 1, 1, 0)
-        self.v = nn.Conv2d(in_channels, in_channels, 1, 1, 0)
-        self.proj_out = nn.Conv2d(in_channels, in_channels, 1, 1, 0)
+        self.q = conv_nd(self.dims, in_channels, in_channels, 1, 1, 0)
+        self.k = conv_nd(self.dims, in_channels, in_channels, 1, 1, 0)
+        self.v = conv_nd(self.dims, in_channels, in_channels, 1, 1, 0)
+        self.proj_out = conv_nd(self.dims, in_channels, in_channels, 1, 1, 0)
 
     def run(self, h: CL) -> CL:
         Cc = self.in_channels
         N, T = h.N, h.S
         pw, pb = packed_cat([self.q, self.k, self.v], h.Cpad, "qkv")
         qkv = norm_conv(h, self.norm, False, pw, pb, 3 * Cc, k=(1, 1, 1), pad=0)
-        att = torch.empty(tuple(h.t.shape[:4]) + (Cc,), dtype=torch.bfloat16, device=h.t.device)
+        att = torch.empty(tuple(h.t.shape[:4]) + (Cc,), dtype=h.t.dtype, device=h.t.device)
         ld = qkv.Cpad
         ops.attention(qkv.t, qkv.t, qkv.t, att, N, 1, Cc, T, T, (ld, Cc), (ld, Cc), (ld, Cc), (Cc, Cc), int(Cc) ** -0.5,
                       q_off=0, k_off=Cc, v_off=2 * Cc)
         pw2, pb2 = packed_conv(self.proj_out, Cc)
         return ops.conv(CL(att, Cc), pw2, pb2, Cc, k=(1, 1, 1), pad=0, residual=h)
+
+
+class AttnBlock3d(AttnBlock2d):
+    """The same block on volumes (model.py:154-206): 1x1x1 Conv3d containers, T = D * H * W tokens of one head of c channels.  The
+    channels-last token order is (d, h, w) where the reference flattens its (h, w, d)-named axes in the same memory order, and attention
+    is invariant under a common permutation of queries and keys anyway.  The head dim is the channel count: one the attention kernel has
+    no instance for is refused here, on the host."""
+    dims = 3
+
+    def __init__(self, in_channels):
+        if in_channels not in ATTN_HEAD_DIMS:
+            raise NotImplementedError(f"AttnBlock3d: head_dim = {in_channels} is not supported (single-head attention over all channels; "
+                                      f"the attention kernel has head_dim in {ATTN_HEAD_DIMS})")
+        super().__init__(in_channels)

@@ -6,6 +6,9 @@ Mirrors the sampling surface of (paths relative to the reference tree, latentdif
   (DDPM/LatentDiffusion/DiffusionWrapper: schedule buffers, apply_model, get_learned_conditioning, decode_first_stage,
   ema_scope), ldm/modules/ema.py (LitEma name mangling), ldm/models/diffusion/ddim.py:11-205 (DDIMSampler),
   ldm/modules/encoders/modules.py:287-289 (IdentityEncoder).
+Volumetric first stages (dims = 3; model.py:42-83,154-206, autoencoder.py:36-52,313-324): the same classes with Conv3d containers,
+AttnBlock3d, a trailing pad of one on D, H and W in front of the stride-2 conv and an x2 upsample of D, H and W; the samplers carry
+[N, C, D, H, W] latents through the same row kernels.
 VQ first stage: ldm/models/autoencoder.py:18-131,283-301,464-481 (VQModel, VQModelInterface, IdentityFirstStage) with taming's
 VectorQuantizer.  Patch-wise evaluation (`split_input_params`, ddpm.py:573-660,718-776,839-876,915-997): SplitPlan / SplitUNet below.
 Training and logging are out of scope.
@@ -21,7 +24,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .blocks import AEDownsample, AEUpsample, AttnBlock2d, Normalize, ResnetBlock, norm_conv, packed_conv
+from .blocks import AEDownsample, AEUpsample, AttnBlock2d, AttnBlock3d, Normalize, ResnetBlock, _k3, conv_nd, norm_conv, packed_conv
 from .config import instantiate_from_config
 from .ops import CL, pad32
 
@@ -46,9 +49,19 @@ class DiagonalGaussianDistribution:
 
 
 def _make_attn(ch, attn_type="vanilla", dims=2):
-    if attn_type != "vanilla" or dims != 2:
-        raise NotImplementedError("only 2-D vanilla attention is used by the shipped AE configs")
-    return AttnBlock2d(ch)
+    """model.py:264-274 for attn_type "vanilla": AttnBlock2d / AttnBlock3d."""
+    if attn_type != "vanilla":
+        raise NotImplementedError(f"attn_type '{attn_type}' is not supported (only 'vanilla' attention is used by the shipped AE configs)")
+    return AttnBlock2d(ch) if dims == 2 else AttnBlock3d(ch)
+
+
+def _refuse_ae_options(who, dims, **options):
+    """The Encoder / Decoder options this engine has no execution rule for, refused by name; dims must be 2 or 3."""
+    if dims not in (2, 3):
+        raise NotImplementedError(f"{who}: dims = {dims} is not supported (2 or 3)")
+    for name, on in options.items():
+        if on:
+            raise NotImplementedError(f"{who}: {name} is not supported (used by no shipped AE config)")
 
 
 class Encoder(nn.Module):
@@ -56,10 +69,10 @@ class Encoder(nn.Module):
                  resamp_with_conv=True, in_channels, resolution, z_channels, double_z=True, use_linear_attn=False,
                  attn_type="vanilla", dims=2, **ignore_kwargs):
         super().__init__()
-        assert dims == 2 and not use_linear_attn
-        self.ch, self.num_resolutions, self.num_res_blocks = ch, len(ch_mult), num_res_blocks
+        _refuse_ae_options("Encoder", dims, use_linear_attn=use_linear_attn, **{"resamp_with_conv=False": not resamp_with_conv})
+        self.ch, self.num_resolutions, self.num_res_blocks, self.dims = ch, len(ch_mult), num_res_blocks, dims
         self.resolution, self.in_channels = resolution, in_channels
-        self.conv_in = nn.Conv2d(in_channels, ch, 3, 1, 1)
+        self.conv_in = conv_nd(dims, in_channels, ch, 3, 1, 1)
         curr_res = resolution
         in_ch_mult = (1,) + tuple(ch_mult)
         self.down = nn.ModuleList()
@@ -68,26 +81,27 @@ class Encoder(nn.Module):
             block, attn = nn.ModuleList(), nn.ModuleList()
             block_in, block_out = ch * in_ch_mult[i_level], ch * ch_mult[i_level]
             for _ in range(num_res_blocks):
-                block.append(ResnetBlock(in_channels=block_in, out_channels=block_out, dropout=dropout))
+                block.append(ResnetBlock(in_channels=block_in, out_channels=block_out, dropout=dropout, dims=dims))
                 block_in = block_out
                 if curr_res in attn_resolutions:
                     attn.append(_make_attn(block_in, attn_type, dims))
             down = nn.Module()
             down.block, down.attn = block, attn
             if i_level != self.num_resolutions - 1:
-                down.downsample = AEDownsample(block_in, resamp_with_conv)
+                down.downsample = AEDownsample(block_in, resamp_with_conv, dims=dims)
                 curr_res //= 2
             self.down.append(down)
         self.mid = nn.Module()
-        self.mid.block_1 = ResnetBlock(in_channels=block_in, out_channels=block_in, dropout=dropout)
+        self.mid.block_1 = ResnetBlock(in_channels=block_in, out_channels=block_in, dropout=dropout, dims=dims)
         self.mid.attn_1 = _make_attn(block_in, attn_type, dims)
-        self.mid.block_2 = ResnetBlock(in_channels=block_in, out_channels=block_in, dropout=dropout)
+        self.mid.block_2 = ResnetBlock(in_channels=block_in, out_channels=block_in, dropout=dropout, dims=dims)
         self.norm_out = Normalize(block_in)
-        self.conv_out = nn.Conv2d(block_in, 2 * z_channels if double_z else z_channels, 3, 1, 1)
+        self.conv_out = conv_nd(dims, block_in, 2 * z_channels if double_z else z_channels, 3, 1, 1)
 
     def run(self, x: CL) -> CL:
+        k = _k3(self.conv_in.weight)
         pw, pb = packed_conv(self.conv_in, x.Cpad)
-        h = ops.conv(x, pw, pb, self.ch, k=(1, 3, 3))
+        h = ops.conv(x, pw, pb, self.ch, k=k)
         for i_level in range(self.num_resolutions):
             lvl = self.down[i_level]
             for i_block in range(self.num_res_blocks):
@@ -98,7 +112,7 @@ class Encoder(nn.Module):
                 h = lvl.downsample.run(h)
         h = self.mid.block_2.run(self.mid.attn_1.run(self.mid.block_1.run(h)))
         pw, pb = packed_conv(self.conv_out, h.Cpad)
-        return norm_conv(h, self.norm_out, True, pw, pb, self.conv_out.weight.shape[0], k=(1, 3, 3))
+        return norm_conv(h, self.norm_out, True, pw, pb, self.conv_out.weight.shape[0], k=k)
 
 
 class Decoder(nn.Module):
@@ -106,38 +120,40 @@ class Decoder(nn.Module):
                  resamp_with_conv=True, in_channels, resolution, z_channels, give_pre_end=False, tanh_out=False,
                  use_linear_attn=False, attn_type="vanilla", dims=2, **ignorekwargs):
         super().__init__()
-        assert dims == 2 and not use_linear_attn and not give_pre_end and not tanh_out
-        self.ch, self.num_resolutions, self.num_res_blocks = ch, len(ch_mult), num_res_blocks
+        _refuse_ae_options("Decoder", dims, use_linear_attn=use_linear_attn, give_pre_end=give_pre_end, tanh_out=tanh_out,
+                           **{"resamp_with_conv=False": not resamp_with_conv})
+        self.ch, self.num_resolutions, self.num_res_blocks, self.dims = ch, len(ch_mult), num_res_blocks, dims
         self.resolution, self.in_channels = resolution, in_channels
         block_in = ch * ch_mult[self.num_resolutions - 1]
         curr_res = resolution // 2 ** (self.num_resolutions - 1)
         self.z_shape = (1, z_channels, curr_res, curr_res)
-        self.conv_in = nn.Conv2d(z_channels, block_in, 3, 1, 1)
+        self.conv_in = conv_nd(dims, z_channels, block_in, 3, 1, 1)
         self.mid = nn.Module()
-        self.mid.block_1 = ResnetBlock(in_channels=block_in, out_channels=block_in, dropout=dropout)
+        self.mid.block_1 = ResnetBlock(in_channels=block_in, out_channels=block_in, dropout=dropout, dims=dims)
         self.mid.attn_1 = _make_attn(block_in, attn_type, dims)
-        self.mid.block_2 = ResnetBlock(in_channels=block_in, out_channels=block_in, dropout=dropout)
+        self.mid.block_2 = ResnetBlock(in_channels=block_in, out_channels=block_in, dropout=dropout, dims=dims)
         self.up = nn.ModuleList()
         for i_level in reversed(range(self.num_resolutions)):
             block, attn = nn.ModuleList(), nn.ModuleList()
             block_out = ch * ch_mult[i_level]
             for _ in range(num_res_blocks + 1):
-                block.append(ResnetBlock(in_channels=block_in, out_channels=block_out, dropout=dropout))
+                block.append(ResnetBlock(in_channels=block_in, out_channels=block_out, dropout=dropout, dims=dims))
                 block_in = block_out
                 if curr_res in attn_resolutions:
                     attn.append(_make_attn(block_in, attn_type, dims))
             up = nn.Module()
             up.block, up.attn = block, attn
             if i_level != 0:
-                up.upsample = AEUpsample(block_in, resamp_with_conv)
+                up.upsample = AEUpsample(block_in, resamp_with_conv, dims=dims)
                 curr_res *= 2
             self.up.insert(0, up)
         self.norm_out = Normalize(block_in)
-        self.conv_out = nn.Conv2d(block_in, out_ch, 3, 1, 1)
+        self.conv_out = conv_nd(dims, block_in, out_ch, 3, 1, 1)
 
     def run(self, z: CL, out_f32: bool = True) -> CL:
+        k = _k3(self.conv_in.weight)
         pw, pb = packed_conv(self.conv_in, z.Cpad)
-        h = ops.conv(z, pw, pb, self.conv_in.weight.shape[0], k=(1, 3, 3))
+        h = ops.conv(z, pw, pb, self.conv_in.weight.shape[0], k=k)
         h = self.mid.block_2.run(self.mid.attn_1.run(self.mid.block_1.run(h)))
         for i_level in reversed(range(self.num_resolutions)):
             lvl = self.up[i_level]
@@ -148,7 +164,30 @@ class Decoder(nn.Module):
             if i_level != 0:
                 h = lvl.upsample.run(h)
         pw, pb = packed_conv(self.conv_out, h.Cpad)
-        return norm_conv(h, self.norm_out, True, pw, pb, self.conv_out.weight.shape[0], k=(1, 3, 3), out_f32=out_f32)
+        return norm_conv(h, self.norm_out, True, pw, pb, self.conv_out.weight.shape[0], k=k, out_f32=out_f32)
+
+
+def first_stage_dims(who, ddconfig, dims) -> int:
+    """The spatial dimensionality of a first stage, by the reference's precedence: Encoder / Decoder take ddconfig["dims"] (2 when the key
+    is absent, model.py:432,528), quant_conv / post_quant_conv take the model's own `dims` argument (3 by default, autoencoder.py:36,
+    313).  Where the two differ the reference builds a model that cannot run (1x1x1 Conv3d on 2-D feature maps or the reverse), so that
+    is refused here -- except ddconfig["dims"] == 2 stated explicitly, which keeps meaning a 2-D model whatever `dims` says, as it did
+    before volumetric first stages existed."""
+    enc = ddconfig.get("dims", 2)
+    if "dims" in ddconfig and enc == 2:
+        return 2
+    if enc != dims or dims not in (2, 3):
+        raise NotImplementedError(f"{who}: dims = {dims} with ddconfig dims = {enc} (absent: 2) is not supported: the Encoder / Decoder "
+                                  "follow ddconfig[\"dims\"], the quant convs the model's dims, and the two must agree on 2 or 3; "
+                                  "the shipped AE configs are 2-D (…_ae.yaml:41-94) and state dims: 2 in both places")
+    return dims
+
+
+def check_rank(who, x, dims) -> None:
+    """Host-side refusal of a tensor whose rank is not the model's: a [N, C, H, W] tensor given to a dims = 3 model would otherwise run
+    as a one-slice volume (to_cl pads D to 1), and a volume given to a dims = 2 model as a stack the 2-D kernels misread."""
+    if x.ndim != dims + 2:
+        raise ValueError(f"{who}: a dims = {dims} model takes [N, C, {'D, ' if dims == 3 else ''}H, W] tensors, got shape {tuple(x.shape)}")
 
 
 class AutoencoderKL(nn.Module):
@@ -156,16 +195,17 @@ class AutoencoderKL(nn.Module):
                  colorize_nlabels=None, monitor=None, dims=3, conditional=False, cond_key=None):
         super().__init__()
         ddconfig = dict(ddconfig)
-        if ddconfig.get("dims", dims) != 2:
-            raise NotImplementedError("the shipped AE configs are 2-D (…_ae.yaml:41-94)")
+        if conditional:
+            raise NotImplementedError("AutoencoderKL: conditional=True / cond_key is not supported (it selects the training target only, "
+                                      "autoencoder.py:333-337,388)")
+        self.dims = first_stage_dims("AutoencoderKL", ddconfig, dims)
         assert ddconfig["double_z"]
         self.image_key = image_key
         self.encoder = Encoder(**ddconfig)
         self.decoder = Decoder(**ddconfig)
         self.loss = nn.Identity()                       # lossconfig is torch.nn.Identity in the shipped yaml; training is out of scope
-        self.dims = 2
-        self.quant_conv = nn.Conv2d(2 * ddconfig["z_channels"], 2 * embed_dim, 1)
-        self.post_quant_conv = nn.Conv2d(embed_dim, ddconfig["z_channels"], 1)
+        self.quant_conv = conv_nd(self.dims, 2 * ddconfig["z_channels"], 2 * embed_dim, 1)
+        self.post_quant_conv = conv_nd(self.dims, embed_dim, ddconfig["z_channels"], 1)
         self.embed_dim = embed_dim
         if ckpt_path is not None:
             self.init_from_ckpt(ckpt_path, ignore_keys=ignore_keys)
@@ -198,13 +238,15 @@ class AutoencoderKL(nn.Module):
 
     # ---- reference surface (NCHW fp32)
     def encode(self, x: torch.Tensor) -> DiagonalGaussianDistribution:
+        check_rank("AutoencoderKL.encode", x, self.dims)
         ops.require_gpu(x, "AutoencoderKL.encode")
         m = self.encode_moments_cl(ops.to_cl(x))
-        return DiagonalGaussianDistribution(ops.from_cl(m, 2))
+        return DiagonalGaussianDistribution(ops.from_cl(m, self.dims))
 
     def decode(self, z: torch.Tensor) -> torch.Tensor:
+        check_rank("AutoencoderKL.decode", z, self.dims)
         ops.require_gpu(z, "AutoencoderKL.decode")
-        return ops.from_cl(self.decode_cl(ops.to_cl(z)), 2)
+        return ops.from_cl(self.decode_cl(ops.to_cl(z)), self.dims)
 
 
 class VectorQuantizer(nn.Module):
@@ -242,14 +284,16 @@ class VectorQuantizer(nn.Module):
         return quant, None, (None, None, idx.long().view(-1, 1))
 
     def get_codebook_entry(self, indices, shape):
-        """Codebook rows of `indices`; shape = (batch, height, width, channel) reshapes them to [batch, channel, height, width]."""
+        """Codebook rows of `indices`; shape = (batch, [depth,] height, width, channel) reshapes them to [batch, channel, [depth,]
+        height, width] (taming's method is 2-D only; volumes follow the same rule)."""
         z_q = self.embedding(indices.reshape(-1).long())
         if shape is not None:
-            z_q = z_q.view(shape).permute(0, 3, 1, 2).contiguous()
+            nd = len(shape) - 2
+            z_q = z_q.view(shape).permute((0, nd + 1) + tuple(range(1, nd + 1))).contiguous()
         return z_q
 
     def embed_code(self, code_b):
-        """Indices [N, H, W] -> codebook rows as [N, C, H, W] (what VQModel.decode_code feeds to decode)."""
+        """Indices [N, [D,] H, W] -> codebook rows as [N, C, [D,] H, W] (what VQModel.decode_code feeds to decode)."""
         return self.get_codebook_entry(code_b, tuple(code_b.shape) + (self.e_dim,))
 
 
@@ -263,8 +307,7 @@ class VQModel(nn.Module):
                  sane_index_shape=False, use_ema=False, l1_weight=0.5, dims=3):
         super().__init__()
         ddconfig = dict(ddconfig)
-        if ddconfig.get("dims", dims) != 2:
-            raise NotImplementedError("the shipped AE configs are 2-D (…_ae.yaml:41-94)")
+        self.dims = first_stage_dims(type(self).__name__, ddconfig, dims)
         for name, on in (("remap", remap is not None), ("sane_index_shape", bool(sane_index_shape)),
                          ("batch_resize_range", batch_resize_range is not None), ("use_ema", bool(use_ema))):
             if on:
@@ -278,9 +321,8 @@ class VQModel(nn.Module):
         self.decoder = Decoder(**ddconfig)
         self.loss = nn.Identity()                       # training is out of scope
         self.quantize = VectorQuantizer(n_embed, embed_dim, beta=0.25)
-        self.dims = 2
-        self.quant_conv = nn.Conv2d(2 * ddconfig["z_channels"], embed_dim, 1)
-        self.post_quant_conv = nn.Conv2d(embed_dim, ddconfig["z_channels"], 1)
+        self.quant_conv = conv_nd(self.dims, 2 * ddconfig["z_channels"], embed_dim, 1)
+        self.post_quant_conv = conv_nd(self.dims, embed_dim, ddconfig["z_channels"], 1)
         if colorize_nlabels is not None:
             self.register_buffer("colorize", torch.randn(3, colorize_nlabels, 1, 1))
         self.use_ema = False
@@ -304,20 +346,24 @@ class VQModel(nn.Module):
 
     # ---- reference surface (NCHW fp32)
     def encode_to_prequant(self, x: torch.Tensor) -> torch.Tensor:
+        check_rank(f"{type(self).__name__}.encode", x, self.dims)
         ops.require_gpu(x, f"{type(self).__name__}.encode")
-        return ops.from_cl(self.prequant_cl(ops.to_cl(x)), 2)
+        return ops.from_cl(self.prequant_cl(ops.to_cl(x)), self.dims)
 
     def encode(self, x: torch.Tensor):
+        check_rank("VQModel.encode", x, self.dims)
         ops.require_gpu(x, "VQModel.encode")
         h = self.prequant_cl(ops.to_cl(x))
-        N, _, H, W, Cp = h.t.shape
+        Cp, nd = h.Cpad, self.dims
+        sp = tuple(h.t.shape[4 - nd:4])
         idx, st = self.quantize.quantize_rows(h.t.view(-1, Cp))        # the padded fp32 rows are read in place
-        quant = st.view(N, H, W, self.embed_dim).permute(0, 3, 1, 2).contiguous()
+        quant = st.view((h.N,) + sp + (self.embed_dim,)).permute((0, nd + 1) + tuple(range(1, nd + 1))).contiguous()
         return quant, None, (None, None, idx.long().view(-1, 1))
 
     def decode(self, quant: torch.Tensor) -> torch.Tensor:
+        check_rank(f"{type(self).__name__}.decode", quant, self.dims)
         ops.require_gpu(quant, f"{type(self).__name__}.decode")
-        return ops.from_cl(self.decode_cl(ops.to_cl(quant)), 2)
+        return ops.from_cl(self.decode_cl(ops.to_cl(quant)), self.dims)
 
     def decode_code(self, code_b):
         return self.decode(self.quantize.embed_code(code_b))
@@ -340,6 +386,7 @@ class VQModelInterface(VQModel):
         return self.encode_to_prequant(x)
 
     def decode(self, h, force_not_quantize=False):
+        check_rank("VQModelInterface.decode", h, self.dims)
         ops.require_gpu(h, "VQModelInterface.decode")
         quant = h if force_not_quantize else self.quantize(h)[0]
         return super().decode(quant)

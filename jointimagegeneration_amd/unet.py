@@ -249,6 +249,9 @@ class UNetModel(_UNetBase):
         super().__init__()
         if use_spatial_transformer:
             assert context_dim is not None, "use_spatial_transformer requires context_dim"
+        if use_spatial_transformer and dims != 2:
+            raise NotImplementedError(f"use_spatial_transformer with dims = {dims} is not supported (the reference's SpatialTransformer is "
+                                      "Conv2d-only, attention.py:218-241); a dims = 3 UNetModel uses AttentionBlock")
         if context_dim is not None:
             assert use_spatial_transformer, "context_dim requires use_spatial_transformer"
             context_dim = list(context_dim) if not isinstance(context_dim, int) else context_dim
