@@ -366,6 +366,23 @@ int gg_ddim_step_vq(float *x, const float *eps, int32_t eps_stride, const float 
                     const float *codebook, int32_t n_embed, int64_t M, int32_t C, int32_t *idx_out, float *pred_x0_out,
                     void *unet_in, int32_t unet_in_stride, void *stream);
 
+/* Pairwise confusion matrices of label volumes (gg_metrics.hip): the one pass over the voxels behind Dice (ccdm/ddpm/evaluator.py:188-190)
+ * and the ensemble scores of ccdm/ddpm/utils.py:190-236 (generalised energy distance, Hungarian-matched IoU), which are fp64 formulas on
+ * these counts (jointimagegeneration_amd/metrics.py).  a int32 [Sa, M], b int32 [Sb, M], contiguous, on the device; a == b (self pairs
+ * on one buffer) is allowed.
+ *   cm_out[i, j, p, q] = #{ m : a[i, m] == p and b[j, m] == q }                      int64 [Sa, Sb, K, K]
+ *   skipped_out[i, j]  = #{ m : a[i, m] or b[j, m] outside [0, K) }                  int64 [Sa, Sb], optional (NULL: not reported)
+ *   A voxel with a label outside [0, K) is counted in skipped_out alone and never indexes a histogram.  Both outputs are zeroed by the
+ *   call (hipMemsetAsync on `stream`, ahead of the launch): a second call into the same buffers gives the same answer.  Exact integer
+ *   counts, independent of the order of execution.  A workgroup takes a chunk of voxels and a tile of up to T x T pairs (T from K:
+ *   6 for K <= 16, 3 for K = 32) and reads each of its volumes once; uint32 histograms in LDS (a chunk has at most 2^24 voxels),
+ *   flushed with 64-bit atomic adds.  GG_CONFUSION_UNIFORM=0 in the environment disables the one-add-per-wave path of waves whose
+ *   labels are uniform (measurement switch; same counts).
+ *   NULL a, b or cm_out, Sa < 1, Sb < 1, M < 1, K outside [1, 32]: GG_ERR_BAD_SHAPE before any launch.  No allocation, no host
+ *   readback, no synchronisation: capturable. */
+int gg_label_confusion(const int32_t *a, int32_t Sa, const int32_t *b, int32_t Sb, int64_t M, int32_t K, int64_t *cm_out,
+                       int64_t *skipped_out, void *stream);
+
 /* Patch-wise evaluation (LatentDiffusion.split_input_params, ddpm.py:573-660), gg_fold.hip.  Geometry of torch.nn.Unfold / Fold with
  * dilation 1 and padding 0: Ly = (H - kh) / sy + 1, Lx = (W - kw) / sx + 1, crop l = ly * Lx + lx starts at (ly * sy, lx * sx); crop l
  * of sample n is row l * N + n of the crop batch.

@@ -1,14 +1,21 @@
 """CCDM mask sampling entry point: `python -m jointimagegeneration_amd.ddpm_eval params_eval.yml [exp_name]`.
 
 Re-creates the CLI/config/checkpoint surface of ccdm/ddpm_eval.py:16-57 + ccdm/ddpm/evaluator.py:127-170,215-237,326-393
-without ignite, datasets or metrics (out of scope, SURVEY.md 2.1 rows 4,7): seeds, flat yaml dict,
+without ignite or datasets (out of scope, SURVEY.md 2.1 rows 4,7): seeds, flat yaml dict,
 `build_model(..., backbone, params[params["backbone"]], ...)`, ignite-style checkpoint {"model", "average_model"} holding the
 UNet's state_dict, x_T ~ uniform one-hot, condition image = zeros, output label = argmax.  Inputs are synthetic (the
 hospital dataset is private): the volume extent comes from --size or the yaml key `input_size`.
+
+Scores (evaluator.py:188-190, ddpm/utils.py:190-236; metrics.py): `--gt DIR` holds `gt_{vid:04d}.nii.gz` label volumes of the run's size;
+the run then accumulates the [K, K] confusion matrix on the device and rank 0 writes `metrics.json` (the integer matrix, Dice per class
+with `--ignore-class` removed, its mean).  `--samples S` (the yaml comment "samples: 12  # For GED calculation") samples S masks per
+volume as one batch, written as `pred_{vid:04d}_s{j:02d}.nii.gz`; with --gt each volume then also gets its GED, the two diversities and
+the Hungarian-matched IoU.  Without these options the run writes exactly what it wrote before they existed.
 """
 from __future__ import annotations
 
 import argparse
+import json
 import os
 import random
 import sys
@@ -19,6 +26,7 @@ import torch
 import yaml
 
 from . import distributed as ggd
+from . import metrics
 from .ccdm import build_model
 from .encoder import build_feature_cond_encoder
 from .io import load_checkpoint, write_nifti
@@ -64,7 +72,12 @@ def main(argv=None):
     ap.add_argument("--num-volumes", type=int, default=None, help="volumes to sample (default: yaml batch_size, reference forces 2)")
     ap.add_argument("--steps", type=int, default=None, help="run K evenly spaced reverse steps (reference convention t = 10000+K)")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--samples", type=int, default=1, help="masks per volume, sampled as one batch (pred_VVVV_sJJ.nii.gz; GED / HM-IoU with --gt)")
+    ap.add_argument("--gt", default=None, help="directory of gt_{vid:04d}.nii.gz label volumes: score the run into metrics.json")
+    ap.add_argument("--ignore-class", type=int, default=None, help="class left out of Dice (default: yaml ignore_class, else 0)")
     args = ap.parse_args(argv)
+    if args.samples < 1:
+        raise ValueError(f"--samples {args.samples}: at least one mask per volume")
     set_seeds(1024)
     with open(args.params_file, "r") as f:
         params = yaml.safe_load(f)
@@ -72,6 +85,10 @@ def main(argv=None):
     size = tuple(args.size or params.get("input_size") or (64, 128, 128))
     K = args.num_classes or params.get("num_classes", 12)
     rank, local, world = ggd.env_rank_world()
+    vids = ggd.shard(params["batch_size"], rank, world)
+    S = args.samples
+    ignore = args.ignore_class if args.ignore_class is not None else params.get("ignore_class", 0)      # ruijin's get_ignore_class: 0
+    gts = metrics.load_gt(args.gt, vids, size, K) if args.gt else None           # a bad ground truth ends the run before any sampling
     assert torch.cuda.is_available(), "the GuideGen engine needs an MI355X (no CPU fallback)"
     dev = torch.device("cuda", local)
     torch.cuda.set_device(dev)
@@ -107,15 +124,45 @@ def main(argv=None):
     os.makedirs(out_dir, exist_ok=True)
     init_t = None if args.steps is None else 10000 + args.steps
     t0 = time.time()
-    for vid in ggd.shard(params["batch_size"], rank, world):                          # volumes are independent units
-        g = torch.Generator(device=dev).manual_seed(1024 + vid)
-        x_T = torch.randint(0, K, (1,) + size, generator=g, device=dev, dtype=torch.int32)   # uniform categorical x_T
-        model.philox_seed = 1024 + vid
-        labels, _ = model.sample_labels(x_T, torch.zeros((1, 1) + size, device=dev), init_t)
-        write_nifti(os.path.join(out_dir, f"pred_{vid:04d}.nii.gz"), labels[0].to(torch.uint8).cpu().numpy())
+    # scores travel as ONE int64 buffer: the [K, K] counts, then 4 fp64 scores per volume stored as their bit patterns (a volume belongs
+    # to one rank and the other ranks hold zeros there, so the integer sum over ranks reproduces the bits)
+    n_vol = params["batch_size"]
+    score_buf = torch.zeros(K * K + 4 * n_vol, dtype=torch.int64, device=dev) if gts is not None else None
+    for vid in vids:                                                                  # volumes are independent units
+        if S == 1:
+            g = torch.Generator(device=dev).manual_seed(1024 + vid)
+            x_T = torch.randint(0, K, (1,) + size, generator=g, device=dev, dtype=torch.int32)   # uniform categorical x_T
+            model.philox_seed = 1024 + vid
+            labels, _ = model.sample_labels(x_T, torch.zeros((1, 1) + size, device=dev), init_t)
+            write_nifti(os.path.join(out_dir, f"pred_{vid:04d}.nii.gz"), labels[0].to(torch.uint8).cpu().numpy())
+        else:                                                                         # the S masks of a volume: one batch, S independent chains
+            seeds = [1024 + vid * S + j for j in range(S)]
+            x_T = torch.cat([torch.randint(0, K, (1,) + size, generator=torch.Generator(device=dev).manual_seed(sd), device=dev, dtype=torch.int32)
+                             for sd in seeds])
+            labels, _ = model.sample_labels(x_T, torch.zeros((S, 1) + size, device=dev), init_t, philox_seeds=seeds)
+            host = labels.to(torch.uint8).cpu().numpy()
+            for j in range(S):
+                write_nifti(os.path.join(out_dir, f"pred_{vid:04d}_s{j:02d}.nii.gz"), host[j])
+        if gts is not None:
+            cm, scores = metrics.score_case(labels, torch.from_numpy(gts[vid]).to(dev), K)
+            score_buf[:K * K] += cm.reshape(-1)
+            if scores is not None:
+                vals = torch.tensor([scores["ged"], scores["diversity_pred"], scores["diversity_gt"], scores["hm_iou"]], dtype=torch.float64)
+                score_buf[K * K + 4 * vid:K * K + 4 * vid + 4] = vals.view(torch.int64).to(dev)
     torch.cuda.synchronize()
-    print(f"[rank {rank}] sampled {len(ggd.shard(params['batch_size'], rank, world))} volume(s) of {size} in {time.time() - t0:.1f}s -> {out_dir}",
-          file=sys.stderr)
+    print(f"[rank {rank}] sampled {len(vids)} volume(s) of {size} in {time.time() - t0:.1f}s -> {out_dir}", file=sys.stderr)
+    if score_buf is not None:
+        if torch.distributed.is_available() and torch.distributed.is_initialized():
+            torch.distributed.all_reduce(score_buf)                                   # once, after the sampling loop: off the data path
+        if rank == 0:
+            host = score_buf.cpu()
+            per = host[K * K:].view(torch.float64).reshape(n_vol, 4).tolist()
+            volumes = [dict(id=v, samples=S, **(dict(zip(("ged", "diversity_pred", "diversity_gt", "hm_iou"), per[v])) if S > 1 else {}))
+                       for v in range(n_vol)]
+            doc = metrics.summarise(host[:K * K].reshape(K, K), volumes, K, ignore)
+            with open(os.path.join(out_dir, "metrics.json"), "w") as f:
+                json.dump(doc, f, indent=1)
+            print(f"[rank 0] {metrics.summary_line(doc)} -> {os.path.join(out_dir, 'metrics.json')}", file=sys.stderr)
     ggd.finalize()
 
 

@@ -889,6 +889,41 @@ def fold_weighted_cl(crops: torch.Tensor, C: int, weight: torch.Tensor, tie: Opt
     return out
 
 
+def _label_rows(t: torch.Tensor, K: int, what: str) -> torch.Tensor:
+    """[S, *spatial] integer labels -> contiguous int32 [S, M] (plumbing; an int64 label is clamped to [-1, K] first, so that no value
+    outside int32 can wrap into the valid range)."""
+    require_gpu(t, what)
+    if t.dim() < 2 or t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
+        raise ValueError(f"{what}: labels must be an integer tensor [S, *spatial], got {t.dtype} {tuple(t.shape)}")
+    if t.dtype == torch.int64:
+        t = t.clamp(-1, K)
+    return t.reshape(t.shape[0], -1).to(torch.int32).contiguous()
+
+
+def label_confusion(a: torch.Tensor, b: torch.Tensor, K: int) -> torch.Tensor:
+    """Pairwise confusion matrices of label volumes (gg_label_confusion): a [Sa, *spatial], b [Sb, *spatial] integer tensors on the device
+    -> int64 [Sa, Sb, K, K] with cm[i, j, p, q] = #{voxels m : a[i, m] == p and b[j, m] == q}.  `b is a` scores the self pairs on one
+    buffer.  A label outside [0, K) raises ValueError naming the first such pair and its voxel count (ignite's ConfusionMatrix raises on
+    such labels too); reading that count back is the one host sync of the call."""
+    ra = _label_rows(a, K, "label_confusion")
+    rb = ra if b is a else _label_rows(b, K, "label_confusion")
+    if ra.shape[1] != rb.shape[1] or ra.device != rb.device:
+        raise ValueError(f"label_confusion: volumes of {tuple(a.shape[1:])} and {tuple(b.shape[1:])} voxels (or on two devices)")
+    if not 1 <= K <= 32:
+        raise ValueError(f"label_confusion: K={K} outside [1, 32]")
+    lib = _lib.load()
+    Sa, Sb, M = ra.shape[0], rb.shape[0], ra.shape[1]
+    cm = torch.empty((Sa, Sb, K, K), dtype=torch.int64, device=ra.device)
+    skipped = torch.empty((Sa, Sb), dtype=torch.int64, device=ra.device)
+    check(lib.gg_label_confusion(ra.data_ptr(), Sa, rb.data_ptr(), Sb, M, K, cm.data_ptr(), skipped.data_ptr(), _stream()), "gg_label_confusion")
+    sk = skipped.cpu()
+    if int(sk.sum()) != 0:
+        i, j = (int(v) for v in torch.nonzero(sk)[0])
+        raise ValueError(f"label_confusion: pair ({i}, {j}) has {int(sk[i, j])} voxel(s) with a label outside [0, {K}) "
+                         f"({int((sk != 0).sum())} of {Sa * Sb} pairs affected)")
+    return cm
+
+
 def minmax_normalise(src: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     lib = _lib.load()
     if out is None:
