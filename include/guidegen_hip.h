@@ -383,6 +383,32 @@ int gg_ddim_step_vq(float *x, const float *eps, int32_t eps_stride, const float 
 int gg_label_confusion(const int32_t *a, int32_t Sa, const int32_t *b, int32_t Sb, int64_t M, int32_t K, int64_t *cm_out,
                        int64_t *skipped_out, void *stream);
 
+/* Three-view LPIPS of CT volumes (ldm/modules/losses/lpips.py; latentdiffusion/sample_diffusion.py:437-475), gg_lpips.hip: the kernels
+ * around the VGG16 convolutions (which are gg_conv_forward / gg_conv_forward_f32 calls).  All three: the caller's stream, no allocation,
+ * no synchronisation, capturable.
+ * gg_volume_views_cl: x fp32 [B, D, H, W] -> out channels-last [n1 - n0, 1, hh, ww, 32] (GG_BF16 or GG_F32), the images [n0, n1) of one
+ *   axis view: view 0 = "(b d) 1 h w" (B * D images of H x W), 1 = "(b h) 1 d w" (B * H images of D x W), 2 = "(b w) 1 d h" (B * W
+ *   images of D x H); view 3 reads x as [B, 3, H, W] three-channel images (D must be 3).  Channel c < 3 of a pixel is
+ *   (x - shift[c]) / scale[c] (views 0..2: the same x for the three channels, ScalingLayer's broadcast of a 1-channel slice), fp32
+ *   subtraction and IEEE fp32 division, rounded once to the output type; channels 3..31 are zero.  shift, scale: device fp32[3].
+ *   Views 0, 1, 3 read along W directly; view 2 stages 32 images x 32 pixels through LDS so that reads and writes both stay
+ *   coalesced.  An image range outside the view, a view outside 0..3: GG_ERR_BAD_SHAPE.
+ * gg_relu_cl: x = max(x, 0) in place on n elements (n % 32 == 0: whole channels-last rows), GG_BF16 or GG_F32.
+ * gg_lpips_tap: a, b channels-last [n, h, w, C] (C % 32 == 0, C <= 2048 bf16 / 1024 fp32), the PRE-ReLU conv outputs of the two images
+ *   at a tap; lin_w device fp32 [C].  Per image
+ *     v = (1 / (h w)) sum_pixels sum_c lin_w[c] * (A_c / (|A| + 1e-10) - B_c / (|B| + 1e-10))^2,  A = relu(a), |A| = sqrt(sum_c A_c^2),
+ *   accumulated in fp32 (an all-zero row contributes through 0 / 1e-10 = 0).  tap_out[i] = v (optional); total[i] = v, or total[i] + v
+ *   with accumulate != 0 (optional).  pool_a / pool_b (both or neither): [n, h / 2, w / 2, C] = MaxPool2d(2, 2)(relu(.)), floor
+ *   semantics, exact.  Deterministic: per-workgroup partial sums (fixed tree), added per image in index order by a second kernel; no
+ *   floating-point atomics; the partition depends on (h, w, C, dtype) only, so an image's value does not depend on n.
+ *   workspace: gg_lpips_tap_workspace_bytes(n, h, w, C, dtype) bytes (a negative gg_status for a refused shape). */
+int gg_volume_views_cl(const float *x, int32_t B, int32_t D, int32_t H, int32_t W, int32_t view, int64_t n0, int64_t n1, const float *shift,
+                       const float *scale, void *out, int32_t out_dtype, void *stream);
+int gg_relu_cl(void *x, int32_t dtype, int64_t n, void *stream);
+int64_t gg_lpips_tap_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t C, int32_t dtype);
+int gg_lpips_tap(const void *a, const void *b, int32_t dtype, int32_t n, int32_t h, int32_t w, int32_t C, const float *lin_w, void *pool_a,
+                 void *pool_b, float *tap_out, float *total, int32_t accumulate, float *workspace, int64_t workspace_bytes, void *stream);
+
 /* Patch-wise evaluation (LatentDiffusion.split_input_params, ddpm.py:573-660), gg_fold.hip.  Geometry of torch.nn.Unfold / Fold with
  * dilation 1 and padding 0: Ly = (H - kh) / sy + 1, Lx = (W - kw) / sx + 1, crop l = ly * Lx + lx starts at (ly * sy, lx * sx); crop l
  * of sample n is row l * N + n of the crop batch.

@@ -84,6 +84,10 @@ SIGNATURES = {
     "gg_vq_nearest": (C.c_int, [vp, i32, vp, i32, i32, i64, vp, vp, i32, vp]),
     "gg_ddim_step_vq": (C.c_int, [vp, vp, i32, vp, vp, i32, vp, i32, i64, i32, vp, vp, vp, i32, vp]),
     "gg_label_confusion": (C.c_int, [vp, i32, vp, i32, i64, i32, vp, vp, vp]),
+    "gg_volume_views_cl": (C.c_int, [vp, i32, i32, i32, i32, i32, i64, i64, vp, vp, vp, i32, vp]),
+    "gg_relu_cl": (C.c_int, [vp, i32, i64, vp]),
+    "gg_lpips_tap_workspace_bytes": (i64, [i32, i32, i32, i32, i32]),
+    "gg_lpips_tap": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, i64, vp]),
     "gg_unfold_cl": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
     "gg_fold_weighted_cl": (C.c_int, [vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "gg_lincomb4": (C.c_int, [vp, vp, vp, vp, f32, f32, f32, f32, f32, i64, vp, vp]),

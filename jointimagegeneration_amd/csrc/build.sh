@@ -8,7 +8,7 @@ FLAGS="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -Wall -Wno-unused-function -fn
 if [ "${GG_CLEAN:-0}" = "1" ]; then rm -f ./*.o libguidegen_hip.so; fi
 OBJS=()
 PIDS=()
-for f in gg_conv gg_conv_halo gg_conv_halo3 gg_conv_box gg_conv_box_spec gg_conv_tiny gg_norm gg_attn gg_sampler gg_vq gg_metrics gg_fold gg_f32 gg_resample gg_ubench; do
+for f in gg_conv gg_conv_halo gg_conv_halo3 gg_conv_box gg_conv_box_spec gg_conv_tiny gg_norm gg_attn gg_sampler gg_vq gg_metrics gg_lpips gg_fold gg_f32 gg_resample gg_ubench; do
   if [ ! -f $f.o ] || [ $f.hip -nt $f.o ] || [ gg_common.h -nt $f.o ] || [ gg_conv.h -nt $f.o ] || [ gg_conv_halo3_asm.inc -nt $f.o ] || [ gg_posterior.h -nt $f.o ] || [ gg_conv_box_kernel.h -nt $f.o ] || [ gg_conv_box_specs.inc -nt $f.o ] || [ ../../include/guidegen_hip.h -nt $f.o ]; then
     echo "hipcc $f.hip"
     EXTRA=""

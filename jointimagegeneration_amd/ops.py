@@ -924,6 +924,67 @@ def label_confusion(a: torch.Tensor, b: torch.Tensor, K: int) -> torch.Tensor:
     return cm
 
 
+# ----------------------------------------------------------------------------------------------- LPIPS (gg_lpips.hip)
+def volume_views_cl(x: torch.Tensor, view: int, n0: int, n1: int, shift: torch.Tensor, scale: torch.Tensor, out: torch.Tensor) -> CL:
+    """Images [n0, n1) of one axis view of an fp32 volume batch x [B, D, H, W] as channels-last rows (gg_volume_views_cl): view 0 =
+    "(b d) 1 h w", 1 = "(b h) 1 d w", 2 = "(b w) 1 d h"; view 3 reads x as [B, 3, H, W] images.  Channels 0..2 = (x - shift_c) /
+    scale_c, channels 3..31 zero.  out: contiguous [n1 - n0, 1, hh, ww, 32], bf16 or fp32; shift, scale: device fp32 with 3 values."""
+    require_gpu(x, "volume_views_cl")
+    if x.dtype != torch.float32 or x.dim() != 4 or not x.is_contiguous():
+        raise ValueError(f"volume_views_cl: x must be a contiguous fp32 [B, D, H, W] tensor, got {x.dtype} {tuple(x.shape)}")
+    B, D, H, W = (int(v) for v in x.shape)
+    if view not in (0, 1, 2, 3) or (view == 3 and D != 3):
+        raise ValueError(f"volume_views_cl: view {view} of a {tuple(x.shape)} tensor")
+    hh, ww = ((H, W), (D, W), (D, H), (H, W))[view]
+    for name, t in (("shift", shift), ("scale", scale)):
+        if t.dtype != torch.float32 or t.numel() != 3 or not t.is_contiguous() or t.device != x.device:
+            raise ValueError(f"volume_views_cl: {name} must be 3 contiguous fp32 values on {x.device}")
+    if tuple(out.shape) != (n1 - n0, 1, hh, ww, 32) or not out.is_contiguous() or out.device != x.device:
+        raise ValueError(f"volume_views_cl: out must be a contiguous {(n1 - n0, 1, hh, ww, 32)} tensor on {x.device}, got {tuple(out.shape)}")
+    check(_lib.load().gg_volume_views_cl(x.data_ptr(), B, D, H, W, view, n0, n1, shift.data_ptr(), scale.data_ptr(), out.data_ptr(),
+                                         _cl_dtype(out, "volume_views_cl"), _stream()), "gg_volume_views_cl")
+    return CL(out, 3)
+
+
+def relu_cl(x: CL) -> CL:
+    """In-place ReLU of a channels-last tensor (gg_relu_cl)."""
+    require_gpu(x.t, "relu_cl")
+    if not x.t.is_contiguous():
+        raise ValueError("relu_cl: a contiguous channels-last tensor")
+    check(_lib.load().gg_relu_cl(x.t.data_ptr(), _cl_dtype(x.t, "relu_cl"), x.t.numel(), _stream()), "gg_relu_cl")
+    return x
+
+
+def lpips_tap(a: torch.Tensor, b: torch.Tensor, lin_w: torch.Tensor, pool: bool = True, tap_out: Optional[torch.Tensor] = None,
+              total: Optional[torch.Tensor] = None, accumulate: bool = False):
+    """One LPIPS tap (gg_lpips_tap).  a, b: channels-last [n, 1, h, w, C] pre-ReLU conv outputs of the two images (views of one tensor
+    are fine as long as each is contiguous); lin_w fp32 [C].  Returns (per-image values fp32 [n], pooled): pooled is
+    MaxPool2d(2, 2)(relu(.)) of both as ONE batch [2 n, 1, h // 2, w // 2, C] (a's images first: the next convolution's input), or None
+    with pool=False.  total (fp32 [n]) receives the value too, added
+    to what it holds with accumulate=True."""
+    require_gpu(a, "lpips_tap")
+    if a.shape != b.shape or a.dtype != b.dtype or a.dim() != 5 or a.shape[1] != 1 or not a.is_contiguous() or not b.is_contiguous():
+        raise ValueError(f"lpips_tap: two contiguous channels-last [n, 1, h, w, C] tensors of one dtype, got {tuple(a.shape)} {a.dtype} and {tuple(b.shape)} {b.dtype}")
+    n, _, h, w, Cc = (int(v) for v in a.shape)
+    if lin_w.dtype != torch.float32 or lin_w.numel() != Cc or not lin_w.is_contiguous() or lin_w.device != a.device:
+        raise ValueError(f"lpips_tap: lin_w must be {Cc} contiguous fp32 weights on {a.device}")
+    lib = _lib.load()
+    dt = _cl_dtype(a, "lpips_tap")
+    wsb = lib.gg_lpips_tap_workspace_bytes(n, h, w, Cc, dt)
+    check(min(wsb, 0), "gg_lpips_tap_workspace_bytes")
+    ws = torch.empty(wsb // 4, dtype=torch.float32, device=a.device)
+    if tap_out is None:
+        tap_out = torch.empty(n, dtype=torch.float32, device=a.device)
+    for name, t in (("tap_out", tap_out), ("total", total)):
+        if t is not None and (t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous() or t.device != a.device):
+            raise ValueError(f"lpips_tap: {name} must be {n} contiguous fp32 values on {a.device}")
+    pooled = torch.empty((2 * n, 1, h // 2, w // 2, Cc), dtype=a.dtype, device=a.device) if pool else None
+    check(lib.gg_lpips_tap(a.data_ptr(), b.data_ptr(), dt, n, h, w, Cc, lin_w.data_ptr(), _ptr(pooled[:n]) if pool else None,
+                           _ptr(pooled[n:]) if pool else None, tap_out.data_ptr(), _ptr(total), 1 if accumulate else 0, ws.data_ptr(), wsb,
+                           _stream()), "gg_lpips_tap")
+    return tap_out, pooled
+
+
 def minmax_normalise(src: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     lib = _lib.load()
     if out is None:

@@ -6,7 +6,9 @@ overrides; config = logdir/configs/*.yaml merged (+ dot-list); model = instantia
 checkpoint's "state_dict" loaded strict=False; sampling under model.ema_scope().  `sample_cond` keeps the reference's
 slice loop exactly (Python indexing quirks included) on the reference-shaped API (get_learned_conditioning /
 DDIMSampler.sample / decode_first_stage); `GuideGenPipeline.sample_ct` is the all-device fast path of the same loop.
-Metrics (LPIPS/FVD), PNG grids and the private datasets are out of scope; the mask comes from `--inputs <dir>` (the
+With `--gt DIR --lpips-vgg PATH --lpips-lin PATH` each sampled volume is scored against the same-named volume of DIR with the
+three-view LPIPS of compute_metrics (sample_diffusion.py:436-475; jointimagegeneration_amd/lpips.py) and metrics.json is written next to
+the samples.  FVD (no I3D network or scripts.fvd in the reference), PNG grids and the private datasets are out of scope; the mask comes from `--inputs <dir>` (the
 `pred_*.nii.gz` label volumes the stage-1 entry point ddpm_eval writes: the hand-off of README.md:21, one CT volume per mask),
 from --mask (.npy label volume [D,H,W]) or is synthetic.
 """
@@ -45,6 +47,10 @@ def get_parser():
     p.add_argument("--slices", type=int, default=64)
     p.add_argument("--size", type=int, default=512)
     p.add_argument("--seed", type=int, default=2048)
+    p.add_argument("--gt", type=str, default=None, help="directory of ground-truth CT volumes named like the samples (<stem>_<ix:04d>.nii.gz): "
+                   "with --lpips-vgg and --lpips-lin each sample is scored against it (three-view LPIPS) and metrics.json is written next to the samples")
+    p.add_argument("--lpips-vgg", type=str, default=None, help="VGG16 feature state dict (torchvision's features.N.* names or net.sliceK.N.*)")
+    p.add_argument("--lpips-lin", type=str, default=None, help="lpips checkpoint with linK.model.1.weight")
     return p
 
 
@@ -127,6 +133,15 @@ def sample_cond(model, instance, n_samples=1, ddim_steps=50, ddim_eta=0.0, noise
 
 def main(argv=None):
     opt, unknown = get_parser().parse_known_args(argv)
+    scoring = (opt.gt, opt.lpips_vgg, opt.lpips_lin)
+    if any(scoring) and not all(scoring):
+        raise SystemExit("--gt, --lpips-vgg and --lpips-lin go together")
+    scorer = None
+    if all(scoring):                         # weights and directory are checked before anything is sampled
+        from .lpips import LPIPS
+        if not os.path.isdir(opt.gt):
+            raise SystemExit(f"--gt {opt.gt!r} is not a directory")
+        scorer = LPIPS.load(opt.lpips_vgg, opt.lpips_lin)
     ckpt, logdir = None, opt.logdir
     if opt.resume:
         if os.path.isfile(opt.resume):
@@ -158,6 +173,7 @@ def main(argv=None):
     else:
         lab = torch.from_numpy(np.load(opt.mask)).long() if opt.mask else synth_mask_volume(opt.slices, opt.size, opt.size)
         jobs = [("sample", lab.float() / 255.0, opt.seed)]
+    written = []
     for stem, wholemask, seed in jobs:
         instance = {"wholemask": wholemask[None, ..., None]}
         t0 = time.time()
@@ -166,7 +182,15 @@ def main(argv=None):
         torch.cuda.synchronize()
         for ix, x in enumerate(pred):
             write_nifti(os.path.join(out_dir, f"{stem}_{ix:04d}.nii.gz"), x[0].float().cpu().numpy())
+            written.append(os.path.join(out_dir, f"{stem}_{ix:04d}.nii.gz"))
         print(f"sampled {tuple(pred.shape)} in {time.time() - t0:.1f}s -> {out_dir}/{stem}_*.nii.gz", file=sys.stderr)
+    if scorer is not None:
+        import json
+        from .lpips import score_directory
+        doc = score_directory(scorer.cuda(), written, opt.gt, torch.device("cuda"))
+        with open(os.path.join(out_dir, "metrics.json"), "w") as f:
+            json.dump(doc, f, indent=1)
+        print(f"mean LPIPS {doc['mean_lpips']:.5f} over {len(written)} volume(s) -> {out_dir}/metrics.json", file=sys.stderr)
 
 
 if __name__ == "__main__":

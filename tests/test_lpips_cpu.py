@@ -1,0 +1,229 @@
+"""Three-view LPIPS, host side: the fixture tests/golden/lpips.npz (recorded from the reference's LPIPS and compute_metrics loop by
+tests/golden/make_golden_lpips.py) against the plain-torch restatement of tests/lpips_ref.py; state-dict names and their mapping;
+every refusal, raised before any device call; the C declarations; sample_diffusion's file list without the new options."""
+import ctypes as C
+import os
+import re
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import lpips_ref as R  # noqa: E402
+
+# fp32 torch on the CPU both times; what differs is the summation order inside the convolution library between builds: a few ulp per
+# layer.  The project's fp32-validation bound covers it.
+RTOL = 2e-5
+
+
+@pytest.fixture(scope="module")
+def gold():
+    return dict(np.load(os.path.join(ROOT, "tests", "golden", "lpips.npz")))
+
+
+@pytest.fixture(scope="module")
+def weights(gold):
+    return R.seeded_vgg_state_dict(), [torch.from_numpy(gold[f"lin{k}"]) for k in range(5)]
+
+
+def close(got, want):
+    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
+    assert got.shape == want.shape
+    assert np.all(np.abs(got - want) <= RTOL * np.abs(want)), float(np.max(np.abs(got - want) / np.abs(want)))
+
+
+def test_fixture_is_what_the_issue_describes(gold):
+    assert gold["pred"].shape == gold["gt"].shape == (2, 1, 16, 20, 40) and gold["pred"].dtype == np.float32
+    assert 0.0 <= gold["pred"].min() and gold["pred"].max() <= 1.0 and 0.0 <= gold["gt"].min() and gold["gt"].max() <= 1.0
+    assert [gold[f"taps_view{v}"].shape for v in range(3)] == [(5, 32), (5, 40), (5, 80)]
+    assert [gold[f"lin{k}"].shape for k in range(5)] == [(64,), (128,), (256,), (512,), (512,)]
+    lo, mid, hi = sorted(gold["view_means"])
+    assert mid / lo > 1.05 and hi / mid > 1.05              # the ordering test on the bf16 path rests on this
+    assert gold["x4"].shape == (2, 3, 20, 40) and gold["out4"].shape == (2, 1, 1, 1)
+    assert gold["score_bps3"] == pytest.approx(1.5 * gold["score"], rel=1e-6)      # one short segment of 2 volumes still weighs 3 / 2
+
+
+@pytest.mark.parametrize("view", [0, 1, 2])
+def test_restatement_reproduces_the_reference_per_tap_and_per_image(gold, weights, view):
+    sd, lins = weights
+    pred, gt = torch.from_numpy(gold["pred"]), torch.from_numpy(gold["gt"])
+    with torch.no_grad():
+        val, taps = R.lpips_images(R.views(pred)[view], R.views(gt)[view], sd, lins)
+    close(taps.numpy(), gold[f"taps_view{view}"])
+    close(val.numpy(), gold[f"images_view{view}"])
+    close(float(val.mean()), gold["view_means"][view])
+
+
+def test_restatement_reproduces_the_scores_and_the_three_channel_call(gold, weights):
+    sd, lins = weights
+    pred, gt = torch.from_numpy(gold["pred"]), torch.from_numpy(gold["gt"])
+    with torch.no_grad():
+        close(R.lpips_3view(pred, gt, sd, lins), gold["score"])
+        close(R.lpips_3view(pred, gt, sd, lins, 1), gold["score_bps1"])
+        close(R.lpips_3view(pred, gt, sd, lins, 3), gold["score_bps3"])
+        close(R.lpips_images(torch.from_numpy(gold["x4"]), torch.from_numpy(gold["y4"]), sd, lins)[0].numpy(), gold["out4"].reshape(-1))
+
+
+# ------------------------------------------------------------------------------------------------ names
+def test_state_dict_names_and_shapes_are_the_reference_s():
+    from jointimagegeneration_amd.lpips import LPIPS
+    sd = LPIPS().state_dict()
+    want, cin = {}, 3
+    for k, idxs, c in ((1, (0, 2), 64), (2, (5, 7), 128), (3, (10, 12, 14), 256), (4, (17, 19, 21), 512), (5, (24, 26, 28), 512)):
+        for i in idxs:
+            want[f"net.slice{k}.{i}.weight"], want[f"net.slice{k}.{i}.bias"] = (c, cin, 3, 3), (c,)
+            cin = c
+    for k, c in enumerate((64, 128, 256, 512, 512)):
+        want[f"lin{k}.model.1.weight"] = (1, c, 1, 1)
+    want.update({"scaling_layer.shift": (1, 3, 1, 1), "scaling_layer.scale": (1, 3, 1, 1), "scaling_layer.shift_p": (1, 1, 1, 1),
+                 "scaling_layer.scale_p": (1, 1, 1, 1)})
+    assert {k: tuple(v.shape) for k, v in sd.items()} == want
+    assert sd["scaling_layer.shift"].reshape(-1).tolist() == torch.tensor([-.030, -.088, -.188]).tolist()
+    assert sd["scaling_layer.scale"].reshape(-1).tolist() == torch.tensor([.458, .448, .450]).tolist()
+
+
+def test_both_vgg_naming_schemes_map_to_the_same_weights(tmp_path, gold):
+    from jointimagegeneration_amd import lpips
+    tv = R.seeded_vgg_state_dict()
+    mapped = lpips.map_vgg_state_dict(tv)
+    assert list(mapped) == list(lpips.vgg_conv_shapes())
+    assert torch.equal(mapped["net.slice3.12.weight"], tv["features.12.weight"]) and torch.equal(mapped["net.slice5.28.bias"], tv["features.28.bias"])
+    again = lpips.map_vgg_state_dict(dict(mapped))
+    assert all(torch.equal(again[k], mapped[k]) for k in mapped)
+    lin = {f"lin{k}.model.1.weight": torch.from_numpy(gold[f"lin{k}"]).reshape(1, -1, 1, 1) for k in range(5)}
+    torch.save(tv, tmp_path / "vgg_tv.pth")
+    torch.save(mapped, tmp_path / "vgg_ref.pth")
+    torch.save(lin, tmp_path / "lin.pth")
+    a = lpips.LPIPS.load(str(tmp_path / "vgg_tv.pth"), str(tmp_path / "lin.pth")).state_dict()
+    b = lpips.LPIPS.load(str(tmp_path / "vgg_ref.pth"), str(tmp_path / "lin.pth")).state_dict()
+    assert all(torch.equal(a[k], b[k]) for k in a)
+    assert torch.equal(a["net.slice1.0.weight"], tv["features.0.weight"]) and torch.equal(a["lin4.model.1.weight"], lin["lin4.model.1.weight"])
+
+
+def test_load_refuses_by_name_before_the_device_is_touched(tmp_path, gold):
+    from jointimagegeneration_amd import lpips
+    tv = R.seeded_vgg_state_dict()
+    lin = {f"lin{k}.model.1.weight": torch.from_numpy(gold[f"lin{k}"]).reshape(1, -1, 1, 1) for k in range(5)}
+    torch.save(tv, tmp_path / "vgg.pth")
+    torch.save(lin, tmp_path / "lin.pth")
+    with pytest.raises(FileNotFoundError, match="never fetched"):
+        lpips.LPIPS.load(str(tmp_path / "absent.pth"), str(tmp_path / "lin.pth"))
+    with pytest.raises(FileNotFoundError, match="absent_lin"):
+        lpips.LPIPS.load(str(tmp_path / "vgg.pth"), str(tmp_path / "absent_lin.pth"))
+    torch.save({k: v for k, v in tv.items() if k != "features.17.bias"}, tmp_path / "vgg_missing.pth")
+    with pytest.raises(KeyError, match=r"net\.slice4\.17\.bias"):
+        lpips.LPIPS.load(str(tmp_path / "vgg_missing.pth"), str(tmp_path / "lin.pth"))
+    torch.save(dict(tv, **{"features.5.weight": torch.zeros(128, 32, 3, 3)}), tmp_path / "vgg_shape.pth")
+    with pytest.raises(ValueError, match=r"features\.5\.weight has shape \(128, 32, 3, 3\)"):
+        lpips.LPIPS.load(str(tmp_path / "vgg_shape.pth"), str(tmp_path / "lin.pth"))
+    torch.save({k: v for k, v in lin.items() if not k.startswith("lin2")}, tmp_path / "lin_missing.pth")
+    with pytest.raises(KeyError, match=r"lin2\.model\.1\.weight"):
+        lpips.LPIPS.load(str(tmp_path / "vgg.pth"), str(tmp_path / "lin_missing.pth"))
+    torch.save(dict(lin, **{"lin3.model.1.weight": torch.zeros(1, 256, 1, 1)}), tmp_path / "lin_shape.pth")
+    with pytest.raises(ValueError, match=r"lin3\.model\.1\.weight has shape"):
+        lpips.LPIPS.load(str(tmp_path / "vgg.pth"), str(tmp_path / "lin_shape.pth"))
+
+
+# ------------------------------------------------------------------------------------------------ refusals (no device here)
+def test_refusals_are_raised_on_the_host():
+    from jointimagegeneration_amd import lpips
+    m = lpips.LPIPS()
+    v = torch.zeros(2, 1, 16, 20, 40)
+    with pytest.raises(ValueError, match=r"pred\.shape != gt\.shape"):
+        lpips.lpips_3view(v, torch.zeros(2, 1, 16, 20, 41), model=m)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        lpips.lpips_3view(v, v, model=m)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        m(torch.zeros(2, 1, 20, 40), torch.zeros(2, 1, 20, 40))
+    with pytest.raises(ValueError, match=r"pred\.shape != gt\.shape"):
+        m(torch.zeros(2, 1, 20, 40), torch.zeros(2, 3, 20, 40))
+    with pytest.raises(NotImplementedError, match="fvd"):
+        lpips.compute_metrics(v, v, ["lpips", "fvd"], model=m)
+    with pytest.raises(ValueError, match="never fetched"):
+        lpips.lpips_3view(v, v)
+    with pytest.raises(ValueError, match="4-D"):
+        m(v, v)
+
+
+@pytest.mark.parametrize("shape", [(1, 1, 15, 20, 40), (1, 1, 16, 8, 40), (1, 1, 16, 20, 15)])
+def test_an_extent_below_16_is_refused_by_name(shape, monkeypatch):
+    """The device check comes first in the code, so it is switched off here: the extent check itself makes no device call."""
+    from jointimagegeneration_amd import lpips, ops
+    monkeypatch.setattr(ops, "require_gpu", lambda t, what: None)
+    m = lpips.LPIPS()
+    with pytest.raises(ValueError, match="below 16"):
+        lpips.lpips_3view(torch.zeros(shape), torch.zeros(shape), model=m)
+    with pytest.raises(ValueError, match="below 16"):
+        m(torch.zeros(2, 1, 15, 40), torch.zeros(2, 1, 15, 40))
+    with pytest.raises(ValueError, match="shift_p / scale_p"):
+        m(torch.zeros(2, 2, 20, 40), torch.zeros(2, 2, 20, 40))
+
+
+# ------------------------------------------------------------------------------------------------ C-ABI
+_CT = {"float": C.c_void_p, "void": C.c_void_p, "int32_t": C.c_int32, "int64_t": C.c_int64}
+
+
+@pytest.mark.parametrize("name,res,nargs", [("gg_volume_views_cl", "int", 13), ("gg_relu_cl", "int", 4), ("gg_lpips_tap", "int", 16),
+                                            ("gg_lpips_tap_workspace_bytes", "int64_t", 5)])
+def test_declarations_match_the_ctypes_signatures(name, res, nargs):
+    from jointimagegeneration_amd import _lib
+    txt = open(os.path.join(ROOT, "include", "guidegen_hip.h")).read()
+    m = re.search(r"\b%s\s+%s\s*\(([^)]*)\)\s*;" % (res, name), txt)
+    assert m, f"{name} is not declared in guidegen_hip.h"
+    want = [C.c_void_p if "*" in arg else _CT[arg.replace("const", "").split()[0]] for arg in m.group(1).split(",")]
+    got_res, args = _lib.SIGNATURES[name]
+    assert got_res is (C.c_int if res == "int" else C.c_int64) and args == want and len(want) == nargs
+    assert "gg_lpips" in open(os.path.join(ROOT, "jointimagegeneration_amd", "csrc", "build.sh")).read()
+
+
+def test_entries_reject_bad_arguments_on_the_host():
+    """No device here: every refusal comes from host code, before any launch."""
+    from jointimagegeneration_amd import _lib
+    lib = _lib.load()
+    buf = (C.c_float * 64)()
+    p = C.cast(buf, C.c_void_p)
+    shape, dtype, unsup, small = -1, -2, -3, -4
+    f = lib.gg_volume_views_cl
+    assert f(None, 1, 16, 16, 16, 0, 0, 1, p, p, p, 0, None) == shape and b"null" in lib.gg_last_error()
+    assert f(p, 1, 16, 16, 16, 4, 0, 1, p, p, p, 0, None) == shape and b"view" in lib.gg_last_error()
+    assert f(p, 1, 16, 16, 16, 3, 0, 1, p, p, p, 0, None) == shape              # view 3 reads three-channel images
+    assert f(p, 1, 16, 16, 16, 0, 0, 1, p, p, p, 2, None) == dtype
+    for n0, n1 in ((-1, 2), (3, 3), (0, 17), (16, 20)):
+        assert f(p, 1, 16, 16, 16, 0, n0, n1, p, p, p, 0, None) == shape, (n0, n1)
+    assert f(p, 2, 16, 20, 40, 2, 0, 81, p, p, p, 1, None) == shape
+    assert lib.gg_relu_cl(None, 0, 64, None) == shape
+    assert lib.gg_relu_cl(p, 0, 48, None) == shape and lib.gg_relu_cl(p, 5, 64, None) == dtype
+    t = lib.gg_lpips_tap
+    assert t(None, p, 0, 1, 4, 4, 64, p, None, None, p, None, 0, p, 1 << 20, None) == shape
+    assert t(p, p, 0, 1, 4, 4, 48, p, None, None, p, None, 0, p, 1 << 20, None) == shape and b"C=48" in lib.gg_last_error()
+    assert t(p, p, 0, 1, 4, 4, 64, p, p, None, p, None, 0, p, 1 << 20, None) == shape          # one pooled output without the other
+    assert t(p, p, 0, 0, 4, 4, 64, p, None, None, p, None, 0, p, 1 << 20, None) == shape
+    assert t(p, p, 7, 1, 4, 4, 64, p, None, None, p, None, 0, p, 1 << 20, None) == dtype
+    assert t(p, p, 1, 1, 4, 4, 2048, p, None, None, p, None, 0, p, 1 << 20, None) == unsup
+    assert t(p, p, 0, 1, 4, 4, 64, p, None, None, p, None, 0, p, 0, None) == small
+    assert lib.gg_lpips_tap_workspace_bytes(3, 20, 40, 64, 0) == 3 * 7 * 4        # 200 quads, 32 per workgroup at 8 lanes per quad
+    assert lib.gg_lpips_tap_workspace_bytes(3, 512, 512, 64, 0) == 3 * 128 * 4
+    assert lib.gg_lpips_tap_workspace_bytes(3, 20, 40, 40, 0) == shape
+
+
+# ------------------------------------------------------------------------------------------------ sample_diffusion
+def test_sample_diffusion_without_the_new_options_writes_the_same_files(tmp_path, monkeypatch):
+    """The sampler and the model are stubbed (no device here); what is checked is main()'s own file list."""
+    from jointimagegeneration_amd import sample_diffusion as sd
+    (tmp_path / "m.yaml").write_text("model:\n  target: none\n")
+    monkeypatch.setattr(sd, "load_model", lambda config, ckpt: (object(), 7))
+    monkeypatch.setattr(sd, "synth_mask_volume", lambda d, h, w: torch.zeros(d, h, w, dtype=torch.long))
+    monkeypatch.setattr(sd, "sample_cond", lambda model, instance, n_samples=1, **kw: torch.zeros(n_samples, 2, 4, 8, 8))
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a, **k: None)
+    monkeypatch.chdir(tmp_path)
+    sd.main(["--config", str(tmp_path / "m.yaml"), "-n", "2", "--slices", "4", "--size", "8"])
+    out = tmp_path / "samples" / "00000007"
+    assert sorted(os.listdir(out)) == ["sample_0000.nii.gz", "sample_0001.nii.gz"]
+    with pytest.raises(SystemExit, match="go together"):
+        sd.main(["--config", str(tmp_path / "m.yaml"), "--gt", str(tmp_path)])
+    with pytest.raises(FileNotFoundError, match="never fetched"):
+        sd.main(["--config", str(tmp_path / "m.yaml"), "--gt", str(tmp_path), "--lpips-vgg", str(tmp_path / "no.pth"), "--lpips-lin", str(tmp_path / "no2.pth")])
+    assert sorted(os.listdir(out)) == ["sample_0000.nii.gz", "sample_0001.nii.gz"]
