@@ -112,14 +112,18 @@ def f32(p: torch.Tensor) -> torch.Tensor:
     return p.detach().float().contiguous()
 
 
+def gn_params(norm: nn.GroupNorm):
+    return f32(norm.weight), f32(norm.bias), norm.eps
+
+
 def gn_silu(h: CL, norm: nn.GroupNorm, act: bool, src2: Optional[CL] = None) -> CL:
     if ops.is_f32(h.t):                      # fp32 validation path
-        return ops.groupnorm_f32(h, f32(norm.weight), f32(norm.bias), norm.eps, act, src2)
+        return ops.groupnorm_f32(h, *gn_params(norm), act, src2)
     if ops.groupnorm_fused_ok(h, src2):     # small tensor: statistics + apply in one launch
-        return ops.groupnorm_fused(h, f32(norm.weight), f32(norm.bias), norm.eps, act, src2)
+        return ops.groupnorm_fused(h, *gn_params(norm), act, src2)
     if ops.has_stats(h, src2):      # the producing convs already left the per-channel sums: no statistics launch
-        return ops.groupnorm_apply_acc(h, f32(norm.weight), f32(norm.bias), norm.eps, act, src2)
-    scale, shift = ops.groupnorm_stats(h, f32(norm.weight), f32(norm.bias), norm.eps, src2)
+        return ops.groupnorm_apply_acc(h, *gn_params(norm), act, src2)
+    scale, shift = ops.groupnorm_stats(h, *gn_params(norm), src2)
     return ops.groupnorm_apply(h, scale, shift, act, src2)
 
 
@@ -132,23 +136,21 @@ def norm_conv(h: CL, norm: nn.GroupNorm, act: bool, weight, bias, cout, src2: Op
     fused into the conv's staging pass (applied once per staged element) -- the activation is never re-written to HBM.
     Gather-kernel convs: separate apply pass (measured: SiLU inside the latency-bound gather loop costs 26 vs 16.6 us/conv)."""
     if ops.is_f32(h.t) and film is not None:  # fp32 validation path of a FiLM norm: the reference's rounding order, nothing folded
-        return ops.conv(ops.groupnorm_f32_film(h, f32(norm.weight), f32(norm.bias), norm.eps, film, act), weight, bias, cout, **conv_kw)
+        return ops.conv(ops.groupnorm_f32_film(h, *gn_params(norm), film, act), weight, bias, cout, **conv_kw)
     if ops.is_f32(h.t):                      # fp32 validation path: separate fp32 GroupNorm launch, then the fp32 conv
-        return ops.conv(ops.groupnorm_f32(h, f32(norm.weight), f32(norm.bias), norm.eps, act, src2), weight, bias, cout, **conv_kw)
+        return ops.conv(ops.groupnorm_f32(h, *gn_params(norm), act, src2), weight, bias, cout, **conv_kw)
     if film is None and ops.conv_prologue_from_acc(h, cout, act, src2=src2, **conv_kw):
         # box conv + producers' sums: the conv folds them and normalises its staged box itself -- NO GroupNorm launch of any kind
-        return ops.conv(h, weight, bias, cout, src2=src2, prologue_acc=(f32(norm.weight), f32(norm.bias), norm.eps), prologue_silu=act, **conv_kw)
+        return ops.conv(h, weight, bias, cout, src2=src2, prologue_acc=gn_params(norm), prologue_silu=act, **conv_kw)
     fused = ops.conv_fuses_prologue(h, cout, src2=src2, **conv_kw)
     if film is None and not fused and ops.groupnorm_fused_ok(h, src2):     # small tensor: statistics + apply in ONE launch
-        a = ops.groupnorm_fused(h, f32(norm.weight), f32(norm.bias), norm.eps, act, src2)
+        a = ops.groupnorm_fused(h, *gn_params(norm), act, src2)
         return ops.conv(a, weight, bias, cout, **conv_kw)
     if film is None and not fused and ops.has_stats(h, src2):     # statistics came with the tensor (conv epilogue accumulators)
-        a = ops.groupnorm_apply_acc(h, f32(norm.weight), f32(norm.bias), norm.eps, act, src2)
+        a = ops.groupnorm_apply_acc(h, *gn_params(norm), act, src2)
         return ops.conv(a, weight, bias, cout, **conv_kw)
-    if ops.has_any_stats(h, src2):     # halo-tile producers: fold their sums instead of re-reading 17..805 MB per norm
-        scale, shift = ops.groupnorm_scale_shift_acc(h, f32(norm.weight), f32(norm.bias), norm.eps, src2)
-    else:
-        scale, shift = ops.groupnorm_stats(h, f32(norm.weight), f32(norm.bias), norm.eps, src2)
+    # halo-tile producers: fold their sums instead of re-reading 17..805 MB per norm
+    scale, shift = (ops.groupnorm_scale_shift_acc if ops.has_any_stats(h, src2) else ops.groupnorm_stats)(h, *gn_params(norm), src2)
     if film is not None:
         ops.film_fold(scale, shift, film, h.C)
     if fused:
@@ -301,12 +303,9 @@ class ResBlock(TimestepBlock):
             else:
                 # avgpool(SiLU(GN(h))) in one resample launch from the per-(n, c) coefficients, then conv1
                 if ops.is_f32(h.t):
-                    a = ops.resample2x(ops.groupnorm_f32(h, f32(n1.weight), f32(n1.bias), n1.eps, True), False, self.dims == 3)
+                    a = ops.resample2x(ops.groupnorm_f32(h, *gn_params(n1), True), False, self.dims == 3)
                 else:
-                    if ops.has_any_stats(h):
-                        sc, sh = ops.groupnorm_scale_shift_acc(h, f32(n1.weight), f32(n1.bias), n1.eps)
-                    else:
-                        sc, sh = ops.groupnorm_stats(h, f32(n1.weight), f32(n1.bias), n1.eps)
+                    sc, sh = (ops.groupnorm_scale_shift_acc if ops.has_any_stats(h) else ops.groupnorm_stats)(h, *gn_params(n1))
                     a = ops.resample2x(h, False, self.dims == 3, prologue=(sc, sh), act=True)
                 h1 = ops.conv(a, pw1, b1, cout, k=k, pad=1, bias_per_sample=b1_ps)
         else:

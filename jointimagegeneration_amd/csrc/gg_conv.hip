@@ -640,6 +640,17 @@ bool gg_conv_box_fuses_prologue(const ConvParams &p);
 int gg_conv_tiny_plan(long long M, int Cout_pad, int KS, int prologue_act);
 int gg_conv_tiny_launch(const ConvParams &p, hipStream_t stream);
 
+// combine + epilogue of a split-K conv.  cap_blocks: at most 2048 blocks (grid-stride loop); the tiny path launches one thread per
+// 4 couts uncapped
+static int launch_splitk_reduce(const ConvParams &p, hipStream_t stream, bool cap_blocks)
+{
+    long long blocks = (p.M * (p.Cout_pad / 4) + 255) / 256;
+    if (cap_blocks && blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(conv_splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, p);
+    GG_CHECK_LAUNCH();
+    return GG_OK;
+}
+
 template <int NT>
 static int launch_gather(const ConvParams &p, hipStream_t stream)
 {
@@ -649,14 +660,18 @@ static int launch_gather(const ConvParams &p, hipStream_t stream)
     else
         hipLaunchKernelGGL((conv_gather_kernel<NT, (NT <= 2 ? 4 : 2), 0>), grid, dim3(256), 0, stream, p);
     GG_CHECK_LAUNCH();
-    if (p.splitk > 1) {
-        long long total = p.M * (p.Cout_pad / 4);
-        long long blocks = (total + 255) / 256;
-        if (blocks > 2048) blocks = 2048;
-        hipLaunchKernelGGL(conv_splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, p);
-        GG_CHECK_LAUNCH();
+    return p.splitk > 1 ? launch_splitk_reduce(p, stream, true) : GG_OK;
+}
+
+static int launch_gather_nt(int NT, const ConvParams &p, hipStream_t stream)
+{
+    switch (NT) {
+        case 5: return launch_gather<5>(p, stream);
+        case 4: return launch_gather<4>(p, stream);
+        case 3: return launch_gather<3>(p, stream);
+        case 2: return launch_gather<2>(p, stream);
+        default: return launch_gather<1>(p, stream);
     }
-    return GG_OK;
 }
 
 // Tile/split plan of the gather kernel. Large grids: widest cout tile (NT in {4,5,3,2,1}) and no split. Under-filled
@@ -739,24 +754,41 @@ static void fill_params(const gg_conv_desc *d, ConvParams &p)
     p.mg_osp = gg_magic_u32(p.M, d->Do * d->Ho * d->Wo); p.mg_ohw = gg_magic_u32(p.M, d->Ho * d->Wo); p.mg_wo = gg_magic_u32(p.M, d->Wo);
 }
 
+// dry runs (stream -1): would the halo-tile / box kernel take this conv?  No HIP call is made.
 static bool halo_try_dry(const ConvParams &p) { return gg_conv_halo_try(p, (hipStream_t)-1) == GG_OK; }
+static bool box_try_dry(const ConvParams &p) { return gg_conv_box_try(p, (hipStream_t)-1) == GG_OK; }
+// what every dispatch predicate asks of a descriptor before it reads anything else
+static bool desc_channels_ok(const gg_conv_desc *d) { return d && d->C1 > 0 && d->C1 % 32 == 0 && d->C2 % 32 == 0 && d->Cout_pad % 32 == 0; }
+
+// split-K over `splitk` slices (1: none): the fp32 slabs live in the caller's workspace (gg_conv_workspace_bytes)
+static int take_splitk_workspace(const gg_conv_desc *d, ConvParams &p, int splitk)
+{
+    if (splitk > 1) {
+        const long long need = (long long)splitk * p.M * p.Cout_pad * 4;
+        if (!d->workspace || d->workspace_bytes < need)
+            GG_FAIL(GG_ERR_WORKSPACE_TOO_SMALL, "conv: split-K needs %lld workspace bytes (gg_conv_workspace_bytes), got %lld", need, (long long)d->workspace_bytes);
+        p.ws = (float *)d->workspace;
+    }
+    p.splitk = splitk;
+    return GG_OK;
+}
 
 extern "C" int gg_conv_runs_halo_tile(const gg_conv_desc *d)
 {
-    if (!d || d->C1 <= 0 || d->C1 % 32 || d->C2 % 32 || d->Cout_pad % 32 || d->epilogue_geglu) return 0;
+    if (!desc_channels_ok(d) || d->epilogue_geglu) return 0;
     ConvParams p;
     fill_params(d, p);
-    return gg_conv_halo_try(p, (hipStream_t)-1) == GG_OK ? 1 : 0;
+    return halo_try_dry(p) ? 1 : 0;
 }
 
 extern "C" int gg_conv_fuses_prologue(const gg_conv_desc *d)
 {
-    if (!d || d->C1 <= 0 || d->C1 % 32 || d->C2 % 32 || d->Cout_pad % 32 || d->epilogue_geglu) return 0;
+    if (!desc_channels_ok(d) || d->epilogue_geglu) return 0;
     ConvParams p;
     fill_params(d, p);
     // halo-tile convs CAN always fuse it; the answer is whether they should (measured rule in gg_conv_halo.hip)
-    if (gg_conv_halo_try(p, (hipStream_t)-1) == GG_OK) return (GG_HALO_SEPARATE_NORM && d->path_hint == 0 && gg_conv_halo_prefers_separate_norm(p)) ? 0 : 1;
-    if (gg_conv_box_try(p, (hipStream_t)-1) == GG_OK) return gg_conv_box_fuses_prologue(p) ? 1 : 0;
+    if (halo_try_dry(p)) return (GG_HALO_SEPARATE_NORM && d->path_hint == 0 && gg_conv_halo_prefers_separate_norm(p)) ? 0 : 1;
+    if (box_try_dry(p)) return gg_conv_box_fuses_prologue(p) ? 1 : 0;
     // GroupNorm*SiLU inside the 160-step gather loop was measured slower (26 vs 16.6 us per conv: SiLU on the load -> LDS critical
     // path once per tap), so the gather kernels never fuse the prologue
     return 0;
@@ -768,7 +800,7 @@ bool gg_conv_halo_fuses_posterior(const ConvParams &p);
 
 extern "C" int gg_conv_fuses_posterior(const gg_conv_desc *d)
 {
-    if (!d || d->C1 <= 0 || d->C1 % 32 || d->C2 % 32 || d->Cout_pad % 32 || d->epilogue_geglu || d->residual || d->out_dtype != GG_F32 || d->gn_acc ||
+    if (!desc_channels_ok(d) || d->epilogue_geglu || d->residual || d->out_dtype != GG_F32 || d->gn_acc ||
         d->ddim_x || d->skip_C1) return 0;
     ConvParams p;
     fill_params(d, p);
@@ -777,47 +809,47 @@ extern "C" int gg_conv_fuses_posterior(const gg_conv_desc *d)
 
 extern "C" int gg_conv_prologue_from_acc(const gg_conv_desc *d)
 {
-    if (!d || d->C1 <= 0 || d->C1 % 32 || d->C2 % 32 || d->Cout_pad % 32 || d->epilogue_geglu || !d->prologue_act) return 0;
+    if (!desc_channels_ok(d) || d->epilogue_geglu || !d->prologue_act) return 0;
     // two sources: the fold takes channel c < C1 from pro_acc1 and c - C1 from pro_acc2, i.e. every channel of the FIRST source must be a
     // logical one (pro_c_logical >= C1 says exactly that: padding lanes may only sit at the end of the second source)
     if (d->pro_c_logical <= 0 || d->pro_c_logical % 32 || d->pro_c_logical > d->C1 + d->C2 || (d->C2 && d->pro_c_logical < d->C1)) return 0;
     ConvParams p;
     fill_params(d, p);
     if (halo_try_dry(p)) return 0;
-    return gg_conv_box_try(p, (hipStream_t)-1) == GG_OK && gg_conv_box_prologue_from_acc(p) ? 1 : 0;
+    return box_try_dry(p) && gg_conv_box_prologue_from_acc(p) ? 1 : 0;
 }
 
 // K-concatenated 1x1 skip projection: box kernel only (3x3, stride 1, no upsample: plan_box checks).
 extern "C" int gg_conv_fuses_skip(const gg_conv_desc *d)
 {
-    if (!d || d->C1 <= 0 || d->C1 % 32 || d->C2 % 32 || d->Cout_pad % 32 || d->epilogue_geglu || d->skip_C1 <= 0 || d->skip_C1 % 32 || d->skip_C2 % 32 ||
+    if (!desc_channels_ok(d) || d->epilogue_geglu || d->skip_C1 <= 0 || d->skip_C1 % 32 || d->skip_C2 % 32 ||
         d->skip_C2 < 0 || d->residual || d->ddim_x)
         return 0;
     ConvParams p;
     fill_params(d, p);
     if (halo_try_dry(p)) return 0;
-    return gg_conv_box_try(p, (hipStream_t)-1) == GG_OK ? 1 : 0;
+    return box_try_dry(p) ? 1 : 0;
 }
 
 // The fused DDIM epilogue lives in the box kernel's epilogue (the latent UNet's head conv at batch 1..4 runs there).
 extern "C" int gg_conv_fuses_ddim(const gg_conv_desc *d)
 {
-    if (!d || d->C1 <= 0 || d->C1 % 32 || d->C2 % 32 || d->Cout_pad % 32 || d->out_dtype != GG_F32 || d->Cout != 4 || d->residual) return 0;
+    if (!desc_channels_ok(d) || d->out_dtype != GG_F32 || d->Cout != 4 || d->residual) return 0;
     ConvParams p;
     fill_params(d, p);
     if (halo_try_dry(p)) return 0;
-    return gg_conv_box_try(p, (hipStream_t)-1) == GG_OK ? 1 : 0;
+    return box_try_dry(p) ? 1 : 0;
 }
 
 
 // Which path a desc takes is decided by the same plan functions gg_conv_forward uses.
 extern "C" int gg_conv_emits_stats(const gg_conv_desc *d)
 {
-    if (!d || d->C1 <= 0 || d->C1 % 32 || d->C2 % 32 || d->Cout_pad % 32 || d->out_dtype != GG_BF16 || d->epilogue_geglu) return 0;
+    if (!desc_channels_ok(d) || d->out_dtype != GG_BF16 || d->epilogue_geglu) return 0;
     ConvParams p;
     fill_params(d, p);
     if (halo_try_dry(p)) return GG_ACC_STRIPES_HALO;
-    if (gg_conv_box_try(p, (hipStream_t)-1) == GG_OK) return gg_conv_box_emits_stats(p) ? GG_ACC_STRIPES : 0;
+    if (box_try_dry(p)) return gg_conv_box_emits_stats(p) ? GG_ACC_STRIPES : 0;
     if (gg_conv_tiny_plan(p.M, p.Cout_pad, p.ntaps * p.nchunk, p.prologue_act)) return 0;
     const long long osp = (long long)d->Do * d->Ho * d->Wo;
     return (plan_gather5(p.M, p.C1, p.C2, p.Cout_pad, p.ntaps) == 1 && osp % 64 == 0) ? GG_ACC_STRIPES : 0;
@@ -889,14 +921,7 @@ extern "C" int gg_conv_forward(const gg_conv_desc *d, void *stream_)
         if (d->kd != 1 || d->kh != 1 || d->kw != 1 || d->stride != 1 || d->upsample || d->residual || d->out_dtype != GG_BF16 || d->gn_acc ||
             d->ddim_x || d->Cout % 32 || d->bias_stride)
             GG_FAIL(GG_ERR_UNSUPPORTED, "conv: the GEGLU epilogue needs a 1x1 conv, bf16 output, Cout = 2*inner with inner %% 16 == 0, a shared bias, no residual / gn_acc / ddim");
-        const GatherPlan plg = plan_gather(p.M, p.Cout_pad, p.ntaps * p.nchunk);
-        switch (plg.NT) {
-            case 5: return launch_gather<5>(p, stream);
-            case 4: return launch_gather<4>(p, stream);
-            case 3: return launch_gather<3>(p, stream);
-            case 2: return launch_gather<2>(p, stream);
-            default: return launch_gather<1>(p, stream);
-        }
+        return launch_gather_nt(plan_gather(p.M, p.Cout_pad, p.ntaps * p.nchunk).NT, p, stream);
     }
 #ifdef GG_EXP_WPREFETCH
     // experiment (tools/experiments/README.md, "warm weights"): every conv preceded by a launch that reads its packed weights with the whole
@@ -926,59 +951,24 @@ extern "C" int gg_conv_forward(const gg_conv_desc *d, void *stream_)
     if (rc != GG_ERR_UNSUPPORTED) return rc;
 
     if (int tsk = gg_conv_tiny_plan(p.M, p.Cout_pad, p.ntaps * p.nchunk, p.prologue_act)) {
-        if (tsk > 1) {
-            const long long need = (long long)tsk * p.M * p.Cout_pad * 4;
-            if (!d->workspace || d->workspace_bytes < need)
-                GG_FAIL(GG_ERR_WORKSPACE_TOO_SMALL, "conv: split-K needs %lld workspace bytes (gg_conv_workspace_bytes), got %lld", need, (long long)d->workspace_bytes);
-            p.ws = (float *)d->workspace;
-        }
-        p.splitk = tsk;
+        if ((rc = take_splitk_workspace(d, p, tsk)) != GG_OK) return rc;
         rc = gg_conv_tiny_launch(p, stream);
         if (rc != GG_OK || tsk == 1) return rc;
-        long long total = p.M * (p.Cout_pad / 4);
-        long long blocks = (total + 255) / 256;
-        hipLaunchKernelGGL(conv_splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, p);
-        GG_CHECK_LAUNCH();
-        return GG_OK;
+        return launch_splitk_reduce(p, stream, false);
     }
 
     if (int s5 = plan_gather5(p.M, p.C1, p.C2, p.Cout_pad, p.ntaps)) {
-        if (s5 > 1) {
-            const long long need = (long long)s5 * p.M * p.Cout_pad * 4;
-            if (!d->workspace || d->workspace_bytes < need)
-                GG_FAIL(GG_ERR_WORKSPACE_TOO_SMALL, "conv: split-K needs %lld workspace bytes (gg_conv_workspace_bytes), got %lld", need, (long long)d->workspace_bytes);
-            p.ws = (float *)d->workspace;
-        }
-        p.splitk = s5;
+        if ((rc = take_splitk_workspace(d, p, s5)) != GG_OK) return rc;
         dim3 grid((unsigned)((p.M + 63) / 64), (unsigned)(p.Cout_pad / 32), (unsigned)s5);
         if (p.prologue_act && (((long long)p.Do * p.Ho * p.Wo) % 64 || p.C1 + p.C2 > 2560))
             GG_FAIL(GG_ERR_UNSUPPORTED, "conv: fused prologue on the 160-step kernel needs Do*Ho*Wo %% 64 == 0 and C <= 2560");
         if (p.prologue_act) hipLaunchKernelGGL(conv_gather5_kernel<1>, grid, dim3(256), 0, stream, p);
         else hipLaunchKernelGGL(conv_gather5_kernel<0>, grid, dim3(256), 0, stream, p);
         GG_CHECK_LAUNCH();
-        if (s5 > 1) {
-            long long total = p.M * (p.Cout_pad / 4);
-            long long blocks = (total + 255) / 256;
-            if (blocks > 2048) blocks = 2048;
-            hipLaunchKernelGGL(conv_splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, p);
-            GG_CHECK_LAUNCH();
-        }
-        return GG_OK;
+        return s5 > 1 ? launch_splitk_reduce(p, stream, true) : GG_OK;
     }
 
     GatherPlan pl = plan_gather(p.M, p.Cout_pad, p.ntaps * p.nchunk);
-    if (pl.splitk > 1) {
-        const long long need = (long long)pl.splitk * p.M * p.Cout_pad * 4;
-        if (!d->workspace || d->workspace_bytes < need)
-            GG_FAIL(GG_ERR_WORKSPACE_TOO_SMALL, "conv: split-K needs %lld workspace bytes (gg_conv_workspace_bytes), got %lld", need, (long long)d->workspace_bytes);
-        p.ws = (float *)d->workspace;
-        p.splitk = pl.splitk;
-    }
-    switch (pl.NT) {
-        case 5: return launch_gather<5>(p, stream);
-        case 4: return launch_gather<4>(p, stream);
-        case 3: return launch_gather<3>(p, stream);
-        case 2: return launch_gather<2>(p, stream);
-        default: return launch_gather<1>(p, stream);
-    }
+    if ((rc = take_splitk_workspace(d, p, pl.splitk)) != GG_OK) return rc;
+    return launch_gather_nt(pl.NT, p, stream);
 }

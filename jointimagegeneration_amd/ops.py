@@ -198,55 +198,9 @@ def conv_out_extent(in_sp: Sequence[int], k: Sequence[int], stride: int, pad: in
     return tuple(out)
 
 
-def conv_prologue_from_acc(src1: CL, cout: int, act: bool, k=(1, 3, 3), stride: int = 1, pad: int = 1, upsample: bool = False,
-                           src2: Optional[CL] = None, **_ignored) -> bool:
-    """True if this conv can compute act(GroupNorm(cat[src1, src2])) itself from the accumulators its producers left (CL.acc, 1-stripe
-    layout): no statistics, scale / shift or apply launch at all (gg_conv_desc.pro_acc1)."""
-    if not PROLOGUE_FROM_ACC or is_f32(src1.t) or not has_stats(src1, src2):
-        return False
-    if src2 is not None and src1.C != src1.Cpad:        # the in-kernel fold indexes channel c - C1 of the second source: C1 must be all logical
-        return False
-    lib = _lib.load()
-    N, D, H, W, C1 = src1.t.shape
-    Do, Ho, Wo = conv_out_extent((D, H, W), k, stride, pad, upsample)
-    d = ConvDesc()
-    d.N, d.D, d.H, d.W = N, D, H, W
-    d.C1, d.C2 = C1, (src2.t.shape[-1] if src2 is not None else 0)
-    d.Cout, d.Cout_pad = cout, pad32(cout)
-    d.kd, d.kh, d.kw = k
-    d.stride, d.pad, d.upsample = stride, pad, 1 if upsample else 0
-    d.Do, d.Ho, d.Wo = Do, Ho, Wo
-    d.prologue_act = 1 if act else 2
-    d.pro_c_logical = src1.C + (src2.C if src2 is not None else 0)
-    d.path_hint = PATH_HINT
-    return bool(lib.gg_conv_prologue_from_acc(C.byref(d)))
-
-
-SKIP_KCONCAT = True                 # ResBlock 1x1 skip projections K-concatenated into conv2 where gg_conv_fuses_skip says so (A/B switch)
-
-
-def conv_fuses_skip(src1: CL, cout: int, skip1: CL, skip2: Optional[CL] = None, k=(1, 3, 3), stride: int = 1, pad: int = 1, upsample: bool = False,
-                    **_ignored) -> bool:
-    """True if this conv (input src1, no second source) can take a K-concatenated 1x1 skip projection of cat[skip1, skip2]
-    (gg_conv_desc.skip_src1): box kernel, 3x3, stride 1."""
-    if not SKIP_KCONCAT or is_f32(src1.t) or (skip2 is not None and skip1.C != skip1.Cpad):
-        return False
-    lib = _lib.load()
-    N, D, H, W, C1 = src1.t.shape
-    Do, Ho, Wo = conv_out_extent((D, H, W), k, stride, pad, upsample)
-    d = ConvDesc()
-    d.N, d.D, d.H, d.W = N, D, H, W
-    d.C1, d.C2 = C1, 0
-    d.Cout, d.Cout_pad = cout, pad32(cout)
-    d.kd, d.kh, d.kw = k
-    d.stride, d.pad, d.upsample = stride, pad, 1 if upsample else 0
-    d.Do, d.Ho, d.Wo = Do, Ho, Wo
-    d.skip_C1, d.skip_C2 = skip1.Cpad, (skip2.Cpad if skip2 is not None else 0)
-    d.path_hint = PATH_HINT
-    return bool(lib.gg_conv_fuses_skip(C.byref(d)))
-
-
 def _shape_desc(src1: CL, cout: int, k, stride: int, pad: int, upsample: bool, src2: Optional[CL]) -> "ConvDesc":
+    """The descriptor of conv(src1 | src2 -> cout): every shape field and path_hint, nothing else.  The dispatch predicates below and
+    conv() all start from this one, so each of them answers for the convolution that conv() launches."""
     N, D, H, W, C1 = src1.t.shape
     Do, Ho, Wo = conv_out_extent((D, H, W), k, stride, pad, upsample)
     d = ConvDesc()
@@ -258,6 +212,34 @@ def _shape_desc(src1: CL, cout: int, k, stride: int, pad: int, upsample: bool, s
     d.Do, d.Ho, d.Wo = Do, Ho, Wo
     d.path_hint = PATH_HINT
     return d
+
+
+def conv_prologue_from_acc(src1: CL, cout: int, act: bool, k=(1, 3, 3), stride: int = 1, pad: int = 1, upsample: bool = False,
+                           src2: Optional[CL] = None, **_ignored) -> bool:
+    """True if this conv can compute act(GroupNorm(cat[src1, src2])) itself from the accumulators its producers left (CL.acc, 1-stripe
+    layout): no statistics, scale / shift or apply launch at all (gg_conv_desc.pro_acc1)."""
+    if not PROLOGUE_FROM_ACC or is_f32(src1.t) or not has_stats(src1, src2):
+        return False
+    if src2 is not None and src1.C != src1.Cpad:        # the in-kernel fold indexes channel c - C1 of the second source: C1 must be all logical
+        return False
+    d = _shape_desc(src1, cout, k, stride, pad, upsample, src2)
+    d.prologue_act = 1 if act else 2
+    d.pro_c_logical = src1.C + (src2.C if src2 is not None else 0)
+    return bool(_lib.load().gg_conv_prologue_from_acc(C.byref(d)))
+
+
+SKIP_KCONCAT = True                 # ResBlock 1x1 skip projections K-concatenated into conv2 where gg_conv_fuses_skip says so (A/B switch)
+
+
+def conv_fuses_skip(src1: CL, cout: int, skip1: CL, skip2: Optional[CL] = None, k=(1, 3, 3), stride: int = 1, pad: int = 1, upsample: bool = False,
+                    **_ignored) -> bool:
+    """True if this conv (input src1, no second source) can take a K-concatenated 1x1 skip projection of cat[skip1, skip2]
+    (gg_conv_desc.skip_src1): box kernel, 3x3, stride 1."""
+    if not SKIP_KCONCAT or is_f32(src1.t) or (skip2 is not None and skip1.C != skip1.Cpad):
+        return False
+    d = _shape_desc(src1, cout, k, stride, pad, upsample, None)
+    d.skip_C1, d.skip_C2 = skip1.Cpad, (skip2.Cpad if skip2 is not None else 0)
+    return bool(_lib.load().gg_conv_fuses_skip(C.byref(d)))
 
 
 def conv_runs_halo_tile(src1: CL, cout: int, k=(1, 3, 3), stride: int = 1, pad: int = 1, upsample: bool = False,
@@ -274,18 +256,7 @@ def conv_fuses_prologue(src1: CL, cout: int, k=(1, 3, 3), stride: int = 1, pad: 
     staging); False: a separate apply pass + the prologue-free conv is faster (gg_conv_fuses_prologue, measured rule in gg_conv_halo.hip)."""
     if is_f32(src1.t):
         return False
-    lib = _lib.load()
-    N, D, H, W, C1 = src1.t.shape
-    Do, Ho, Wo = conv_out_extent((D, H, W), k, stride, pad, upsample)
-    d = ConvDesc()
-    d.N, d.D, d.H, d.W = N, D, H, W
-    d.C1, d.C2 = C1, (src2.t.shape[-1] if src2 is not None else 0)
-    d.Cout, d.Cout_pad = cout, pad32(cout)
-    d.kd, d.kh, d.kw = k
-    d.stride, d.pad, d.upsample = stride, pad, 1 if upsample else 0
-    d.Do, d.Ho, d.Wo = Do, Ho, Wo
-    d.path_hint = PATH_HINT
-    return bool(lib.gg_conv_fuses_prologue(C.byref(d)))
+    return bool(_lib.load().gg_conv_fuses_prologue(C.byref(_shape_desc(src1, cout, k, stride, pad, upsample, src2))))
 
 
 # ---- GroupNorm statistics emitted by conv epilogues (gg_conv_desc.gn_acc).  One int64 arena per device, bump-allocated per
@@ -360,22 +331,14 @@ def conv(src1: CL, weight: torch.Tensor, bias: Optional[torch.Tensor], cout: int
     written); otherwise the caller launches gg_ccdm_posterior_sample on the logits."""
     lib = _lib.load()
     t1 = src1.t
-    N, D, H, W, C1 = t1.shape
-    Do, Ho, Wo = conv_out_extent((D, H, W), k, stride, pad, upsample)
-    cp = pad32(cout)
+    d = _shape_desc(src1, cout, k, stride, pad, upsample, src2)
+    N, Do, Ho, Wo, cp = d.N, d.Do, d.Ho, d.Wo, d.Cout_pad
     if is_f32(t1):                                  # fp32 validation path (gg_conv_forward_f32)
         if geglu or prologue is not None or not is_f32(weight) or (residual is not None and not is_f32(residual.t)):
             raise RuntimeError("fp32 validation conv: fp32 weights / residual, no fused prologue or GEGLU (enter ops.fp32_validation() before the first forward)")
         if out is None:
             out = torch.empty((N, Do, Ho, Wo, cp), dtype=torch.float32, device=t1.device)
-        d = ConvDesc()
-        d.N, d.D, d.H, d.W = N, D, H, W
-        d.C1, d.C2 = C1, (src2.t.shape[-1] if src2 is not None else 0)
-        d.Cout, d.Cout_pad = cout, cp
-        d.kd, d.kh, d.kw = k
-        d.stride, d.pad, d.upsample = stride, pad, 1 if upsample else 0
-        d.Do, d.Ho, d.Wo = Do, Ho, Wo
-        d.out_dtype = GG_F32
+        d.out_dtype = GG_F32                        # (path_hint comes along from _shape_desc: gg_conv_forward_f32 does not read it)
         d.src1, d.src2 = t1.data_ptr(), (_ptr(src2.t) if src2 is not None else None)
         d.weight, d.bias, d.bias_stride = weight.data_ptr(), _ptr(bias), (cp if bias_per_sample else 0)
         d.residual = _ptr(residual.t) if residual is not None else None
@@ -388,13 +351,6 @@ def conv(src1: CL, weight: torch.Tensor, bias: Optional[torch.Tensor], cout: int
         out = torch.empty((N, Do, Ho, Wo, cp // 2), dtype=torch.bfloat16, device=t1.device)
     if out is None:
         out = torch.empty((N, Do, Ho, Wo, cp), dtype=torch.float32 if out_f32 else torch.bfloat16, device=t1.device)
-    d = ConvDesc()
-    d.N, d.D, d.H, d.W = N, D, H, W
-    d.C1, d.C2 = C1, (src2.t.shape[-1] if src2 is not None else 0)
-    d.Cout, d.Cout_pad = cout, cp
-    d.kd, d.kh, d.kw = k
-    d.stride, d.pad, d.upsample = stride, pad, 1 if upsample else 0
-    d.Do, d.Ho, d.Wo = Do, Ho, Wo
     d.out_dtype = GG_F32 if out.dtype == torch.float32 else GG_BF16
     d.prologue_act = (1 if prologue_silu else 2) if (prologue is not None or prologue_acc is not None) else 0
     if prologue_acc is not None:
@@ -406,7 +362,6 @@ def conv(src1: CL, weight: torch.Tensor, bias: Optional[torch.Tensor], cout: int
         d.skip_src1, d.skip_C1 = skip[0].t.data_ptr(), skip[0].Cpad
         d.skip_src2, d.skip_C2 = (skip[1].t.data_ptr(), skip[1].Cpad) if skip[1] is not None else (None, 0)
         d.skip_weight = skip[2].data_ptr()
-    d.path_hint = PATH_HINT
     d.src1 = t1.data_ptr()
     d.src2 = _ptr(src2.t) if src2 is not None else None
     d.weight = weight.data_ptr()
@@ -457,21 +412,29 @@ def conv(src1: CL, weight: torch.Tensor, bias: Optional[torch.Tensor], cout: int
 
 
 # ----------------------------------------------------------------------------------------------- norms / elementwise
+def _gn_sources(src1: CL, src2: Optional[CL], padded_first: str = "raise"):
+    """What every GroupNorm(cat[src1, src2]) wrapper needs: (N, S, C1, C2, logical channels, pointer of the second source or None).
+    The kernels that find channel c >= C1 at c - C1 of the second source need a first source without padding lanes; `padded_first`
+    says what happens otherwise: "raise", "ignore", or "none" (None is returned: groupnorm_fused_ok)."""
+    if src2 is not None and src1.C != src1.Cpad and padded_first != "ignore":
+        if padded_first == "none":
+            return None
+        raise RuntimeError("two-source GroupNorm needs an unpadded first source")
+    if src2 is None:
+        return src1.N, src1.S, src1.Cpad, 0, src1.C, None
+    return src1.N, src1.S, src1.Cpad, src2.Cpad, src1.C + src2.C, src2.t.data_ptr()
+
+
 def groupnorm_stats(src1: CL, gamma: torch.Tensor, beta: torch.Tensor, eps: float, src2: Optional[CL] = None):
     """Returns per-(n, c) fp32 (scale, shift) with y = x*scale + shift == GroupNorm(32, C)(x)."""
     lib = _lib.load()
-    N, S = src1.N, src1.S
-    C1 = src1.Cpad
-    C2 = src2.Cpad if src2 is not None else 0
-    c_log = src1.C + (src2.C if src2 is not None else 0)
-    if src2 is not None and src1.C != C1:
-        raise RuntimeError("two-source GroupNorm needs an unpadded first source")
+    N, S, C1, C2, c_log, p2 = _gn_sources(src1, src2)
     Ct = C1 + C2
     ws_bytes = lib.gg_groupnorm_workspace_bytes(N, S, Ct)
     ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=src1.t.device)
     scale = torch.empty((N, Ct), dtype=torch.float32, device=src1.t.device)
     shift = torch.empty_like(scale)
-    check(lib.gg_groupnorm_stats(src1.t.data_ptr(), C1, _ptr(src2.t) if src2 is not None else None, C2, N, S, c_log,
+    check(lib.gg_groupnorm_stats(src1.t.data_ptr(), C1, p2, C2, N, S, c_log,
                                  gamma.data_ptr(), beta.data_ptr(), eps, scale.data_ptr(), shift.data_ptr(), ws.data_ptr(),
                                  ws_bytes, _stream()), "gg_groupnorm_stats")
     return scale, shift
@@ -479,34 +442,29 @@ def groupnorm_stats(src1: CL, gamma: torch.Tensor, beta: torch.Tensor, eps: floa
 
 def groupnorm_apply(src1: CL, scale: torch.Tensor, shift: torch.Tensor, act: bool, src2: Optional[CL] = None) -> CL:
     lib = _lib.load()
-    N, S = src1.N, src1.S
-    C1 = src1.Cpad
-    C2 = src2.Cpad if src2 is not None else 0
+    N, S, C1, C2, c_log, p2 = _gn_sources(src1, src2, "ignore")       # per-(n, c) tables: padding lanes of the first source have their own rows
     out = torch.empty(tuple(src1.t.shape[:4]) + (C1 + C2,), dtype=torch.bfloat16, device=src1.t.device)
-    check(lib.gg_groupnorm_apply(src1.t.data_ptr(), C1, _ptr(src2.t) if src2 is not None else None, C2, N, S, scale.data_ptr(),
+    check(lib.gg_groupnorm_apply(src1.t.data_ptr(), C1, p2, C2, N, S, scale.data_ptr(),
                                  shift.data_ptr(), 1 if act else 0, out.data_ptr(), _stream()), "gg_groupnorm_apply")
-    return CL(out, src1.C + (src2.C if src2 is not None else 0))
+    return CL(out, c_log)
 
 
 def groupnorm_fused_ok(src1: CL, src2: Optional[CL] = None) -> bool:
     if is_f32(src1.t):
         return False
-    C2 = src2.Cpad if src2 is not None else 0
-    c_log = src1.C + (src2.C if src2 is not None else 0)
-    if src2 is not None and src1.C != src1.Cpad:
+    hdr = _gn_sources(src1, src2, "none")
+    if hdr is None:
         return False
-    return bool(_lib.load().gg_groupnorm_fused_supported(src1.S, src1.Cpad, C2, c_log))
+    N, S, C1, C2, c_log, p2 = hdr
+    return bool(_lib.load().gg_groupnorm_fused_supported(S, C1, C2, c_log))
 
 
 def groupnorm_fused(src1: CL, gamma: torch.Tensor, beta: torch.Tensor, eps: float, act: bool, src2: Optional[CL] = None) -> CL:
     """act(GroupNorm(32)(cat[src1, src2])) in one launch (small tensors: see groupnorm_fused_ok)."""
     lib = _lib.load()
-    N, S = src1.N, src1.S
-    C1 = src1.Cpad
-    C2 = src2.Cpad if src2 is not None else 0
-    c_log = src1.C + (src2.C if src2 is not None else 0)
+    N, S, C1, C2, c_log, p2 = _gn_sources(src1, src2, "ignore")       # the caller asked groupnorm_fused_ok
     out = torch.empty(tuple(src1.t.shape[:4]) + (C1 + C2,), dtype=torch.bfloat16, device=src1.t.device)
-    check(lib.gg_groupnorm_fused(src1.t.data_ptr(), C1, _ptr(src2.t) if src2 is not None else None, C2, N, S, c_log, gamma.data_ptr(),
+    check(lib.gg_groupnorm_fused(src1.t.data_ptr(), C1, p2, C2, N, S, c_log, gamma.data_ptr(),
                                  beta.data_ptr(), eps, 1 if act else 0, out.data_ptr(), _stream()), "gg_groupnorm_fused")
     return CL(out, c_log)
 
@@ -514,15 +472,10 @@ def groupnorm_fused(src1: CL, gamma: torch.Tensor, beta: torch.Tensor, eps: floa
 def groupnorm_f32(src1: CL, gamma: torch.Tensor, beta: torch.Tensor, eps: float, act: bool, src2: Optional[CL] = None) -> CL:
     """fp32 validation path: act(GroupNorm(32)(cat[src1, src2])) on fp32 CL tensors (fp64 statistics, ATen's fp32 affine order)."""
     lib = _lib.load()
-    N, S = src1.N, src1.S
-    C1 = src1.Cpad
-    C2 = src2.Cpad if src2 is not None else 0
-    c_log = src1.C + (src2.C if src2 is not None else 0)
-    if src2 is not None and src1.C != C1:
-        raise RuntimeError("two-source GroupNorm needs an unpadded first source")
+    N, S, C1, C2, c_log, p2 = _gn_sources(src1, src2)
     out = torch.empty(tuple(src1.t.shape[:4]) + (C1 + C2,), dtype=torch.float32, device=src1.t.device)
     ws = torch.empty(64 * N, dtype=torch.float32, device=src1.t.device)
-    check(lib.gg_groupnorm_f32(src1.t.data_ptr(), C1, _ptr(src2.t) if src2 is not None else None, C2, N, S, c_log, gamma.data_ptr(), beta.data_ptr(),
+    check(lib.gg_groupnorm_f32(src1.t.data_ptr(), C1, p2, C2, N, S, c_log, gamma.data_ptr(), beta.data_ptr(),
                                eps, 1 if act else 0, out.data_ptr(), ws.data_ptr(), _stream()), "gg_groupnorm_f32")
     return CL(out, c_log)
 
@@ -573,14 +526,9 @@ def resample2x(src: CL, up: bool, resample_d: bool, prologue: Optional[Tuple[tor
 def groupnorm_apply_acc(src1: CL, gamma: torch.Tensor, beta: torch.Tensor, eps: float, act: bool, src2: Optional[CL] = None) -> CL:
     """act(GroupNorm(32)(cat[src1, src2])) with the statistics taken from the accumulators the producing convs left in CL.acc."""
     lib = _lib.load()
-    N, S = src1.N, src1.S
-    C1 = src1.Cpad
-    C2 = src2.Cpad if src2 is not None else 0
-    c_log = src1.C + (src2.C if src2 is not None else 0)
-    if src2 is not None and src1.C != C1:
-        raise RuntimeError("two-source GroupNorm needs an unpadded first source")
+    N, S, C1, C2, c_log, p2 = _gn_sources(src1, src2)
     out = torch.empty(tuple(src1.t.shape[:4]) + (C1 + C2,), dtype=torch.bfloat16, device=src1.t.device)
-    check(lib.gg_groupnorm_apply_acc(src1.t.data_ptr(), C1, src1.acc.data_ptr(), _ptr(src2.t) if src2 is not None else None, C2,
+    check(lib.gg_groupnorm_apply_acc(src1.t.data_ptr(), C1, src1.acc.data_ptr(), p2, C2,
                                      src2.acc.data_ptr() if src2 is not None else None, N, S, c_log, gamma.data_ptr(),
                                      beta.data_ptr(), eps, 1 if act else 0, out.data_ptr(), _stream()), "gg_groupnorm_apply_acc")
     return CL(out, c_log)
@@ -600,12 +548,7 @@ def has_any_stats(src1: CL, src2: Optional[CL] = None) -> bool:
 def groupnorm_scale_shift_acc(src1: CL, gamma: torch.Tensor, beta: torch.Tensor, eps: float, src2: Optional[CL] = None):
     """Per-(n, c) fp32 (scale, shift) of GroupNorm(32)(cat[src1, src2]) from the accumulators in CL.acc (no pass over the tensors)."""
     lib = _lib.load()
-    N, S = src1.N, src1.S
-    C1 = src1.Cpad
-    C2 = src2.Cpad if src2 is not None else 0
-    c_log = src1.C + (src2.C if src2 is not None else 0)
-    if src2 is not None and src1.C != C1:
-        raise RuntimeError("two-source GroupNorm needs an unpadded first source")
+    N, S, C1, C2, c_log, p2 = _gn_sources(src1, src2)
     scale = torch.empty((N, C1 + C2), dtype=torch.float32, device=src1.t.device)
     shift = torch.empty_like(scale)
     check(lib.gg_groupnorm_scale_shift_acc(src1.acc.data_ptr(), src1.acc.shape[1], C1, src2.acc.data_ptr() if src2 is not None else None,

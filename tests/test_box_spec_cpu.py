@@ -49,5 +49,8 @@ def test_table_entries_are_consistent():
 def test_build_compiles_the_table_and_tracks_its_dependencies():
     sh = open(os.path.join(CSRC, "build.sh")).read()
     assert re.search(r"for f in [^;]*\bgg_conv_box_spec\b", sh)
+    # every object depends on every *.h / *.inc of csrc/ (a loop, not a list that a new header can be missing from): these two are such files
+    assert re.search(r'for dep in \$1\.hip \./\*\.h \./\*\.inc [^;]*guidegen_hip\.h; do\s+if \[ "\$dep" -nt \$1\.o \]; then return 0; fi', sh)
+    assert re.search(r"if stale \$f; then\s+echo \"hipcc \$f\.hip\"", sh)
     for dep in ("gg_conv_box_kernel.h", "gg_conv_box_specs.inc"):
-        assert f"[ {dep} -nt $f.o ]" in sh, dep
+        assert os.path.isfile(os.path.join(CSRC, dep)), dep
