@@ -463,6 +463,38 @@ int gg_minmax_normalise_scatter(const float *src, int32_t N, int64_t n_per_sampl
                                 int32_t iterations, int32_t *iter_dev, int32_t advance, int32_t depth, float *volume, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Cond stages (ldm/modules/encoders/modules.py:22-136: ClassEmbedder, TransformerEmbedder / BERTEmbedder, SpatialRescaler), gg_cond.hip.
+ * All four: no allocation, no synchronisation, capturable; a refused shape is GG_ERR_BAD_SHAPE.
+ * ------------------------------------------------------------------------------------------------ */
+/* Embedding gather: for each of rows = B * T int32 ids, out[r, d] = tok[ids[r], d] (+ pos[r % T, d] when pos != NULL), d < D.
+ * tok fp32 [V, D], pos fp32 [P, D] (T <= P); out: rows of out_stride >= D elements, GG_F32 or GG_BF16; lanes [D, out_stride) are
+ * written as zeros.  The add is one fp32 add, then one round-to-nearest-even to bf16.  An id outside [0, V) gives a zero row and
+ * reads neither table (the callers check the range on the host; the kernel never reads out of bounds). */
+int gg_embed_rows(const int32_t *ids, int64_t rows, int32_t T, const float *tok, int32_t V, int32_t D, const float *pos, int32_t P,
+                  void *out, int32_t out_dtype, int32_t out_stride, void *stream);
+/* Elementwise erf-form GELU (nn.GELU, F.gelu): bf16 in, bf16 out, fp32 arithmetic, 0.5 x erfc(-x / sqrt 2) (the left tail keeps its
+ * relative accuracy).  n > 0 elements, any n; x and out 16-byte aligned. */
+int gg_gelu(const void *x, int64_t n, void *out, void *stream);
+/* LayerNorm over the first C lanes of bf16 rows `stride` >= C lanes apart (channels-last token rows whose width is padded to a multiple
+ * of 32); lanes [C, stride) of out are written as zeros.  gamma, beta fp32 [C]; fp32 arithmetic in gg_layernorm's order.  Not in place. */
+int gg_layernorm_rows(const void *x, int64_t rows, int32_t C, int32_t stride, const float *gamma, const float *beta, float eps, void *out,
+                      void *stream);
+/* torch.nn.functional.interpolate(x, scale_factor=s, mode=...) with align_corners=False and no recompute_scale_factor on `planes` =
+ * N * C independent fp32 H x W planes (NCHW in, NCHW out), as ATen's fp32 CPU kernels compute it.  The caller passes the output extent
+ * Ho = floor(H * s), Wo = floor(W * s) (the product in double) and the coordinate scales scale_h = scale_w = float(1.0 / s) -- the value
+ * ATen uses when a scale factor is given, NOT H / Ho.  mode:
+ *   0 nearest:  source index min(floorf(dst * scale), in - 1) per axis
+ *   1 bilinear: src = scale * (dst + 0.5) - 0.5, clamped below at 0; i0 = min(int(src), in - 1), i1 = i0 + 1 only when i0 < in - 1,
+ *               weights (1 - l, l) with l = src - i0; (row i0 interpolated along W) * (1 - ly) + (row i1 ...) * ly
+ *   2 bicubic:  the same src NOT clamped, i = floorf(src), t = src - i, four taps i - 1 .. i + 2 with indices clamped to [0, in - 1]
+ *               and the cubic convolution weights of A = -0.75; rows along W first, then along H, taps added in ascending order
+ *   3 area:     adaptive average pooling, window [floor(i * in / out), ceil((i + 1) * in / out)) per axis (integer arithmetic), summed
+ *               in row-major order in fp32, then sum / kh / kw (two IEEE divisions, ATen's order); the scales are not read
+ * Every source index is clamped into the plane, whatever the scales. */
+int gg_interpolate2d_f32(const float *src, int64_t planes, int32_t H, int32_t W, int32_t Ho, int32_t Wo, float scale_h, float scale_w,
+                         int32_t mode, float *dst, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * fp32 VALIDATION mode of the CCDM path (gg_f32.hip): the same network functions on fp32 channels-last tensors with fp32 weights
  * and fp32 FMA accumulation in a fixed order, so that integer outputs (labels) can be compared exactly with the fp32 CPU
  * reference (the reference's own precision switch: ccdm/ddpm/models/unet_openai/unet.py:447,742-756).  Not a fast path.

@@ -25,6 +25,10 @@ TARGET_ALIASES = {
     "taming.modules.vqvae.quantize.VectorQuantizer": "jointimagegeneration_amd.ldm.VectorQuantizer",
     "ldm.models.diffusion.ddpm.LatentDiffusion": "jointimagegeneration_amd.ldm.LatentDiffusion",
     "ldm.modules.encoders.modules.IdentityEncoder": "jointimagegeneration_amd.ldm.IdentityEncoder",
+    "ldm.modules.encoders.modules.ClassEmbedder": "jointimagegeneration_amd.cond.ClassEmbedder",
+    "ldm.modules.encoders.modules.TransformerEmbedder": "jointimagegeneration_amd.cond.TransformerEmbedder",
+    "ldm.modules.encoders.modules.BERTEmbedder": "jointimagegeneration_amd.cond.BERTEmbedder",
+    "ldm.modules.encoders.modules.SpatialRescaler": "jointimagegeneration_amd.cond.SpatialRescaler",
     "ldm.models.diffusion.ddim.DDIMSampler": "jointimagegeneration_amd.ldm.DDIMSampler",
     "ldm.models.diffusion.plms.PLMSSampler": "jointimagegeneration_amd.ldm.PLMSSampler",
     "torch.nn.Identity": "torch.nn.Identity",

@@ -993,6 +993,8 @@ class LatentDiffusion(nn.Module):
         c_concat = cond if (cond is not None and ck == "concat" and not isinstance(cond, dict)) else \
             (cond.get("c_concat", [None])[0] if isinstance(cond, dict) else None)
         context = cond if (cond is not None and ck == "crossattn" and not isinstance(cond, dict)) else None
+        if isinstance(cond, dict) and cond.get("c_crossattn"):        # hybrid / explicit dicts: the reference's apply_model passes them through
+            context = torch.cat(cond["c_crossattn"], 1)
         Cc = c_concat.shape[1] if c_concat is not None else 0
         perm = (0,) + tuple(range(2, nd + 2)) + (1,)
         img = torch.randn(tuple(shape), device=dev) if x_T is None else x_T.to(dev).float()

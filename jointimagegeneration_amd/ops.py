@@ -581,6 +581,94 @@ def add(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     return out
 
 
+# ----------------------------------------------------------------------------------------------- cond stages (gg_cond.hip)
+def embed_rows(ids: torch.Tensor, tok: torch.Tensor, pos: Optional[torch.Tensor] = None, bf16: bool = False) -> torch.Tensor:
+    """Embedding gather (gg_embed_rows): ids integer [B, T] on the device, tok fp32 [V, D], pos fp32 [P, D] or None ->
+    tok[ids] (+ pos[t]) as fp32 [B, T, D], or with bf16=True as channels-last token rows bf16 [B, 1, 1, T, pad32(D)] (pad lanes zero).
+    The id range and T <= P are checked on the host first (ValueError naming the values): one sync, outside any captured graph."""
+    require_gpu(ids, "embed_rows")
+    if ids.dim() != 2 or ids.is_floating_point() or ids.is_complex() or ids.dtype == torch.bool:
+        raise ValueError(f"embed_rows: tokens must be an integer tensor of rank 2 [B, T], got {ids.dtype} {tuple(ids.shape)}")
+    for name, t in (("tok", tok), ("pos", pos)):
+        if t is not None and (t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous() or t.device != ids.device):
+            raise ValueError(f"embed_rows: {name} must be a contiguous fp32 [rows, D] table on {ids.device}")
+    B, T = (int(v) for v in ids.shape)
+    V, D = (int(v) for v in tok.shape)
+    if B < 1 or T < 1:
+        raise ValueError(f"embed_rows: empty token tensor {tuple(ids.shape)}")
+    P = 0
+    if pos is not None:
+        P = int(pos.shape[0])
+        if pos.shape[1] != D:
+            raise ValueError(f"embed_rows: pos has width {pos.shape[1]}, tok has {D}")
+        if T > P:
+            raise ValueError(f"embed_rows: sequence length {T} exceeds max_seq_len {P}")
+    lo, hi = int(ids.min()), int(ids.max())                 # the one host sync of the call
+    if lo < 0 or hi >= V:
+        raise ValueError(f"embed_rows: token ids span [{lo}, {hi}], outside the table's [0, {V})")
+    ids32 = ids.to(torch.int32).contiguous()
+    if bf16:
+        out = torch.empty((B, 1, 1, T, pad32(D)), dtype=torch.bfloat16, device=ids.device)
+    else:
+        out = torch.empty((B, T, D), dtype=torch.float32, device=ids.device)
+    check(_lib.load().gg_embed_rows(ids32.data_ptr(), B * T, T, tok.data_ptr(), V, D, _ptr(pos), P, out.data_ptr(),
+                                    GG_BF16 if bf16 else GG_F32, out.shape[-1], _stream()), "gg_embed_rows")
+    return out
+
+
+def gelu(x: torch.Tensor) -> torch.Tensor:
+    """Elementwise erf-form GELU of a contiguous bf16 tensor (gg_gelu)."""
+    require_gpu(x, "gelu")
+    if x.dtype != torch.bfloat16 or not x.is_contiguous() or x.numel() == 0:
+        raise ValueError(f"gelu: a non-empty contiguous bf16 tensor, got {x.dtype} {tuple(x.shape)}")
+    out = torch.empty_like(x)
+    check(_lib.load().gg_gelu(x.data_ptr(), x.numel(), out.data_ptr(), _stream()), "gg_gelu")
+    return out
+
+
+def layernorm_rows(x: CL, gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-5) -> CL:
+    """LayerNorm over the x.C logical channels of channels-last bf16 rows (gg_layernorm_rows; pad lanes of the result are zero).
+    `layernorm` normalises whole rows: it serves widths that are a multiple of 32, this one the others."""
+    if x.t.dtype != torch.bfloat16 or not x.t.is_contiguous() or gamma.numel() != x.C or beta.numel() != x.C:
+        raise ValueError(f"layernorm_rows: contiguous bf16 rows and {x.C} fp32 coefficients, got {x.t.dtype} {tuple(x.t.shape)}")
+    out = torch.empty_like(x.t)
+    check(_lib.load().gg_layernorm_rows(x.t.data_ptr(), x.t.numel() // x.Cpad, x.C, x.Cpad, gamma.data_ptr(), beta.data_ptr(), eps,
+                                        out.data_ptr(), _stream()), "gg_layernorm_rows")
+    return CL(out, x.C)
+
+
+INTERPOLATE_MODES = {"nearest": 0, "bilinear": 1, "bicubic": 2, "area": 3}
+
+
+def interpolate_extent(n_in: int, scale_factor: float) -> int:
+    """Output extent of F.interpolate(scale_factor=s): floor(in * s), the product in double."""
+    import math
+    return int(math.floor(float(n_in) * float(scale_factor)))
+
+
+def interpolate2d(x: torch.Tensor, scale_factor: float, mode: str) -> torch.Tensor:
+    """torch.nn.functional.interpolate(x, scale_factor=s, mode=mode) of an fp32 NCHW tensor on the device (gg_interpolate2d_f32;
+    align_corners=False, no recompute_scale_factor): the coordinate scale is float(1.0 / s), the output extent floor(in * s)."""
+    require_gpu(x, "interpolate2d")
+    if mode not in INTERPOLATE_MODES:
+        raise NotImplementedError(f"interpolate2d: mode {mode!r} is not supported (nearest, bilinear, bicubic, area)")
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise ValueError(f"interpolate2d: an fp32 [N, C, H, W] tensor, got {x.dtype} {tuple(x.shape)}")
+    s = float(scale_factor)
+    if not s > 0.0:
+        raise ValueError(f"interpolate2d: scale_factor = {scale_factor} must be positive")
+    N, Cc, H, W = (int(v) for v in x.shape)
+    Ho, Wo = interpolate_extent(H, s), interpolate_extent(W, s)
+    if min(N, Cc, H, W) < 1 or Ho < 1 or Wo < 1:
+        raise ValueError(f"interpolate2d: scale_factor {s} takes {tuple(x.shape)} to an extent of 0 ({Ho} x {Wo})")
+    x = x.contiguous()
+    out = torch.empty((N, Cc, Ho, Wo), dtype=torch.float32, device=x.device)
+    scale = 1.0 / s                                         # ctypes rounds the double to fp32: float(1.0 / s)
+    check(_lib.load().gg_interpolate2d_f32(x.data_ptr(), N * Cc, H, W, Ho, Wo, scale, scale, INTERPOLATE_MODES[mode], out.data_ptr(),
+                                           _stream()), "gg_interpolate2d_f32")
+    return out
+
+
 # ----------------------------------------------------------------------------------------------- attention
 def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, N: int, heads: int, head_dim: int, Tq: int,
               Tkv: int, ld_hs_q, ld_hs_k, ld_hs_v, ld_hs_o, scale: float, q_off=0, k_off=0, v_off=0) -> None:

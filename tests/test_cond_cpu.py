@@ -1,0 +1,181 @@
+"""CPU suite of the cond stages (jointimagegeneration_amd/cond.py): state-dict surfaces and dotted paths against the reference's
+(tests/golden/cond_surface.json, make_golden_cond.py), every host-side refusal, and the torch restatement tests/cond_ref.py -- which the
+GPU suite compares the kernels with -- against the reference's recorded outputs and against torch.nn.functional.interpolate itself."""
+import json
+import os
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+import cond_ref
+from util import AE_SMALL, GOLD, LDM_SMALL, T, gold, sd_cpu, seeded, surface
+
+TE = dict(n_embed=48, n_layer=2, vocab_size=97, max_seq_len=20)
+TE64 = dict(n_embed=64, n_layer=1, vocab_size=97, max_seq_len=20)
+TOKEN_SHAPES = ((3, 7), (1, 1), (2, 20))
+PATHS = ("ClassEmbedder", "TransformerEmbedder", "BERTEmbedder", "SpatialRescaler")
+
+
+def surfaces():
+    with open(os.path.join(GOLD, "cond_surface.json")) as f:
+        return json.load(f)
+
+
+def embedder(name):
+    from jointimagegeneration_amd import cond
+    if name == "bert":
+        return seeded(cond.BERTEmbedder(**TE, use_tokenizer=False), "cond_bert."), TE
+    kw = TE if name == "te" else TE64
+    return seeded(cond.TransformerEmbedder(**kw), f"cond_{name}."), kw
+
+
+def cond_ldm(cond_cfg, key="crossattn", timesteps=999, in_channels=4):
+    """The LatentDiffusion of make_golden_cond.py's chain: small SpatialTransformer UNet (context 48), cond stage from its dotted path."""
+    from jointimagegeneration_amd.ldm import LatentDiffusion
+    unet = dict(LDM_SMALL, in_channels=in_channels, use_spatial_transformer=True, transformer_depth=1, context_dim=48)
+    cfg_ae = dict(target="ldm.models.autoencoder.AutoencoderKL", params=dict(embed_dim=4, dims=2, ddconfig=dict(AE_SMALL), lossconfig=dict(target="torch.nn.Identity")))
+    return LatentDiffusion(first_stage_config=cfg_ae, cond_stage_config=cond_cfg,
+                           unet_config=dict(target="ldm.modules.diffusionmodules.openaimodel.UNetModel", params=unet), conditioning_key=key,
+                           linear_start=0.0015, linear_end=0.0195, timesteps=timesteps, image_size=8, channels=4, dims=2,
+                           first_stage_key="image", cond_stage_key="caption", num_timesteps_cond=1)
+
+
+def test_dotted_paths_resolve_to_the_product_classes():
+    from jointimagegeneration_amd import cond
+    from jointimagegeneration_amd.config import get_obj_from_str, instantiate_from_config
+    for name in PATHS:
+        assert get_obj_from_str(f"ldm.modules.encoders.modules.{name}") is getattr(cond, name)
+    m = instantiate_from_config(dict(target="ldm.modules.encoders.modules.ClassEmbedder", params=dict(embed_dim=16, n_classes=11)))
+    assert isinstance(m, cond.ClassEmbedder) and m.key == "class"
+
+
+def test_c_abi_declares_the_cond_kernels():
+    import __graft_entry__ as ge
+    from jointimagegeneration_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        ge.build()
+    lib = _lib.load()
+    for s in ("gg_embed_rows", "gg_gelu", "gg_layernorm_rows", "gg_interpolate2d_f32"):
+        assert s in _lib.SIGNATURES and hasattr(lib, s)
+
+
+def test_state_dict_surfaces_equal_the_references():
+    from jointimagegeneration_amd import cond
+    want = surfaces()
+    for name in ("te", "bert", "te64"):
+        assert surface(embedder(name)[0]) == want[name], name
+    assert any(k == "transformer.to_logits.weight" for k, _ in want["te"])           # unused by the embedders, in every checkpoint
+    assert surface(cond.ClassEmbedder(16, 11)) == want["cls"]
+    for method in cond_ref.MODES:
+        for bias in (False, True):
+            m = cond.SpatialRescaler(n_stages=1, method=method, multiplier=0.5, in_channels=3, out_channels=5, bias=bias)
+            assert surface(m) == want[f"rs_{method}_b{int(bias)}"]
+    assert surface(cond.SpatialRescaler()) == []
+    ld = cond_ldm(dict(target="ldm.modules.encoders.modules.TransformerEmbedder", params=dict(TE, device="cpu")))
+    assert [e for e in surface(ld) if e[0].startswith("cond_stage_model.")] == want["chain_cond_stage"]
+    assert not ld.cond_stage_model.training
+
+
+def test_every_refusal_raises_and_names_the_option():
+    from jointimagegeneration_amd import cond
+    with pytest.raises(NotImplementedError, match="use_tokenizer"):
+        cond.BERTEmbedder(48, 2)
+    with pytest.raises(NotImplementedError, match="use_tokenizer"):
+        cond.BERTEmbedder(48, 2, use_tokenizer=True)
+    cond.BERTEmbedder(48, 1, vocab_size=97, max_seq_len=20, use_tokenizer=False, embedding_dropout=0.1)       # accepted: identity in eval mode
+    for method in ("linear", "trilinear"):
+        with pytest.raises(NotImplementedError, match=f"{method!r}"):
+            cond.SpatialRescaler(method=method)
+    rs = cond.SpatialRescaler(n_stages=2, multiplier=0.5).eval()
+    for bad in (torch.zeros(3, 8, 8), torch.zeros(1, 3, 4, 8, 8)):
+        with pytest.raises(ValueError, match="4-D"):
+            rs(bad)
+    with pytest.raises(ValueError, match="extent of 0"):
+        rs(torch.zeros(1, 3, 3, 8))                                                   # 3 -> 1 -> 0
+    te = cond.TransformerEmbedder(**TE, device="anything").eval()
+    for bad in (torch.zeros(2, 7), torch.zeros(7, dtype=torch.long), torch.zeros(1, 2, 7, dtype=torch.long), torch.zeros(2, 7, dtype=torch.bool), [[1, 2]]):
+        with pytest.raises(ValueError, match="integer tensor of rank 2"):
+            te.encode(bad)
+    ce = cond.ClassEmbedder(16, 11).eval()
+    with pytest.raises(ValueError, match="integer tensor of rank"):
+        ce({"class": torch.zeros(4)})
+    # training mode (a fresh module is in it)
+    for m, arg in ((cond.TransformerEmbedder(**TE), torch.zeros(2, 7, dtype=torch.long)), (cond.ClassEmbedder(16, 11), {"class": torch.zeros(2, dtype=torch.long)}),
+                   (cond.SpatialRescaler(), torch.zeros(1, 3, 8, 8))):
+        with pytest.raises(RuntimeError, match="training mode"):
+            m(arg)
+    # CPU tensors
+    for m, arg in ((te, torch.zeros(2, 7, dtype=torch.long)), (ce, {"class": torch.zeros(2, dtype=torch.long)}), (cond.SpatialRescaler().eval(), torch.zeros(1, 3, 8, 8))):
+        with pytest.raises(RuntimeError, match="no CPU fallback"):
+            m(arg)
+
+
+def test_get_learned_conditioning_passes_dict_and_integer_input_to_the_cond_stage():
+    """LatentDiffusion.get_learned_conditioning hands its argument to the cond stage untouched: the embedder's `encode` (integer tokens)
+    and the ClassEmbedder's `__call__` (a dict) see it and refuse the CPU tensors by name."""
+    ld = cond_ldm(dict(target="ldm.modules.encoders.modules.TransformerEmbedder", params=dict(TE)))
+    with pytest.raises(RuntimeError, match="TransformerEmbedder.forward.*no CPU fallback"):
+        ld.get_learned_conditioning(torch.zeros(2, 7, dtype=torch.long))
+    ld = cond_ldm(dict(target="ldm.modules.encoders.modules.ClassEmbedder", params=dict(embed_dim=48, n_classes=11)))
+    assert not hasattr(ld.cond_stage_model, "encode")
+    with pytest.raises(RuntimeError, match="ClassEmbedder.forward.*no CPU fallback"):
+        ld.get_learned_conditioning({"class": torch.zeros(2, dtype=torch.long)})
+
+
+def test_restatement_reproduces_the_reference_outputs():
+    """tests/cond_ref.py on the seed-recipe weights against what the reference modules produced: 2e-5 absolute, the bound of
+    test_oracle_golden.py::test_text_encoder_oracle_and_surface_match_reference_fixture."""
+    from jointimagegeneration_amd import cond
+    g = gold("cond")
+    for name in ("te", "bert", "te64"):
+        m, kw = embedder(name)
+        for b, t in TOKEN_SHAPES:
+            got = cond_ref.transformer_embed(sd_cpu(m), T(g[f"{name}_{b}x{t}_tokens"]), kw["n_layer"])
+            assert float((got - T(g[f"{name}_{b}x{t}_z"])).abs().max()) < 2e-5, (name, b, t)
+    ce = seeded(cond.ClassEmbedder(16, 11), "cond_cls.")
+    assert torch.equal(cond_ref.class_embed(sd_cpu(ce), T(g["cls_labels"])), T(g["cls_z"]))
+    x = T(g["rs_x"])
+    for method in cond_ref.MODES:
+        for bias in (False, True):
+            m = seeded(cond.SpatialRescaler(n_stages=1, method=method, multiplier=0.5, in_channels=3, out_channels=5, bias=bias), f"cond_rs_{method}_b{int(bias)}.")
+            got = cond_ref.spatial_rescale(sd_cpu(m), x, 1, method, 0.5)
+            assert float((got - T(g[f"rs_{method}_b{int(bias)}"])).abs().max()) < 2e-5, (method, bias)
+        got = cond_ref.spatial_rescale({}, x, 2, method, 0.5)
+        assert tuple(got.shape) == (2, 3, 3, 2) and float((got - T(g[f"rs_{method}_plain2"])).abs().max()) < 2e-5, method
+
+
+def test_restated_nearest_rule_equals_torch_bit_for_bit():
+    gen = torch.Generator().manual_seed(5)
+    for shape in cond_ref.EXACT_SHAPES:
+        x = torch.randn(shape, generator=gen)
+        for s in cond_ref.GENERAL_MULTIPLIERS + cond_ref.exact_multipliers("nearest"):
+            assert torch.equal(cond_ref.interpolate(x, s, "nearest"), F.interpolate(x, scale_factor=s, mode="nearest")), (shape, s)
+
+
+@pytest.mark.parametrize("mode", cond_ref.MODES)
+def test_restated_rules_equal_torch_on_the_exact_cases(mode):
+    """Integer-valued planes and multipliers with dyadic tap weights: fp32 torch, fp64 torch and the restatement agree bit for bit.
+    (area: the window sums are exact integers and the one division is correctly rounded, so fp32 results are unique too, but a window of
+    3 or 6 elements -- the 13 x 10 plane at 0.5 -- does not divide exactly, and fp64 torch is not compared there.)"""
+    for i, shape in enumerate(cond_ref.EXACT_SHAPES):
+        x = cond_ref.exact_input(shape, seed=i)
+        for s in cond_ref.exact_multipliers(mode):
+            want = F.interpolate(x, scale_factor=s, mode=mode)
+            assert tuple(want.shape[2:]) == (cond_ref.out_extent(shape[2], s), cond_ref.out_extent(shape[3], s))
+            if mode != "area":
+                assert torch.equal(want.double(), F.interpolate(x.double(), scale_factor=s, mode=mode)), (shape, s)
+            assert torch.equal(cond_ref.interpolate(x, s, mode), want), (shape, s)
+
+
+def test_restated_rules_stay_within_torchs_own_fp32_error_on_general_multipliers():
+    """At multipliers whose weights round, the restatement is one valid fp32 evaluation: its error against fp64 torch is of the size of
+    fp32 torch's own (the GPU suite's bound, 4 x torch's error + 2^-22 max|x|)."""
+    gen = torch.Generator().manual_seed(6)
+    x = torch.randn(2, 3, 13, 10, generator=gen)
+    for mode in ("bilinear", "bicubic", "area"):
+        for s in cond_ref.GENERAL_MULTIPLIERS:
+            ref = F.interpolate(x.double(), scale_factor=s, mode=mode)
+            e_t = float((F.interpolate(x, scale_factor=s, mode=mode).double() - ref).abs().max())
+            e_r = float((cond_ref.interpolate(x, s, mode).double() - ref).abs().max())
+            assert e_r <= 4 * e_t + 2.0 ** -22 * float(x.abs().max()), (mode, s, e_r, e_t)
