@@ -494,6 +494,31 @@ int gg_layernorm_rows(const void *x, int64_t rows, int32_t C, int32_t stride, co
 int gg_interpolate2d_f32(const float *src, int64_t planes, int32_t H, int32_t W, int32_t Ho, int32_t Wo, float scale_h, float scale_w,
                          int32_t mode, float *dst, void *stream);
 
+/* Rendering of sampled volumes (gg_render.hip): the picture latentdiffusion/sample_diffusion.py:241-261 saves, bit for bit.  Both: the
+ * caller's stream, no allocation, no workspace, no atomics on global memory, no synchronisation: capturable.
+ * gg_mask_overlay: combine_mask_and_im (sample_diffusion.py:23-58).  x fp32 [N, 2, D, H, W] (channel 0 the CT, channel 1 the mask as
+ *   label / 11), out fp32 [N, D, 3, H, W], both contiguous on the device; colors: 12 x 3 int32 on the HOST (read during the call).  Per
+ *   voxel, every step one correctly rounded fp32 operation (nothing is contracted into an FMA):
+ *     image = 255 * clamp(x0, 0, 1);  m = x1 * 11, and m = 11 where m == 255
+ *     colored = colors[trunc(m)] where m > 0, image where m == 0 (and 0 where m < 0);  im = colored * coef + image * rest, with
+ *     coef = (float)overlay_coef and rest = (float)(1.0 - overlay_coef), the two Python floats of the reference
+ *     out = colors[i] when the voxel is a boundary voxel of class i, the lowest such i in 1..11; im otherwise
+ *   Boundary voxel of class i: with b = (m == i) and zeros outside the volume, one of the three integer Sobel responses of b ([-1, 0, 1]
+ *   along one axis, [1, 2, 1] along the two others) is non-zero -- what scipy.ndimage.sobel(mode='constant') leaves in a bool array.
+ *   trunc(m) outside 0..11 is the caller's error (the reference raises IndexError); the kernel clamps the index and never reads outside
+ *   the table.  Tiles of 8 x 8 x 64 voxels with a one-voxel halo of class ids in LDS; no extent need be a multiple of the tile; a tile
+ *   whose halo holds one class id skips the stencil.
+ * gg_make_grid_u8: torchvision.utils.make_grid(imgs, nrow, padding, pad_value) followed by permute(1, 2, 0) and .astype(uint8).  imgs
+ *   fp32 [B, C, H, W], C 1 (repeated to three channels) or 3; out uint8 [Hg, Wg, 3].  B == 1: the image itself (Hg = H, Wg = W, no
+ *   padding).  Otherwise xmaps = min(nrow, B), ymaps = ceil(B / xmaps), Hg = ymaps * (H + padding) + padding, Wg = xmaps * (W + padding)
+ *   + padding, image k at (k / xmaps * (H + padding) + padding, k % xmaps * (W + padding) + padding), pad_value elsewhere.  The cast
+ *   truncates toward zero and saturates to [0, 255] (NaN gives 0).
+ *   N, D, H, W, B < 1, C outside {1, 3}, nrow < 1, padding < 0, a null pointer: GG_ERR_BAD_SHAPE before any launch. */
+int gg_mask_overlay(const float *x, int32_t N, int32_t D, int32_t H, int32_t W, double overlay_coef, const int32_t *colors, float *out,
+                    void *stream);
+int gg_make_grid_u8(const float *imgs, int32_t B, int32_t C, int32_t H, int32_t W, int32_t nrow, int32_t padding, float pad_value,
+                    uint8_t *out, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * fp32 VALIDATION mode of the CCDM path (gg_f32.hip): the same network functions on fp32 channels-last tensors with fp32 weights
  * and fp32 FMA accumulation in a fixed order, so that integer outputs (labels) can be compared exactly with the fp32 CPU

@@ -3,12 +3,14 @@
 write_nifti / read_nifti: single-file NIfTI-1 (.nii / .nii.gz), enough for the label and CT volumes the reference writes with
 SimpleITK (ccdm/ddpm/evaluator.py:147-148, latentdiffusion/sample_diffusion.py:248-250) and reads back with nibabel when the
 stage-1 masks are handed to the CT generator (README.md:21; recipe latentdiffusion/sample_diffusion.py:199-200).
+write_png: the 8-bit RGB PNG of a rendered slice grid (render.py), on zlib + struct (PIL is not a dependency).
 Checkpoints are read with torch.load(weights_only=True) only.
 """
 from __future__ import annotations
 
 import gzip
 import struct
+import zlib
 
 import numpy as np
 import torch
@@ -76,6 +78,26 @@ def read_nifti(path: str) -> np.ndarray:
     if slope not in (0.0, 1.0) or inter != 0.0:
         arr = arr.astype(np.float32) * np.float32(slope) + np.float32(inter)
     return np.ascontiguousarray(arr)
+
+
+def write_png(path: str, img: np.ndarray) -> None:
+    """An 8-bit RGB PNG of a uint8 [H, W, 3] array (what `PIL.Image.fromarray(grid).save(path)` stores, latentdiffusion/
+    sample_diffusion.py:252-261): signature, IHDR, one IDAT of the zlib-compressed scanlines (filter type 0 on every row), IEND."""
+    img = np.asarray(img)
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3 or img.shape[0] < 1 or img.shape[1] < 1:
+        raise ValueError(f"write_png: a uint8 [H, W, 3] array, got {img.dtype} {img.shape}")
+    H, W = img.shape[:2]
+    rows = np.zeros((H, 1 + 3 * W), dtype=np.uint8)          # a filter byte (0: none) in front of every scanline
+    rows[:, 1:] = img.reshape(H, 3 * W)
+
+    def chunk(tag: bytes, data: bytes) -> bytes:
+        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
+
+    with open(path, "wb") as f:
+        f.write(b"\x89PNG\r\n\x1a\n")
+        f.write(chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, 2, 0, 0, 0)))      # 8 bits, colour type 2 (RGB), no interlace
+        f.write(chunk(b"IDAT", zlib.compress(rows.tobytes(), 6)))
+        f.write(chunk(b"IEND", b""))
 
 
 def load_checkpoint(path: str) -> dict:

@@ -1016,6 +1016,55 @@ def lpips_tap(a: torch.Tensor, b: torch.Tensor, lin_w: torch.Tensor, pool: bool 
     return tap_out, pooled
 
 
+# ----------------------------------------------------------------------------------------------- rendering (gg_render.hip)
+def make_grid_extent(B: int, H: int, W: int, nrow: int, padding: int) -> Tuple[int, int]:
+    """(Hg, Wg) of torchvision's make_grid for B images of H x W: a single image is returned as it is, without padding."""
+    if B == 1:
+        return H, W
+    xmaps = min(nrow, B)
+    ymaps = -(-B // xmaps)
+    return ymaps * (H + padding) + padding, xmaps * (W + padding) + padding
+
+
+def mask_overlay(x: torch.Tensor, colors: Sequence[Sequence[int]], overlay_coef: float = 0.2, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """combine_mask_and_im of the reference on the device (gg_mask_overlay): x fp32 [N, 2, D, H, W] (CT, mask as label / 11) ->
+    fp32 [N, D, 3, H, W], bit for bit.  colors: 12 rows of 3 integers.  The range of trunc(x[:, 1] * 11) is the caller's to check
+    (render.combine_mask_and_im does); the kernel clamps the table index."""
+    if x.dim() != 5 or x.shape[1] != 2 or x.dtype != torch.float32 or not x.is_contiguous() or x.numel() == 0:
+        raise ValueError(f"mask_overlay: x must be a contiguous non-empty fp32 [N, 2, D, H, W] tensor, got {x.dtype} {tuple(x.shape)}")
+    table = [int(v) for row in colors for v in row]
+    if len(table) != 36 or any(len(row) != 3 for row in colors):
+        raise ValueError(f"mask_overlay: colors must be 12 rows of 3 integers, got {len(table)} values")
+    require_gpu(x, "mask_overlay")
+    N, _, D, H, W = (int(v) for v in x.shape)
+    if out is None:
+        out = torch.empty((N, D, 3, H, W), dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (N, D, 3, H, W) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
+        raise ValueError(f"mask_overlay: out must be a contiguous fp32 {(N, D, 3, H, W)} tensor on {x.device}, got {out.dtype} {tuple(out.shape)}")
+    check(_lib.load().gg_mask_overlay(x.data_ptr(), N, D, H, W, float(overlay_coef), (C.c_int32 * 36)(*table), out.data_ptr(), _stream()),
+          "gg_mask_overlay")
+    return out
+
+
+def make_grid_u8(imgs: torch.Tensor, nrow: int = 8, padding: int = 2, pad_value: float = 0.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """torchvision's make_grid + permute(1, 2, 0) + astype(uint8) on the device (gg_make_grid_u8): imgs fp32 [B, C, H, W], C 1 or 3 ->
+    uint8 [Hg, Wg, 3].  The cast truncates toward zero and saturates to [0, 255]."""
+    if imgs.dim() != 4 or imgs.shape[1] not in (1, 3) or imgs.dtype != torch.float32 or not imgs.is_contiguous() or imgs.numel() == 0:
+        raise ValueError(f"make_grid_u8: imgs must be a contiguous non-empty fp32 [B, 1 or 3, H, W] tensor, got {imgs.dtype} {tuple(imgs.shape)}")
+    if int(nrow) < 1 or int(padding) < 0:
+        raise ValueError(f"make_grid_u8: nrow={nrow} padding={padding}")
+    require_gpu(imgs, "make_grid_u8")
+    B, Cc, H, W = (int(v) for v in imgs.shape)
+    Hg, Wg = make_grid_extent(B, H, W, int(nrow), int(padding))
+    if out is None:
+        out = torch.empty((Hg, Wg, 3), dtype=torch.uint8, device=imgs.device)
+    elif tuple(out.shape) != (Hg, Wg, 3) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != imgs.device:
+        raise ValueError(f"make_grid_u8: out must be a contiguous uint8 {(Hg, Wg, 3)} tensor on {imgs.device}, got {out.dtype} {tuple(out.shape)}")
+    check(_lib.load().gg_make_grid_u8(imgs.data_ptr(), B, Cc, H, W, int(nrow), int(padding), float(pad_value), out.data_ptr(), _stream()),
+          "gg_make_grid_u8")
+    return out
+
+
 def minmax_normalise(src: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     lib = _lib.load()
     if out is None:

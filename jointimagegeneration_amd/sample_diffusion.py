@@ -8,7 +8,9 @@ slice loop exactly (Python indexing quirks included) on the reference-shaped API
 DDIMSampler.sample / decode_first_stage); `GuideGenPipeline.sample_ct` is the all-device fast path of the same loop.
 With `--gt DIR --lpips-vgg PATH --lpips-lin PATH` each sampled volume is scored against the same-named volume of DIR with the
 three-view LPIPS of compute_metrics (sample_diffusion.py:436-475; jointimagegeneration_amd/lpips.py) and metrics.json is written next to
-the samples.  FVD (no I3D network or scripts.fvd in the reference), PNG grids and the private datasets are out of scope; the mask comes from `--inputs <dir>` (the
+the samples.  With `--png` each sampled volume is also rendered as `<stem>_<ix:04d>.png`: the organ overlay and slice grid of
+sample_diffusion.py:241-261 (jointimagegeneration_amd/render.py).  FVD (no I3D network or scripts.fvd in the reference), the per-slice
+`layers/*.png` and the private datasets are out of scope; the mask comes from `--inputs <dir>` (the
 `pred_*.nii.gz` label volumes the stage-1 entry point ddpm_eval writes: the hand-off of README.md:21, one CT volume per mask),
 from --mask (.npy label volume [D,H,W]) or is synthetic.
 """
@@ -27,6 +29,7 @@ from .config import apply_dotlist, instantiate_from_config, load_yaml, merge
 from . import ops
 from .io import load_checkpoint, read_nifti, write_nifti
 from .ldm import DDIMSampler, PLMSSampler
+from .render import volume_png
 from .synth import randomize_parameters, synth_mask_volume
 
 
@@ -51,6 +54,9 @@ def get_parser():
                    "with --lpips-vgg and --lpips-lin each sample is scored against it (three-view LPIPS) and metrics.json is written next to the samples")
     p.add_argument("--lpips-vgg", type=str, default=None, help="VGG16 feature state dict (torchvision's features.N.* names or net.sliceK.N.*)")
     p.add_argument("--lpips-lin", type=str, default=None, help="lpips checkpoint with linK.model.1.weight")
+    p.add_argument("--png", default=False, action="store_true", help="render each sampled volume as <stem>_<ix:04d>.png beside its NIfTI file: "
+                   "the mask blended over the CT at 20 %% with organ boundaries, slices tiled 8 per row.  The overlay is given the mask as "
+                   "label / 11, the convention its colour table needs; the reference's own call passes label / 255, for which no organ is painted")
     return p
 
 
@@ -131,6 +137,12 @@ def sample_cond(model, instance, n_samples=1, ddim_steps=50, ddim_eta=0.0, noise
         return torch.cat([samples, gen_mask], dim=1)
 
 
+def render_input(x: torch.Tensor) -> torch.Tensor:
+    """One sampled volume [2, D, H, W] = (CT, label / 255) as render.combine_mask_and_im takes it: (CT, label / 11).  The reference
+    renders `pred` as it is (sample_diffusion.py:257); label / 255 * 11 truncates to 0 for every label, so nothing would be painted."""
+    return torch.cat([x[:1].float(), torch.round(x[1:2].float() * 255) / 11])
+
+
 def main(argv=None):
     opt, unknown = get_parser().parse_known_args(argv)
     scoring = (opt.gt, opt.lpips_vgg, opt.lpips_lin)
@@ -183,6 +195,8 @@ def main(argv=None):
         for ix, x in enumerate(pred):
             write_nifti(os.path.join(out_dir, f"{stem}_{ix:04d}.nii.gz"), x[0].float().cpu().numpy())
             written.append(os.path.join(out_dir, f"{stem}_{ix:04d}.nii.gz"))
+            if opt.png:
+                volume_png(render_input(x), os.path.join(out_dir, f"{stem}_{ix:04d}.png"))
         print(f"sampled {tuple(pred.shape)} in {time.time() - t0:.1f}s -> {out_dir}/{stem}_*.nii.gz", file=sys.stderr)
     if scorer is not None:
         import json
