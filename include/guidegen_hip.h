@@ -332,6 +332,27 @@ int gg_ddim_step(float *x, const float *eps, int32_t eps_stride, const float *no
 int gg_ddpm_step(float *x, const float *eps, int32_t eps_stride, const float *noise, const float *scalars_dev, int64_t M, int32_t C,
                  void *unet_in, int32_t unet_in_stride, void *stream);
 
+/* Ancestral step with the reference's options (p_mean_variance, ddpm.py:1072-1083, + p_sample :1109-1120), fp32 elementwise on CL rows:
+ *   xr = s[0]*x - s[1]*out;  flags & GG_DDPM_PREDICTS_X0: xr = out (parameterization "x0");  flags & GG_DDPM_CLIP: xr clamped to [-1, 1];
+ *   pred_x0_out <- xr;  xn = s[2]*xr + s[3]*x;  noise != NULL: xn = xn + s[4]*noise;  x <- xn;  unet_in channels [0, C) <- bf16(xn).
+ *   Evaluated in that order without contraction; scalars device fp32[5] as in gg_ddpm_step.  With flags == 0 and pred_x0_out == NULL the
+ *   result is bit-equal to gg_ddpm_step's.  x fp32 [M, C] (in/out), out fp32 [M, out_stride] (the UNet's output), noise fp32 [M, C] or
+ *   NULL, pred_x0_out fp32 [M, C] or NULL, unet_in bf16 CL [M, unet_in_stride] or NULL (pad lanes are not touched).
+ *   GG_ERR_BAD_SHAPE: NULL x / out / scalars, out_stride < C, unet_in_stride < C; GG_ERR_UNSUPPORTED: flag bits other than the two.
+ *   M == 0 returns GG_OK without a launch.  C == 4 with 16-byte aligned rows (out_stride and unet_in_stride multiples of 4, 8-byte
+ *   unet_in rows) runs one row per lane; any other case a grid-stride loop per element.  A NaN through the clamp is unspecified.
+ *   No allocation, no synchronisation. */
+#define GG_DDPM_PREDICTS_X0 1
+#define GG_DDPM_CLIP 2
+int gg_ddpm_step_x0(float *x, const float *out, int32_t out_stride, const float *noise, const float *scalars_dev, int32_t flags,
+                    int64_t M, int32_t C, float *pred_x0_out, void *unet_in, int32_t unet_in_stride, void *stream);
+
+/* Sampler log entry: the fp32 channels-last state [N * S, C] (dense rows; S voxels per sample) -> slot fp32 [N, C, S], one entry of a
+ * caller-allocated log buffer.  It runs gg_cl_to_nchw_f32's kernel with C_pad == C, at a fixed destination: no allocation, no
+ * synchronisation, so it can sit inside a captured chain.  GG_ERR_BAD_SHAPE: NULL pointers, C <= 0, negative N or S; an empty extent
+ * returns GG_OK without a launch. */
+int gg_log_rows(const float *state, int32_t N, int32_t C, int64_t S, float *slot, void *stream);
+
 /* Inpainting blend of the LDM samplers (ddim.py:144-148, plms.py:147-150, ddpm.py:1212-1214), fp32 elementwise on CL rows [M, C]:
  *   x <- (s[0]*x0 + s[1]*noise) * mask + (1 - mask) * x      (the q_sample of ddpm.py:275-278, then the blend; mask 1 keeps x0)
  *   evaluated without contraction in the reference's order: t1 = s0*x0; t2 = s1*n; o = t1 + t2; p = o*m; q = (1 - m)*x; x = p + q.

@@ -81,6 +81,8 @@ SIGNATURES = {
     "gg_minmax_normalise": (C.c_int, [vp, i64, vp, vp, vp]),
     "gg_ddpm_step": (C.c_int, [vp, vp, i32, vp, vp, i64, i32, vp, i32, vp]),
     "gg_inpaint_blend": (C.c_int, [vp, vp, vp, i32, vp, vp, i64, i32, vp, i32, vp]),
+    "gg_ddpm_step_x0": (C.c_int, [vp, vp, i32, vp, vp, i32, i64, i32, vp, vp, i32, vp]),
+    "gg_log_rows": (C.c_int, [vp, i32, i32, i64, vp, vp]),
     "gg_vq_nearest": (C.c_int, [vp, i32, vp, i32, i32, i64, vp, vp, i32, vp]),
     "gg_ddim_step_vq": (C.c_int, [vp, vp, i32, vp, vp, i32, vp, i32, i64, i32, vp, vp, vp, i32, vp]),
     "gg_label_confusion": (C.c_int, [vp, i32, vp, i32, i64, i32, vp, vp, vp]),

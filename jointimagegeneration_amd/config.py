@@ -24,6 +24,7 @@ TARGET_ALIASES = {
     "ldm.models.autoencoder.IdentityFirstStage": "jointimagegeneration_amd.ldm.IdentityFirstStage",
     "taming.modules.vqvae.quantize.VectorQuantizer": "jointimagegeneration_amd.ldm.VectorQuantizer",
     "ldm.models.diffusion.ddpm.LatentDiffusion": "jointimagegeneration_amd.ldm.LatentDiffusion",
+    "ldm.models.diffusion.ddpm.DDPM": "jointimagegeneration_amd.ldm.DDPM",
     "ldm.modules.encoders.modules.IdentityEncoder": "jointimagegeneration_amd.ldm.IdentityEncoder",
     "ldm.modules.encoders.modules.ClassEmbedder": "jointimagegeneration_amd.cond.ClassEmbedder",
     "ldm.modules.encoders.modules.TransformerEmbedder": "jointimagegeneration_amd.cond.TransformerEmbedder",

@@ -200,6 +200,99 @@ extern "C" int gg_ddpm_step(float *x, const float *eps, int32_t eps_stride, cons
 }
 
 // ------------------------------------------------------------------------------------------------------------
+// Ancestral step with the reference's options (ddpm.py:1072-1083 + p_sample :1109-1120): x0 parameterisation, clip_denoised, and
+// the prediction of x_0 as an output.  Same scalars and the same expression order as ddpm_step_kernel, so that flags == 0 gives its bits.
+// ------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float ddpm_step_x0_one(float xv, float ov, float a, float b, float c1, float c2, int flags, float &xr_out)
+{
+#pragma clang fp contract(off)
+    float xr = a * xv - b * ov;
+    if (flags & GG_DDPM_PREDICTS_X0) xr = ov;
+    if (flags & GG_DDPM_CLIP) xr = fminf(fmaxf(xr, -1.0f), 1.0f);
+    xr_out = xr;
+    return c1 * xr + c2 * xv;
+}
+
+// C == 4: one row per lane, 16-byte accesses of x / out / noise / pred_x0_out, one 8-byte bf16x4 store into the UNet input (the layout of
+// inpaint_blend_c4_kernel).  The host checks the alignment these accesses need.
+__global__ __launch_bounds__(256) void ddpm_step_x0_c4_kernel(float *__restrict__ x, const float *__restrict__ out, int out_stride,
+                                                              const float *__restrict__ noise, const float *__restrict__ sc, int flags,
+                                                              long long M, float *__restrict__ pred_x0_out, bf16_t *__restrict__ unet_in,
+                                                              int unet_in_stride)
+{
+#pragma clang fp contract(off)
+    const float a = sc[0], b = sc[1], c1 = sc[2], c2 = sc[3], sg = sc[4];
+    for (long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x; m < M; m += (long long)gridDim.x * blockDim.x) {
+        const f32x4 xv = *reinterpret_cast<const f32x4 *>(x + m * 4);
+        const f32x4 ov = *reinterpret_cast<const f32x4 *>(out + m * out_stride);
+        f32x4 nv = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (noise) nv = *reinterpret_cast<const f32x4 *>(noise + m * 4);
+        f32x4 r, p;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            float xr;
+            float xn = ddpm_step_x0_one(xv[c], ov[c], a, b, c1, c2, flags, xr);
+            if (noise) xn = xn + sg * nv[c];
+            r[c] = xn;
+            p[c] = xr;
+        }
+        *reinterpret_cast<f32x4 *>(x + m * 4) = r;
+        if (pred_x0_out) *reinterpret_cast<f32x4 *>(pred_x0_out + m * 4) = p;
+        if (unet_in) {
+            bf16x4 o;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) o[c] = (bf16_t)r[c];
+            *reinterpret_cast<bf16x4 *>(unet_in + m * unet_in_stride) = o;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void ddpm_step_x0_kernel(float *__restrict__ x, const float *__restrict__ out, int out_stride,
+                                                           const float *__restrict__ noise, const float *__restrict__ sc, int flags,
+                                                           long long M, int C, float *__restrict__ pred_x0_out,
+                                                           bf16_t *__restrict__ unet_in, int unet_in_stride)
+{
+#pragma clang fp contract(off)
+    const float a = sc[0], b = sc[1], c1 = sc[2], c2 = sc[3], sg = sc[4];
+    const long long total = M * C;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const long long m = i / C;
+        const int c = (int)(i - m * C);
+        float xr;
+        float xn = ddpm_step_x0_one(x[i], out[m * out_stride + c], a, b, c1, c2, flags, xr);
+        if (noise) xn = xn + sg * noise[i];
+        x[i] = xn;
+        if (pred_x0_out) pred_x0_out[i] = xr;
+        if (unet_in) unet_in[m * unet_in_stride + c] = (bf16_t)xn;
+    }
+}
+
+extern "C" int gg_ddpm_step_x0(float *x, const float *out, int32_t out_stride, const float *noise, const float *scalars_dev, int32_t flags,
+                               int64_t M, int32_t C, float *pred_x0_out, void *unet_in, int32_t unet_in_stride, void *stream_)
+{
+    if (!x || !out || !scalars_dev) GG_FAIL(GG_ERR_BAD_SHAPE, "ddpm_step_x0: null pointer");
+    if (C <= 0 || out_stride < C) GG_FAIL(GG_ERR_BAD_SHAPE, "ddpm_step_x0: out_stride %d < C=%d", out_stride, C);
+    if (unet_in && unet_in_stride < C) GG_FAIL(GG_ERR_BAD_SHAPE, "ddpm_step_x0: unet_in_stride %d < C=%d", unet_in_stride, C);
+    if (flags & ~(GG_DDPM_PREDICTS_X0 | GG_DDPM_CLIP)) GG_FAIL(GG_ERR_UNSUPPORTED, "ddpm_step_x0: unknown flag bits 0x%x", flags);
+    if (M <= 0) return GG_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    const auto al = [](const void *p, uintptr_t n) { return ((uintptr_t)p & (n - 1)) == 0; };
+    const bool vec = C == 4 && al(x, 16) && al(out, 16) && out_stride % 4 == 0 && (!noise || al(noise, 16)) &&
+                     (!pred_x0_out || al(pred_x0_out, 16)) && (!unet_in || (al(unet_in, 8) && unet_in_stride % 4 == 0));
+    const long long work = vec ? (long long)M : (long long)M * C;
+    long long blocks = (work + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    if (vec)
+        hipLaunchKernelGGL(ddpm_step_x0_c4_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, x, out, out_stride, noise, scalars_dev,
+                           flags, (long long)M, pred_x0_out, (bf16_t *)unet_in, unet_in_stride);
+    else
+        hipLaunchKernelGGL(ddpm_step_x0_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, x, out, out_stride, noise, scalars_dev, flags,
+                           (long long)M, C, pred_x0_out, (bf16_t *)unet_in, unet_in_stride);
+    GG_CHECK_LAUNCH();
+    return GG_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------
 // Inpainting blend (ddim.py:144-148, plms.py:147-150, ddpm.py:1212-1214), fp32, the reference's operation order:
 //   o = s[0]*x0 + s[1]*noise  (q_sample, ddpm.py:275-278) ;  x <- o*mask + (1 - mask)*x
 // scalars device fp32[2] = {sqrt_alphas_cumprod[t], sqrt_one_minus_alphas_cumprod[t]}; mask has 1 or C channels.
@@ -629,6 +722,21 @@ extern "C" int gg_cl_to_nchw_f32(const void *src, int32_t src_dtype, int32_t N, 
                            (long long)S, C_pad, dst);
     else
         GG_FAIL(GG_ERR_BAD_DTYPE, "cl_to_nchw: dtype");
+    GG_CHECK_LAUNCH();
+    return GG_OK;
+}
+
+// Sampler log entry: the fp32 channels-last state [N * S, C] into one [N, C, S] slot of a caller-owned log buffer.  This is
+// cl_to_nchw_kernel<float> on dense rows (C_pad == C), which already writes into a given destination: no second transpose kernel.
+extern "C" int gg_log_rows(const float *state, int32_t N, int32_t C, int64_t S, float *slot, void *stream_)
+{
+    if (!state || !slot) GG_FAIL(GG_ERR_BAD_SHAPE, "log_rows: null pointer");
+    if (N < 0 || C <= 0 || S < 0) GG_FAIL(GG_ERR_BAD_SHAPE, "log_rows: N=%d C=%d S=%lld", N, C, (long long)S);
+    long long total = (long long)N * C * S;
+    if (total <= 0) return GG_OK;
+    long long blocks = (total + 255) / 256;
+    if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(cl_to_nchw_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, state, N, C, (long long)S, C, slot);
     GG_CHECK_LAUNCH();
     return GG_OK;
 }

@@ -445,9 +445,29 @@ class IdentityEncoder(nn.Module):
 
 # ================================================================================================ diffusion wrapper
 def make_beta_schedule(schedule, n_timestep, linear_start=1e-4, linear_end=2e-2, cosine_s=8e-3):
-    if schedule != "linear":
-        raise NotImplementedError("only the 'linear' schedule is used by the shipped configs")
-    return (torch.linspace(linear_start ** 0.5, linear_end ** 0.5, n_timestep, dtype=torch.float64, device="cpu") ** 2).numpy()
+    """fp64 betas of the reference's four schedules (ldm/modules/diffusionmodules/util.py:21-43); anything else is its ValueError."""
+    lin = lambda a, b: torch.linspace(a, b, n_timestep, dtype=torch.float64, device="cpu")
+    if schedule == "linear":
+        return (lin(linear_start ** 0.5, linear_end ** 0.5) ** 2).numpy()
+    if schedule == "cosine":
+        timesteps = torch.arange(n_timestep + 1, dtype=torch.float64, device="cpu") / n_timestep + cosine_s
+        alphas = torch.cos(timesteps / (1 + cosine_s) * np.pi / 2).pow(2)
+        alphas = alphas / alphas[0]
+        return np.clip((1 - alphas[1:] / alphas[:-1]).numpy(), 0, 0.999)
+    if schedule == "sqrt_linear":
+        return lin(linear_start, linear_end).numpy()
+    if schedule == "sqrt":
+        return (lin(linear_start, linear_end) ** 0.5).numpy()
+    raise ValueError(f"schedule '{schedule}' unknown.")
+
+
+def logged_steps(n: int, log_every_t: int) -> List[int]:
+    """The loop values at which the reference's samplers append to their intermediates, in loop order (n - 1 down to 0): the timestep i
+    of p_sample_loop / progressive_denoising (ddpm.py:1172,1220), the index of DDIM / PLMS (ddim.py:160, plms.py:166)."""
+    k = int(log_every_t)
+    if k < 1:
+        raise ValueError(f"log_every_t = {log_every_t} must be a positive integer")
+    return [i for i in range(n - 1, -1, -1) if i % k == 0 or i == n - 1]
 
 
 class LitEma(nn.Module):
@@ -642,50 +662,22 @@ class DiffusionWrapper(nn.Module):
         raise NotImplementedError(ck)
 
 
-class LatentDiffusion(nn.Module):
-    """Sampling-only LatentDiffusion: schedule buffers + UNet + first/cond stage (ddpm.py:40-170,429-571)."""
+class GaussianDiffusion(nn.Module):
+    """What DDPM and LatentDiffusion share on the sampling side (the reference's base class, ddpm.py:44-278): the schedule buffers,
+    checkpoint and EMA handling, q_sample, and the ancestral loop on the channels-last engine."""
 
-    def __init__(self, first_stage_config, cond_stage_config, unet_config, num_timesteps_cond=None, cond_stage_key="image",
-                 cond_stage_trainable=False, concat_mode=True, cond_stage_forward=None, conditioning_key=None, scale_factor=1.0,
-                 scale_by_std=False, dims=3, timesteps=1000, beta_schedule="linear", linear_start=1e-4, linear_end=2e-2,
-                 cosine_s=8e-3, use_ema=True, first_stage_key="image", image_size=256, channels=3, parameterization="eps",
-                 v_posterior=0.0, ckpt_path=None, ignore_keys=[], **unused):
-        super().__init__()
-        assert parameterization == "eps"
-        self.parameterization = parameterization
-        self.no_first_stage = first_stage_config == "__is_no_first_stage__"
-        if conditioning_key is None:
-            conditioning_key = "concat" if concat_mode else "crossattn"
-        if cond_stage_config == "__is_unconditional__":
-            conditioning_key = None
-        self.image_size, self.channels, self.dims = image_size, channels, dims
-        self.first_stage_key, self.cond_stage_key = first_stage_key, cond_stage_key
-        self.cond_stage_forward = cond_stage_forward
-        self.v_posterior = v_posterior
-        self.model = DiffusionWrapper(unet_config, conditioning_key)
-        self.use_ema = use_ema
-        if use_ema:
-            self.model_ema = LitEma(self.model)
-        self.scale_by_std = scale_by_std
-        if not scale_by_std:
-            self.scale_factor = scale_factor
+    parameterization = "eps"
+    clip_denoised = False
+    log_every_t = 100
+    num_timesteps_cond = 1
+
+    def register_schedule(self, given_betas=None, beta_schedule="linear", timesteps=1000, linear_start=1e-4, linear_end=2e-2, cosine_s=8e-3):
+        """fp64 numpy schedule stored as 13 fp32 buffers with the reference's names (ddpm.py:118-170); `given_betas` (an array of
+        betas) takes the place of the named schedule, as there."""
+        if given_betas is not None:
+            betas = np.asarray(given_betas.detach().cpu().numpy() if isinstance(given_betas, torch.Tensor) else given_betas, dtype=np.float64)
         else:
-            self.register_buffer("scale_factor", torch.tensor(scale_factor))
-        self.register_schedule(beta_schedule, timesteps, linear_start, linear_end, cosine_s)
-        self.register_buffer("logvar", torch.full(fill_value=0.0, size=(self.num_timesteps,)))
-        if not self.no_first_stage:
-            self.first_stage_model = instantiate_from_config(first_stage_config).eval()
-        self.cond_stage_model = None
-        if cond_stage_config == "__is_first_stage__":
-            self.cond_stage_model = self.first_stage_model
-        elif cond_stage_config != "__is_unconditional__":
-            self.cond_stage_model = instantiate_from_config(cond_stage_config).eval()
-        if ckpt_path is not None:
-            self.init_from_ckpt(ckpt_path, ignore_keys)
-
-    def register_schedule(self, beta_schedule, timesteps, linear_start, linear_end, cosine_s):
-        """fp64 numpy schedule stored as 13 fp32 buffers with the reference's names (ddpm.py:118-170)."""
-        betas = make_beta_schedule(beta_schedule, timesteps, linear_start, linear_end, cosine_s)
+            betas = make_beta_schedule(beta_schedule, timesteps, linear_start, linear_end, cosine_s)
         alphas = 1.0 - betas
         ac = np.cumprod(alphas, axis=0)
         acp = np.append(1.0, ac[:-1])
@@ -728,6 +720,172 @@ class LatentDiffusion(nn.Module):
         finally:
             if self.use_ema:
                 self.model_ema.restore(self.model.parameters())
+
+    def q_sample(self, x_start, t, noise=None):
+        noise = torch.randn_like(x_start) if noise is None else noise
+        sh = (-1,) + (1,) * (x_start.ndim - 1)
+        return self.sqrt_alphas_cumprod[t].reshape(sh) * x_start + self.sqrt_one_minus_alphas_cumprod[t].reshape(sh) * noise
+
+    def _refuse_cond_schedule(self, who) -> None:
+        if int(self.num_timesteps_cond or 1) > 1:
+            raise NotImplementedError(f"{who}: num_timesteps_cond = {self.num_timesteps_cond} > 1 (shorten_cond_schedule: the conditioning is "
+                                      "noised by a cumulative q_sample at every step, ddpm.py:1157-1160,1208-1211) is not supported")
+
+    def _ancestral_loop(self, who, cond, shape, *, x_T=None, T=None, quantize_denoised=False, mask=None, x0=None, noise_tape=None,
+                        mask_noise_tape=None, log_every_t=None, log_x0=False, callback=None, img_callback=None, temperature=1.0,
+                        noise_dropout=0.0):
+        """The ancestral chain over timesteps T - 1 .. 0, channels-last on the GPU: per step one UNet forward and one fused step kernel
+        (`gg_ddpm_step`; `gg_ddpm_step_x0` when the model predicts x_0, clip_denoised is set or the prediction of x_0 is logged;
+        `gg_ddim_step_vq` in its ancestral form under quantize_denoised -- with an x0 model or clip_denoised, which that kernel does not
+        know, `gg_ddpm_step_x0` for x_recon, `gg_vq_nearest`, and `gg_ddpm_step_x0` again for the posterior mean), then the inpainting blend.  log_every_t (an integer): the
+        state -- with log_x0 the step's prediction of x_0, after clip and quantisation -- is copied by `gg_log_rows` into a pre-allocated
+        buffer at the timesteps `logged_steps` names.  temperature (a number, or a sequence indexed by the timestep) and noise_dropout act
+        on the step's noise on the host side, in the reference's order (ddpm.py:1109-1111), and only when one of them is set.
+        Returns (img [N, C, *sp], x_T as used, the list of logged tensors)."""
+        px0, clip = self.parameterization == "x0", bool(self.clip_denoised)
+        codebook = first_stage_codebook(self, f"{who}: quantize_denoised", shape[1]) if quantize_denoised else None
+        self._refuse_cond_schedule(who)
+        if hasattr(self, "split_input_params"):                      # refusals of the patch-wise path, before any launch
+            self.split_check_cond(cond)
+            self.get_fold_unfold(tuple(shape), self.split_input_params["ks"], self.split_input_params["stride"])
+        if not 0.0 <= float(noise_dropout) < 1.0:
+            raise ValueError(f"{who}: noise_dropout = {noise_dropout} outside [0, 1)")
+        dev = self.device
+        unet = self.model.diffusion_model
+        ck = self.model.conditioning_key
+        N, Cx = shape[0], shape[1]
+        sp = tuple(shape[2:])
+        sp3 = (1,) * (3 - len(sp)) + sp
+        nd = len(sp)
+        if mask is not None and x0 is not None and tuple(x0.shape[2:3]) != tuple(mask.shape[2:3]):
+            raise ValueError(f"{who}: x0 {tuple(x0.shape)} and mask {tuple(mask.shape)} differ in spatial size "
+                             "(ddpm.py:1200 asserts x0.shape[2:3] == mask.shape[2:3])")
+        ip = inpaint_operands(mask, x0, shape, mask_noise_tape, T)
+        logged = logged_steps(T, log_every_t) if (log_every_t is not None and T > 0) else []
+        per_step_temp = None
+        if isinstance(temperature, (list, tuple)) or (isinstance(temperature, (torch.Tensor, np.ndarray)) and temperature.ndim > 0):
+            if len(temperature) < T:
+                raise ValueError(f"{who}: temperature holds {len(temperature)} values, the chain has {T} timesteps (it is indexed by the timestep)")
+            per_step_temp = [float(v) for v in temperature]
+        elif float(temperature) != 1.0:
+            per_step_temp = [float(temperature)] * T
+        c_concat = cond if (cond is not None and ck == "concat" and not isinstance(cond, dict)) else \
+            (cond.get("c_concat", [None])[0] if isinstance(cond, dict) else None)
+        context = cond if (cond is not None and ck == "crossattn" and not isinstance(cond, dict)) else None
+        if isinstance(cond, dict) and cond.get("c_crossattn"):        # hybrid / explicit dicts: the reference's apply_model passes them through
+            context = torch.cat(cond["c_crossattn"], 1)
+        Cc = c_concat.shape[1] if c_concat is not None else 0
+        perm = (0,) + tuple(range(2, nd + 2)) + (1,)
+        back = (0, nd + 1) + tuple(range(1, nd + 1))
+        img = torch.randn(tuple(shape), device=dev) if x_T is None else x_T.to(dev).float()
+        x = img.permute(perm).contiguous().view((N,) + sp3 + (Cx,))
+        unet_in = torch.zeros((N,) + sp3 + (pad32(Cx + Cc),), dtype=torch.bfloat16, device=dev)
+        ops.to_cl(img, out=unet_in, c_offset=0, zero_fill=False)
+        if c_concat is not None:
+            ops.to_cl(c_concat.float(), out=unet_in, c_offset=Cx, zero_fill=False)
+        ctx_cl = unet.context_cl(context) if context is not None else None
+        ts = torch.arange(T - 1, -1, -1, device=dev)
+        split = None
+        if hasattr(self, "split_input_params"):                      # patch-wise eps (ddpm.py:915-997): crops of x, one UNet forward, fold
+            split = SplitUNet(self, N, Cx, Cc, sp, dev)
+            split.bind(unet_in, ctx_cl)
+        table = unet.time_bias_table(ts.float(), N) if split is None else split.time_bias_table(unet, ts.float())
+        sig = torch.exp(0.5 * self.posterior_log_variance_clipped[ts]) * (ts > 0).float()
+        scal = torch.stack([self.sqrt_recip_alphas_cumprod[ts], self.sqrt_recipm1_alphas_cumprod[ts], self.posterior_mean_coef1[ts],
+                            self.posterior_mean_coef2[ts], sig], 1).float().contiguous()
+        eps = torch.empty((N,) + sp3 + (pad32(unet.out_channels),), dtype=torch.float32, device=dev)
+        M = x.numel() // Cx
+        want_x0 = bool(log_x0 and logged)
+        vq_split = codebook is not None and (px0 or clip)        # gg_ddim_step_vq quantises the unclipped eps prediction: three launches instead
+        p0 = torch.empty_like(x) if (want_x0 or vq_split) else None
+        x_keep = torch.empty_like(x) if vq_split else None
+        log = torch.empty((len(logged), N, Cx) + sp, dtype=torch.float32, device=dev) if logged else None      # the pre-allocated log buffer
+        slot = {t: j for j, t in enumerate(logged)}
+        if ip is not None:
+            x0_cl = ip[0].to(dev).permute(perm).contiguous()
+            mask_cl = ip[1].to(dev).permute(perm).contiguous()
+            qscal = torch.stack([self.sqrt_alphas_cumprod[ts], self.sqrt_one_minus_alphas_cumprod[ts]], 1).contiguous()
+        for i in range(T):
+            t = T - 1 - i
+            unet_eps(unet, split, x, unet_in, Cx + Cc, table[i], ctx_cl, eps)
+            nz = noise_tape[i].to(dev).float() if noise_tape is not None else torch.randn_like(x)
+            if per_step_temp is not None:                # host-side ops on the noise as given (the tape's [N, C, *sp] tensor, or the draw)
+                nz = nz * per_step_temp[t]
+            if noise_dropout > 0.0:
+                nz = torch.nn.functional.dropout(nz, p=float(noise_dropout))
+            if noise_tape is not None:
+                nz = nz.permute(perm).contiguous()
+            if vq_split:
+                # x_recon (x0 / clip) on a scratch copy of x -> quantised in place -> the posterior mean and noise with x_recon given
+                x_keep.copy_(x)
+                ops.ddpm_step_x0(x_keep.view(M, Cx), eps.view(M, -1), scal[i], predicts_x0=px0, clip=clip, pred_x0_out=p0.view(M, Cx))
+                ops.vq_nearest(p0.view(M, Cx), codebook, Cx, st_out=p0.view(M, Cx))
+                ops.ddpm_step_x0(x.view(M, Cx), p0.view(M, Cx), scal[i], noise=nz.view(M, Cx), predicts_x0=True, unet_in=unet_in.view(M, -1))
+            elif codebook is not None:
+                ops.ddim_step_vq(x.view(M, Cx), eps.view(M, -1), scal[i], codebook, noise=nz.view(M, Cx),
+                                 pred_x0_out=p0.view(M, Cx) if want_x0 else None, unet_in=unet_in.view(M, -1), ancestral=True)
+            elif px0 or clip or want_x0:
+                ops.ddpm_step_x0(x.view(M, Cx), eps.view(M, -1), scal[i], noise=nz.view(M, Cx), predicts_x0=px0, clip=clip,
+                                 pred_x0_out=p0.view(M, Cx) if want_x0 else None, unet_in=unet_in.view(M, -1))
+            else:
+                ops.ddpm_step(x.view(M, Cx), eps.view(M, -1), scal[i], noise=nz.view(M, Cx), unet_in=unet_in.view(M, -1))
+            if ip is not None:
+                nm = mask_noise_tape[i].to(dev).float().permute(perm).contiguous() if mask_noise_tape is not None else torch.randn_like(x)
+                ops.inpaint_blend(x.view(M, Cx), x0_cl.view(M, Cx), mask_cl.view(M, -1), nm.view(M, Cx), qscal[i], unet_in=unet_in.view(M, -1))
+            if t in slot:
+                ops.log_rows((p0 if log_x0 else x).view(M, Cx), N, log[slot[t]])
+            if callback:
+                callback(t)
+            if img_callback:
+                img_callback(x.view((N,) + sp + (Cx,)).permute(back).contiguous(), t)
+        out = x.view((N,) + sp + (Cx,)).permute(back).contiguous()
+        return out, img, (list(log.unbind(0)) if logged else [])
+
+
+class LatentDiffusion(GaussianDiffusion):
+    """Sampling-only LatentDiffusion: schedule buffers + UNet + first/cond stage (ddpm.py:40-170,429-571)."""
+
+    def __init__(self, first_stage_config, cond_stage_config, unet_config, num_timesteps_cond=None, cond_stage_key="image",
+                 cond_stage_trainable=False, concat_mode=True, cond_stage_forward=None, conditioning_key=None, scale_factor=1.0,
+                 scale_by_std=False, dims=3, timesteps=1000, beta_schedule="linear", linear_start=1e-4, linear_end=2e-2,
+                 cosine_s=8e-3, use_ema=True, first_stage_key="image", image_size=256, channels=3, parameterization="eps",
+                 v_posterior=0.0, ckpt_path=None, ignore_keys=[], given_betas=None, log_every_t=100, **unused):
+        super().__init__()
+        if parameterization not in ("eps", "x0"):
+            raise ValueError(f"LatentDiffusion: parameterization '{parameterization}' is not supported ('eps' or 'x0', ddpm.py:76)")
+        self.parameterization = parameterization
+        self.log_every_t = log_every_t
+        self.clip_denoised = False                      # ddpm.py:471
+        self.num_timesteps_cond = 1 if num_timesteps_cond is None else num_timesteps_cond
+        self.no_first_stage = first_stage_config == "__is_no_first_stage__"
+        if conditioning_key is None:
+            conditioning_key = "concat" if concat_mode else "crossattn"
+        if cond_stage_config == "__is_unconditional__":
+            conditioning_key = None
+        self.image_size, self.channels, self.dims = image_size, channels, dims
+        self.first_stage_key, self.cond_stage_key = first_stage_key, cond_stage_key
+        self.cond_stage_forward = cond_stage_forward
+        self.v_posterior = v_posterior
+        self.model = DiffusionWrapper(unet_config, conditioning_key)
+        self.use_ema = use_ema
+        if use_ema:
+            self.model_ema = LitEma(self.model)
+        self.scale_by_std = scale_by_std
+        if not scale_by_std:
+            self.scale_factor = scale_factor
+        else:
+            self.register_buffer("scale_factor", torch.tensor(scale_factor))
+        self.register_schedule(given_betas, beta_schedule, timesteps, linear_start, linear_end, cosine_s)
+        self.register_buffer("logvar", torch.full(fill_value=0.0, size=(self.num_timesteps,)))
+        if not self.no_first_stage:
+            self.first_stage_model = instantiate_from_config(first_stage_config).eval()
+        self.cond_stage_model = None
+        if cond_stage_config == "__is_first_stage__":
+            self.cond_stage_model = self.first_stage_model
+        elif cond_stage_config != "__is_unconditional__":
+            self.cond_stage_model = instantiate_from_config(cond_stage_config).eval()
+        if ckpt_path is not None:
+            self.init_from_ckpt(ckpt_path, ignore_keys)
 
     # ---- reference methods (NCHW fp32 tensors)
     def get_learned_conditioning(self, c):
@@ -971,70 +1129,77 @@ class LatentDiffusion(nn.Module):
         draws a fresh device `randn`, which matches the reference's `randn_like` in distribution, not in stream (that stream is CPU
         torch's).  `noise_tape` / `mask_noise_tape` exist so that tests can feed the reference's draws.
         quantize_denoised (ddpm.py:1081-1082): x_recon goes through the first stage's quantiser before the posterior mean; the step is
-        then one `gg_ddim_step_vq` (ancestral form) in place of `gg_ddpm_step`."""
-        codebook = first_stage_codebook(self, "p_sample_loop: quantize_denoised", shape[1]) if quantize_denoised else None
-        if hasattr(self, "split_input_params"):                      # refusals of the patch-wise path, before any launch
-            self.split_check_cond(cond)
-            self.get_fold_unfold(tuple(shape), self.split_input_params["ks"], self.split_input_params["stride"])
-        dev = self.device
-        unet = self.model.diffusion_model
-        ck = self.model.conditioning_key
-        N, Cx = shape[0], shape[1]
-        sp = tuple(shape[2:])
-        sp3 = (1,) * (3 - len(sp)) + sp
-        nd = len(sp)
+        then one `gg_ddim_step_vq` (ancestral form) in place of `gg_ddpm_step`.
+        The model's `parameterization` ("x0": the UNet's output is the prediction of x_0) and `clip_denoised` (False for LatentDiffusion,
+        ddpm.py:471; an attribute, as there) select `gg_ddpm_step_x0`; otherwise the launches are the ones above.
+        log_every_t: an integer gives the reference's list -- [x_T], then x after the step (and blend) at every timestep i with
+        i % log_every_t == 0 or i == timesteps - 1, copied by `gg_log_rows` into a pre-allocated buffer.  None keeps [x_T, out]: the
+        reference falls back to self.log_every_t there (ddpm.py:1184-1185); this package's callers index [1] as the last entry, so the
+        two-entry default stays.  callback(i) and img_callback(img, i) are called after each step as in the reference (ddpm.py:1222-1223),
+        img an [N, C, *sp] tensor that is formed only when img_callback is given.  num_timesteps_cond > 1 is refused."""
         T = self.num_timesteps if timesteps is None else timesteps
         if start_T is not None:
             T = min(T, start_T)
-        if mask is not None and x0 is not None and tuple(x0.shape[2:3]) != tuple(mask.shape[2:3]):
-            raise ValueError(f"p_sample_loop: x0 {tuple(x0.shape)} and mask {tuple(mask.shape)} differ in spatial size "
-                             "(ddpm.py:1200 asserts x0.shape[2:3] == mask.shape[2:3])")
-        ip = inpaint_operands(mask, x0, shape, mask_noise_tape, T)
-        c_concat = cond if (cond is not None and ck == "concat" and not isinstance(cond, dict)) else \
-            (cond.get("c_concat", [None])[0] if isinstance(cond, dict) else None)
-        context = cond if (cond is not None and ck == "crossattn" and not isinstance(cond, dict)) else None
-        if isinstance(cond, dict) and cond.get("c_crossattn"):        # hybrid / explicit dicts: the reference's apply_model passes them through
-            context = torch.cat(cond["c_crossattn"], 1)
-        Cc = c_concat.shape[1] if c_concat is not None else 0
-        perm = (0,) + tuple(range(2, nd + 2)) + (1,)
-        img = torch.randn(tuple(shape), device=dev) if x_T is None else x_T.to(dev).float()
-        x = img.permute(perm).contiguous().view((N,) + sp3 + (Cx,))
-        unet_in = torch.zeros((N,) + sp3 + (pad32(Cx + Cc),), dtype=torch.bfloat16, device=dev)
-        ops.to_cl(img, out=unet_in, c_offset=0, zero_fill=False)
-        if c_concat is not None:
-            ops.to_cl(c_concat.float(), out=unet_in, c_offset=Cx, zero_fill=False)
-        ctx_cl = unet.context_cl(context) if context is not None else None
-        ts = torch.arange(T - 1, -1, -1, device=dev)
-        split = None
-        if hasattr(self, "split_input_params"):                      # patch-wise eps (ddpm.py:915-997): crops of x, one UNet forward, fold
-            split = SplitUNet(self, N, Cx, Cc, sp, dev)
-            split.bind(unet_in, ctx_cl)
-        table = unet.time_bias_table(ts.float(), N) if split is None else split.time_bias_table(unet, ts.float())
-        sig = torch.exp(0.5 * self.posterior_log_variance_clipped[ts]) * (ts > 0).float()
-        scal = torch.stack([self.sqrt_recip_alphas_cumprod[ts], self.sqrt_recipm1_alphas_cumprod[ts], self.posterior_mean_coef1[ts],
-                            self.posterior_mean_coef2[ts], sig], 1).float().contiguous()
-        eps = torch.empty((N,) + sp3 + (pad32(unet.out_channels),), dtype=torch.float32, device=dev)
-        M = x.numel() // Cx
-        if ip is not None:
-            x0_cl = ip[0].to(dev).permute(perm).contiguous()
-            mask_cl = ip[1].to(dev).permute(perm).contiguous()
-            qscal = torch.stack([self.sqrt_alphas_cumprod[ts], self.sqrt_one_minus_alphas_cumprod[ts]], 1).contiguous()
-        for i in range(T):
-            unet_eps(unet, split, x, unet_in, Cx + Cc, table[i], ctx_cl, eps)
-            if noise_tape is not None:
-                nz = noise_tape[i].to(dev).float().permute(perm).contiguous()
+        out, img, log = self._ancestral_loop("p_sample_loop", cond, shape, x_T=x_T, T=T, quantize_denoised=quantize_denoised, mask=mask, x0=x0,
+                                             noise_tape=noise_tape, mask_noise_tape=mask_noise_tape, log_every_t=log_every_t,
+                                             callback=callback, img_callback=img_callback)
+        if not return_intermediates:
+            return out
+        return out, ([img, out] if log_every_t is None else [img] + log)
+
+    @torch.no_grad()
+    def progressive_denoising(self, cond, shape, verbose=True, callback=None, quantize_denoised=False, img_callback=None, mask=None, x0=None,
+                              temperature=1.0, noise_dropout=0.0, score_corrector=None, corrector_kwargs=None, batch_size=None, x_T=None,
+                              start_T=None, log_every_t=None, noise_tape=None, mask_noise_tape=None):
+        """Ancestral sampling that records each logged step's prediction of x_0 (ddpm.py:1123-1176): returns (img, intermediates),
+        intermediates holding x_recon -- after clip_denoised and quantize_denoised -- at the timesteps i with i % log_every_t == 0 or
+        i == timesteps - 1, with no leading entry; log_every_t falls back to self.log_every_t.  batch_size: `shape` is then the per-sample
+        shape and the conditioning is cut to the batch, as in the reference.  temperature: a float, an int (the reference indexes an int
+        and fails), or a sequence indexed by the timestep value; noise is drawn, multiplied by the temperature, dropped out, then scaled
+        by sigma (ddpm.py:1109-1120).  The inpainting blend follows the step, as in p_sample_loop.  `noise_tape` / `mask_noise_tape` are
+        this package's additions, as there.  Runs on the GPU only; score_corrector and num_timesteps_cond > 1 are refused."""
+        if score_corrector is not None:
+            raise NotImplementedError("progressive_denoising: score_corrector not supported (a user callback inside the step)")
+        self._refuse_cond_schedule("progressive_denoising")
+        if self.device.type != "cuda":
+            raise NotImplementedError(f"progressive_denoising: not supported for a model on {self.device} (the step kernels are the GPU's; "
+                                      "there is no CPU path)")
+        if not log_every_t:
+            log_every_t = self.log_every_t
+        T = self.num_timesteps
+        if batch_size is not None:
+            shape = [batch_size] + list(shape)
+        else:
+            batch_size = shape[0]
+        if cond is not None:
+            if isinstance(cond, dict):
+                cond = {key: cond[key][:batch_size] if not isinstance(cond[key], list) else [c[:batch_size] for c in cond[key]] for key in cond}
             else:
-                nz = torch.randn_like(x)
-            if codebook is not None:
-                ops.ddim_step_vq(x.view(M, Cx), eps.view(M, -1), scal[i], codebook, noise=nz.view(M, Cx), unet_in=unet_in.view(M, -1),
-                                 ancestral=True)
-            else:
-                ops.ddpm_step(x.view(M, Cx), eps.view(M, -1), scal[i], noise=nz.view(M, Cx), unet_in=unet_in.view(M, -1))
-            if ip is not None:
-                nm = mask_noise_tape[i].to(dev).float().permute(perm).contiguous() if mask_noise_tape is not None else torch.randn_like(x)
-                ops.inpaint_blend(x.view(M, Cx), x0_cl.view(M, Cx), mask_cl.view(M, -1), nm.view(M, Cx), qscal[i], unet_in=unet_in.view(M, -1))
-        out = x.view((N,) + sp + (Cx,)).permute((0, nd + 1) + tuple(range(1, nd + 1))).contiguous()
-        return (out, [img, out]) if return_intermediates else out
+                cond = [c[:batch_size] for c in cond] if isinstance(cond, list) else cond[:batch_size]
+        if start_T is not None:
+            T = min(T, start_T)
+        out, _, log = self._ancestral_loop("progressive_denoising", cond, tuple(shape), x_T=x_T, T=T, quantize_denoised=quantize_denoised,
+                                           mask=mask, x0=x0, noise_tape=noise_tape, mask_noise_tape=mask_noise_tape, log_every_t=log_every_t,
+                                           log_x0=True, callback=callback, img_callback=img_callback, temperature=temperature,
+                                           noise_dropout=noise_dropout)
+        return out, log
+
+    @torch.no_grad()
+    def denoise_row(self, samples, force_no_decoder_quantization=False, value_range=None):
+        """The reference's _get_denoise_row_from_list (ddpm.py:539-549): every entry of `samples` ([b, C, *sp] latents) is decoded, the
+        pictures are ordered (b n) -- one row per sample, one column per logged step -- and tiled by render.make_grid(nrow=len(samples))
+        into a uint8 [Hg, Wg, 3] picture on the device.  By default the decoded values are tiled as they are, as in the
+        reference.  `value_range` is this package's addition for callers that write the picture: render.make_grid tiles values that are
+        already 0..255, so with value_range = (lo, hi) (the first stage's (-1, 1)) the decoded pictures are first mapped to [0, 255], which
+        the reference leaves to its image logger."""
+        from .render import make_grid
+        row = torch.stack([self.decode_first_stage(zd.to(self.device), force_not_quantize=force_no_decoder_quantization) for zd in samples])
+        n, b = row.shape[:2]
+        grid = row.transpose(0, 1).reshape((b * n,) + tuple(row.shape[2:])).float()     # 'n b c h w -> (b n) c h w'
+        if value_range is not None:
+            lo, hi = (float(v) for v in value_range)
+            grid = torch.clamp((grid - lo) / (hi - lo), 0.0, 1.0) * 255.0
+        return make_grid(grid.contiguous(), nrow=n)
 
     @torch.no_grad()
     def sample(self, cond, batch_size=16, return_intermediates=False, x_T=None, verbose=True, timesteps=None, quantize_denoised=False,
@@ -1061,10 +1226,58 @@ class LatentDiffusion(nn.Module):
             return sampler.sample(ddim_steps, batch_size, shape, cond, verbose=False, **kwargs)
         return self.sample(cond=cond, batch_size=batch_size, return_intermediates=True, **kwargs)
 
-    def q_sample(self, x_start, t, noise=None):
-        noise = torch.randn_like(x_start) if noise is None else noise
-        sh = (-1,) + (1,) * (x_start.ndim - 1)
-        return self.sqrt_alphas_cumprod[t].reshape(sh) * x_start + self.sqrt_one_minus_alphas_cumprod[t].reshape(sh) * noise
+
+class DDPM(GaussianDiffusion):
+    """Sampling side of the reference's base class (ldm.models.diffusion.ddpm.DDPM, ddpm.py:44-278): the pixel-space, unconditional model
+    with clip_denoised=True.  The constructor takes the reference's arguments; those that serve training only (loss_type, monitor,
+    original_elbo_weight, l_simple_weight, scheduler_config, learn_logvar, use_positional_encodings) are accepted and unused.
+    state_dict: model.diffusion_model.*, model_ema.*, the 12 schedule buffers and logvar."""
+
+    def __init__(self, unet_config, timesteps=1000, beta_schedule="linear", loss_type="l2", ckpt_path=None, ignore_keys=[],
+                 load_only_unet=False, monitor="val/loss", use_ema=True, first_stage_key="image", image_size=256, channels=3,
+                 log_every_t=100, clip_denoised=True, linear_start=1e-4, linear_end=2e-2, cosine_s=8e-3, given_betas=None,
+                 original_elbo_weight=0.0, v_posterior=0.0, l_simple_weight=1.0, conditioning_key=None, parameterization="eps",
+                 scheduler_config=None, use_positional_encodings=False, learn_logvar=False, logvar_init=0.0):
+        super().__init__()
+        if parameterization not in ("eps", "x0"):
+            raise ValueError(f"DDPM: parameterization '{parameterization}' is not supported ('eps' or 'x0', ddpm.py:76)")
+        self.parameterization = parameterization
+        self.cond_stage_model = None
+        self.clip_denoised = clip_denoised
+        self.log_every_t = log_every_t
+        self.first_stage_key = first_stage_key
+        self.image_size = image_size if isinstance(image_size, int) else tuple(image_size)
+        self.channels = channels
+        self.model = DiffusionWrapper(unet_config, conditioning_key)
+        self.use_ema = use_ema
+        if use_ema:
+            self.model_ema = LitEma(self.model)
+        self.v_posterior = v_posterior
+        if ckpt_path is not None:
+            self.init_from_ckpt(ckpt_path, ignore_keys=ignore_keys, only_model=load_only_unet)
+        self.register_schedule(given_betas, beta_schedule, timesteps, linear_start, linear_end, cosine_s)
+        self.register_buffer("logvar", torch.full(fill_value=float(logvar_init), size=(self.num_timesteps,)))
+
+    @torch.no_grad()
+    def p_sample_loop(self, shape, return_intermediates=False, x_T=None, noise_tape=None):
+        """ddpm.py:253-266 on the shared ancestral loop: every step is one `gg_ddpm_step_x0` (clip_denoised, parameterization).  The
+        intermediates are [x_T], then x after the step at every timestep i with i % self.log_every_t == 0 or i == num_timesteps - 1.
+        `x_T` and `noise_tape` are this package's additions (the reference draws both itself).  Runs on the GPU only."""
+        if self.model.conditioning_key is not None:
+            raise NotImplementedError(f"DDPM.p_sample_loop: conditioning_key '{self.model.conditioning_key}' is not supported (the reference's "
+                                      "DDPM calls its UNet without conditioning, ddpm.py:233)")
+        if self.device.type != "cuda":
+            raise NotImplementedError(f"DDPM.p_sample_loop: not supported for a model on {self.device} (the step kernels are the GPU's; "
+                                      "there is no CPU path)")
+        out, img, log = self._ancestral_loop("DDPM.p_sample_loop", None, tuple(shape), x_T=x_T, T=self.num_timesteps, noise_tape=noise_tape,
+                                             log_every_t=self.log_every_t if return_intermediates else None)
+        return (out, [img] + log) if return_intermediates else out
+
+    @torch.no_grad()
+    def sample(self, batch_size=16, return_intermediates=False, **kwargs):
+        """ddpm.py:268-273: `batch_size` square images of image_size; kwargs (x_T=, noise_tape=) go to p_sample_loop."""
+        size = self.image_size if isinstance(self.image_size, tuple) else (self.image_size, self.image_size)
+        return self.p_sample_loop((batch_size, self.channels) + tuple(size), return_intermediates=return_intermediates, **kwargs)
 
 
 def inpaint_operands(mask, x0, shape, tape=None, steps=0):
@@ -1169,7 +1382,7 @@ class DDIMSampler(object):
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
                quantize_x0=False, eta=0.0, mask=None, x0=None, temperature=1.0, noise_dropout=0.0, score_corrector=None,
-               corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.0,
+               corrector_kwargs=None, verbose=True, x_T=None, log_every_t=None, unconditional_guidance_scale=1.0,
                unconditional_conditioning=None, noise_tape: Optional[Sequence[torch.Tensor]] = None, ddim_discretize="uniform",
                mask_noise_tape: Optional[Sequence[torch.Tensor]] = None, **kwargs):
         """`ddim_discretize` ("uniform" | "quad": make_schedule's argument, ddim.py:24) is this package's addition to the signature: the
@@ -1187,7 +1400,23 @@ class DDIMSampler(object):
         of the per-step scalar table (rewritten on each call, so temperatures share one state); dir_xt keeps sigma_t unscaled.  noise_dropout (ddim.py:202-203): torch.nn.functional.dropout(p)
         on each step's noise as it is loaded (the tape's tensor as given, or the device draw), outside any graph; it draws from the
         device's default generator.  With eta = 0 the noise term is zero whatever the two are.  A call with none of the three takes the
-        state, graph and launches it took before they existed."""
+        state, graph and launches it took before they existed.
+        log_every_t: None (the default here; the reference's is 100) returns the two-entry lists {"x_inter": [x_T, z], "pred_x0": [x_T,
+        pred_x0]}.  An integer gives the reference's lists (ddim.py:134,160-162, plms.py:166-168): both start with x_T, then hold an entry
+        for every step whose index = steps - 1 - i has index % log_every_t == 0 or index == steps - 1, steps being the schedule's own
+        count (ddim_timesteps.shape[0]: S + 1 for a uniform schedule whose S does not divide the DDPM timesteps); x_inter holds x after the step, pred_x0
+        that step's prediction (the quantised one under quantize_x0).  The entries are written by `gg_log_rows` into log buffers of the
+        chain's state, so the eta = 0 chain stays one captured graph with the copies inside; the logged indices are part of the state
+        key, and a call without log_every_t keeps the state and graph it had.
+        callback(i) and img_callback(pred_x0, i) are called after each step (ddim.py:157-158).  A chain with a callback runs eagerly: a
+        host call sits between its steps, so it cannot be one captured graph.
+        A model with parameterization "x0" is refused: the reference's DDIM / PLMS would read its output as eps."""
+        who = f"{type(self).__name__}.sample"
+        if getattr(self.model, "parameterization", "eps") != "eps":
+            raise NotImplementedError(f"{who}: parameterization '{self.model.parameterization}' is not supported (the DDIM / PLMS update "
+                                      "reads the model's output as eps, ddim.py:173-180; use p_sample_loop / progressive_denoising)")
+        if log_every_t is not None:
+            logged_steps(1, log_every_t)                    # a bad interval is refused here, before any launch
         if score_corrector is not None:
             raise NotImplementedError(f"{type(self).__name__}.sample: score_corrector not supported (a user callback inside the step)")
         if not 0.0 <= float(noise_dropout) < 1.0:
@@ -1211,13 +1440,19 @@ class DDIMSampler(object):
             self.model.get_fold_unfold(size, par["ks"], par["stride"])
         ip = inpaint_operands(mask, x0, size, mask_noise_tape, S)
         self.make_schedule(ddim_num_steps=S, ddim_discretize=ddim_discretize, ddim_eta=eta, verbose=False)
+        # the chain's own step count, as the reference's total_steps (ddim.py:136,160): the uniform schedule holds more than S steps
+        # when S does not divide the number of DDPM timesteps
+        logged = tuple(logged_steps(int(self.ddim_timesteps.shape[0]), log_every_t)) if log_every_t is not None else None
         dev = self.model.device
         img = torch.randn(size, device=dev) if x_T is None else x_T.to(dev).float()
         vq = None
         if codebook is not None or (float(temperature) != 1.0 and eta != 0.0):        # eta = 0: sigma_t = 0, the temperature has no effect
             vq = (codebook, float(temperature))
-        z, pred_x0 = self._sample_cl(img, conditioning, eta, noise_tape, cfg, ip, mask_noise_tape, vq=vq, noise_dropout=float(noise_dropout))
-        return z, {"x_inter": [img, z], "pred_x0": [img, pred_x0]}
+        z, pred_x0, logs = self._sample_cl(img, conditioning, eta, noise_tape, cfg, ip, mask_noise_tape, vq=vq, noise_dropout=float(noise_dropout),
+                                           logged=logged, callbacks=(callback, img_callback) if (callback or img_callback) else None)
+        if logs is None:
+            return z, {"x_inter": [img, z], "pred_x0": [img, pred_x0]}
+        return z, {"x_inter": [img] + logs[0], "pred_x0": [img] + logs[1]}
 
     # ---- channels-last fast path -------------------------------------------------------------------------
     def _split_cond(self, conditioning):
@@ -1235,7 +1470,7 @@ class DDIMSampler(object):
         return c_concat, context
 
     def _sample_cl(self, x_T: torch.Tensor, conditioning, eta: float, noise_tape, cfg=None, inpaint=None, mask_noise_tape=None, *, vq=None,
-                   noise_dropout=0.0):
+                   noise_dropout=0.0, logged=None, callbacks=None):
         model = self.model
         unet = model.model.diffusion_model
         ck = model.model.conditioning_key
@@ -1245,32 +1480,45 @@ class DDIMSampler(object):
         nd = len(sp)
         c_concat, context = self._split_cond(conditioning)
         st = self.prepare_state(N, Cx, sp, dev, c_concat.shape[1] if c_concat is not None else 0,
-                                ctx_shape=tuple(context.shape[1:]) if context is not None else None, mask_C=inpaint[2] if inpaint else 0, vq=vq)
+                                ctx_shape=tuple(context.shape[1:]) if context is not None else None, mask_C=inpaint[2] if inpaint else 0, vq=vq,
+                                logged=logged)
         self.load_state(st, x_T, c_concat, context)
         if inpaint is not None:
             self.load_inpaint(st, inpaint[0], inpaint[1], mask_noise_tape)
-        if cfg is not None:
-            self._run_steps_cfg(st, x_T, cfg, eta, noise_tape, noise_dropout)
-        else:
-            self.run_steps(st, st["ctx"], eta, noise_tape, noise_dropout)
+        st["callbacks"] = callbacks                      # host calls between the steps: such a chain runs eagerly (chain_graphable)
+        try:
+            if cfg is not None:
+                self._run_steps_cfg(st, x_T, cfg, eta, noise_tape, noise_dropout)
+            else:
+                self.run_steps(st, st["ctx"], eta, noise_tape, noise_dropout)
+        finally:
+            st["callbacks"] = None
         perm = (0, nd + 1) + tuple(range(1, nd + 1))
         z = st["x"].view((N,) + sp + (Cx,)).permute(perm).contiguous()
         p0 = st["pred_x0"].view((N,) + sp + (Cx,)).permute(perm).contiguous()
-        return z, p0
+        logs = None
+        if logged is not None:                           # copies: the state's log buffers are rewritten by the next logged call
+            logs = (list(st["log_x"].clone().unbind(0)), list(st["log_p0"].clone().unbind(0)))
+        return z, p0, logs
 
-    def prepare_state(self, N, Cx, sp, dev, Cc, ctx_shape=None, *, mask_C=0, vq=None):
+    def prepare_state(self, N, Cx, sp, dev, Cc, ctx_shape=None, *, mask_C=0, vq=None, logged=None):
         """Static buffers (and the captured graph) of one chain shape.  mask_C > 0: the inpainting state of a mask with mask_C channels --
         static fp32 CL buffers for x0 [M, Cx], the mask [M, mask_C] and the per-step q_sample noise [S, M, Cx], plus the [S, 2] q_sample
         scalar table; it lives under its own key, so a mask-free call never sees it.  vq = (codebook or None, temperature): the state of
         a chain whose update is `gg_ddim_step_vq` -- its scalar table has a fifth column sigma_t * temperature, refreshed here on every
         call (outside any graph: the steps read their rows in place), and "vq" holds the codebook the steps read in place; also under
-        its own key (quantised or not; the temperature is not part of it), with the codebook's identity in the token."""
+        its own key (quantised or not; the temperature is not part of it), with the codebook's identity in the token.
+        logged (a tuple of step indices, `logged_steps`): the state of a chain that records its intermediates -- "log" maps a sampling step
+        i to its slot, "log_x" / "log_p0" are the fp32 log buffers [L, N, Cx, *sp] that `gg_log_rows` fills in place; the tuple joins the
+        key, so an unlogged call never sees this state or its graph."""
         unet = self.model.model.diffusion_model
         sp3 = (1,) * (3 - len(sp)) + tuple(sp)
         S = self.ddim_timesteps.shape[0]
         key = (N, Cx, sp3, Cc, str(dev), ctx_shape) + ((("inpaint", mask_C),) if mask_C else ())
         if vq is not None:
             key = key + (("vq", vq[0] is not None),)
+        if logged is not None:
+            key = key + (("log", tuple(logged)),)
         par = getattr(self.model, "split_input_params", None)
         if par is not None:            # patch-wise eps: a state of its own (crop buffers, time-bias rows for L * N), keyed by the geometry
             key = key + (("split",) + tuple((k, str(par.get(k))) for k in ("ks", "stride", "tie_braker", "clip_min_weight", "clip_max_weight",
@@ -1287,7 +1535,7 @@ class DDIMSampler(object):
             return st
         steps = torch.tensor(np.flip(self.ddim_timesteps).copy(), dtype=torch.float32, device=dev)
         split = SplitUNet(self.model, N, Cx, Cc, sp, dev) if par is not None else None
-        st = dict(N=N, Cx=Cx, sp3=sp3, Cc=Cc, S=S, token=token,
+        st = dict(N=N, Cx=Cx, sp3=sp3, sp=tuple(sp), Cc=Cc, S=S, token=token, callbacks=None,
                   table=unet.time_bias_table(steps, N) if split is None else split.time_bias_table(unet, steps), scal=self.step_scalar_table().to(dev),
                   x=torch.empty((N,) + sp3 + (Cx,), dtype=torch.float32, device=dev),
                   pred_x0=torch.empty((N,) + sp3 + (Cx,), dtype=torch.float32, device=dev),
@@ -1304,6 +1552,10 @@ class DDIMSampler(object):
                       ip_scal=self.q_sample_scalar_table().to(dev))
         if split is not None:
             st["split"] = split
+        if logged is not None:
+            st.update(log={S - 1 - index: j for j, index in enumerate(logged)},
+                      log_x=torch.empty((len(logged), N, Cx) + tuple(sp), dtype=torch.float32, device=dev),
+                      log_p0=torch.empty((len(logged), N, Cx) + tuple(sp), dtype=torch.float32, device=dev))
         if vq is not None:
             sc = self.step_scalar_table().to(dev)
             st.update(vq=vq[0], scal=torch.cat([sc, sc[:, 2:3] * vq[1]], 1).contiguous())          # fp32 product sigma_t * temperature
@@ -1354,6 +1606,24 @@ class DDIMSampler(object):
         M = st["x"].numel() // Cx
         ops.inpaint_blend(st["x"].view(M, Cx), st["ip_x0"].view(M, Cx), st["ip_mask"].view(M, -1), st["ip_noise"][i].view(M, Cx),
                           st["ip_scal"][i], unet_in=st["unet_in"].view(M, -1))
+
+    def _after_step(self, st, i):
+        """What follows sampling step i's update: on a logging state the two `gg_log_rows` copies of x and pred_x0 into their slots
+        (launches like any other, so they are captured with the chain); with callbacks, callback(i) and img_callback(pred_x0, i)."""
+        j = st["log"].get(i) if "log" in st else None
+        Cx = st["Cx"]
+        M = st["x"].numel() // Cx
+        if j is not None:
+            ops.log_rows(st["x"].view(M, Cx), st["N"], st["log_x"][j])
+            ops.log_rows(st["pred_x0"].view(M, Cx), st["N"], st["log_p0"][j])
+        cb = st.get("callbacks")
+        if cb is not None:
+            if cb[0]:
+                cb[0](i)
+            if cb[1]:
+                p0 = torch.empty((st["N"], Cx) + tuple(d for d in st["sp"]), dtype=torch.float32, device=st["x"].device)
+                ops.log_rows(st["pred_x0"].view(M, Cx), st["N"], p0)
+                cb[1](p0, i)
 
     def _update(self, st, eps, scal, noise=None):
         """The DDIM update as its own launch on the state's buffers: gg_ddim_step, or gg_ddim_step_vq on a "vq" state (quantised pred_x0
@@ -1438,10 +1708,12 @@ class DDIMSampler(object):
             ops.lincomb4([eps_u, st["eps"]], [1.0 - scale, scale], 1.0, st["eps"])        # (1 - s) e_u + s e_c
             self._update(st, st["eps"], st["scal"][i], noise)
             uin_u[..., :Cx].copy_(st["unet_in"][..., :Cx])
+            self._after_step(st, i)
         self.last_step_fused = False
 
     def chain_graphable(self, st, ctx_cl=None, eta=0.0, noise_tape=None) -> bool:
-        return bool(self.use_graph and eta == 0.0 and noise_tape is None and (ctx_cl is None or ctx_cl is st["ctx"]) and st["S"] > 2)
+        return bool(self.use_graph and eta == 0.0 and noise_tape is None and (ctx_cl is None or ctx_cl is st["ctx"]) and st["S"] > 2
+                    and st.get("callbacks") is None)
 
     def chain(self, st, ctx_cl=None):
         """All S deterministic steps back to back, every step reading ITS rows of the time-bias / scalar tables in place: no
@@ -1449,6 +1721,7 @@ class DDIMSampler(object):
         for i in range(st["S"]):
             self._blend(st, i)
             self._step(st, ctx_cl, st["table"][i], st["scal"][i], None)
+            self._after_step(st, i)
 
     def run_steps(self, st, ctx_cl, eta, noise_tape, noise_dropout=0.0):
         S = st["S"]
@@ -1466,6 +1739,7 @@ class DDIMSampler(object):
             noise = self._noise(st, i, eta, noise_tape, noise_dropout)
             self._blend(st, i)
             self._step(st, ctx_cl, st["table"][i], st["scal"][i], noise)
+            self._after_step(st, i)
 
 
 class PLMSSampler(DDIMSampler):
@@ -1506,6 +1780,7 @@ class PLMSSampler(DDIMSampler):
             else:
                 ops.lincomb4([e_t, old[-1], old[-2], old[-3]], [55.0, -59.0, 37.0, -9.0], 24.0, e_prime)
             update(e_prime, st["scal"][i])
+            self._after_step(st, i)
             old.append(e_t)
             if len(old) >= 4:
                 old.pop(0)

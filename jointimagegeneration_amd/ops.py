@@ -1146,3 +1146,32 @@ def ddpm_step(x: torch.Tensor, eps: torch.Tensor, scalars: torch.Tensor, noise: 
     M = x.numel() // Cc
     check(lib.gg_ddpm_step(x.data_ptr(), eps.data_ptr(), eps.shape[-1], _ptr(noise), scalars.data_ptr(), M, Cc, _ptr(unet_in),
                            unet_in.shape[-1] if unet_in is not None else 0, _stream()), "gg_ddpm_step")
+
+
+DDPM_PREDICTS_X0, DDPM_CLIP = 1, 2        # gg_ddpm_step_x0 flag bits (include/guidegen_hip.h)
+
+
+def ddpm_step_x0(x: torch.Tensor, out: torch.Tensor, scalars: torch.Tensor, noise: Optional[torch.Tensor] = None, *, predicts_x0: bool = False,
+                 clip: bool = False, pred_x0_out: Optional[torch.Tensor] = None, unet_in: Optional[torch.Tensor] = None) -> None:
+    """Ancestral update with the reference's options, in place (gg_ddpm_step_x0): x fp32 CL [M, C], out fp32 CL [M, stride] (the UNet's
+    output: eps, or x_0 with predicts_x0), scalars fp32[5] on device as for ddpm_step; clip clamps the prediction of x_0 to [-1, 1];
+    pred_x0_out fp32 [M, C] receives it."""
+    lib = _lib.load()
+    Cc = x.shape[-1]
+    M = x.numel() // Cc
+    flags = (DDPM_PREDICTS_X0 if predicts_x0 else 0) | (DDPM_CLIP if clip else 0)
+    check(lib.gg_ddpm_step_x0(x.data_ptr(), out.data_ptr(), out.shape[-1], _ptr(noise), scalars.data_ptr(), flags, M, Cc, _ptr(pred_x0_out),
+                              _ptr(unet_in), unet_in.shape[-1] if unet_in is not None else 0, _stream()), "gg_ddpm_step_x0")
+
+
+def log_rows(state: torch.Tensor, N: int, slot: torch.Tensor) -> None:
+    """The fp32 channels-last state [N * S, C] -> slot fp32 [N, C, *sp] (prod(sp) = S), one entry of a pre-allocated log buffer
+    (gg_log_rows: from_cl's kernel at a given destination; no allocation, capturable)."""
+    lib = _lib.load()
+    Cc = state.shape[-1]
+    S = state.numel() // (Cc * N) if N else 0
+    if state.dtype != torch.float32 or slot.dtype != torch.float32 or not state.is_contiguous() or not slot.is_contiguous() \
+            or slot.numel() != state.numel() or state.numel() != N * S * Cc or (slot.ndim >= 2 and tuple(slot.shape[:2]) != (N, Cc)):
+        raise ValueError(f"log_rows: state {tuple(state.shape)} {state.dtype} does not fill a slot {tuple(slot.shape)} {slot.dtype} as "
+                         f"[{N}, {Cc}, S]")
+    check(lib.gg_log_rows(state.data_ptr(), N, Cc, S, slot.data_ptr(), _stream()), "gg_log_rows")

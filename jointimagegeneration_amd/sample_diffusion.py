@@ -9,7 +9,9 @@ DDIMSampler.sample / decode_first_stage); `GuideGenPipeline.sample_ct` is the al
 With `--gt DIR --lpips-vgg PATH --lpips-lin PATH` each sampled volume is scored against the same-named volume of DIR with the
 three-view LPIPS of compute_metrics (sample_diffusion.py:436-475; jointimagegeneration_amd/lpips.py) and metrics.json is written next to
 the samples.  With `--png` each sampled volume is also rendered as `<stem>_<ix:04d>.png`: the organ overlay and slice grid of
-sample_diffusion.py:241-261 (jointimagegeneration_amd/render.py).  FVD (no I3D network or scripts.fvd in the reference), the per-slice
+sample_diffusion.py:241-261 (jointimagegeneration_amd/render.py).  With `-v --progress-png [--log-every-t K]` the last generated slice
+is sampled by `progressive_denoising` (sample_diffusion.py:116-122) and its denoise row -- the decoded predictions of x_0 at the logged
+timesteps, one row per sample (ddpm.py:539-549) -- is written as `<stem>_progress.png`.  FVD (no I3D network or scripts.fvd in the reference), the per-slice
 `layers/*.png` and the private datasets are out of scope; the mask comes from `--inputs <dir>` (the
 `pred_*.nii.gz` label volumes the stage-1 entry point ddpm_eval writes: the hand-off of README.md:21, one CT volume per mask),
 from --mask (.npy label volume [D,H,W]) or is synthetic.
@@ -27,7 +29,7 @@ import torch
 
 from .config import apply_dotlist, instantiate_from_config, load_yaml, merge
 from . import ops
-from .io import load_checkpoint, read_nifti, write_nifti
+from .io import load_checkpoint, read_nifti, write_nifti, write_png
 from .ldm import DDIMSampler, PLMSSampler
 from .render import volume_png
 from .synth import randomize_parameters, synth_mask_volume
@@ -57,6 +59,9 @@ def get_parser():
     p.add_argument("--png", default=False, action="store_true", help="render each sampled volume as <stem>_<ix:04d>.png beside its NIfTI file: "
                    "the mask blended over the CT at 20 %% with organ boundaries, slices tiled 8 per row.  The overlay is given the mask as "
                    "label / 11, the convention its colour table needs; the reference's own call passes label / 255, for which no organ is painted")
+    p.add_argument("--progress-png", default=False, action="store_true", help="with -v: sample the last generated slice with "
+                   "progressive_denoising and write its denoise row (decoded x_0 predictions at the logged timesteps) as <stem>_progress.png")
+    p.add_argument("--log-every-t", type=int, default=None, help="with --progress-png: log every K-th timestep (default: the model's log_every_t)")
     return p
 
 
@@ -106,10 +111,13 @@ def stage1_mask_to_wholemask(labels, depth: int, hw: int) -> torch.Tensor:
 
 
 @torch.no_grad()
-def sample_cond(model, instance, n_samples=1, ddim_steps=50, ddim_eta=0.0, noise_seed=None, vanilla=False, plms=False, x_T_tape=None):
+def sample_cond(model, instance, n_samples=1, ddim_steps=50, ddim_eta=0.0, noise_seed=None, vanilla=False, plms=False, x_T_tape=None,
+                progress=None):
     """The reference slice loop (sample_diffusion.py:196-224) on the reference-shaped API. instance["wholemask"] is
     [1, D, H, W, 1] (label/255); returns pred [n, 2, D, H, W] = cat([samples, gen_mask]).  `x_T_tape` (parity runs): one
-    [n, C, h, w] start latent per generated slice, in loop order, instead of the generator draw of ddim.py:124."""
+    [n, C, h, w] start latent per generated slice, in loop order, instead of the generator draw of ddim.py:124.  `progress` (a dict, with
+    vanilla): the last slice is sampled by progressive_denoising(log_every_t=progress.get("log_every_t")) and its list of x_0 predictions
+    is left in progress["intermediates"]; the other slices, and every call without it, run as before."""
     sampler = PLMSSampler(model) if plms else DDIMSampler(model)
     with model.ema_scope():
         wholemask = instance["wholemask"].permute(0, 4, 1, 2, 3).cuda()
@@ -120,14 +128,18 @@ def sample_cond(model, instance, n_samples=1, ddim_steps=50, ddim_eta=0.0, noise
         samples = torch.zeros((n_samples,) + wholemask.shape[1:], dtype=torch.float32, device=wholemask.device)
         gen_mask = wholemask.repeat(n_samples, 1, 1, 1, 1)
         g = torch.Generator(device=wholemask.device).manual_seed(noise_seed) if noise_seed is not None else None
-        for it, m_ in enumerate(range(start_layer.item() - 1, end_layer.item() + 1)):
+        layers = range(start_layer.item() - 1, end_layer.item() + 1)
+        for it, m_ in enumerate(layers):
             concat_cond = torch.cat([samples[:, :, max(0, m_ - 1)], gen_mask[:, :, m_]], axis=1)
             c = model.get_learned_conditioning(concat_cond)
             if x_T_tape is not None:
                 x_T = x_T_tape[it].to(wholemask.device).float()
             else:
                 x_T = torch.randn((n_samples,) + shape, generator=g, device=wholemask.device) if g is not None else None
-            if vanilla:
+            if vanilla and progress is not None and it == len(layers) - 1:
+                s, progress["intermediates"] = model.progressive_denoising(c, (n_samples,) + shape, x_T=x_T, verbose=False,
+                                                                           log_every_t=progress.get("log_every_t"))
+            elif vanilla:
                 s = model.p_sample_loop(c, (n_samples,) + shape, x_T=x_T, verbose=False)
             else:
                 s, _ = sampler.sample(S=ddim_steps, dims=len(shape) - 1, conditioning=c, batch_size=n_samples, shape=shape,
@@ -148,6 +160,10 @@ def main(argv=None):
     scoring = (opt.gt, opt.lpips_vgg, opt.lpips_lin)
     if any(scoring) and not all(scoring):
         raise SystemExit("--gt, --lpips-vgg and --lpips-lin go together")
+    if opt.progress_png and not opt.vanilla_sample:
+        raise SystemExit("--progress-png goes with -v / --vanilla_sample (the denoise row comes from progressive_denoising)")
+    if opt.log_every_t is not None and not opt.progress_png:
+        raise SystemExit("--log-every-t goes with --progress-png")
     scorer = None
     if all(scoring):                         # weights and directory are checked before anything is sampled
         from .lpips import LPIPS
@@ -189,9 +205,12 @@ def main(argv=None):
     for stem, wholemask, seed in jobs:
         instance = {"wholemask": wholemask[None, ..., None]}
         t0 = time.time()
+        progress = dict(log_every_t=opt.log_every_t) if opt.progress_png else None
         pred = sample_cond(model, instance, n_samples=opt.n_samples, ddim_steps=opt.custom_steps, ddim_eta=opt.eta, noise_seed=seed,
-                           vanilla=opt.vanilla_sample, plms=opt.plms)
+                           vanilla=opt.vanilla_sample, plms=opt.plms, progress=progress)
         torch.cuda.synchronize()
+        if progress is not None:
+            write_png(os.path.join(out_dir, f"{stem}_progress.png"), model.denoise_row(progress["intermediates"], value_range=(-1.0, 1.0)).cpu().numpy())
         for ix, x in enumerate(pred):
             write_nifti(os.path.join(out_dir, f"{stem}_{ix:04d}.nii.gz"), x[0].float().cpu().numpy())
             written.append(os.path.join(out_dir, f"{stem}_{ix:04d}.nii.gz"))
