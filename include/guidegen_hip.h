@@ -541,6 +541,47 @@ int gg_make_grid_u8(const float *imgs, int32_t B, int32_t C, int32_t H, int32_t 
                     uint8_t *out, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Held-out objectives, forward only (gg_loss.hip): noise a sample to step t, run ONE UNet forward, reduce.  All four: the caller's
+ * stream, caller-owned buffers, no allocation, no readback, no floating-point atomics: capturable, and two runs on the same input
+ * give the same bits (every reduction: fp32 term -> fp64 sum per workgroup -> one fp64 partial in the workspace -> a second launch adds
+ * the partials in index order).  gg_loss_workspace_bytes(N, rows_per_sample) is enough workspace for either reduction.
+ * Replaces: q_sample + get_loss + mean of p_losses and the integrand of _prior_bpd (ldm/models/diffusion/ddpm.py:275-322,1011-1058);
+ * q_xt_given_x0(x0, t).sample(), theta_post, kl_div and cross_entropy of ccdm/ddpm/trainer.py:299-327.
+ * ------------------------------------------------------------------------------------------------ */
+typedef enum { GG_LOSS_L2 = 0, GG_LOSS_L1 = 1, GG_LOSS_PRIOR_KL = 2 } gg_loss_mode;
+int64_t gg_loss_workspace_bytes(int32_t N, int64_t rows_per_sample);
+/* x_noisy[n] = s0[n] * x[n] + s1[n] * noise[n]: two multiplies and one add, each rounded to fp32 (nothing contracted), which is q_sample
+ * on the CPU.  x, noise fp32 [N, C, S] (NC(D)HW); scalars_dev fp32 [N, 2] = (s0, s1).  out: fp32 [N, C, S] or NULL.  unet_in: channels
+ * [0, C) of a channels-last [N * S, unet_in_stride] buffer of unet_in_dtype (GG_BF16, or GG_F32 in validation mode) or NULL; other lanes
+ * are not touched.  At least one output. */
+int gg_q_sample_rows(const float *x, const float *noise, const float *scalars_dev, int32_t N, int32_t C, int64_t S, float *out,
+                     void *unet_in, int32_t unet_in_dtype, int32_t unet_in_stride, void *stream);
+/* out[n] (fp64) = mean over the C * S elements of sample n of
+ *   GG_LOSS_L2        (target - pred)^2          GG_LOSS_L1   |target - pred|
+ *   GG_LOSS_PRIOR_KL  0.5 * (-1 - lv + exp(lv) + m^2),  m = s[n] * x_start, scalars_dev fp32 [N, 2] = (s, lv); pred / target unused
+ * pred: the UNet head's fp32 channels-last output [N * S, pred_stride], C logical channels; target, x_start fp32 [N, C, S].  Every term is
+ * computed in fp32 (nothing contracted).  workspace: gg_loss_workspace_bytes(N, S). */
+int gg_loss_rows(const float *pred, int32_t pred_stride, const float *target, const float *x_start, const float *scalars_dev, int32_t mode,
+                 int32_t N, int32_t C, int64_t S, double *out, void *workspace, int64_t workspace_bytes, void *stream);
+/* Forward categorical noising of labels: p_c = keep[n] * [c == x0] + unif[n] / K, pn_c = p_c / sum(p) (summed left to right),
+ * label = argmax_c pn_c / E_c (first maximum on a tie).  x0 int32 [M], sample n = row / rows_per_sample; mix_dev fp32 [N, 2] = (keep,
+ * unif): (cumalphas[t_n - 1], 1 - cumalphas[t_n - 1]) for q(x_t | x_0), (1 - betas[t_n - 1], betas[t_n - 1]) for q(x_t | x_{t-1}) -- the
+ * reference's own two operands, so that neither is re-derived from the other in fp32.  E: fp32 [M, K] exponentials, or NULL: Philox4x32-10 with key philox_seeds_dev[n] (uint64 [N]) and the counter of
+ * gg_ccdm_posterior_sample_seeds (row within the sample, draw index, philox_offset_dev[0] or 0).  labels_out int32 [M]; onehot_out: bf16
+ * rows [M, onehot_stride], channels [0, K) written, or NULL.  2 <= K <= 16. */
+int gg_ccdm_q_sample(const int32_t *x0, const float *mix_dev, int64_t rows_per_sample, int32_t K, const float *E,
+                     const uint64_t *philox_seeds_dev, const int64_t *philox_offset_dev, int64_t M, int32_t *labels_out, void *onehot_out,
+                     int32_t onehot_stride, void *stream);
+/* out fp64 [N, 2] = per-sample sums over the voxels of (class_weights[x0] * KL, CE), trainer.py:305-320 with its quirks kept:
+ *   p = softmax(logits);  q_pred = max(theta_post_prob(xt, p), 1e-12) NOT renormalised;  q_true = theta_post(xt, x0);
+ *   KL = sum_c (q_true > 0 ? q_true * log(q_true) : 0) - q_true * log(q_pred);  CE = cross_entropy(p, x0) on the PROBABILITIES.
+ * logits fp32 [M, logits_stride]; xt, x0 int32 [M]; scalars_dev fp32 [N, 2] = (alphas[t-1], cumalphas[t-2]), (0, 1) at t == 1;
+ * class_weights fp32 [K]; 2 <= K <= 16.  workspace: gg_loss_workspace_bytes(N, rows_per_sample). */
+int gg_ccdm_step_loss(const float *logits, int32_t logits_stride, const int32_t *xt, const int32_t *x0, const float *scalars_dev,
+                      int64_t rows_per_sample, const float *class_weights, int32_t K, int64_t M, double *out, void *workspace,
+                      int64_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * fp32 VALIDATION mode of the CCDM path (gg_f32.hip): the same network functions on fp32 channels-last tensors with fp32 weights
  * and fp32 FMA accumulation in a fixed order, so that integer outputs (labels) can be compared exactly with the fp32 CPU
  * reference (the reference's own precision switch: ccdm/ddpm/models/unet_openai/unet.py:447,742-756).  Not a fast path.

@@ -108,6 +108,11 @@ SIGNATURES = {
     "gg_interpolate2d_f32": (C.c_int, [vp, i64, i32, i32, i32, i32, f32, f32, i32, vp, vp]),
     "gg_mask_overlay": (C.c_int, [vp, i32, i32, i32, i32, C.c_double, C.POINTER(i32), vp, vp]),
     "gg_make_grid_u8": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, f32, vp, vp]),
+    "gg_loss_workspace_bytes": (i64, [i32, i64]),
+    "gg_q_sample_rows": (C.c_int, [vp, vp, vp, i32, i32, i64, vp, vp, i32, i32, vp]),
+    "gg_loss_rows": (C.c_int, [vp, i32, vp, vp, vp, i32, i32, i32, i64, vp, vp, i64, vp]),
+    "gg_ccdm_q_sample": (C.c_int, [vp, vp, i64, i32, vp, vp, vp, i64, vp, vp, i32, vp]),
+    "gg_ccdm_step_loss": (C.c_int, [vp, i32, vp, vp, vp, i64, vp, i32, i64, vp, vp, i64, vp]),
     "gg_ubench_mfma_bf16": (C.c_int, [i32, i32, i32, vp, C.POINTER(C.c_double), vp]),
     "gg_ubench_stream_copy": (C.c_int, [vp, vp, i64, vp]),
 }

@@ -39,6 +39,40 @@ def cosine_schedule(time_steps: int, s: float = 8e-3):
     return betas, 1 - betas, cumalphas
 
 
+class CategoricalBCHW:
+    """What q_xt_given_x0 / q_xt_given_xtm1 return (the reference's OneHotCategoricalBCHW, one_hot_categorical.py): the distribution
+    keep[b] * x + unif[b] / K around a one-hot x (mix [B, 2] = (keep, unif)).  `.probs` is channels-last [B, *sp, K], normalised as torch's Categorical does
+    (torch plumbing); `.sample` is one `gg_ccdm_q_sample` launch on the labels of x."""
+
+    def __init__(self, x: Tensor, mix: Tensor, K: int):
+        self.x, self.mix, self.K = x, mix, K
+
+    @property
+    def probs(self) -> Tensor:
+        nd = self.x.ndim
+        k, u = (self.mix[:, i].view((-1,) + (1,) * (nd - 1)) for i in (0, 1))
+        p = (k * self.x + u / self.K).permute((0,) + tuple(range(2, nd)) + (1,))
+        return p / p.sum(-1, keepdim=True)
+
+    def sample_labels(self, rng_tape: Optional[Tensor] = None, philox_seeds: Optional[Sequence[int]] = None) -> Tensor:
+        """int32 labels [B, *sp].  rng_tape: fp32 [M, K] exponentials (channels-last voxel order); otherwise Philox, one key per sample
+        (philox_seeds, default 1024 + b)."""
+        x = self.x
+        lab = x.argmax(dim=1).to(torch.int32).contiguous()
+        if rng_tape is not None:
+            out = ops.ccdm_q_sample(lab.view(-1), self.mix, self.K, E=rng_tape.to(x.device).float().contiguous())
+        else:
+            keys = philox_seeds if philox_seeds is not None else [1024 + b for b in range(x.shape[0])]
+            out = ops.ccdm_q_sample(lab.view(-1), self.mix, self.K, philox_seeds=ops.philox_seed_tensor(keys, x.device))
+        return out.view(lab.shape)
+
+    def sample(self, rng_tape: Optional[Tensor] = None, philox_seeds: Optional[Sequence[int]] = None) -> Tensor:
+        """One-hot NC[D]HW sample in x's dtype (index scatter of the kernel's labels: plumbing)."""
+        lab = self.sample_labels(rng_tape, philox_seeds)
+        nd = self.x.ndim
+        return torch.nn.functional.one_hot(lab.long(), self.K).permute((0, nd - 1) + tuple(range(1, nd - 1))).to(self.x.dtype)
+
+
 class DiffusionModel(nn.Module):
     """Schedule buffers `betas/alphas/cumalphas` (diffusion_denoising.py:42-71)."""
     betas: Tensor
@@ -65,6 +99,38 @@ class DiffusionModel(nn.Module):
         al, ca = self.alphas.detach().cpu(), self.cumalphas.detach().cpu()
         rows = [(0.0, 1.0) if t == 1 else (float(al[t - 1]), float(ca[t - 2])) for t in t_values]
         return torch.tensor(rows, dtype=torch.float32)
+
+    def step_scalar_rows(self, t: Tensor) -> Tensor:
+        """Per-sample form of `step_scalars`: 1-based t [B] -> fp32 [B, 2] on the schedule's device (index arithmetic only)."""
+        t = t.to(self.alphas.device).long()
+        if int(t.min()) < 1 or int(t.max()) > self.time_steps:
+            raise ValueError(f"t = {t.tolist()} outside 1..{self.time_steps}")
+        one = t == 1
+        a = torch.where(one, torch.zeros_like(self.alphas[t - 1]), self.alphas[t - 1])
+        abar = torch.where(one, torch.ones_like(a), self.cumalphas[(t - 2).clamp(min=0)])
+        return torch.stack([a, abar], 1).float().contiguous()
+
+    def _mix_rows(self, keep: Tensor, unif: Tensor, x: Tensor, who: str) -> "CategoricalBCHW":
+        ops.require_gpu(x, who)
+        if x.shape[1] != self.num_classes:
+            raise ValueError(f"{who}: {x.shape[1]} channels for {self.num_classes} classes")
+        return CategoricalBCHW(x, torch.stack([keep, unif], 1).to(x.device).float().contiguous(), self.num_classes)
+
+    def q_xt_given_xtm1(self, xtm1: Tensor, t: Tensor) -> "CategoricalBCHW":
+        """q(x_t | x_{t-1}) (diffusion_denoising.py:73-80): one-hot xtm1 NC[D]HW, 1-based t [B]."""
+        betas = self.betas[t.to(self.betas.device).long() - 1]
+        return self._mix_rows(1 - betas, betas, xtm1, "q_xt_given_xtm1")
+
+    def q_xt_given_x0(self, x0: Tensor, t: Tensor) -> "CategoricalBCHW":
+        """q(x_t | x_0) (diffusion_denoising.py:82-89): one-hot x0 NC[D]HW, 1-based t [B]."""
+        ca = self.cumalphas[t.to(self.cumalphas.device).long() - 1]
+        return self._mix_rows(ca, 1 - ca, x0, "q_xt_given_x0")
+
+    def theta_post(self, xt: Tensor, x0: Tensor, t: Tensor) -> Tensor:
+        """q(x_{t-1} | x_t, x_0) for one-hot xt, x0 (diffusion_denoising.py:91-103), evaluated by the posterior kernel with the one-hot x0
+        in the place of the predicted distribution: the sum over the predicted x_0 then has one non-zero term.  As theta_post_prob's, the
+        values have passed that kernel's clamp (>= 1e-12) and normalisation, so the exact zeros of t == 1 come out as 1e-12."""
+        return self.theta_post_prob(xt, x0.float(), t)
 
     def theta_post_prob(self, xt: Tensor, theta_x0: Tensor, t: Tensor) -> Tensor:
         """Reference signature (NC[D]HW one-hot xt, probs theta_x0, 1-based t [B]); evaluated by the fused HIP kernel

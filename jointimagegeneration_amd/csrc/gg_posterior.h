@@ -133,3 +133,70 @@ __device__ __forceinline__ void ccdm_onehot_row(bf16_t *__restrict__ oh, const i
         }
     }
 }
+
+// ------------------------------------------------------------------------------------------------------------
+// CCDM training objective of ONE voxel (ccdm/ddpm/trainer.py:305-320), forward only.  lg: the head's K fp32 logits, overwritten with
+// p = softmax(lg) (the model's diffusion_out).  kl_out = class_weight * sum_c kl_div(log(max(theta_post_prob(xt, p), 1e-12)),
+// theta_post(xt, x0)): the predicted posterior is clamped and NOT renormalised there, and a zero target contributes zero (xlogy; t == 1
+// makes theta_post one-hot).  ce_out = cross_entropy(p, x0) on the PROBABILITIES, as the trainer feeds them (log_softmax in ATen's
+// form: p - max - log(sum(exp(p - max)))).  The softmax and the unnormalised posterior repeat ccdm_posterior_voxel's expressions in its
+// order (that function is left as it is: the exact-label tests rest on its instruction order).
+// ------------------------------------------------------------------------------------------------------------
+template <int KMAX>
+__device__ __forceinline__ void ccdm_loss_voxel(float (&lg)[KMAX], const int x, const int x0, const float a, const float abar, const int K,
+                                                const float cw, float &kl_out, float &ce_out)
+{
+#pragma clang fp contract(off)
+    const float Kf = (float)K;
+    const float u = (1.0f - a) / Kf;
+    const float v = (1.0f - abar) / Kf;
+    const float bd = abar * 1.0f + v;
+    const float bo = abar * 0.0f + v;
+    float mx = lg[0];
+#pragma unroll
+    for (int c = 1; c < KMAX; ++c) if (c < K) mx = fmaxf(mx, lg[c]);
+    float s = 0.f;
+#pragma unroll
+    for (int c = 0; c < KMAX; ++c) if (c < K) { lg[c] = expf(lg[c] - mx); s = s + lg[c]; }
+#pragma unroll
+    for (int c = 0; c < KMAX; ++c) if (c < K) lg[c] = lg[c] / s;
+    const float Ax = a * 1.0f + u, Ao = a * 0.0f + u;
+    const float n_xd = Ax * bd, n_xo = Ax * bo, n_od = Ao * bd, n_oo = Ao * bo;
+    float qp[KMAX];
+#pragma unroll
+    for (int c = 0; c < KMAX; ++c) qp[c] = 0.f;
+#pragma unroll
+    for (int d = 0; d < KMAX; ++d) {
+        if (d < K) {
+            float den = 0.f;
+#pragma unroll
+            for (int c = 0; c < KMAX; ++c) if (c < K) den = den + ((c == x) ? (c == d ? n_xd : n_xo) : (c == d ? n_od : n_oo));
+            const float pd = lg[d];
+            const float q_dd = ((d == x) ? n_xd : n_od) / den, q_xo = n_xo / den, q_oo = n_oo / den;
+#pragma unroll
+            for (int c = 0; c < KMAX; ++c) if (c < K) {
+                const float post = (c == d) ? q_dd : ((c == x) ? q_xo : q_oo);
+                qp[c] = qp[c] + post * pd;
+            }
+        }
+    }
+    // theta_post(xt, x0): the column d == x0 of the table above, normalised
+    float den0 = 0.f;
+#pragma unroll
+    for (int c = 0; c < KMAX; ++c) if (c < K) den0 = den0 + ((c == x) ? (c == x0 ? n_xd : n_xo) : (c == x0 ? n_od : n_oo));
+    float kl = 0.f, pmx = lg[0], px0 = 0.f;
+#pragma unroll
+    for (int c = 0; c < KMAX; ++c) if (c < K) {
+        const float qt = ((c == x) ? (c == x0 ? n_xd : n_xo) : (c == x0 ? n_od : n_oo)) / den0;
+        const float lq = logf(fmaxf(qp[c], 1e-12f));
+        const float ent = qt > 0.f ? qt * logf(qt) : 0.f;
+        kl = kl + (ent - qt * lq);
+        pmx = fmaxf(pmx, lg[c]);
+        if (c == x0) px0 = lg[c];
+    }
+    float se = 0.f;
+#pragma unroll
+    for (int c = 0; c < KMAX; ++c) if (c < K) se = se + expf(lg[c] - pmx);
+    kl_out = kl * cw;
+    ce_out = -((px0 - pmx) - logf(se));
+}

@@ -11,6 +11,10 @@ the run then accumulates the [K, K] confusion matrix on the device and rank 0 wr
 with `--ignore-class` removed, its mean).  `--samples S` (the yaml comment "samples: 12  # For GED calculation") samples S masks per
 volume as one batch, written as `pred_{vid:04d}_s{j:02d}.nii.gz`; with --gt each volume then also gets its GED, the two diversities and
 the Hungarian-matched IoU.  Without these options the run writes exactly what it wrote before they existed.
+
+Objectives (trainer.py:298-327; losses.py): `--gt DIR --loss-t T1,T2,...` adds a `loss` block to metrics.json: per listed step t the
+KL, cross-entropy and their sum of the ground-truth volumes noised to t, averaged over the volumes.  The noise of volume v at step t
+comes from the Philox key (1024 + v) + (t << 32), so reruns agree and a volume's terms do not depend on the rank that scored it.
 """
 from __future__ import annotations
 
@@ -30,6 +34,7 @@ from . import metrics
 from .ccdm import build_model
 from .encoder import build_feature_cond_encoder
 from .io import load_checkpoint, write_nifti
+from .losses import ccdm_step_losses
 from .synth import randomize_parameters
 
 
@@ -63,6 +68,11 @@ def load_weights(model, params: dict, log=print) -> str:
     return "random-init"
 
 
+def loss_key(vid: int, t: int) -> int:
+    """The Philox key of volume `vid` at step `t` of the --loss-t block."""
+    return (1024 + vid) + (t << 32)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("params_file", nargs="?", default="params_eval.yml")
@@ -75,9 +85,13 @@ def main(argv=None):
     ap.add_argument("--samples", type=int, default=1, help="masks per volume, sampled as one batch (pred_VVVV_sJJ.nii.gz; GED / HM-IoU with --gt)")
     ap.add_argument("--gt", default=None, help="directory of gt_{vid:04d}.nii.gz label volumes: score the run into metrics.json")
     ap.add_argument("--ignore-class", type=int, default=None, help="class left out of Dice (default: yaml ignore_class, else 0)")
+    ap.add_argument("--loss-t", default=None, help="comma-separated steps t (1..time_steps): KL / CE / loss of the --gt volumes noised to t, into metrics.json")
     args = ap.parse_args(argv)
     if args.samples < 1:
         raise ValueError(f"--samples {args.samples}: at least one mask per volume")
+    loss_ts = [int(v) for v in args.loss_t.split(",") if v.strip()] if args.loss_t else []
+    if loss_ts and not args.gt:
+        raise ValueError("--loss-t needs --gt DIR: the objectives are evaluated on the ground-truth volumes")
     set_seeds(1024)
     with open(args.params_file, "r") as f:
         params = yaml.safe_load(f)
@@ -89,6 +103,8 @@ def main(argv=None):
     S = args.samples
     ignore = args.ignore_class if args.ignore_class is not None else params.get("ignore_class", 0)      # ruijin's get_ignore_class: 0
     gts = metrics.load_gt(args.gt, vids, size, K) if args.gt else None           # a bad ground truth ends the run before any sampling
+    if any(t < 1 or t > params["time_steps"] for t in loss_ts):
+        raise ValueError(f"--loss-t {args.loss_t}: steps are 1..{params['time_steps']}")
     assert torch.cuda.is_available(), "the GuideGen engine needs an MI355X (no CPU fallback)"
     dev = torch.device("cuda", local)
     torch.cuda.set_device(dev)
@@ -127,7 +143,9 @@ def main(argv=None):
     # scores travel as ONE int64 buffer: the [K, K] counts, then 4 fp64 scores per volume stored as their bit patterns (a volume belongs
     # to one rank and the other ranks hold zeros there, so the integer sum over ranks reproduces the bits)
     n_vol = params["batch_size"]
-    score_buf = torch.zeros(K * K + 4 * n_vol, dtype=torch.int64, device=dev) if gts is not None else None
+    L = len(loss_ts)
+    loss_at = K * K + 4 * n_vol                                                       # then 3 fp64 (kl, ce, loss) per (volume, listed t)
+    score_buf = torch.zeros(loss_at + 3 * L * n_vol, dtype=torch.int64, device=dev) if gts is not None else None
     for vid in vids:                                                                  # volumes are independent units
         if S == 1:
             g = torch.Generator(device=dev).manual_seed(1024 + vid)
@@ -149,6 +167,11 @@ def main(argv=None):
             if scores is not None:
                 vals = torch.tensor([scores["ged"], scores["diversity_pred"], scores["diversity_gt"], scores["hm_iou"]], dtype=torch.float64)
                 score_buf[K * K + 4 * vid:K * K + 4 * vid + 4] = vals.view(torch.int64).to(dev)
+            for j, t in enumerate(loss_ts):
+                r = ccdm_step_losses(model, torch.from_numpy(gts[vid])[None].to(dev), torch.zeros((1, 1) + size, device=dev), torch.tensor([t]),
+                                     philox_seeds=[loss_key(vid, t)])
+                at = loss_at + 3 * (vid * L + j)
+                score_buf[at:at + 3] = torch.stack([r["loss_kl"], r["loss_ce"], r["loss"]]).view(torch.int64)
     torch.cuda.synchronize()
     print(f"[rank {rank}] sampled {len(vids)} volume(s) of {size} in {time.time() - t0:.1f}s -> {out_dir}", file=sys.stderr)
     if score_buf is not None:
@@ -156,10 +179,15 @@ def main(argv=None):
             torch.distributed.all_reduce(score_buf)                                   # once, after the sampling loop: off the data path
         if rank == 0:
             host = score_buf.cpu()
-            per = host[K * K:].view(torch.float64).reshape(n_vol, 4).tolist()
+            per = host[K * K:loss_at].view(torch.float64).reshape(n_vol, 4).tolist()
             volumes = [dict(id=v, samples=S, **(dict(zip(("ged", "diversity_pred", "diversity_gt", "hm_iou"), per[v])) if S > 1 else {}))
                        for v in range(n_vol)]
             doc = metrics.summarise(host[:K * K].reshape(K, K), volumes, K, ignore)
+            if L:
+                lv = host[loss_at:].view(torch.float64).reshape(n_vol, L, 3)
+                mean = lv.sum(0) / n_vol                                              # volume order: the same bits on every run
+                doc["loss"] = [dict(t=t, loss_kl=float(mean[j, 0]), loss_ce=float(mean[j, 1]), loss=float(mean[j, 2]), volumes=n_vol)
+                               for j, t in enumerate(loss_ts)]
             with open(os.path.join(out_dir, "metrics.json"), "w") as f:
                 json.dump(doc, f, indent=1)
             print(f"[rank 0] {metrics.summary_line(doc)} -> {os.path.join(out_dir, 'metrics.json')}", file=sys.stderr)

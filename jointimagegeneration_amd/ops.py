@@ -1175,3 +1175,124 @@ def log_rows(state: torch.Tensor, N: int, slot: torch.Tensor) -> None:
         raise ValueError(f"log_rows: state {tuple(state.shape)} {state.dtype} does not fill a slot {tuple(slot.shape)} {slot.dtype} as "
                          f"[{N}, {Cc}, S]")
     check(lib.gg_log_rows(state.data_ptr(), N, Cc, S, slot.data_ptr(), _stream()), "gg_log_rows")
+
+
+# ----------------------------------------------------------------------------------------------- held-out objectives (gg_loss.hip)
+LOSS_MODES = {"l2": 0, "l1": 1, "prior_kl": 2}        # gg_loss_mode (include/guidegen_hip.h)
+
+
+def _f32_dev(t: torch.Tensor, numel: int, what: str) -> torch.Tensor:
+    if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.numel() != numel:
+        raise ValueError(f"{what} must be a contiguous device fp32 tensor of {numel} elements, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    return t
+
+
+def _i32_dev(t: torch.Tensor, numel: int, what: str) -> torch.Tensor:
+    if t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous() or t.numel() != numel:
+        raise ValueError(f"{what} must be a contiguous device int32 tensor of {numel} elements, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    return t
+
+
+def loss_workspace(N: int, rows_per_sample: int, device) -> torch.Tensor:
+    """The workspace either reduction of gg_loss.hip needs for N samples of rows_per_sample rows."""
+    nbytes = int(_lib.load().gg_loss_workspace_bytes(N, rows_per_sample))
+    return torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=device)
+
+
+def q_sample_rows(x: torch.Tensor, noise: torch.Tensor, scalars: torch.Tensor, out: Optional[torch.Tensor] = None,
+                  unet_in: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+    """x_noisy[n] = s0[n] * x[n] + s1[n] * noise[n] (gg_q_sample_rows): x, noise fp32 NC(D)HW on the device, scalars fp32 [N, 2].
+    out: fp32 NC(D)HW; unet_in: channels-last [N, ..., Cpad] bf16 (or fp32 in validation mode), channels [0, C) written."""
+    lib = _lib.load()
+    require_gpu(x, "q_sample_rows")
+    N, Cc = int(x.shape[0]), int(x.shape[1])
+    S = x.numel() // (N * Cc)
+    _f32_dev(x, N * Cc * S, "q_sample_rows: x"); _f32_dev(noise, N * Cc * S, "q_sample_rows: noise"); _f32_dev(scalars, 2 * N, "q_sample_rows: scalars")
+    if out is None and unet_in is None:
+        out = torch.empty_like(x)
+    if out is not None:
+        _f32_dev(out, N * Cc * S, "q_sample_rows: out")
+    dt, stride = GG_BF16, 0
+    if unet_in is not None:
+        stride = int(unet_in.shape[-1])
+        if unet_in.dtype not in (torch.bfloat16, torch.float32) or not unet_in.is_contiguous() or unet_in.numel() != N * S * stride or stride < Cc:
+            raise ValueError(f"q_sample_rows: unet_in {unet_in.dtype} {tuple(unet_in.shape)} is not a channels-last buffer of {N * S} rows, >= {Cc} lanes")
+        dt = GG_F32 if is_f32(unet_in) else GG_BF16
+    check(lib.gg_q_sample_rows(x.data_ptr(), noise.data_ptr(), scalars.data_ptr(), N, Cc, S, _ptr(out), _ptr(unet_in), dt, stride, _stream()),
+          "gg_q_sample_rows")
+    return out
+
+
+def loss_rows(mode: str, N: int, C: int, S: int, *, pred: Optional[torch.Tensor] = None, target: Optional[torch.Tensor] = None,
+              x_start: Optional[torch.Tensor] = None, scalars: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+              workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Per-sample means, fp64 [N] (gg_loss_rows).  "l2" / "l1": pred fp32 channels-last [N * S, stride] (the UNet head's output) against
+    target fp32 NC(D)HW; "prior_kl": x_start fp32 NC(D)HW and scalars fp32 [N, 2] = (sqrt_alphas_cumprod[T-1], log_one_minus_alphas_cumprod[T-1])."""
+    lib = _lib.load()
+    if mode not in LOSS_MODES:
+        raise ValueError(f"loss_rows: unknown mode '{mode}' (one of {sorted(LOSS_MODES)})")
+    stride = 0
+    if mode == "prior_kl":
+        _f32_dev(x_start, N * C * S, "loss_rows: x_start"); _f32_dev(scalars, 2 * N, "loss_rows: scalars")
+        dev = x_start.device
+    else:
+        stride = int(pred.shape[-1])
+        _f32_dev(pred, N * S * stride, "loss_rows: pred"); _f32_dev(target, N * C * S, "loss_rows: target")
+        dev = pred.device
+    if out is None:
+        out = torch.empty(N, dtype=torch.float64, device=dev)
+    if workspace is None:
+        workspace = loss_workspace(N, S, dev)
+    check(lib.gg_loss_rows(_ptr(pred), stride, _ptr(target), _ptr(x_start), _ptr(scalars), LOSS_MODES[mode], N, C, S, out.data_ptr(),
+                           workspace.data_ptr(), workspace.numel() * 8, _stream()), "gg_loss_rows")
+    return out
+
+
+def ccdm_q_sample(x0: torch.Tensor, mix: torch.Tensor, K: int, *, E: Optional[torch.Tensor] = None,
+                  philox_seeds: Optional[torch.Tensor] = None, philox_offset: Optional[torch.Tensor] = None,
+                  labels_out: Optional[torch.Tensor] = None, onehot_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """q_xt_given_x0(x0, t).sample() on labels (gg_ccdm_q_sample): x0 int32 [M] of N equal samples, mix fp32 [N, 2] = (keep, unif), the
+    weights of the one-hot and of the uniform part: (cumalphas[t - 1], 1 - cumalphas[t - 1]), or (1 - betas[t - 1], betas[t - 1]).
+    E: fp32 [M, K] exponential tape, or philox_seeds: device int64 [N] keys.  Returns int32 [M]."""
+    lib = _lib.load()
+    require_gpu(x0, "ccdm_q_sample")
+    M, N = x0.numel(), mix.numel() // 2
+    if N < 1 or M % N:
+        raise ValueError(f"ccdm_q_sample: {M} rows do not split into {N} samples")
+    _i32_dev(x0, M, "ccdm_q_sample: x0"); _f32_dev(mix, 2 * N, "ccdm_q_sample: mix")
+    if (E is None) == (philox_seeds is None):
+        raise ValueError("ccdm_q_sample: give either an exponential tape E or philox_seeds")
+    if E is not None:
+        _f32_dev(E, M * K, "ccdm_q_sample: E")
+    if labels_out is None:
+        labels_out = torch.empty(M, dtype=torch.int32, device=x0.device)
+    _i32_dev(labels_out, M, "ccdm_q_sample: labels_out")
+    if onehot_out is not None and (onehot_out.dtype != torch.bfloat16 or not onehot_out.is_contiguous() or onehot_out.numel() != M * onehot_out.shape[-1]):
+        raise ValueError(f"ccdm_q_sample: onehot_out must be contiguous bf16 rows [{M}, stride], got {onehot_out.dtype} {tuple(onehot_out.shape)}")
+    check(lib.gg_ccdm_q_sample(x0.data_ptr(), mix.data_ptr(), M // N, K, _ptr(E),
+                               _seeds_ptr(philox_seeds, N) if philox_seeds is not None else None, _ptr(philox_offset), M,
+                               labels_out.data_ptr(), _ptr(onehot_out), onehot_out.shape[-1] if onehot_out is not None else 0, _stream()),
+          "gg_ccdm_q_sample")
+    return labels_out
+
+
+def ccdm_step_loss(logits: torch.Tensor, xt: torch.Tensor, x0: torch.Tensor, scalars: torch.Tensor, class_weights: torch.Tensor, K: int, *,
+                   out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp64 [N, 2] per-sample sums of (class-weighted KL, CE) of trainer.py:305-320 (gg_ccdm_step_loss): logits fp32 channels-last
+    [M, stride], xt / x0 int32 [M], scalars fp32 [N, 2] per sample, class_weights fp32 [K]."""
+    lib = _lib.load()
+    require_gpu(logits, "ccdm_step_loss")
+    stride = int(logits.shape[-1])
+    M = logits.numel() // stride
+    N = scalars.numel() // 2
+    if N < 1 or M % N:
+        raise ValueError(f"ccdm_step_loss: {M} rows do not split into {N} samples")
+    _f32_dev(logits, M * stride, "ccdm_step_loss: logits"); _i32_dev(xt, M, "ccdm_step_loss: xt"); _i32_dev(x0, M, "ccdm_step_loss: x0")
+    _f32_dev(scalars, 2 * N, "ccdm_step_loss: scalars"); _f32_dev(class_weights, K, "ccdm_step_loss: class_weights")
+    if out is None:
+        out = torch.empty((N, 2), dtype=torch.float64, device=logits.device)
+    if workspace is None:
+        workspace = loss_workspace(N, M // N, logits.device)
+    check(lib.gg_ccdm_step_loss(logits.data_ptr(), stride, xt.data_ptr(), x0.data_ptr(), scalars.data_ptr(), M // N, class_weights.data_ptr(),
+                                K, M, out.data_ptr(), workspace.data_ptr(), workspace.numel() * 8, _stream()), "gg_ccdm_step_loss")
+    return out
