@@ -98,3 +98,16 @@ __device__ __forceinline__ bf16x8 gg_f32_to_bf16x8(f32x8 v)
 }
 
 static inline int gg_cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+
+// Host side of the pointwise LDM steps (gg_sampler.hip, for gg_vq.hip's codebook-free step): one launch of the per-element DDIM
+// (ancestral == 0) or ancestral update over [M, C] rows, the noise coefficient read from scalars[noise_idx].  No argument checks: the
+// extern "C" entries do theirs and then call this.
+int gg_step_launch(int ancestral, float *x, const float *out, int out_stride, const float *noise, const float *scalars_dev, int noise_idx,
+                   int flags, long long M, int C, float *pred_x0_out, void *unet_in, int unet_in_stride, hipStream_t stream);
+
+// grid of a grid-stride kernel with 256 threads per block: one thread per unit of work, at most cap blocks (0 when there is no work)
+static inline unsigned gg_blocks256(long long work, long long cap)
+{
+    const long long blocks = work > 0 ? (work + 255) / 256 : 0;
+    return (unsigned)(blocks > cap ? cap : blocks);
+}

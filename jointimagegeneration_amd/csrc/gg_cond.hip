@@ -40,9 +40,8 @@ extern "C" int gg_embed_rows(const int32_t *ids, int64_t rows, int32_t T, const 
     if (pos && T > P) GG_FAIL(GG_ERR_BAD_SHAPE, "embed_rows: sequence length %d exceeds the %d positions of the table", T, P);
     if (!ids || !tok || !out) GG_FAIL(GG_ERR_BAD_SHAPE, "embed_rows: null pointer");
     const long long total = (long long)rows * out_stride;
-    long long blocks = (total + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    const dim3 g((unsigned)blocks), b(256);
+    const unsigned blocks = gg_blocks256(total, 8192);
+    const dim3 g(blocks), b(256);
     if (out_dtype == GG_BF16)
         hipLaunchKernelGGL(embed_rows_kernel<bf16_t>, g, b, 0, (hipStream_t)stream_, ids, (long long)rows, T, tok, V, D, pos, (bf16_t *)out, out_stride);
     else
@@ -78,9 +77,8 @@ extern "C" int gg_gelu(const void *x, int64_t n, void *out, void *stream_)
     if (n <= 0) GG_FAIL(GG_ERR_BAD_SHAPE, "gelu: n = %lld", (long long)n);
     if (!x || !out) GG_FAIL(GG_ERR_BAD_SHAPE, "gelu: null pointer");
     if (((uintptr_t)x | (uintptr_t)out) & 15) GG_FAIL(GG_ERR_BAD_SHAPE, "gelu: x and out must be 16-byte aligned");
-    long long blocks = ((n + 7) / 8 + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(gelu_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, (const bf16_t *)x, (long long)n, (bf16_t *)out);
+    const unsigned blocks = gg_blocks256((n + 7) / 8, 8192);
+    hipLaunchKernelGGL(gelu_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, (const bf16_t *)x, (long long)n, (bf16_t *)out);
     GG_CHECK_LAUNCH();
     return GG_OK;
 }
@@ -223,9 +221,8 @@ extern "C" int gg_interpolate2d_f32(const float *src, int64_t planes, int32_t H,
     if ((long long)H * W >= (1LL << 31) || (long long)Ho * Wo >= (1LL << 31)) GG_FAIL(GG_ERR_BAD_SHAPE, "interpolate2d: a plane of 2^31 elements or more");
     if (!src || !dst) GG_FAIL(GG_ERR_BAD_SHAPE, "interpolate2d: null pointer");
     const long long total = (long long)planes * Ho * Wo;
-    long long blocks = (total + 255) / 256;
-    if (blocks > 16384) blocks = 16384;
-    const dim3 g((unsigned)blocks), b(256);
+    const unsigned blocks = gg_blocks256(total, 16384);
+    const dim3 g(blocks), b(256);
     switch (mode) {
     case GG_INTERP_NEAREST: hipLaunchKernelGGL(interpolate2d_kernel<GG_INTERP_NEAREST>, g, b, 0, stream, src, H, W, Ho, Wo, scale_h, scale_w, total, dst); break;
     case GG_INTERP_BILINEAR: hipLaunchKernelGGL(interpolate2d_kernel<GG_INTERP_BILINEAR>, g, b, 0, stream, src, H, W, Ho, Wo, scale_h, scale_w, total, dst); break;

@@ -3,6 +3,7 @@
 #pragma once
 #include <atomic>
 #include "gg_conv.h"
+#include "gg_step.h"
 #ifndef GG_BOX_K1_MAX_M_ACC
 #define GG_BOX_K1_MAX_M_ACC 256
 #endif
@@ -799,17 +800,16 @@ __global__ __launch_bounds__(GG_BOX_NW * 64) void conv_box2d_kernel(const ConvPa
             }
             *reinterpret_cast<f32x4 *>((float *)p.out + o) = a;
             if (dd) {
-                // fused DDIM update (ddim.py:190-204), the UNet head conv's eps still in registers; same fp32 expression order as
-                // ddim_step_kernel (bit-identical results)
-#pragma clang fp contract(off)
+                // fused DDIM update (gg_step.h), the UNet head conv's eps still in registers
                 const float a_t = dsc[0], a_prev = dsc[1], sigma = dsc[2], s1m = dsc[3];
-                const float sqrt_at = sqrtf(a_t), sqrt_ap = sqrtf(a_prev), dirc = sqrtf(1.0f - a_prev - sigma * sigma);
+                float sqrt_at, sqrt_ap, dirc;
+                ddim_roots(a_t, a_prev, sigma, sqrt_at, sqrt_ap, dirc);
                 f32x4 px0, xn;
                 bf16x4 xb;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    px0[j] = (xv[j] - s1m * a[j]) / sqrt_at;
-                    xn[j] = sqrt_ap * px0[j] + dirc * a[j];
+                    px0[j] = ddim_pred_x0(xv[j], a[j], s1m, sqrt_at);
+                    xn[j] = ddim_x_prev(px0[j], a[j], sqrt_ap, dirc);
                     xb[j] = (bf16_t)xn[j];
                 }
                 *reinterpret_cast<f32x4 *>(p.ddim_x + mo * 4) = xn;

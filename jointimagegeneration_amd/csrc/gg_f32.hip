@@ -208,9 +208,8 @@ extern "C" int gg_groupnorm_f32(const float *src1, int32_t C1, const float *src2
     hipLaunchKernelGGL(gn_f32_stats_kernel, dim3(32, (unsigned)N), dim3(256), 0, stream, src1, C1, src2, C2, (long long)S, C_logical, eps, mean, rstd);
     GG_CHECK_LAUNCH();
     const long long total = (long long)N * S * (C1 + C2);
-    long long blocks = (total + 255) / 256;
-    if (blocks > 16384) blocks = 16384;
-    hipLaunchKernelGGL(gn_f32_apply_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, src1, C1, src2, C2, (long long)S, C_logical, gamma, beta,
+    const unsigned blocks = gg_blocks256(total, 16384);
+    hipLaunchKernelGGL(gn_f32_apply_kernel, dim3(blocks), dim3(256), 0, stream, src1, C1, src2, C2, (long long)S, C_logical, gamma, beta,
                        (const float *)mean, (const float *)rstd, act, out, total);
     GG_CHECK_LAUNCH();
     return GG_OK;
@@ -258,9 +257,8 @@ extern "C" int gg_groupnorm_f32_film(const float *src, int32_t C_pad, int32_t N,
                        eps, mean, rstd);
     GG_CHECK_LAUNCH();
     const long long total = (long long)N * S * C_pad;
-    long long blocks = (total + 255) / 256;
-    if (blocks > 16384) blocks = 16384;
-    hipLaunchKernelGGL(gn_f32_apply_film_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, src, C_pad, (long long)S, C_logical, gamma, beta,
+    const unsigned blocks = gg_blocks256(total, 16384);
+    hipLaunchKernelGGL(gn_f32_apply_film_kernel, dim3(blocks), dim3(256), 0, stream, src, C_pad, (long long)S, C_logical, gamma, beta,
                        (const float *)mean, (const float *)rstd, film, (long long)film_stride, act, out, total);
     GG_CHECK_LAUNCH();
     return GG_OK;

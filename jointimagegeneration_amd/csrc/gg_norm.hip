@@ -412,9 +412,8 @@ extern "C" int gg_groupnorm_apply(const void *src1, int32_t C1, const void *src2
     if (C1 <= 0 || C1 % 32 || C2 % 32 || C2 < 0) GG_FAIL(GG_ERR_BAD_SHAPE, "groupnorm_apply: C1/C2 must be multiples of 32");
     if (!src1 || (C2 && !src2) || !scale || !shift || !out) GG_FAIL(GG_ERR_BAD_SHAPE, "groupnorm_apply: null pointer");
     long long total = (long long)N * S * ((C1 + C2) / 8);
-    long long blocks = (total + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(gn_apply_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, (const bf16_t *)src1, C1,
+    const unsigned blocks = gg_blocks256(total, 8192);
+    hipLaunchKernelGGL(gn_apply_kernel, dim3(blocks), dim3(256), 0, stream, (const bf16_t *)src1, C1,
                        (const bf16_t *)src2, C2, (long long)S, total, scale, shift, act, (bf16_t *)out, gg_magic_u32(total, (C1 + C2) / 8), N);
     GG_CHECK_LAUNCH();
     return GG_OK;
@@ -854,10 +853,9 @@ extern "C" int gg_geglu(const void *h, int64_t rows, int32_t inner, void *out, v
 {
     if (inner % 8 || inner <= 0) GG_FAIL(GG_ERR_BAD_SHAPE, "geglu: inner %% 8");
     long long total = (long long)rows * (inner / 8);
-    long long blocks = (total + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
+    const unsigned blocks = gg_blocks256(total, 8192);
     if (blocks < 1) return GG_OK;
-    hipLaunchKernelGGL(geglu_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, (const bf16_t *)h, (long long)rows,
+    hipLaunchKernelGGL(geglu_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, (const bf16_t *)h, (long long)rows,
                        inner, (bf16_t *)out);
     GG_CHECK_LAUNCH();
     return GG_OK;
@@ -880,10 +878,9 @@ extern "C" int gg_add(const void *a, const void *b, int64_t n, void *out, void *
 {
     if (n % 8) GG_FAIL(GG_ERR_BAD_SHAPE, "add: n %% 8");
     long long n8 = n / 8;
-    long long blocks = (n8 + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
+    const unsigned blocks = gg_blocks256(n8, 8192);
     if (blocks < 1) return GG_OK;
-    hipLaunchKernelGGL(add_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, (const bf16_t *)a, (const bf16_t *)b,
+    hipLaunchKernelGGL(add_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, (const bf16_t *)a, (const bf16_t *)b,
                        n8, (bf16_t *)out);
     GG_CHECK_LAUNCH();
     return GG_OK;

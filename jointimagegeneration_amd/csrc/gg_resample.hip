@@ -109,9 +109,8 @@ extern "C" int gg_resample2x(const void *src, int32_t dtype, int32_t N, int32_t 
     const int Do = mode == 0 ? (resample_d ? 2 * D : D) : (resample_d ? D / 2 : D);
     const int Ho = mode == 0 ? 2 * H : H / 2, Wo = mode == 0 ? 2 * W : W / 2;
     const long long total = (long long)N * Do * Ho * Wo * (C_pad / 8);
-    long long blocks = (total + 255) / 256;
-    if (blocks > 16384) blocks = 16384;
-    const dim3 g((unsigned)blocks), b(256);
+    const unsigned blocks = gg_blocks256(total, 16384);
+    const dim3 g(blocks), b(256);
     if (dtype == GG_BF16) {
         const bf16_t *s = (const bf16_t *)src;
         bf16_t *o = (bf16_t *)dst;

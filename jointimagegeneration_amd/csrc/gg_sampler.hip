@@ -1,6 +1,7 @@
 // Sampler-side kernels: CCDM fused posterior+sample, DDIM update, layout movers, small fp32 linears.
 #include "gg_common.h"
 #include "gg_posterior.h"
+#include "gg_step.h"
 
 // ------------------------------------------------------------------------------------------------------------
 // CCDM reverse step, one voxel per thread (gg_posterior.h holds the arithmetic).
@@ -110,118 +111,56 @@ extern "C" int gg_labels_to_onehot(const int32_t *labels, int64_t M, int32_t K, 
     if (stride % 8 || stride < K) GG_FAIL(GG_ERR_BAD_SHAPE, "labels_to_onehot: stride %d (K=%d)", stride, K);
     if (M <= 0) return GG_OK;
     long long total = (long long)M * (stride / 8);
-    long long blocks = (total + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(labels_to_onehot_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, labels, (long long)M, K,
+    const unsigned blocks = gg_blocks256(total, 8192);
+    hipLaunchKernelGGL(labels_to_onehot_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, labels, (long long)M, K,
                        (bf16_t *)onehot_out, stride);
     GG_CHECK_LAUNCH();
     return GG_OK;
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// DDIM update (ddim.py:190-204), fp32; same expression order as oracle/samplers.py:ddim_step.
+// Pointwise reverse steps of the LDM samplers, fp32 (gg_step.h holds the arithmetic): the DDIM update and the ancestral update with the
+// reference's options (x0 parameterisation, clip_denoised, the prediction of x_0 as an output), one kernel templated on the formula, and
+// the row-per-lane kernel of gg_ddpm_step_x0 at C == 4.
 // ------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void ddim_step_kernel(float *__restrict__ x, const float *__restrict__ eps, int eps_stride,
-                                                        const float *__restrict__ noise, const float *__restrict__ sc,
-                                                        long long M, int C, float *__restrict__ pred_x0_out,
-                                                        bf16_t *__restrict__ unet_in, int unet_in_stride)
+enum { STEP_DDIM = 0, STEP_ANCESTRAL = 1 };
+
+// the four constants of a step in the order step_one takes them: DDIM {sqrt(1 - a_t), the three roots}, ancestral the scalar row itself
+template <int F>
+__device__ __forceinline__ void step_consts(const float *__restrict__ sc, float (&k)[4])
 {
-#pragma clang fp contract(off)
-    const float a_t = sc[0], a_prev = sc[1], sigma = sc[2], s1m = sc[3];
-    const float sqrt_at = sqrtf(a_t), sqrt_ap = sqrtf(a_prev), dirc = sqrtf(1.0f - a_prev - sigma * sigma);
-    const long long total = M * C;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        long long m = i / C;
-        int c = (int)(i - m * C);
-        float e = eps[m * eps_stride + c];
-        float xv = x[i];
-        float px0 = (xv - s1m * e) / sqrt_at;
-        float xn = sqrt_ap * px0 + dirc * e;
-        if (noise) xn = xn + sigma * noise[i];
-        x[i] = xn;
-        if (pred_x0_out) pred_x0_out[i] = px0;
-        if (unet_in) unet_in[m * unet_in_stride + c] = (bf16_t)xn;
+    if constexpr (F == STEP_DDIM) {
+        k[0] = sc[3];
+        ddim_roots(sc[0], sc[1], sc[2], k[1], k[2], k[3]);
+    } else {
+        k[0] = sc[0]; k[1] = sc[1]; k[2] = sc[2]; k[3] = sc[3];
     }
 }
 
-extern "C" int gg_ddim_step(float *x, const float *eps, int32_t eps_stride, const float *noise, const float *scalars_dev,
-                            int64_t M, int32_t C, float *pred_x0_out, void *unet_in, int32_t unet_in_stride, void *stream_)
+// -> x_prev before its noise term; p: the prediction of x_0
+template <int F>
+__device__ __forceinline__ float step_one(float xv, float ov, const float (&k)[4], int flags, float &p)
 {
-    if (!x || !eps || !scalars_dev) GG_FAIL(GG_ERR_BAD_SHAPE, "ddim_step: null pointer");
-    if (eps_stride < C || (unet_in && unet_in_stride < C)) GG_FAIL(GG_ERR_BAD_SHAPE, "ddim_step: stride < C");
-    long long total = (long long)M * C;
-    if (total <= 0) return GG_OK;
-    long long blocks = (total + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(ddim_step_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, x, eps, eps_stride, noise,
-                       scalars_dev, (long long)M, C, pred_x0_out, (bf16_t *)unet_in, unet_in_stride);
-    GG_CHECK_LAUNCH();
-    return GG_OK;
-}
-
-// ------------------------------------------------------------------------------------------------------------
-// Ancestral DDPM step (LatentDiffusion.p_sample, ldm/models/diffusion/ddpm.py:217-230,1060-1120), fp32, same order:
-//   x_recon = sqrt_recip_ac*x - sqrt_recipm1_ac*eps ; mean = coef1*x_recon + coef2*x ; x_prev = mean + sigma*noise
-//   scalars device fp32[5] = {sqrt_recip_alphas_cumprod[t], sqrt_recipm1_alphas_cumprod[t], posterior_mean_coef1[t],
-//                             posterior_mean_coef2[t], (t > 0) * exp(0.5*posterior_log_variance_clipped[t])}
-// ------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void ddpm_step_kernel(float *__restrict__ x, const float *__restrict__ eps, int eps_stride,
-                                                        const float *__restrict__ noise, const float *__restrict__ sc, long long M,
-                                                        int C, bf16_t *__restrict__ unet_in, int unet_in_stride)
-{
-#pragma clang fp contract(off)
-    const float a = sc[0], b = sc[1], c1 = sc[2], c2 = sc[3], sg = sc[4];
-    const long long total = M * C;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        const long long m = i / C;
-        const int c = (int)(i - m * C);
-        const float xv = x[i];
-        const float xr = a * xv - b * eps[m * eps_stride + c];
-        float xn = c1 * xr + c2 * xv;
-        if (noise) xn = xn + sg * noise[i];
-        x[i] = xn;
-        if (unet_in) unet_in[m * unet_in_stride + c] = (bf16_t)xn;
+    if constexpr (F == STEP_DDIM) {
+        p = ddim_pred_x0(xv, ov, k[0], k[1]);
+        return ddim_x_prev(p, ov, k[2], k[3]);
+    } else {
+        p = ddpm_x_recon(xv, ov, k[0], k[1], flags);
+        return ddpm_mean(p, xv, k[2], k[3]);
     }
 }
 
-extern "C" int gg_ddpm_step(float *x, const float *eps, int32_t eps_stride, const float *noise, const float *scalars_dev, int64_t M,
-                            int32_t C, void *unet_in, int32_t unet_in_stride, void *stream_)
+// Ancestral form at C == 4: one row per lane, 16-byte accesses of x / out / noise / pred_x0_out, one 8-byte bf16x4 store into the UNet
+// input (the layout of inpaint_blend_c4_kernel).  gg_ddpm_step_x0 alone launches it, after checking the alignment these accesses need:
+// the other entries run per element, which measured faster at the latent sizes.
+__global__ __launch_bounds__(256) void ddpm_step_c4_kernel(float *__restrict__ x, const float *__restrict__ out, int out_stride,
+                                                           const float *__restrict__ noise, const float *__restrict__ sc, int flags,
+                                                           long long M, float *__restrict__ pred_x0_out, bf16_t *__restrict__ unet_in,
+                                                           int unet_in_stride)
 {
-    if (!x || !eps || !scalars_dev) GG_FAIL(GG_ERR_BAD_SHAPE, "ddpm_step: null pointer");
-    if (eps_stride < C || (unet_in && unet_in_stride < C)) GG_FAIL(GG_ERR_BAD_SHAPE, "ddpm_step: stride < C");
-    long long total = (long long)M * C;
-    if (total <= 0) return GG_OK;
-    long long blocks = (total + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(ddpm_step_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, x, eps, eps_stride, noise, scalars_dev,
-                       (long long)M, C, (bf16_t *)unet_in, unet_in_stride);
-    GG_CHECK_LAUNCH();
-    return GG_OK;
-}
-
-// ------------------------------------------------------------------------------------------------------------
-// Ancestral step with the reference's options (ddpm.py:1072-1083 + p_sample :1109-1120): x0 parameterisation, clip_denoised, and
-// the prediction of x_0 as an output.  Same scalars and the same expression order as ddpm_step_kernel, so that flags == 0 gives its bits.
-// ------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float ddpm_step_x0_one(float xv, float ov, float a, float b, float c1, float c2, int flags, float &xr_out)
-{
-#pragma clang fp contract(off)
-    float xr = a * xv - b * ov;
-    if (flags & GG_DDPM_PREDICTS_X0) xr = ov;
-    if (flags & GG_DDPM_CLIP) xr = fminf(fmaxf(xr, -1.0f), 1.0f);
-    xr_out = xr;
-    return c1 * xr + c2 * xv;
-}
-
-// C == 4: one row per lane, 16-byte accesses of x / out / noise / pred_x0_out, one 8-byte bf16x4 store into the UNet input (the layout of
-// inpaint_blend_c4_kernel).  The host checks the alignment these accesses need.
-__global__ __launch_bounds__(256) void ddpm_step_x0_c4_kernel(float *__restrict__ x, const float *__restrict__ out, int out_stride,
-                                                              const float *__restrict__ noise, const float *__restrict__ sc, int flags,
-                                                              long long M, float *__restrict__ pred_x0_out, bf16_t *__restrict__ unet_in,
-                                                              int unet_in_stride)
-{
-#pragma clang fp contract(off)
-    const float a = sc[0], b = sc[1], c1 = sc[2], c2 = sc[3], sg = sc[4];
+    float k[4];
+    step_consts<STEP_ANCESTRAL>(sc, k);
+    const float kn = sc[4];
     for (long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x; m < M; m += (long long)gridDim.x * blockDim.x) {
         const f32x4 xv = *reinterpret_cast<const f32x4 *>(x + m * 4);
         const f32x4 ov = *reinterpret_cast<const f32x4 *>(out + m * out_stride);
@@ -230,11 +169,11 @@ __global__ __launch_bounds__(256) void ddpm_step_x0_c4_kernel(float *__restrict_
         f32x4 r, p;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            float xr;
-            float xn = ddpm_step_x0_one(xv[c], ov[c], a, b, c1, c2, flags, xr);
-            if (noise) xn = xn + sg * nv[c];
+            float pc;
+            float xn = step_one<STEP_ANCESTRAL>(xv[c], ov[c], k, flags, pc);
+            if (noise) xn = step_add_noise(xn, kn, nv[c]);
             r[c] = xn;
-            p[c] = xr;
+            p[c] = pc;
         }
         *reinterpret_cast<f32x4 *>(x + m * 4) = r;
         if (pred_x0_out) *reinterpret_cast<f32x4 *>(pred_x0_out + m * 4) = p;
@@ -247,24 +186,63 @@ __global__ __launch_bounds__(256) void ddpm_step_x0_c4_kernel(float *__restrict_
     }
 }
 
-__global__ __launch_bounds__(256) void ddpm_step_x0_kernel(float *__restrict__ x, const float *__restrict__ out, int out_stride,
-                                                           const float *__restrict__ noise, const float *__restrict__ sc, int flags,
-                                                           long long M, int C, float *__restrict__ pred_x0_out,
-                                                           bf16_t *__restrict__ unet_in, int unet_in_stride)
+template <int F>
+__global__ __launch_bounds__(256) void step_kernel(float *__restrict__ x, const float *__restrict__ out, int out_stride,
+                                                   const float *__restrict__ noise, const float *__restrict__ sc, int noise_idx, int flags,
+                                                   long long M, int C, float *__restrict__ pred_x0_out, bf16_t *__restrict__ unet_in,
+                                                   int unet_in_stride)
 {
-#pragma clang fp contract(off)
-    const float a = sc[0], b = sc[1], c1 = sc[2], c2 = sc[3], sg = sc[4];
+    float k[4];
+    step_consts<F>(sc, k);
+    const float kn = sc[noise_idx];
     const long long total = M * C;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
         const long long m = i / C;
         const int c = (int)(i - m * C);
-        float xr;
-        float xn = ddpm_step_x0_one(x[i], out[m * out_stride + c], a, b, c1, c2, flags, xr);
-        if (noise) xn = xn + sg * noise[i];
+        float p;
+        float xn = step_one<F>(x[i], out[m * out_stride + c], k, flags, p);
+        if (noise) xn = step_add_noise(xn, kn, noise[i]);
         x[i] = xn;
-        if (pred_x0_out) pred_x0_out[i] = xr;
+        if (pred_x0_out) pred_x0_out[i] = p;
         if (unet_in) unet_in[m * unet_in_stride + c] = (bf16_t)xn;
     }
+}
+
+template <int F>
+static int step_launch(float *x, const float *out, int out_stride, const float *noise, const float *scalars_dev, int noise_idx, int flags,
+                       long long M, int C, float *pred_x0_out, void *unet_in, int unet_in_stride, hipStream_t stream)
+{
+    if (M <= 0 || C <= 0) return GG_OK;
+    hipLaunchKernelGGL(step_kernel<F>, dim3(gg_blocks256(M * C, 4096)), dim3(256), 0, stream, x, out, out_stride, noise, scalars_dev, noise_idx,
+                       flags, M, C, pred_x0_out, (bf16_t *)unet_in, unet_in_stride);
+    GG_CHECK_LAUNCH();
+    return GG_OK;
+}
+
+int gg_step_launch(int ancestral, float *x, const float *out, int out_stride, const float *noise, const float *scalars_dev, int noise_idx,
+                   int flags, long long M, int C, float *pred_x0_out, void *unet_in, int unet_in_stride, hipStream_t stream)
+{
+    if (ancestral)
+        return step_launch<STEP_ANCESTRAL>(x, out, out_stride, noise, scalars_dev, noise_idx, flags, M, C, pred_x0_out, unet_in, unet_in_stride, stream);
+    return step_launch<STEP_DDIM>(x, out, out_stride, noise, scalars_dev, noise_idx, flags, M, C, pred_x0_out, unet_in, unet_in_stride, stream);
+}
+
+// scalars device fp32[4] = {a_t, a_prev, sigma_t, sqrt(1 - a_t)}: the noise coefficient is sigma_t
+extern "C" int gg_ddim_step(float *x, const float *eps, int32_t eps_stride, const float *noise, const float *scalars_dev,
+                            int64_t M, int32_t C, float *pred_x0_out, void *unet_in, int32_t unet_in_stride, void *stream_)
+{
+    if (!x || !eps || !scalars_dev) GG_FAIL(GG_ERR_BAD_SHAPE, "ddim_step: null pointer");
+    if (eps_stride < C || (unet_in && unet_in_stride < C)) GG_FAIL(GG_ERR_BAD_SHAPE, "ddim_step: stride < C");
+    return step_launch<STEP_DDIM>(x, eps, eps_stride, noise, scalars_dev, 2, 0, M, C, pred_x0_out, unet_in, unet_in_stride, (hipStream_t)stream_);
+}
+
+// scalars device fp32[5]: the ancestral row of gg_step.h
+extern "C" int gg_ddpm_step(float *x, const float *eps, int32_t eps_stride, const float *noise, const float *scalars_dev, int64_t M,
+                            int32_t C, void *unet_in, int32_t unet_in_stride, void *stream_)
+{
+    if (!x || !eps || !scalars_dev) GG_FAIL(GG_ERR_BAD_SHAPE, "ddpm_step: null pointer");
+    if (eps_stride < C || (unet_in && unet_in_stride < C)) GG_FAIL(GG_ERR_BAD_SHAPE, "ddpm_step: stride < C");
+    return step_launch<STEP_ANCESTRAL>(x, eps, eps_stride, noise, scalars_dev, 4, 0, M, C, nullptr, unet_in, unet_in_stride, (hipStream_t)stream_);
 }
 
 extern "C" int gg_ddpm_step_x0(float *x, const float *out, int32_t out_stride, const float *noise, const float *scalars_dev, int32_t flags,
@@ -274,39 +252,21 @@ extern "C" int gg_ddpm_step_x0(float *x, const float *out, int32_t out_stride, c
     if (C <= 0 || out_stride < C) GG_FAIL(GG_ERR_BAD_SHAPE, "ddpm_step_x0: out_stride %d < C=%d", out_stride, C);
     if (unet_in && unet_in_stride < C) GG_FAIL(GG_ERR_BAD_SHAPE, "ddpm_step_x0: unet_in_stride %d < C=%d", unet_in_stride, C);
     if (flags & ~(GG_DDPM_PREDICTS_X0 | GG_DDPM_CLIP)) GG_FAIL(GG_ERR_UNSUPPORTED, "ddpm_step_x0: unknown flag bits 0x%x", flags);
-    if (M <= 0) return GG_OK;
-    hipStream_t stream = (hipStream_t)stream_;
     const auto al = [](const void *p, uintptr_t n) { return ((uintptr_t)p & (n - 1)) == 0; };
     const bool vec = C == 4 && al(x, 16) && al(out, 16) && out_stride % 4 == 0 && (!noise || al(noise, 16)) &&
                      (!pred_x0_out || al(pred_x0_out, 16)) && (!unet_in || (al(unet_in, 8) && unet_in_stride % 4 == 0));
-    const long long work = vec ? (long long)M : (long long)M * C;
-    long long blocks = (work + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    if (vec)
-        hipLaunchKernelGGL(ddpm_step_x0_c4_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, x, out, out_stride, noise, scalars_dev,
-                           flags, (long long)M, pred_x0_out, (bf16_t *)unet_in, unet_in_stride);
-    else
-        hipLaunchKernelGGL(ddpm_step_x0_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, x, out, out_stride, noise, scalars_dev, flags,
-                           (long long)M, C, pred_x0_out, (bf16_t *)unet_in, unet_in_stride);
+    if (!vec || M <= 0)
+        return step_launch<STEP_ANCESTRAL>(x, out, out_stride, noise, scalars_dev, 4, flags, M, C, pred_x0_out, unet_in, unet_in_stride, (hipStream_t)stream_);
+    hipLaunchKernelGGL(ddpm_step_c4_kernel, dim3(gg_blocks256(M, 4096)), dim3(256), 0, (hipStream_t)stream_, x, out, out_stride, noise, scalars_dev,
+                       flags, (long long)M, pred_x0_out, (bf16_t *)unet_in, unet_in_stride);
     GG_CHECK_LAUNCH();
     return GG_OK;
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// Inpainting blend (ddim.py:144-148, plms.py:147-150, ddpm.py:1212-1214), fp32, the reference's operation order:
-//   o = s[0]*x0 + s[1]*noise  (q_sample, ddpm.py:275-278) ;  x <- o*mask + (1 - mask)*x
+// Inpainting blend x <- q_sample(x0, t, noise) * mask + (1 - mask) * x, fp32 (inpaint_blend_one of gg_step.h).
 // scalars device fp32[2] = {sqrt_alphas_cumprod[t], sqrt_one_minus_alphas_cumprod[t]}; mask has 1 or C channels.
 // ------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float inpaint_blend_one(float xv, float x0v, float nv, float mv, float a, float b)
-{
-#pragma clang fp contract(off)
-    const float t1 = a * x0v;
-    const float t2 = b * nv;
-    const float o = t1 + t2;
-    const float p = o * mv;
-    const float q = (1.0f - mv) * xv;
-    return p + q;
-}
 
 // C == 4 (the latent channels of every shipped config): one row per lane, 16-byte loads of x / x0 / noise (and of a 4-channel mask),
 // one 8-byte bf16x4 store into the UNet input.  The host checks the alignment these accesses need.
@@ -368,16 +328,15 @@ extern "C" int gg_inpaint_blend(float *x, const float *x0, const float *mask, in
     const bool vec = C == 4 && al(x, 16) && al(x0, 16) && al(noise, 16) && (mask_C == 1 || al(mask, 16)) &&
                      (!unet_in || (al(unet_in, 8) && unet_in_stride % 4 == 0));
     const long long work = vec ? (long long)M : (long long)M * C;
-    long long blocks = (work + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
+    const unsigned blocks = gg_blocks256(work, 4096);
     if (vec && mask_C == 4)
-        hipLaunchKernelGGL(inpaint_blend_c4_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, stream, x, x0, mask, noise, scalars_dev,
+        hipLaunchKernelGGL(inpaint_blend_c4_kernel<4>, dim3(blocks), dim3(256), 0, stream, x, x0, mask, noise, scalars_dev,
                            (long long)M, (bf16_t *)unet_in, unet_in_stride);
     else if (vec)
-        hipLaunchKernelGGL(inpaint_blend_c4_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, stream, x, x0, mask, noise, scalars_dev,
+        hipLaunchKernelGGL(inpaint_blend_c4_kernel<1>, dim3(blocks), dim3(256), 0, stream, x, x0, mask, noise, scalars_dev,
                            (long long)M, (bf16_t *)unet_in, unet_in_stride);
     else
-        hipLaunchKernelGGL(inpaint_blend_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, x, x0, mask, mask_C, noise, scalars_dev,
+        hipLaunchKernelGGL(inpaint_blend_kernel, dim3(blocks), dim3(256), 0, stream, x, x0, mask, mask_C, noise, scalars_dev,
                            (long long)M, C, (bf16_t *)unet_in, unet_in_stride);
     GG_CHECK_LAUNCH();
     return GG_OK;
@@ -406,33 +365,38 @@ extern "C" int gg_lincomb4(const float *e0, const float *e1, const float *e2, co
 {
     if (!e0 || !out) GG_FAIL(GG_ERR_BAD_SHAPE, "lincomb4: null pointer");
     if (n <= 0) return GG_OK;
-    long long blocks = (n + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(lincomb4_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, e0, e1, e2, e3, c0, c1, c2, c3, denom,
+    const unsigned blocks = gg_blocks256(n, 4096);
+    hipLaunchKernelGGL(lincomb4_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, e0, e1, e2, e3, c0, c1, c2, c3, denom,
                        (long long)n, out);
     GG_CHECK_LAUNCH();
     return GG_OK;
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// min-max normalisation over a whole tensor (ordered-uint atomics; deterministic)
+// min-max normalisation (ordered-uint atomics; deterministic): segment n = blockIdx.y of N holds n_per values, its min / max go to
+// ws[2 * n], ws[2 * n + 1].  A whole tensor is one segment.
 // ------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t f2ord(float f) { uint32_t b = __float_as_uint(f); return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }
 __device__ __forceinline__ float ord2f(uint32_t o) { return __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o); }
 
-__global__ void minmax_init_kernel(uint32_t *ws) { ws[0] = 0xFFFFFFFFu; ws[1] = 0u; }
-
-__global__ __launch_bounds__(256) void minmax_reduce_kernel(const float *__restrict__ src, long long n, uint32_t *ws)
+__global__ __launch_bounds__(256) void minmax_seg_init_kernel(uint32_t *ws, int N)
 {
+    for (int i = threadIdx.x; i < N; i += blockDim.x) { ws[2 * i] = 0xFFFFFFFFu; ws[2 * i + 1] = 0u; }
+}
+
+__global__ __launch_bounds__(256) void minmax_seg_reduce_kernel(const float *__restrict__ src, long long n_per, uint32_t *ws)
+{
+    const int n = blockIdx.y;
+    const float *s = src + (long long)n * n_per;
     float mn = INFINITY, mx = -INFINITY;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        float v = src[i];
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n_per; i += (long long)gridDim.x * blockDim.x) {
+        float v = s[i];
         mn = fminf(mn, v);
         mx = fmaxf(mx, v);
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) { mn = fminf(mn, __shfl_xor(mn, o)); mx = fmaxf(mx, __shfl_xor(mx, o)); }
-    if ((threadIdx.x & 63) == 0) { atomicMin(&ws[0], f2ord(mn)); atomicMax(&ws[1], f2ord(mx)); }
+    if ((threadIdx.x & 63) == 0) { atomicMin(&ws[2 * n], f2ord(mn)); atomicMax(&ws[2 * n + 1], f2ord(mx)); }
 }
 
 __global__ __launch_bounds__(256) void minmax_apply_kernel(const float *__restrict__ src, long long n, const uint32_t *ws,
@@ -450,11 +414,10 @@ extern "C" int gg_minmax_normalise(const float *src, int64_t n, float *dst, floa
     hipStream_t stream = (hipStream_t)stream_;
     if (!src || !dst || !workspace2) GG_FAIL(GG_ERR_BAD_SHAPE, "minmax_normalise: null pointer");
     if (n <= 0) return GG_OK;
-    long long blocks = (n + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(minmax_init_kernel, dim3(1), dim3(1), 0, stream, (uint32_t *)workspace2);
-    hipLaunchKernelGGL(minmax_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, src, (long long)n, (uint32_t *)workspace2);
-    hipLaunchKernelGGL(minmax_apply_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, src, (long long)n, (const uint32_t *)workspace2, dst);
+    const dim3 grid(gg_blocks256(n, 2048)), block(256);
+    hipLaunchKernelGGL(minmax_seg_init_kernel, dim3(1), block, 0, stream, (uint32_t *)workspace2, 1);
+    hipLaunchKernelGGL(minmax_seg_reduce_kernel, grid, block, 0, stream, src, (long long)n, (uint32_t *)workspace2);
+    hipLaunchKernelGGL(minmax_apply_kernel, grid, block, 0, stream, src, (long long)n, (const uint32_t *)workspace2, dst);
     GG_CHECK_LAUNCH();
     return GG_OK;
 }
@@ -477,27 +440,39 @@ __device__ __forceinline__ int zoom0_index(int o, double zf, int n_in)
     return i < 0 ? 0 : (i > n_in - 1 ? n_in - 1 : i);
 }
 
+struct MaskGrid {             // the label volume [N][Dm][Hm][Wm], the slice extent (H == W) and the three zoom factors
+    const int *labels;
+    int Dm, Hm, Wm, H, W;
+    double zd, zh, zw;
+};
+
+// One conditioning row: pixel r = i * W + j of sample n's slice `slice`; pv: that pixel of the previous generated slice.  Writes the
+// whole padded row and returns the mask value.
+__device__ __forceinline__ float mask_to_cond_row(const MaskGrid &g, int n, int slice, long long r, float pv, bf16_t *__restrict__ row, int stride)
+{
+    const int sd = zoom0_index(slice, g.zd, g.Dm);
+    const int j = (int)(r % g.W), i = (int)(r / g.W);
+    const int y = g.H - 1 - j, x = i;                     // rot90(k=3) on (H, W): out[i][j] = up[H-1-j][i]  (H == W)
+    const int sy = zoom0_index(y, g.zh, g.Hm), sx = zoom0_index(x, g.zw, g.Wm);
+    const int lab = g.labels[(((long long)n * g.Dm + sd) * g.Hm + sy) * g.Wm + sx];
+    const float mv = (float)lab / 255.0f;
+    bf16x8 o = {(bf16_t)pv, (bf16_t)mv, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f};
+    *reinterpret_cast<bf16x8 *>(row) = o;
+    bf16x8 z = {(bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f};
+    for (int c = 8; c < stride; c += 8) *reinterpret_cast<bf16x8 *>(row + c) = z;
+    return mv;
+}
+
 __global__ __launch_bounds__(256) void mask_to_cond_slice_kernel(const int *__restrict__ labels, int N, int Dm, int Hm, int Wm,
                                                                  int slice, int D, int H, int W, double zd, double zh, double zw,
                                                                  const float *__restrict__ prev, bf16_t *__restrict__ cond, int stride,
                                                                  float *__restrict__ mask_out)
 {
-    const long long total = (long long)N * H * W;
-    const int sd = zoom0_index(slice, zd, Dm);
+    const MaskGrid g{labels, Dm, Hm, Wm, H, W, zd, zh, zw};
+    const long long HW = (long long)H * W, total = (long long)N * HW;
     for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
-        int j = (int)(t % W);
-        int i = (int)((t / W) % H);
-        int n = (int)(t / ((long long)W * H));
-        int y = H - 1 - j, x = i;                         // rot90(k=3) on (H, W): out[i][j] = up[H-1-j][i]  (H == W)
-        int sy = zoom0_index(y, zh, Hm), sx = zoom0_index(x, zw, Wm);
-        int lab = labels[(((long long)n * Dm + sd) * Hm + sy) * Wm + sx];
-        float mv = (float)lab / 255.0f;
-        float pv = prev ? prev[t] : 0.f;
-        bf16_t *row = cond + t * stride;
-        bf16x8 o = {(bf16_t)pv, (bf16_t)mv, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f};
-        *reinterpret_cast<bf16x8 *>(row) = o;
-        bf16x8 z = {(bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f};
-        for (int c = 8; c < stride; c += 8) *reinterpret_cast<bf16x8 *>(row + c) = z;
+        const int n = (int)(t / HW);
+        const float mv = mask_to_cond_row(g, n, slice, t - n * HW, prev ? prev[t] : 0.f, cond + t * stride, stride);
         if (mask_out) mask_out[t] = mv;
     }
 }
@@ -514,9 +489,8 @@ extern "C" int gg_mask_to_cond_slice(const int32_t *labels, int32_t N, int32_t D
     if (slice < 0 || slice >= D) GG_FAIL(GG_ERR_BAD_SHAPE, "mask_to_cond_slice: slice %d outside [0,%d)", slice, D);
     if (N < 1 || Dm < 1 || Hm < 1 || Wm < 1) GG_FAIL(GG_ERR_BAD_SHAPE, "mask_to_cond_slice: empty label volume");
     long long total = (long long)N * H * W;
-    long long blocks = (total + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(mask_to_cond_slice_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, labels, N, Dm, Hm, Wm, slice,
+    const unsigned blocks = gg_blocks256(total, 4096);
+    hipLaunchKernelGGL(mask_to_cond_slice_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, labels, N, Dm, Hm, Wm, slice,
                        D, H, W, zoom0_factor(Dm, D), zoom0_factor(Hm, H), zoom0_factor(Wm, W), prev, (bf16_t *)cond_cl, stride, mask_out);
     GG_CHECK_LAUNCH();
     return GG_OK;
@@ -535,25 +509,14 @@ __global__ __launch_bounds__(256) void mask_to_cond_slices_kernel(const int *__r
 {
     const int it = iter_dev[0];
     if (it < 0 || it >= iterations) return;                // a schedule overrun writes nothing
+    const MaskGrid g{labels, Dm, Hm, Wm, H, W, zd, zh, zw};
     const long long HW = (long long)H * W, total = (long long)N * HW;
     for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
         const int n = (int)(t / HW);
         const long long r = t - n * HW;
         const int *row = sched + ((long long)it * N + n) * 3;
         const int slice = min(max(row[0], 0), D - 1), prev = min(max(row[1], 0), D - 1);
-        const int sd = zoom0_index(slice, zd, Dm);
-        int j = (int)(r % W);
-        int i = (int)(r / W);
-        int y = H - 1 - j, x = i;                         // rot90(k=3), as mask_to_cond_slice_kernel
-        int sy = zoom0_index(y, zh, Hm), sx = zoom0_index(x, zw, Wm);
-        int lab = labels[(((long long)n * Dm + sd) * Hm + sy) * Wm + sx];
-        float mv = (float)lab / 255.0f;
-        float pv = volume[((long long)prev * N + n) * HW + r];
-        bf16_t *crow = cond + t * stride;
-        bf16x8 o = {(bf16_t)pv, (bf16_t)mv, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f};
-        *reinterpret_cast<bf16x8 *>(crow) = o;
-        bf16x8 z = {(bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f};
-        for (int c = 8; c < stride; c += 8) *reinterpret_cast<bf16x8 *>(crow + c) = z;
+        mask_to_cond_row(g, n, slice, r, volume[((long long)prev * N + n) * HW + r], cond + t * stride, stride);
     }
 }
 
@@ -566,9 +529,8 @@ extern "C" int gg_mask_to_cond_slices(const int32_t *labels, int32_t N, int32_t 
     if (stride % 8 || stride < 8) GG_FAIL(GG_ERR_BAD_SHAPE, "mask_to_cond_slices: stride");
     if (N < 1 || Dm < 1 || Hm < 1 || Wm < 1 || D < 1 || H < 1 || iterations < 1) GG_FAIL(GG_ERR_BAD_SHAPE, "mask_to_cond_slices: empty extent");
     long long total = (long long)N * H * W;
-    long long blocks = (total + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(mask_to_cond_slices_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, labels, N, Dm, Hm, Wm, D, H, W,
+    const unsigned blocks = gg_blocks256(total, 4096);
+    hipLaunchKernelGGL(mask_to_cond_slices_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, labels, N, Dm, Hm, Wm, D, H, W,
                        zoom0_factor(Dm, D), zoom0_factor(Hm, H), zoom0_factor(Wm, W), schedule_dev, iterations, iter_dev, volume,
                        (bf16_t *)cond_cl, stride);
     GG_CHECK_LAUNCH();
@@ -578,26 +540,6 @@ extern "C" int gg_mask_to_cond_slices(const int32_t *labels, int32_t N, int32_t 
 // Segmented form of gg_minmax_normalise: sample n's min / max over its own n_per values (workspace [N][2], ordered uints), then
 // (src - mn) / den with the same operands and the same rounding, so that each segment is bit-equal to gg_minmax_normalise on that sample
 // alone.  The result goes to volume[slice_n][n] for the samples whose schedule row is active; the others are left untouched.
-__global__ __launch_bounds__(256) void minmax_seg_init_kernel(uint32_t *ws, int N)
-{
-    for (int i = threadIdx.x; i < N; i += blockDim.x) { ws[2 * i] = 0xFFFFFFFFu; ws[2 * i + 1] = 0u; }
-}
-
-__global__ __launch_bounds__(256) void minmax_seg_reduce_kernel(const float *__restrict__ src, long long n_per, uint32_t *ws)
-{
-    const int n = blockIdx.y;
-    const float *s = src + (long long)n * n_per;
-    float mn = INFINITY, mx = -INFINITY;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n_per; i += (long long)gridDim.x * blockDim.x) {
-        float v = s[i];
-        mn = fminf(mn, v);
-        mx = fmaxf(mx, v);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { mn = fminf(mn, __shfl_xor(mn, o)); mx = fmaxf(mx, __shfl_xor(mx, o)); }
-    if ((threadIdx.x & 63) == 0) { atomicMin(&ws[2 * n], f2ord(mn)); atomicMax(&ws[2 * n + 1], f2ord(mx)); }
-}
-
 __global__ __launch_bounds__(256) void minmax_seg_scatter_kernel(const float *__restrict__ src, int N, long long n_per, const uint32_t *ws,
                                                                  const int *__restrict__ sched, int iterations, const int *__restrict__ iter_dev,
                                                                  int depth, float *__restrict__ volume)
@@ -626,13 +568,11 @@ extern "C" int gg_minmax_normalise_scatter(const float *src, int32_t N, int64_t 
     hipStream_t stream = (hipStream_t)stream_;
     if (!src || !workspace2n || !schedule_dev || !iter_dev || !volume) GG_FAIL(GG_ERR_BAD_SHAPE, "minmax_normalise_scatter: null pointer");
     if (N < 1 || N > 65535 || n_per_sample <= 0 || depth < 1 || iterations < 1) GG_FAIL(GG_ERR_BAD_SHAPE, "minmax_normalise_scatter: bad extent");
-    long long bx = (n_per_sample + 255) / 256;
-    long long cap = 2048 / N > 1 ? 2048 / N : 1;           // about gg_minmax_normalise's grid over the whole batch
-    if (bx > cap) bx = cap;
+    const unsigned bx = gg_blocks256(n_per_sample, 2048 / N > 1 ? 2048 / N : 1);       // about gg_minmax_normalise's grid over the whole batch
     hipLaunchKernelGGL(minmax_seg_init_kernel, dim3(1), dim3(256), 0, stream, (uint32_t *)workspace2n, N);
-    hipLaunchKernelGGL(minmax_seg_reduce_kernel, dim3((unsigned)bx, (unsigned)N), dim3(256), 0, stream, src, (long long)n_per_sample,
+    hipLaunchKernelGGL(minmax_seg_reduce_kernel, dim3(bx, (unsigned)N), dim3(256), 0, stream, src, (long long)n_per_sample,
                        (uint32_t *)workspace2n);
-    hipLaunchKernelGGL(minmax_seg_scatter_kernel, dim3((unsigned)bx, (unsigned)N), dim3(256), 0, stream, src, N, (long long)n_per_sample,
+    hipLaunchKernelGGL(minmax_seg_scatter_kernel, dim3(bx, (unsigned)N), dim3(256), 0, stream, src, N, (long long)n_per_sample,
                        (const uint32_t *)workspace2n, schedule_dev, iterations, iter_dev, depth, volume);
     if (advance) hipLaunchKernelGGL(schedule_advance_kernel, dim3(1), dim3(1), 0, stream, iter_dev);
     GG_CHECK_LAUNCH();
@@ -683,9 +623,8 @@ extern "C" int gg_nchw_f32_to_cl_bf16(const float *src, int32_t N, int32_t C, in
     if (C_pad % 8 || c_offset < 0 || c_offset + C > C_pad) GG_FAIL(GG_ERR_BAD_SHAPE, "nchw_to_cl: C=%d offset=%d C_pad=%d", C, c_offset, C_pad);
     long long total = (long long)N * S * (C_pad / 8);
     if (total <= 0) return GG_OK;
-    long long blocks = (total + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(nchw_to_cl_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, src, N, C, (long long)S,
+    const unsigned blocks = gg_blocks256(total, 8192);
+    hipLaunchKernelGGL(nchw_to_cl_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, src, N, C, (long long)S,
                        (bf16_t *)dst, C_pad, c_offset, zero_fill);
     GG_CHECK_LAUNCH();
     return GG_OK;
@@ -712,13 +651,12 @@ extern "C" int gg_cl_to_nchw_f32(const void *src, int32_t src_dtype, int32_t N, 
     if (C > C_pad) GG_FAIL(GG_ERR_BAD_SHAPE, "cl_to_nchw: C > C_pad");
     long long total = (long long)N * C * S;
     if (total <= 0) return GG_OK;
-    long long blocks = (total + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
+    const unsigned blocks = gg_blocks256(total, 8192);
     if (src_dtype == GG_BF16)
-        hipLaunchKernelGGL(cl_to_nchw_kernel<bf16_t>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, (const bf16_t *)src, N, C,
+        hipLaunchKernelGGL(cl_to_nchw_kernel<bf16_t>, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, (const bf16_t *)src, N, C,
                            (long long)S, C_pad, dst);
     else if (src_dtype == GG_F32)
-        hipLaunchKernelGGL(cl_to_nchw_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, (const float *)src, N, C,
+        hipLaunchKernelGGL(cl_to_nchw_kernel<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, (const float *)src, N, C,
                            (long long)S, C_pad, dst);
     else
         GG_FAIL(GG_ERR_BAD_DTYPE, "cl_to_nchw: dtype");
@@ -734,9 +672,8 @@ extern "C" int gg_log_rows(const float *state, int32_t N, int32_t C, int64_t S, 
     if (N < 0 || C <= 0 || S < 0) GG_FAIL(GG_ERR_BAD_SHAPE, "log_rows: N=%d C=%d S=%lld", N, C, (long long)S);
     long long total = (long long)N * C * S;
     if (total <= 0) return GG_OK;
-    long long blocks = (total + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(cl_to_nchw_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, state, N, C, (long long)S, C, slot);
+    const unsigned blocks = gg_blocks256(total, 8192);
+    hipLaunchKernelGGL(cl_to_nchw_kernel<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, state, N, C, (long long)S, C, slot);
     GG_CHECK_LAUNCH();
     return GG_OK;
 }

@@ -19,6 +19,7 @@
 // staged and never read.  16 rows per block (not 64 or 256) because the chain's batch-1 latent has 4096 rows: 256 blocks keep every CU
 // busy, at the price of one pass over the codebook (L2-resident) per 16 rows.
 #include "gg_common.h"
+#include "gg_step.h"
 
 namespace {
 
@@ -55,14 +56,10 @@ __global__ __launch_bounds__(256) void vq_kernel(const float *rows, int row_stri
 
     // the row to quantise: loaded (VQ_NEAREST) or the step's prediction of x_0 (every lane of a row computes the same values)
     float z[C], xv[C], ev[C];
-    float k0 = 0.f, k1 = 0.f, k2 = 0.f, k3 = 0.f, k4 = 0.f;
+    float k0 = 0.f, k1 = 0.f, k2 = 0.f, k3 = 0.f, k4 = 0.f;                     // the step's constants (gg_step.h), k4 the noise coefficient
     if constexpr (MODE == VQ_DDIM) {
-        // ddim.py:190-204: scalars {a_t, a_prev, sigma_t, sqrt(1 - a_t), noise coefficient}
-        const float a_t = s.sc[0], a_prev = s.sc[1], sigma = s.sc[2];
         k0 = s.sc[3];                                   // sqrt(1 - a_t)
-        k1 = sqrtf(a_t);
-        k2 = sqrtf(a_prev);
-        k3 = sqrtf(1.0f - a_prev - sigma * sigma);      // dir_xt uses sigma_t unscaled by the temperature
+        ddim_roots(s.sc[0], s.sc[1], s.sc[2], k1, k2, k3);
         k4 = s.sc[4];
     } else if constexpr (MODE == VQ_ANCESTRAL) {
         k0 = s.sc[0]; k1 = s.sc[1]; k2 = s.sc[2]; k3 = s.sc[3]; k4 = s.sc[4];
@@ -78,8 +75,8 @@ __global__ __launch_bounds__(256) void vq_kernel(const float *rows, int row_stri
                 xv[c] = s.x[m * C + c];
                 ev[c] = s.eps[m * s.eps_stride + c];
             }
-            if constexpr (MODE == VQ_DDIM) z[c] = (xv[c] - k0 * ev[c]) / k1;
-            else z[c] = k0 * xv[c] - k1 * ev[c];
+            if constexpr (MODE == VQ_DDIM) z[c] = ddim_pred_x0(xv[c], ev[c], k0, k1);
+            else z[c] = ddpm_x_recon(xv[c], ev[c], k0, k1, 0);
         }
     }
     float zz = z[0] * z[0];
@@ -126,11 +123,8 @@ __global__ __launch_bounds__(256) void vq_kernel(const float *rows, int row_stri
     float q[C];
 #pragma unroll
     for (int c = 0; c < C; ++c) {
-        q[c] = z[c];
-        if (n_embed > 0) {                               // n_embed == 0: the step without a quantiser
-            const float t = E[(long long)bi * C + c] - z[c];
-            q[c] = z[c] + t;
-        }
+        const float t = E[(long long)bi * C + c] - z[c];
+        q[c] = z[c] + t;
     }
     if (idx_out) idx_out[m] = bi;
     if constexpr (MODE == VQ_NEAREST) {
@@ -142,9 +136,9 @@ __global__ __launch_bounds__(256) void vq_kernel(const float *rows, int row_stri
 #pragma unroll
         for (int c = 0; c < C; ++c) {
             float xn;
-            if constexpr (MODE == VQ_DDIM) xn = k2 * q[c] + k3 * ev[c];
-            else xn = k2 * q[c] + k3 * xv[c];
-            if (s.noise) xn = xn + k4 * s.noise[m * C + c];
+            if constexpr (MODE == VQ_DDIM) xn = ddim_x_prev(q[c], ev[c], k2, k3);
+            else xn = ddpm_mean(q[c], xv[c], k2, k3);
+            if (s.noise) xn = step_add_noise(xn, k4, s.noise[m * C + c]);
             s.x[m * C + c] = xn;
             if (s.pred_x0) s.pred_x0[m * C + c] = q[c];
             if (s.unet_in) s.unet_in[m * s.unet_in_stride + c] = (bf16_t)xn;
@@ -198,6 +192,9 @@ extern "C" int gg_ddim_step_vq(float *x, const float *eps, int32_t eps_stride, c
     if (idx_out && n_embed == 0) GG_FAIL(GG_ERR_BAD_SHAPE, "ddim_step_vq: idx_out without a codebook");
     if (eps_stride < C || (unet_in && unet_in_stride < C)) GG_FAIL(GG_ERR_BAD_SHAPE, "ddim_step_vq: stride < C");
     if (M <= 0) return GG_OK;
+    if (n_embed == 0)                                    // nothing to quantise: the pointwise step, its noise coefficient the fifth scalar
+        return gg_step_launch(ancestral, x, eps, eps_stride, noise, scalars_dev, 4, 0, (long long)M, C, pred_x0_out, unet_in, unet_in_stride,
+                              (hipStream_t)stream_);
     VqStep s{x, eps, noise, scalars_dev, pred_x0_out, (bf16_t *)unet_in, eps_stride, unet_in_stride};
     if (ancestral)
         return vq_launch<VQ_ANCESTRAL>(C, nullptr, 0, codebook, n_embed, (long long)M, idx_out, nullptr, 0, s, (hipStream_t)stream_);

@@ -29,6 +29,41 @@ from .config import instantiate_from_config
 from .ops import CL, pad32
 
 
+def nc_to_rows(t: torch.Tensor) -> torch.Tensor:
+    """[N, C, *sp] -> [N, *sp, C], the channels-last view (a permutation, no copy)."""
+    return t.permute((0,) + tuple(range(2, t.ndim)) + (1,))
+
+
+def rows_to_nc(t: torch.Tensor) -> torch.Tensor:
+    """[N, *sp, C] -> [N, C, *sp], the inverse view."""
+    return t.permute((0, t.ndim - 1) + tuple(range(1, t.ndim - 1)))
+
+
+def cut_cond(cond, batch_size: int):
+    """The conditioning cut to the batch (ddpm.py:1237-1242): a tensor, a list of tensors, or a dict of either."""
+    if cond is None:
+        return None
+    if isinstance(cond, dict):
+        return {key: cond[key][:batch_size] if not isinstance(cond[key], list) else [c[:batch_size] for c in cond[key]] for key in cond}
+    return [c[:batch_size] for c in cond] if isinstance(cond, list) else cond[:batch_size]
+
+
+def split_cond(conditioning, conditioning_key):
+    """-> (c_concat, context) of a conditioning: a dict as the reference's apply_model takes it (c_concat's first entry, c_crossattn
+    concatenated), or a bare tensor read by the model's conditioning key."""
+    c_concat, context = None, None
+    if conditioning is not None:
+        if isinstance(conditioning, dict):
+            c_concat = conditioning.get("c_concat", [None])[0]
+            cc = conditioning.get("c_crossattn")
+            context = torch.cat(cc, 1) if cc else None
+        elif conditioning_key == "concat":
+            c_concat = conditioning
+        elif conditioning_key == "crossattn":
+            context = conditioning
+    return c_concat, context
+
+
 # ================================================================================================ autoencoder
 class DiagonalGaussianDistribution:
     """moments = [mean | logvar] on dim 1; logvar clamped to [-30, 20] (distributions.py:24-33)."""
@@ -277,10 +312,9 @@ class VectorQuantizer(nn.Module):
         ops.require_gpu(z, "VectorQuantizer.forward")
         if z.shape[1] != self.e_dim:
             raise ValueError(f"VectorQuantizer: z has {z.shape[1]} channels, the codebook has e_dim = {self.e_dim}")
-        nd = z.ndim - 2
-        cl = z.float().permute((0,) + tuple(range(2, nd + 2)) + (1,)).contiguous()                  # plumbing: layout copy
+        cl = nc_to_rows(z.float()).contiguous()                                                     # plumbing: layout copy
         idx, st = self.quantize_rows(cl)
-        quant = st.view(cl.shape).permute((0, nd + 1) + tuple(range(1, nd + 1))).contiguous()
+        quant = rows_to_nc(st.view(cl.shape)).contiguous()
         return quant, None, (None, None, idx.long().view(-1, 1))
 
     def get_codebook_entry(self, indices, shape):
@@ -288,8 +322,7 @@ class VectorQuantizer(nn.Module):
         height, width] (taming's method is 2-D only; volumes follow the same rule)."""
         z_q = self.embedding(indices.reshape(-1).long())
         if shape is not None:
-            nd = len(shape) - 2
-            z_q = z_q.view(shape).permute((0, nd + 1) + tuple(range(1, nd + 1))).contiguous()
+            z_q = rows_to_nc(z_q.view(shape)).contiguous()
         return z_q
 
     def embed_code(self, code_b):
@@ -357,7 +390,7 @@ class VQModel(nn.Module):
         Cp, nd = h.Cpad, self.dims
         sp = tuple(h.t.shape[4 - nd:4])
         idx, st = self.quantize.quantize_rows(h.t.view(-1, Cp))        # the padded fp32 rows are read in place
-        quant = st.view((h.N,) + sp + (self.embed_dim,)).permute((0, nd + 1) + tuple(range(1, nd + 1))).contiguous()
+        quant = rows_to_nc(st.view((h.N,) + sp + (self.embed_dim,))).contiguous()
         return quant, None, (None, None, idx.long().view(-1, 1))
 
     def decode(self, quant: torch.Tensor) -> torch.Tensor:
@@ -862,11 +895,9 @@ class GaussianDiffusion(nn.Module):
             raise ValueError(f"{who}: noise_dropout = {noise_dropout} outside [0, 1)")
         dev = self.device
         unet = self.model.diffusion_model
-        ck = self.model.conditioning_key
         N, Cx = shape[0], shape[1]
         sp = tuple(shape[2:])
         sp3 = (1,) * (3 - len(sp)) + sp
-        nd = len(sp)
         if mask is not None and x0 is not None and tuple(x0.shape[2:3]) != tuple(mask.shape[2:3]):
             raise ValueError(f"{who}: x0 {tuple(x0.shape)} and mask {tuple(mask.shape)} differ in spatial size "
                              "(ddpm.py:1200 asserts x0.shape[2:3] == mask.shape[2:3])")
@@ -879,16 +910,10 @@ class GaussianDiffusion(nn.Module):
             per_step_temp = [float(v) for v in temperature]
         elif float(temperature) != 1.0:
             per_step_temp = [float(temperature)] * T
-        c_concat = cond if (cond is not None and ck == "concat" and not isinstance(cond, dict)) else \
-            (cond.get("c_concat", [None])[0] if isinstance(cond, dict) else None)
-        context = cond if (cond is not None and ck == "crossattn" and not isinstance(cond, dict)) else None
-        if isinstance(cond, dict) and cond.get("c_crossattn"):        # hybrid / explicit dicts: the reference's apply_model passes them through
-            context = torch.cat(cond["c_crossattn"], 1)
+        c_concat, context = split_cond(cond, self.model.conditioning_key)
         Cc = c_concat.shape[1] if c_concat is not None else 0
-        perm = (0,) + tuple(range(2, nd + 2)) + (1,)
-        back = (0, nd + 1) + tuple(range(1, nd + 1))
         img = torch.randn(tuple(shape), device=dev) if x_T is None else x_T.to(dev).float()
-        x = img.permute(perm).contiguous().view((N,) + sp3 + (Cx,))
+        x = nc_to_rows(img).contiguous().view((N,) + sp3 + (Cx,))
         unet_in = torch.zeros((N,) + sp3 + (pad32(Cx + Cc),), dtype=torch.bfloat16, device=dev)
         ops.to_cl(img, out=unet_in, c_offset=0, zero_fill=False)
         if c_concat is not None:
@@ -912,8 +937,8 @@ class GaussianDiffusion(nn.Module):
         log = torch.empty((len(logged), N, Cx) + sp, dtype=torch.float32, device=dev) if logged else None      # the pre-allocated log buffer
         slot = {t: j for j, t in enumerate(logged)}
         if ip is not None:
-            x0_cl = ip[0].to(dev).permute(perm).contiguous()
-            mask_cl = ip[1].to(dev).permute(perm).contiguous()
+            x0_cl = nc_to_rows(ip[0].to(dev)).contiguous()
+            mask_cl = nc_to_rows(ip[1].to(dev)).contiguous()
             qscal = torch.stack([self.sqrt_alphas_cumprod[ts], self.sqrt_one_minus_alphas_cumprod[ts]], 1).contiguous()
         for i in range(T):
             t = T - 1 - i
@@ -924,7 +949,7 @@ class GaussianDiffusion(nn.Module):
             if noise_dropout > 0.0:
                 nz = torch.nn.functional.dropout(nz, p=float(noise_dropout))
             if noise_tape is not None:
-                nz = nz.permute(perm).contiguous()
+                nz = nc_to_rows(nz).contiguous()
             if vq_split:
                 # x_recon (x0 / clip) on a scratch copy of x -> quantised in place -> the posterior mean and noise with x_recon given
                 x_keep.copy_(x)
@@ -940,15 +965,15 @@ class GaussianDiffusion(nn.Module):
             else:
                 ops.ddpm_step(x.view(M, Cx), eps.view(M, -1), scal[i], noise=nz.view(M, Cx), unet_in=unet_in.view(M, -1))
             if ip is not None:
-                nm = mask_noise_tape[i].to(dev).float().permute(perm).contiguous() if mask_noise_tape is not None else torch.randn_like(x)
+                nm = nc_to_rows(mask_noise_tape[i].to(dev).float()).contiguous() if mask_noise_tape is not None else torch.randn_like(x)
                 ops.inpaint_blend(x.view(M, Cx), x0_cl.view(M, Cx), mask_cl.view(M, -1), nm.view(M, Cx), qscal[i], unet_in=unet_in.view(M, -1))
             if t in slot:
                 ops.log_rows((p0 if log_x0 else x).view(M, Cx), N, log[slot[t]])
             if callback:
                 callback(t)
             if img_callback:
-                img_callback(x.view((N,) + sp + (Cx,)).permute(back).contiguous(), t)
-        out = x.view((N,) + sp + (Cx,)).permute(back).contiguous()
+                img_callback(rows_to_nc(x.view((N,) + sp + (Cx,))).contiguous(), t)
+        out = rows_to_nc(x.view((N,) + sp + (Cx,))).contiguous()
         return out, img, (list(log.unbind(0)) if logged else [])
 
 
@@ -1329,11 +1354,7 @@ class LatentDiffusion(GaussianDiffusion):
             shape = [batch_size] + list(shape)
         else:
             batch_size = shape[0]
-        if cond is not None:
-            if isinstance(cond, dict):
-                cond = {key: cond[key][:batch_size] if not isinstance(cond[key], list) else [c[:batch_size] for c in cond[key]] for key in cond}
-            else:
-                cond = [c[:batch_size] for c in cond] if isinstance(cond, list) else cond[:batch_size]
+        cond = cut_cond(cond, batch_size)
         if start_T is not None:
             T = min(T, start_T)
         out, _, log = self._ancestral_loop("progressive_denoising", cond, tuple(shape), x_T=x_T, T=T, quantize_denoised=quantize_denoised,
@@ -1367,11 +1388,7 @@ class LatentDiffusion(GaussianDiffusion):
         spatial extent there, which no caller of this package reaches with a meaningful result."""
         if shape is None:
             shape = (batch_size, self.channels) + (self.image_size if isinstance(self.image_size, tuple) else (self.image_size,) * self.dims)
-        if cond is not None:
-            if isinstance(cond, dict):
-                cond = {key: cond[key][:batch_size] if not isinstance(cond[key], list) else [c[:batch_size] for c in cond[key]] for key in cond}
-            else:
-                cond = [c[:batch_size] for c in cond] if isinstance(cond, list) else cond[:batch_size]
+        cond = cut_cond(cond, batch_size)
         return self.p_sample_loop(cond, shape, return_intermediates=return_intermediates, x_T=x_T, verbose=verbose, timesteps=timesteps,
                                   quantize_denoised=quantize_denoised, mask=mask, x0=x0, noise_tape=noise_tape, mask_noise_tape=mask_noise_tape)
 
@@ -1652,20 +1669,6 @@ class DDIMSampler(object):
         return z, {"x_inter": [img] + logs[0], "pred_x0": [img] + logs[1]}
 
     # ---- channels-last fast path -------------------------------------------------------------------------
-    def _split_cond(self, conditioning):
-        ck = self.model.model.conditioning_key
-        c_concat, context = None, None
-        if conditioning is not None:
-            if isinstance(conditioning, dict):
-                c_concat = conditioning.get("c_concat", [None])[0]
-                cc = conditioning.get("c_crossattn")
-                context = torch.cat(cc, 1) if cc else None
-            elif ck == "concat":
-                c_concat = conditioning
-            elif ck == "crossattn":
-                context = conditioning
-        return c_concat, context
-
     def _sample_cl(self, x_T: torch.Tensor, conditioning, eta: float, noise_tape, cfg=None, inpaint=None, mask_noise_tape=None, *, vq=None,
                    noise_dropout=0.0, logged=None, callbacks=None):
         model = self.model
@@ -1674,8 +1677,7 @@ class DDIMSampler(object):
         dev = x_T.device
         N, Cx = x_T.shape[:2]
         sp = tuple(x_T.shape[2:])
-        nd = len(sp)
-        c_concat, context = self._split_cond(conditioning)
+        c_concat, context = split_cond(conditioning, ck)
         st = self.prepare_state(N, Cx, sp, dev, c_concat.shape[1] if c_concat is not None else 0,
                                 ctx_shape=tuple(context.shape[1:]) if context is not None else None, mask_C=inpaint[2] if inpaint else 0, vq=vq,
                                 logged=logged)
@@ -1690,9 +1692,8 @@ class DDIMSampler(object):
                 self.run_steps(st, st["ctx"], eta, noise_tape, noise_dropout)
         finally:
             st["callbacks"] = None
-        perm = (0, nd + 1) + tuple(range(1, nd + 1))
-        z = st["x"].view((N,) + sp + (Cx,)).permute(perm).contiguous()
-        p0 = st["pred_x0"].view((N,) + sp + (Cx,)).permute(perm).contiguous()
+        z = rows_to_nc(st["x"].view((N,) + sp + (Cx,))).contiguous()
+        p0 = rows_to_nc(st["pred_x0"].view((N,) + sp + (Cx,))).contiguous()
         logs = None
         if logged is not None:                           # copies: the state's log buffers are rewritten by the next logged call
             logs = (list(st["log_x"].clone().unbind(0)), list(st["log_p0"].clone().unbind(0)))
@@ -1764,9 +1765,7 @@ class DDIMSampler(object):
         [N, L, C] -> the state's channels-last context buffer."""
         if context is not None:
             ops.to_cl(context.permute(0, 2, 1).contiguous().float(), out=st["ctx"].t, c_offset=0, zero_fill=False)
-        nd = x_T.ndim - 2
-        perm = (0,) + tuple(range(2, nd + 2)) + (1,)
-        st["x"].view((st["N"],) + tuple(x_T.shape[2:]) + (st["Cx"],)).copy_(x_T.permute(perm))        # plumbing: layout copy
+        st["x"].view((st["N"],) + tuple(x_T.shape[2:]) + (st["Cx"],)).copy_(nc_to_rows(x_T))          # plumbing: layout copy
         ops.to_cl(x_T, out=st["unet_in"], c_offset=0, zero_fill=False)
         if c_concat is not None:
             ops.to_cl(c_concat.float(), out=st["unet_in"], c_offset=st["Cx"], zero_fill=False)
@@ -1784,13 +1783,12 @@ class DDIMSampler(object):
         dev = st["x"].device
         sp = tuple(x0.shape[2:])
         nd = len(sp)
-        perm = (0,) + tuple(range(2, nd + 2)) + (1,)
-        st["ip_x0"].view((N,) + sp + (Cx,)).copy_(x0.to(dev).permute(perm))            # plumbing: layout copies
-        st["ip_mask"].view((N,) + sp + (mask.shape[1],)).copy_(mask.to(dev).permute(perm))
+        st["ip_x0"].view((N,) + sp + (Cx,)).copy_(nc_to_rows(x0.to(dev)))              # plumbing: layout copies
+        st["ip_mask"].view((N,) + sp + (mask.shape[1],)).copy_(nc_to_rows(mask.to(dev)))
         noise = st["ip_noise"].view((S, N) + sp + (Cx,))
         if mask_noise_tape is not None:
             for i in range(S):
-                noise[i].copy_(mask_noise_tape[i].to(dev).float().permute(perm))
+                noise[i].copy_(nc_to_rows(mask_noise_tape[i].to(dev).float()))
         else:
             noise.copy_(torch.randn((S, N, Cx) + sp, device=dev).permute((0, 1) + tuple(range(3, nd + 3)) + (2,)))
 
@@ -1840,8 +1838,7 @@ class DDIMSampler(object):
             nt = noise_tape[i].to(st["x"].device).float()
             if p > 0.0:
                 nt = torch.nn.functional.dropout(nt, p=p)
-            nd = nt.ndim - 2
-            return nt.permute((0,) + tuple(range(2, nd + 2)) + (1,)).contiguous()
+            return nc_to_rows(nt).contiguous()
         if eta != 0.0:
             noise = torch.randn_like(st["x"])
             return torch.nn.functional.dropout(noise, p=p) if p > 0.0 else noise
@@ -1865,7 +1862,7 @@ class DDIMSampler(object):
         every layer of the UNet is per sample, so two evaluations on the same x with the two conditionings give the same two halves.
         Eager (off the timed path); the update kernel refreshes the conditional UNet input, the unconditional one copies x from it."""
         unet = self.model.model.diffusion_model
-        uc_concat, uc_ctx = self._split_cond(cfg[0])
+        uc_concat, uc_ctx = split_cond(cfg[0], self.model.model.conditioning_key)
         scale = cfg[1]
         Cx, Cc = st["Cx"], st["Cc"]
         M = st["x"].numel() // Cx

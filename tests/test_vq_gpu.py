@@ -1,5 +1,5 @@
 """GPU suite for the VQ first stage and quantised sampling (gg_vq.hip): gg_vq_nearest bit for bit against the fp64 restatement on inputs
-whose fp32 arithmetic is exact, and on random inputs outside near-ties; gg_ddim_step_vq against the same step as separate fp32 torch ops;
+whose fp32 arithmetic is exact, and on random inputs outside near-ties; gg_ddim_step_vq and gg_ddim_step against the same step as separate fp32 torch ops;
 the quantised DDIM chain teacher-forced, captured and eager; VQModelInterface against the reference fixture (tests/golden/vq.npz,
 make_golden_vq.py); temperature and noise_dropout.
 
@@ -199,6 +199,76 @@ def test_ancestral_step_vq_equals_the_separate_torch_ops(dev):
     xs3 = x.clone()
     ops.ddpm_step(xs3, e.contiguous(), sc, noise=nz)
     assert torch.equal(xs2, xs3)
+
+
+def ddim_scalars(eta, dev):
+    """The scalar row of test_ddim_step_vq_equals_the_separate_torch_ops (vq_ref is written around these roots), fp32[4]."""
+    a_t, a_prev = 0.6132, 0.6811
+    sigma = eta * float(np.sqrt((1 - a_prev) / (1 - a_t) * (1 - a_t / a_prev)))
+    return torch.tensor([a_t, a_prev, sigma, float(np.sqrt(1 - a_t))], dtype=torch.float32).to(dev)
+
+
+def ddim_want(x, e, sc, noise):
+    """gg_ddim_step's result as separate torch ops: the step of vq_ref without a codebook, its noise coefficient sigma_t."""
+    want_x, want_p, _, _, _ = vq_ref.ddim_step_vq(x, e, torch.cat([sc, sc[2:3]]), None, noise)
+    return want_x, want_p
+
+
+@pytest.mark.parametrize("eta", [0.0, 0.6])
+@pytest.mark.parametrize("C", [4, 3], ids=["C4", "C3"])
+@pytest.mark.parametrize("M", [1000, 4099])
+def test_ddim_step_is_bit_equal_to_the_torch_expression(dev, M, C, eta):
+    from jointimagegeneration_amd import ops
+    gen = torch.Generator().manual_seed(17 * M + C)
+    x0_, e, nz = (torch.randn(M, C, generator=gen).to(dev) for _ in range(3))
+    eps = torch.full((M, 32), 55.0, device=dev)
+    eps[:, :C] = e
+    sc = ddim_scalars(eta, dev)
+    for with_noise in (True, False):
+        want_x, want_p = ddim_want(x0_, e, sc, nz if with_noise else None)
+        for with_p0 in (True, False):
+            for with_uin in (True, False):
+                x = x0_.clone()
+                p0 = torch.full((M, C), 9.0, device=dev) if with_p0 else None
+                uin = torch.full((M, 32), 7.0, dtype=torch.bfloat16, device=dev) if with_uin else None      # pad lanes: a sentinel that must survive
+                ops.ddim_step(x, eps, sc, noise=nz if with_noise else None, pred_x0_out=p0, unet_in=uin)
+                torch.cuda.synchronize()
+                tag = (with_noise, with_p0, with_uin)
+                assert torch.equal(x, want_x), tag
+                if with_p0:
+                    assert torch.equal(p0, want_p), tag
+                if with_uin:
+                    assert torch.equal(uin[:, :C], want_x.bfloat16()) and bool((uin[:, C:] == 7.0).all()), tag
+
+
+def test_ddim_step_misaligned_rows_give_the_same_bits(dev):
+    """gg_ddim_step has no path that depends on alignment, and this pins it: the two misaligned views of the gg_ddpm_step_x0 suite
+    (tests/test_progressive_gpu.py), x one row into a C = 3 buffer (12 bytes off any 16-byte boundary) and C = 4 rows one float in with a
+    unet_in stride that is no multiple of 4, give the bits of the torch expression and touch nothing in front of the views."""
+    from jointimagegeneration_amd import ops
+    sc = ddim_scalars(0.6, dev)
+    gen = torch.Generator(device=dev).manual_seed(78)
+    M = 4099
+    buf = torch.randn(M + 1, 3, device=dev, generator=gen)
+    x, row0 = buf[1:], buf[0].clone()
+    assert x.data_ptr() % 16 != 0 and x.is_contiguous()
+    eps, noise = torch.randn(M, 5, device=dev, generator=gen), torch.randn(M, 3, device=dev, generator=gen)
+    want_x, want_p = ddim_want(x.clone(), eps[:, :3].contiguous(), sc, noise)
+    p0, uin = torch.empty(M, 3, device=dev), torch.full((M, 6), -3.0, dtype=torch.bfloat16, device=dev)
+    ops.ddim_step(x, eps, sc, noise=noise, pred_x0_out=p0, unet_in=uin)
+    torch.cuda.synchronize()
+    assert torch.equal(x, want_x) and torch.equal(p0, want_p) and torch.equal(uin[:, :3], want_x.bfloat16()) and bool((uin[:, 3:] == -3.0).all())
+    assert torch.equal(buf[0], row0)                         # the row in front of the view is not touched
+    flat = torch.randn(3, M * 4 + 1, device=dev, generator=gen)
+    col0 = flat[:, 0].clone()
+    x, noise, p0 = (flat[i, 1:].view(M, 4) for i in range(3))
+    eps = torch.randn(M, 4, device=dev, generator=gen)
+    want_x, want_p = ddim_want(x.clone(), eps, sc, noise.clone())
+    uin = torch.full((M, 6), -3.0, dtype=torch.bfloat16, device=dev)
+    ops.ddim_step(x, eps, sc, noise=noise, pred_x0_out=p0, unet_in=uin)
+    torch.cuda.synchronize()
+    assert torch.equal(x, want_x) and torch.equal(p0, want_p) and torch.equal(uin[:, :4], want_x.bfloat16()) and bool((uin[:, 4:] == -3.0).all())
+    assert torch.equal(flat[:, 0], col0)
 
 
 # ------------------------------------------------------------------------------------------------ 4. chains
