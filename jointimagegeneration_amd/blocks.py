@@ -116,46 +116,53 @@ def gn_params(norm: nn.GroupNorm):
     return f32(norm.weight), f32(norm.bias), norm.eps
 
 
-def gn_silu(h: CL, norm: nn.GroupNorm, act: bool, src2: Optional[CL] = None) -> CL:
-    if ops.is_f32(h.t):                      # fp32 validation path
-        return ops.groupnorm_f32(h, *gn_params(norm), act, src2)
-    if ops.groupnorm_fused_ok(h, src2):     # small tensor: statistics + apply in one launch
+# The GroupNorm kernel-choice ladder, one implementation per arm (gn_silu, norm_conv, the down ResBlock).  fp32 validation arm: a separate launch
+def _gn_f32(h: CL, norm: nn.GroupNorm, act: bool, src2: Optional[CL] = None, film: Optional[torch.Tensor] = None) -> CL:
+    return ops.groupnorm_f32_film(h, *gn_params(norm), film, act) if film is not None else ops.groupnorm_f32(h, *gn_params(norm), act, src2)
+
+
+def _gn_direct(h: CL, norm: nn.GroupNorm, act: bool, src2: Optional[CL]) -> Optional[CL]:
+    """No coefficient table: statistics + apply in ONE launch (small tensors), else apply from the producers' accumulators, else None"""
+    if ops.groupnorm_fused_ok(h, src2):
         return ops.groupnorm_fused(h, *gn_params(norm), act, src2)
-    if ops.has_stats(h, src2):      # the producing convs already left the per-channel sums: no statistics launch
-        return ops.groupnorm_apply_acc(h, *gn_params(norm), act, src2)
-    scale, shift = ops.groupnorm_stats(h, *gn_params(norm), src2)
-    return ops.groupnorm_apply(h, scale, shift, act, src2)
+    return ops.groupnorm_apply_acc(h, *gn_params(norm), act, src2) if ops.has_stats(h, src2) else None
+
+
+def _gn_coeffs(h: CL, norm: nn.GroupNorm, src2: Optional[CL] = None, film: Optional[torch.Tensor] = None, fold_acc: bool = True):
+    """Per-(n, c) (scale, shift): the producers' accumulators folded (halo-tile producers: not 17..805 MB re-read) or a statistics pass; FiLM"""
+    stats = ops.groupnorm_scale_shift_acc if fold_acc and ops.has_any_stats(h, src2) else ops.groupnorm_stats
+    scale, shift = stats(h, *gn_params(norm), src2)
+    if film is not None:
+        ops.film_fold(scale, shift, film, h.C)
+    return scale, shift
+
+
+def gn_silu(h: CL, norm: nn.GroupNorm, act: bool, src2: Optional[CL] = None) -> CL:
+    a = _gn_f32(h, norm, act, src2) if ops.is_f32(h.t) else _gn_direct(h, norm, act, src2)
+    # nothing to apply from: ALWAYS a statistics pass here, also where 32-stripe accumulators exist (norm_conv folds those instead;
+    # the asymmetry is kept as it was: removing it changes which kernels run)
+    return a if a is not None else ops.groupnorm_apply(h, *_gn_coeffs(h, norm, src2, fold_acc=False), act, src2)
 
 
 def norm_conv(h: CL, norm: nn.GroupNorm, act: bool, weight, bias, cout, src2: Optional[CL] = None, film: Optional[torch.Tensor] = None,
               **conv_kw) -> CL:
     """conv(act(GroupNorm(cat[h, src2]))), or with film (fp32 [N, >= 2C] rows [s | t], use_scale_shift_norm)
-    conv(act(GroupNorm(h) * (1 + s) + t)): FiLM takes the coefficient route (statistics or accumulator fold -> gg_film_fold -> fused
-    prologue or gg_groupnorm_apply), never the kernels that compute the coefficients inside another launch.
+    conv(act(GroupNorm(h) * (1 + s) + t)): FiLM takes the coefficient arm, never the kernels that compute the coefficients inside another launch.
     Halo-tile convs (3x3(x3), stride 1, large extents): one stats pass, then normalise*affine(+SiLU) and the skip concat are
     fused into the conv's staging pass (applied once per staged element) -- the activation is never re-written to HBM.
     Gather-kernel convs: separate apply pass (measured: SiLU inside the latency-bound gather loop costs 26 vs 16.6 us/conv)."""
-    if ops.is_f32(h.t) and film is not None:  # fp32 validation path of a FiLM norm: the reference's rounding order, nothing folded
-        return ops.conv(ops.groupnorm_f32_film(h, *gn_params(norm), film, act), weight, bias, cout, **conv_kw)
-    if ops.is_f32(h.t):                      # fp32 validation path: separate fp32 GroupNorm launch, then the fp32 conv
-        return ops.conv(ops.groupnorm_f32(h, *gn_params(norm), act, src2), weight, bias, cout, **conv_kw)
+    if ops.is_f32(h.t):                      # (a FiLM norm takes no second source)
+        return ops.conv(_gn_f32(h, norm, act, src2, film), weight, bias, cout, **conv_kw)
     if film is None and ops.conv_prologue_from_acc(h, cout, act, src2=src2, **conv_kw):
         # box conv + producers' sums: the conv folds them and normalises its staged box itself -- NO GroupNorm launch of any kind
         return ops.conv(h, weight, bias, cout, src2=src2, prologue_acc=gn_params(norm), prologue_silu=act, **conv_kw)
     fused = ops.conv_fuses_prologue(h, cout, src2=src2, **conv_kw)
-    if film is None and not fused and ops.groupnorm_fused_ok(h, src2):     # small tensor: statistics + apply in ONE launch
-        a = ops.groupnorm_fused(h, *gn_params(norm), act, src2)
-        return ops.conv(a, weight, bias, cout, **conv_kw)
-    if film is None and not fused and ops.has_stats(h, src2):     # statistics came with the tensor (conv epilogue accumulators)
-        a = ops.groupnorm_apply_acc(h, *gn_params(norm), act, src2)
-        return ops.conv(a, weight, bias, cout, **conv_kw)
-    # halo-tile producers: fold their sums instead of re-reading 17..805 MB per norm
-    scale, shift = (ops.groupnorm_scale_shift_acc if ops.has_any_stats(h, src2) else ops.groupnorm_stats)(h, *gn_params(norm), src2)
-    if film is not None:
-        ops.film_fold(scale, shift, film, h.C)
-    if fused:
-        return ops.conv(h, weight, bias, cout, src2=src2, prologue=(scale, shift), prologue_silu=act, **conv_kw)
-    a = ops.groupnorm_apply(h, scale, shift, act, src2)
+    a = _gn_direct(h, norm, act, src2) if film is None and not fused else None
+    if a is None:
+        scale, shift = _gn_coeffs(h, norm, src2, film)
+        if fused:
+            return ops.conv(h, weight, bias, cout, src2=src2, prologue=(scale, shift), prologue_silu=act, **conv_kw)
+        a = ops.groupnorm_apply(h, scale, shift, act, src2)
     return ops.conv(a, weight, bias, cout, **conv_kw)
 
 
@@ -303,10 +310,9 @@ class ResBlock(TimestepBlock):
             else:
                 # avgpool(SiLU(GN(h))) in one resample launch from the per-(n, c) coefficients, then conv1
                 if ops.is_f32(h.t):
-                    a = ops.resample2x(ops.groupnorm_f32(h, *gn_params(n1), True), False, self.dims == 3)
+                    a = ops.resample2x(_gn_f32(h, n1, True), False, self.dims == 3)
                 else:
-                    sc, sh = (ops.groupnorm_scale_shift_acc if ops.has_any_stats(h) else ops.groupnorm_stats)(h, *gn_params(n1))
-                    a = ops.resample2x(h, False, self.dims == 3, prologue=(sc, sh), act=True)
+                    a = ops.resample2x(h, False, self.dims == 3, prologue=_gn_coeffs(h, n1), act=True)
                 h1 = ops.conv(a, pw1, b1, cout, k=k, pad=1, bias_per_sample=b1_ps)
         else:
             h1 = norm_conv(h, n1, True, pw1, b1, cout, src2=src2, k=k, bias_per_sample=b1_ps)

@@ -8,7 +8,7 @@
 //   interpolate2d_kernel    F.interpolate(x, scale_factor=s, mode=nearest | bilinear | bicubic | area) on NCHW fp32 planes
 //
 // A cond stage runs once per sample, before the chain: these are plain memory-bound kernels, one work item per output element.
-#include "gg_common.h"
+#include "gg_norm.h"
 
 // ------------------------------------------------------------------------------------------------------------ embedding rows
 template <class T>
@@ -95,17 +95,13 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(const bf16_t *__res
     const bf16_t *xr = x + row * stride;
     float s = 0.f;
     for (int c = lane; c < C; c += 64) s += (float)xr[c];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    const float mean = s / (float)C;
+    const float mean = gg_wave_sum_f32(s) / (float)C;
     float q = 0.f;
     for (int c = lane; c < C; c += 64) { const float d = (float)xr[c] - mean; q += d * d; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o);
-    const float rstd = rsqrtf(q / (float)C + eps);
+    const float rstd = rsqrtf(gg_wave_sum_f32(q) / (float)C + eps);
     bf16_t *orow = out + row * stride;
     for (int c = lane; c < stride; c += 64)
-        orow[c] = c < C ? (bf16_t)(((float)xr[c] - mean) * rstd * gamma[c] + beta[c]) : (bf16_t)0.f;
+        orow[c] = c < C ? (bf16_t)ln_normalise((float)xr[c], mean, rstd, gamma[c], beta[c]) : (bf16_t)0.f;
 }
 
 extern "C" int gg_layernorm_rows(const void *x, int64_t rows, int32_t C, int32_t stride, const float *gamma, const float *beta, float eps,

@@ -12,7 +12,7 @@
 //                  two-source concat, optional GroupNorm*SiLU prologue), staged through registers into a
 //                  swizzled, double-buffered LDS tile.
 //   conv_halo    : fast path for 3x3(x3) stride-1 convs on large extents (see gg_conv_halo.hip).
-#include "gg_conv.h"
+#include "gg_norm.h"
 #include <stdlib.h>
 
 template <int NT, int PF, int PRO>
@@ -526,9 +526,9 @@ __global__ __launch_bounds__(256) void conv_gather5_kernel(const ConvParams p)
         if (tid < 64) {
             const int c = tid >> 1, which = tid & 1;
             const float t = ((statp[0][c][which] + statp[1][c][which]) + statp[2][c][which]) + statp[3][c][which];
-            const long long fx = __double2ll_rn((double)t * (double)(which ? GG_ACC_SQ_SCALE : GG_ACC_SUM_SCALE));
+            const long long fx = gn_acc_from_f32(t, which);
             const long long nb = (long long)((unsigned)m0 / osp);
-            atomicAdd(reinterpret_cast<unsigned long long *>(p.gn_acc + (((nb * GG_ACC_STRIPES + (blockIdx.x & (GG_ACC_STRIPES - 1))) * p.Cout_pad + g0 * 32 + c) * 2 + which)),
+            atomicAdd(reinterpret_cast<unsigned long long *>(p.gn_acc + (((nb * GG_ACC_STRIPES + (blockIdx.x & (GG_ACC_STRIPES - 1))) * p.Cout_pad + g0 * 32 + c) * 2 + which)),      // (gn_acc_index, gg_norm.h)
                       (unsigned long long)fx);
         }
     }

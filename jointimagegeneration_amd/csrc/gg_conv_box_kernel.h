@@ -2,7 +2,7 @@
 // (gg_conv_box.hip) and the shape-specialised ones of the latent UNet's batch-1 layers (gg_conv_box_spec.hip).
 #pragma once
 #include <atomic>
-#include "gg_conv.h"
+#include "gg_norm.h"
 #include "gg_step.h"
 #ifndef GG_BOX_K1_MAX_M_ACC
 #define GG_BOX_K1_MAX_M_ACC 256
@@ -457,11 +457,11 @@ __global__ __launch_bounds__(GG_BOX_NW * 64) void conv_box2d_kernel(const ConvPa
                 if constexpr (LPT == 8) psum += __shfl_xor(psum, 4);      // the LPT parts of a task
                 const long long other = __shfl_xor(psum, LPT);            // sumsq task of the same group sits LPT lanes up
                 if ((tidh & (2 * LPT - 1)) == 0) {
-                    const double a = (double)psum * (1.0 / (double)GG_ACC_SUM_SCALE);
-                    const double b = (double)other * (1.0 / (double)GG_ACC_SQ_SCALE);
+                    const double a = gn_acc_to_f64(psum, 0);
+                    const double b = gn_acc_to_f64(other, 1);
                     const double cnt = (double)p.H * (double)p.W * (double)cpg;
                     double inv = (double)(1.0f / (float)cnt);
-                    inv = inv * (2.0 - cnt * inv);             // fp32 reciprocal + one Newton step in fp64 (as gn_apply_acc_kernel)
+                    inv = inv * (2.0 - cnt * inv);             // (gn_moments_fast, gg_norm.h, spelled out: through the function a few instructions move)
                     const double mean = a * inv;
                     double var = b * inv - mean * mean;
                     if (var < 0.0) var = 0.0;
@@ -478,8 +478,8 @@ __global__ __launch_bounds__(GG_BOX_NW * 64) void conv_box2d_kernel(const ConvPa
                     float sc = 0.f, sh = 0.f;
                     if (c < p.pro_clog) {
                         const int gg = gg_div_small(c, rcpg);
-                        sc = pro_grstd[gg] * pgam[k];
-                        sh = pbet[k] - pro_gmean[gg] * sc;
+                        sc = gn_scale(pro_grstd[gg], pgam[k]);
+                        sh = gn_shift(pbet[k], pro_gmean[gg], sc);
                     }
                     gns[c] = sc;
                     gns[Ct + c] = sh;
@@ -845,9 +845,9 @@ __global__ __launch_bounds__(GG_BOX_NW * 64) void conv_box2d_kernel(const ConvPa
 #pragma unroll
             for (int w = 0; w < NW; ++w)
                 if (w % CT == ct) t += statp[w][cw][which];  // waves whose slices carry cout tile ct, fixed order
-            const long long fx = __double2ll_rn((double)t * (double)(which ? GG_ACC_SQ_SCALE : GG_ACC_SUM_SCALE));
+            const long long fx = gn_acc_from_f32(t, which);
             if (NS == 1 || cw / CSZ == sub)                  // cout sub-split: the sums of this workgroup's couts only
-                atomicAdd(reinterpret_cast<unsigned long long *>(p.gn_acc + ((((long long)n * GG_ACC_STRIPES + stripe) * p.Cout_pad + g * 32 + half * 16 + c) * 2 + which)),
+                atomicAdd(reinterpret_cast<unsigned long long *>(p.gn_acc + ((((long long)n * GG_ACC_STRIPES + stripe) * p.Cout_pad + g * 32 + half * 16 + c) * 2 + which)),      // (gn_acc_index, gg_norm.h)
                           (unsigned long long)fx);
         }
     }

@@ -11,7 +11,7 @@
 //      MFMAs run; the activation operand of tap (kd,kh,kw) is the same LDS box read at a shifted row.
 // HBM/L2 traffic per block and chunk: one box (41 KB) instead of 27 gathered tiles (27 x 16 KB) in the generic kernel.
 #include <atomic>
-#include "gg_conv.h"
+#include "gg_norm.h"
 #include "gg_posterior.h"
 #include <stdlib.h>
 #ifndef GG_HALO_G3
@@ -500,9 +500,9 @@ __global__ __launch_bounds__((GG_HALO_W16(D3, NT, HB) ? 1024 : (NT <= 2 && HB !=
             float t = 0.f;
 #pragma unroll
             for (int w = 0; w < NWAVE; ++w) t += statp[((w * (32 * NT) + c) << 1) + which];
-            const long long fx = __double2ll_rn((double)t * (double)(which ? GG_ACC_SQ_SCALE : GG_ACC_SUM_SCALE));
+            const long long fx = gn_acc_from_f32(t, which);
             const int stripe = blockIdx.x % GG_ACC_STRIPES_HALO;
-            atomicAdd(reinterpret_cast<unsigned long long *>(p.gn_acc + ((((long long)n * GG_ACC_STRIPES_HALO + stripe) * p.Cout_pad + g0 * 32 + c) * 2 + which)),
+            atomicAdd(reinterpret_cast<unsigned long long *>(p.gn_acc + ((((long long)n * GG_ACC_STRIPES_HALO + stripe) * p.Cout_pad + g0 * 32 + c) * 2 + which)),      // (gn_acc_index, gg_norm.h)
                       (unsigned long long)fx);
         }
     }

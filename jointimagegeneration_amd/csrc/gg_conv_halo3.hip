@@ -14,7 +14,7 @@
 // Results are bit-identical to conv_halo_kernel: same MFMA, same tap / chunk order per accumulator, same epilogue arithmetic.
 #include <atomic>
 #include <type_traits>
-#include "gg_conv.h"
+#include "gg_norm.h"
 // wave priorities of the two roles (s_setprio): what the tapping team's waves run at, and the staging team's (A/B-measured)
 #ifndef GG_H3_TPRIO
 #define GG_H3_TPRIO "0"
@@ -359,9 +359,9 @@ __global__ __launch_bounds__(512, 2) void conv_halo3_team_kernel(const ConvParam
                             for (int j = 0; j < 4; ++j) {
                                 const float a = gg_row16_sum(ssum[ct][j]), b = gg_row16_sum(ssq[ct][j]);
                                 if (fr < 2) {
-                                    const long long fx = __double2ll_rn((double)(fr ? b : a) * (double)(fr ? GG_ACC_SQ_SCALE : GG_ACC_SUM_SCALE));
+                                    const long long fx = gn_acc_from_f32(fr ? b : a, fr);
                                     const int stripe = (ei.idx * 8 + wave) % GG_ACC_STRIPES_HALO;
-                                    atomicAdd(reinterpret_cast<unsigned long long *>(p.gn_acc + ((((long long)ei.n * GG_ACC_STRIPES_HALO + stripe) * p.Cout_pad + ei.g0 * 32 + ct * 16 + fq * 4 + j) * 2 + fr)),
+                                    atomicAdd(reinterpret_cast<unsigned long long *>(p.gn_acc + ((((long long)ei.n * GG_ACC_STRIPES_HALO + stripe) * p.Cout_pad + ei.g0 * 32 + ct * 16 + fq * 4 + j) * 2 + fr)),      // (gn_acc_index, gg_norm.h)
                                               (unsigned long long)fx);
                                 }
                             }

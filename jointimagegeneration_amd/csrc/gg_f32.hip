@@ -163,7 +163,7 @@ __global__ __launch_bounds__(256) void gn_f32_stats_kernel(const float *__restri
         if (tid < s) { ra[tid] += ra[tid + s]; rb[tid] += rb[tid + s]; }
         __syncthreads();
     }
-    if (tid == 0) {
+    if (tid == 0) {   // (gn_moments_ieee, gg_norm.h, spelled out: through the function the store of the mean moves behind the square root)
         const double cnt = (double)total, mean = ra[0] / cnt;
         double var = rb[0] / cnt - mean * mean;
         if (var < 0.0) var = 0.0;

@@ -1,6 +1,6 @@
 // GroupNorm(32) statistics + fused normalise*affine(+SiLU), LayerNorm, GEGLU, add. HBM-bound kernels:
 // 16-byte (8 x bf16) accesses per lane, fp32 math, two-source aware (fused skip concat).
-#include "gg_conv.h"
+#include "gg_norm.h"
 
 // ------------------------------------------------------------------------------------------------------------
 // Stage 1: per-block partial sums. grid = (nblk, N). Block b of sample n owns rows [b*rpb, (b+1)*rpb).
@@ -26,6 +26,7 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const bf16_t *__restric
     if (rsub < rpi) {
         const int c0 = piece * 8;
         const bool second = c0 >= C1;
+        // (gn_piece_ptr of row n * S, spelled out: through the function the sample offset is multiplied in another order)
         const bf16_t *base = second ? s2 + (long long)n * S * C2 + (c0 - C1) : s1 + (long long)n * S * C1 + c0;
         const int Cs = second ? C2 : C1;
         for (long long r = r0 + rsub; r < r1; r += rpi) {
@@ -98,47 +99,20 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(const float *__restric
         if (tid < s) { ra[tid] += ra[tid + s]; rb[tid] += rb[tid + s]; }
         __syncthreads();
     }
-    const double cnt = (double)S * cpg;
-    const double mean = ra[0] / cnt;
-    double var = rb[0] / cnt - mean * mean;
-    if (var < 0.0) var = 0.0;
-    const float fmean = (float)mean, frstd = (float)(1.0 / sqrt(var + (double)eps));
+    float fmean, frstd;
+    gn_moments_ieee(ra[0], rb[0], (double)S * cpg, eps, fmean, frstd);
     if (tid < cpg) {
         const int c = g * cpg + tid;
-        const float sc = frstd * gamma[c];
+        const float sc = gn_scale(frstd, gamma[c]);
         scale[(long long)n * C + c] = sc;
-        shift[(long long)n * C + c] = beta[c] - fmean * sc;
+        shift[(long long)n * C + c] = gn_shift(beta[c], fmean, sc);
     }
-    if (g == 0)   // zero the pad lanes once
-        for (int c = C_logical + tid; c < C; c += 256) { scale[(long long)n * C + c] = 0.f; shift[(long long)n * C + c] = 0.f; }
+    if (g == 0) gn_zero_pad_lanes(scale, shift, n, C, C_logical, tid);   // once
 }
 
 // Small-tensor fast path: ONE launch. Block (g, n) reduces its group's S x cpg elements (fp32 per thread, fp64 tree),
 // then writes the folded scale/shift of its channels. Used when N*S*C is small enough that launch latency, not HBM,
 // is the cost (LDM latent UNet, deep CCDM levels).
-// x + (x of the DPP-selected lane) in fp64: two DPP moves + one add, no LDS round trip (a 64-bit __shfl_xor is two ds_bpermute, ~150 cycles
-// of dependent latency per butterfly step: six steps were ~0.4 us of a 3.4 us kernel)
-template <int CTRL>
-__device__ __forceinline__ double gg_dpp_add_f64(double x)
-{
-    const unsigned long long u = __builtin_bit_cast(unsigned long long, x);
-    const unsigned lo = (unsigned)__builtin_amdgcn_mov_dpp((int)(unsigned)u, CTRL, 0xF, 0xF, true);
-    const unsigned hi = (unsigned)__builtin_amdgcn_mov_dpp((int)(unsigned)(u >> 32), CTRL, 0xF, 0xF, true);
-    return x + __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
-// sum over the 64 lanes of a wave, fixed order (deterministic): the 16 lanes of a row by DPP (quad xor 1, quad xor 2, half-row mirror,
-// row mirror), the four rows by two xor shuffles
-__device__ __forceinline__ double gg_wave_sum_f64(double x)
-{
-    x = gg_dpp_add_f64<0xB1>(x);
-    x = gg_dpp_add_f64<0x4E>(x);
-    x = gg_dpp_add_f64<0x141>(x);
-    x = gg_dpp_add_f64<0x140>(x);
-    x += __shfl_xor(x, 16);
-    x += __shfl_xor(x, 32);
-    return x;
-}
-
 __global__ __launch_bounds__(256) void gn_stats_small_kernel(const bf16_t *__restrict__ s1, int C1, const bf16_t *__restrict__ s2,
                                                              int C2, long long S, int C_logical, const float *__restrict__ gamma,
                                                              const float *__restrict__ beta, float eps, float *__restrict__ scale,
@@ -165,8 +139,7 @@ __global__ __launch_bounds__(256) void gn_stats_small_kernel(const bf16_t *__res
     for (int i = tid; i < work; i += 256) {
         const int r = gg_div_small(i, rnp);
         const int c0 = (p_lo + (i - r * np)) * 8;
-        const bf16_t *src = (c0 < C1) ? b1 + (long long)r * C1 + c0 : b2 + (long long)r * C2 + (c0 - C1);
-        const bf16x8 v = *reinterpret_cast<const bf16x8 *>(src);
+        const bf16x8 v = *reinterpret_cast<const bf16x8 *>(gn_piece_ptr(b1, C1, b2, C2, (long long)r, c0));
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int c = c0 + j;
@@ -175,27 +148,17 @@ __global__ __launch_bounds__(256) void gn_stats_small_kernel(const bf16_t *__res
             b += f * f;
         }
     }
-    // fixed-order reduction: fp64 butterfly inside each wave (6 steps), then the 4 waves through LDS: one barrier, not eight
-    const double da = gg_wave_sum_f64((double)a), db = gg_wave_sum_f64((double)b);
-    __shared__ double ra[4], rb[4];
-    if ((tid & 63) == 0) { ra[tid >> 6] = da; rb[tid >> 6] = db; }
-    __syncthreads();
-    const double sa = (ra[0] + ra[1]) + (ra[2] + ra[3]), sb = (rb[0] + rb[1]) + (rb[2] + rb[3]);
-    // (no fp64 division / square root: each is a ~50-100-instruction sequence every thread would issue between the reduction and
-    // its stores; the same formulas as gn_apply_acc_kernel: fp32 reciprocal of the exact count, v_rsq_f32)
-    const double cnt = (double)S * (double)cpg; double inv = (double)(1.0f / (float)cnt); inv = inv * (2.0 - cnt * inv);      // fp32 reciprocal + one Newton step in fp64 (error ~1e-14: no fp64 division, and mean^2 is not polluted when |mean| >> std)
-    const double mean = sa * inv;
-    double var = sb * inv - mean * mean;
-    if (var < 0.0) var = 0.0;
-    const float fmean = (float)mean, frstd = rsqrtf((float)var + eps);
+    double sa, sb;
+    gn_block_sum2_f64(a, b, sa, sb);
+    float fmean, frstd;
+    gn_moments_fast(sa, sb, (double)S * (double)cpg, eps, fmean, frstd);
     if (tid < cpg) {
         const int c = g * cpg + tid;
-        const float sc = frstd * gmm;
+        const float sc = gn_scale(frstd, gmm);
         scale[(long long)n * C + c] = sc;
-        shift[(long long)n * C + c] = bta - fmean * sc;
+        shift[(long long)n * C + c] = gn_shift(bta, fmean, sc);
     }
-    if (g == 0)
-        for (int c = C_logical + tid; c < C; c += 256) { scale[(long long)n * C + c] = 0.f; shift[(long long)n * C + c] = 0.f; }
+    if (g == 0) gn_zero_pad_lanes(scale, shift, n, C, C_logical, tid);
 }
 
 // Small tensors, ONE launch for the whole norm: block (g, n) keeps its group's S x cpg elements in registers (as the 16-byte pieces
@@ -232,7 +195,7 @@ __global__ __launch_bounds__(256) void gn_fused_small_kernel(const bf16_t *__res
         if (i < work) {
             const int r = gg_div_small(i, rnp);
             const int c0 = (p_lo + (i - r * np)) * 8;
-            v[k] = *reinterpret_cast<const u32x4 *>((c0 < C1) ? b1 + (long long)r * C1 + c0 : b2 + (long long)r * C2 + (c0 - C1));
+            v[k] = *reinterpret_cast<const u32x4 *>(gn_piece_ptr(b1, C1, b2, C2, (long long)r, c0));
         }
     }
     float a = 0.f, b = 0.f;
@@ -252,16 +215,14 @@ __global__ __launch_bounds__(256) void gn_fused_small_kernel(const bf16_t *__res
             }
         }
     }
+    // (gn_block_sum2_f64, spelled out: through the function this kernel gains a scalar instruction at the branch around the LDS stores)
     const double da = gg_wave_sum_f64((double)a), db = gg_wave_sum_f64((double)b);
     __shared__ double ra[4], rb[4];
     if ((tid & 63) == 0) { ra[tid >> 6] = da; rb[tid >> 6] = db; }
     __syncthreads();
     const double sa = (ra[0] + ra[1]) + (ra[2] + ra[3]), sb = (rb[0] + rb[1]) + (rb[2] + rb[3]);
-    const double cnt = (double)S * (double)cpg; double inv = (double)(1.0f / (float)cnt); inv = inv * (2.0 - cnt * inv);      // fp32 reciprocal + Newton step in fp64; no fp64 division / sqrt (see above)
-    const double mean = sa * inv;
-    double var = sb * inv - mean * mean;
-    if (var < 0.0) var = 0.0;
-    const float fmean = (float)mean, frstd = rsqrtf((float)var + eps);
+    float fmean, frstd;
+    gn_moments_fast(sa, sb, (double)S * (double)cpg, eps, fmean, frstd);
 #pragma unroll
     for (int k = 0; k < GG_GN_FUSED_MAXP; ++k) {
         const int i = tid + 256 * k;
@@ -274,10 +235,8 @@ __global__ __launch_bounds__(256) void gn_fused_small_kernel(const bf16_t *__res
             for (int j = 0; j < 8; ++j) {
                 int cl = c0 + j - c_lo;                         // channel inside the group (clamped for the foreign lanes: not stored)
                 cl = cl < 0 ? 0 : (cl >= cpg ? cpg - 1 : cl);
-                const float sc = frstd * gb[0][cl];             // the same fp32 scale / shift the two-launch path tabulates
-                float t = (float)x[j] * sc + (gb[1][cl] - fmean * sc);
-                if (act) t = gg_silu(t);
-                y[j] = (bf16_t)t;
+                const float sc = gn_scale(frstd, gb[0][cl]);    // the same fp32 scale / shift the two-launch path tabulates
+                y[j] = (bf16_t)gn_affine((float)x[j], sc, gn_shift(gb[1][cl], fmean, sc), act);
             }
             bf16_t *dst = o + (long long)r * C + c0;
             if (c0 >= c_lo && c0 + 8 <= c_hi) {
@@ -290,6 +249,20 @@ __global__ __launch_bounds__(256) void gn_fused_small_kernel(const bf16_t *__res
         }
     }
 }
+
+// The argument checks the GroupNorm entry points share, in the order they have always run.  `what`: the entry's name in gg_last_error;
+// logical_text (a format of the name and C_logical): null where C_logical is not checked here; ptrs_ok: the entry's own pointer / extent test.
+static int gn_check_entry(const char *what, int C1, int C2, int C_logical, const char *logical_text, bool cap2048, bool ptrs_ok, const char *ptr_text)
+{
+    const int C = C1 + C2;
+    if (C1 <= 0 || C1 % 32 || C2 % 32 || C2 < 0) GG_FAIL(GG_ERR_BAD_SHAPE, "%s: C1/C2 must be multiples of 32", what);
+    if (logical_text && (C_logical % 32 || C_logical > C || C_logical <= 0)) GG_FAIL(GG_ERR_BAD_SHAPE, logical_text, what, C_logical);
+    if (cap2048 && C > 2048) GG_FAIL(GG_ERR_UNSUPPORTED, "%s: C > 2048", what);
+    if (!ptrs_ok) GG_FAIL(GG_ERR_BAD_SHAPE, "%s: %s", what, ptr_text);
+    return GG_OK;
+}
+#define GN_LOGICAL_TEXT "%s: logical channels %d not divisible by 32 groups"
+#define GN_CHECK(...) do { if (int e_ = gn_check_entry(__VA_ARGS__)) return e_; } while (0)
 
 static bool gn_fused_small_ok(long long S, int C1, int C2, int C_logical)
 {
@@ -315,8 +288,7 @@ extern "C" int gg_groupnorm_fused(const void *src1, int32_t C1, const void *src2
                                   const float *gamma, const float *beta, float eps, int32_t act, void *out, void *stream_)
 {
     hipStream_t stream = (hipStream_t)stream_;
-    if (C1 <= 0 || C1 % 32 || C2 % 32 || C2 < 0) GG_FAIL(GG_ERR_BAD_SHAPE, "groupnorm_fused: C1/C2 must be multiples of 32");
-    if (!src1 || (C2 && !src2) || !gamma || !beta || !out || N <= 0 || S <= 0) GG_FAIL(GG_ERR_BAD_SHAPE, "groupnorm_fused: null pointer / empty");
+    GN_CHECK("groupnorm_fused", C1, C2, 0, nullptr, false, src1 && (!C2 || src2) && gamma && beta && out && N > 0 && S > 0, "null pointer / empty");
     if (!gn_fused_small_ok(S, C1, C2, C_logical)) GG_FAIL(GG_ERR_UNSUPPORTED, "groupnorm_fused: tensor too large for the single-launch path (gg_groupnorm_fused_supported)");
     hipLaunchKernelGGL(gn_fused_small_kernel, dim3(32, N), dim3(256), 0, stream, (const bf16_t *)src1, C1, (const bf16_t *)src2, C2,
                        (long long)S, gamma, beta, eps, act, (bf16_t *)out);
@@ -348,10 +320,7 @@ extern "C" int gg_groupnorm_stats(const void *src1, int32_t C1, const void *src2
 {
     hipStream_t stream = (hipStream_t)stream_;
     const int C = C1 + C2;
-    if (C1 <= 0 || C1 % 32 || C2 % 32 || C2 < 0) GG_FAIL(GG_ERR_BAD_SHAPE, "groupnorm: C1/C2 must be multiples of 32");
-    if (C_logical % 32 || C_logical > C || C_logical <= 0) GG_FAIL(GG_ERR_BAD_SHAPE, "groupnorm: logical channels %d not divisible by 32 groups", C_logical);
-    if (C / 8 > 256) GG_FAIL(GG_ERR_UNSUPPORTED, "groupnorm: C > 2048");
-    if (!src1 || (C2 && !src2) || !gamma || !beta || !scale_out || !shift_out || !workspace) GG_FAIL(GG_ERR_BAD_SHAPE, "groupnorm: null pointer");
+    GN_CHECK("groupnorm", C1, C2, C_logical, GN_LOGICAL_TEXT, true, src1 && (!C2 || src2) && gamma && beta && scale_out && shift_out && workspace, "null pointer");
     if ((long long)S * C <= (1 << 19)) {   // small tensors (deep UNet levels): single-launch path
         hipLaunchKernelGGL(gn_stats_small_kernel, dim3(32, N), dim3(256), 0, stream, (const bf16_t *)src1, C1, (const bf16_t *)src2, C2,
                            (long long)S, C_logical, gamma, beta, eps, scale_out, shift_out);
@@ -386,22 +355,13 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const bf16_t *__restrict_
         int piece = (int)(i - row * P);
         int c0 = piece * 8;
         int n = N == 1 ? 0 : (int)(row / S);
-        const bf16_t *src = (c0 >= C1) ? s2 + row * C2 + (c0 - C1) : s1 + row * C1 + c0;
+        const bf16_t *src = gn_piece_ptr(s1, C1, s2, C2, row, c0);
         bf16x8 v = *reinterpret_cast<const bf16x8 *>(src);
         const float *sc = scale + (long long)n * C + c0;
         const float *sh = shift + (long long)n * C + c0;
         f32x4 a0 = *reinterpret_cast<const f32x4 *>(sc), a1 = *reinterpret_cast<const f32x4 *>(sc + 4);
         f32x4 b0 = *reinterpret_cast<const f32x4 *>(sh), b1 = *reinterpret_cast<const f32x4 *>(sh + 4);
-        bf16x8 o;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float y0 = (float)v[j] * a0[j] + b0[j];
-            float y1 = (float)v[j + 4] * a1[j] + b1[j];
-            if (act) { y0 = gg_silu(y0); y1 = gg_silu(y1); }
-            o[j] = (bf16_t)y0;
-            o[j + 4] = (bf16_t)y1;
-        }
-        *reinterpret_cast<bf16x8 *>(out + row * C + c0) = o;
+        *reinterpret_cast<bf16x8 *>(out + row * C + c0) = gn_affine8(v, a0, a1, b0, b1, act);
     }
 }
 
@@ -409,8 +369,7 @@ extern "C" int gg_groupnorm_apply(const void *src1, int32_t C1, const void *src2
                                   const float *scale, const float *shift, int32_t act, void *out, void *stream_)
 {
     hipStream_t stream = (hipStream_t)stream_;
-    if (C1 <= 0 || C1 % 32 || C2 % 32 || C2 < 0) GG_FAIL(GG_ERR_BAD_SHAPE, "groupnorm_apply: C1/C2 must be multiples of 32");
-    if (!src1 || (C2 && !src2) || !scale || !shift || !out) GG_FAIL(GG_ERR_BAD_SHAPE, "groupnorm_apply: null pointer");
+    GN_CHECK("groupnorm_apply", C1, C2, 0, nullptr, false, src1 && (!C2 || src2) && scale && shift && out, "null pointer");
     long long total = (long long)N * S * ((C1 + C2) / 8);
     const unsigned blocks = gg_blocks256(total, 8192);
     hipLaunchKernelGGL(gn_apply_kernel, dim3(blocks), dim3(256), 0, stream, (const bf16_t *)src1, C1,
@@ -435,8 +394,6 @@ extern "C" int gg_gn_stamps_read(unsigned long long *host, int n) { return hipMe
 #ifndef GG_GN_APPLY_ACC_LEAN
 #define GG_GN_APPLY_ACC_LEAN 1           /* one-piece-per-thread form of gn_apply_acc for batch-1 shapes (A/B: tools/experiments) */
 #endif
-#define GG_ACC_SUM_SCALE_D 268435456.0   /* 2^28, must match gg_conv.h */
-#define GG_ACC_SQ_SCALE_D 1048576.0      /* 2^20 */
 __global__ __launch_bounds__(256) void gn_apply_acc_kernel(const bf16_t *__restrict__ s1, int C1, const long long *__restrict__ acc1,
                                                            const bf16_t *__restrict__ s2, int C2, const long long *__restrict__ acc2,
                                                            long long S, int C_logical, const float *__restrict__ gamma,
@@ -471,7 +428,7 @@ __global__ __launch_bounds__(256) void gn_apply_acc_kernel(const bf16_t *__restr
         if (i < pieces) {
             const long long row = gg_fastdiv(i, P, pmagic);
             const int c0 = (int)(i - row * P) * 8;
-            pv[u] = *reinterpret_cast<const u32x4 *>((c0 >= C1) ? b2 + row * C2 + (c0 - C1) : b1 + row * C1 + c0);
+            pv[u] = *reinterpret_cast<const u32x4 *>(gn_piece_ptr(b1, C1, b2, C2, row, c0));
         }
     }
     // this thread's channels: GG_ACC_STRIPES x (sum, sumsq) as 16-byte loads, gamma / beta; everything requested before the first wait
@@ -485,15 +442,9 @@ __global__ __launch_bounds__(256) void gn_apply_acc_kernel(const bf16_t *__restr
         sa[k] = 0;
         sb[k] = 0;
         if (c < C_logical) {
-            const long long *q = (c < C1) ? acc1 + ((long long)n * GG_ACC_STRIPES * C1 + c) * 2 : acc2 + ((long long)n * GG_ACC_STRIPES * C2 + (c - C1)) * 2;
+            const long long *q = (c < C1) ? acc1 + gn_acc_index(n, GG_ACC_STRIPES, 0, C1, c) : acc2 + gn_acc_index(n, GG_ACC_STRIPES, 0, C2, c - C1);
             const long long cs = (c < C1) ? (long long)C1 * 2 : (long long)C2 * 2;
-            typedef __attribute__((ext_vector_type(2))) long long i64x2;
-#pragma unroll
-            for (int st = 0; st < GG_ACC_STRIPES; ++st) {
-                const i64x2 v = *reinterpret_cast<const i64x2 *>(q + st * cs);
-                sa[k] += v[0];
-                sb[k] += v[1];
-            }
+            gn_acc_fold_channel(q, cs, sa[k], sb[k]);
             gam[k] = gamma[c];
             bet[k] = beta[c];
         }
@@ -513,14 +464,8 @@ __global__ __launch_bounds__(256) void gn_apply_acc_kernel(const bf16_t *__restr
     __syncthreads();
     GG_GSTAMP(3);
     if (tid < 32) {
-        const double a = (double)(long long)gacc[tid][0] * (1.0 / GG_ACC_SUM_SCALE_D);
-        const double b = (double)(long long)gacc[tid][1] * (1.0 / GG_ACC_SQ_SCALE_D);
-        const double cnt = (double)S * (double)cpg; double inv = (double)(1.0f / (float)cnt); inv = inv * (2.0 - cnt * inv);      // fp32 reciprocal + Newton step in fp64 (as gn_stats_small)
-        const double mean = a * inv;
-        double var = b * inv - mean * mean;
-        if (var < 0.0) var = 0.0;
-        gmean[tid] = (float)mean;
-        grstd[tid] = rsqrtf((float)var + eps);
+        gn_moments_fast(gn_acc_to_f64((long long)gacc[tid][0], 0), gn_acc_to_f64((long long)gacc[tid][1], 1), (double)S * (double)cpg, eps,
+                        gmean[tid], grstd[tid]);
     }
     __syncthreads();
     GG_GSTAMP(4);
@@ -531,8 +476,8 @@ __global__ __launch_bounds__(256) void gn_apply_acc_kernel(const bf16_t *__restr
             float sc = 0.f, sh = 0.f;
             if (c < C_logical) {
                 const int g = gg_div_small(c, rcpg);
-                sc = grstd[g] * gam[k];
-                sh = bet[k] - gmean[g] * sc;
+                sc = gn_scale(grstd[g], gam[k]);
+                sh = gn_shift(bet[k], gmean[g], sc);
             }
             ss[c] = sc;
             ss[C + c] = sh;
@@ -546,16 +491,7 @@ __global__ __launch_bounds__(256) void gn_apply_acc_kernel(const bf16_t *__restr
         const bf16x8 v = __builtin_bit_cast(bf16x8, raw);
         const f32x4 a0 = *reinterpret_cast<const f32x4 *>(ss + c0), a1 = *reinterpret_cast<const f32x4 *>(ss + c0 + 4);
         const f32x4 h0 = *reinterpret_cast<const f32x4 *>(ss + C + c0), h1 = *reinterpret_cast<const f32x4 *>(ss + C + c0 + 4);
-        bf16x8 y;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float y0 = (float)v[j] * a0[j] + h0[j];
-            float y1 = (float)v[j + 4] * a1[j] + h1[j];
-            if (act) { y0 = gg_silu(y0); y1 = gg_silu(y1); }
-            y[j] = (bf16_t)y0;
-            y[j + 4] = (bf16_t)y1;
-        }
-        *reinterpret_cast<bf16x8 *>(o + row * C + c0) = y;
+        *reinterpret_cast<bf16x8 *>(o + row * C + c0) = gn_affine8(v, a0, a1, h0, h1, act);
     };
 #pragma unroll
     for (int u = 0; u < U; ++u)
@@ -563,7 +499,7 @@ __global__ __launch_bounds__(256) void gn_apply_acc_kernel(const bf16_t *__restr
     for (long long i = i0 + U * stride; i < pieces; i += stride) {
         const long long row = gg_fastdiv(i, P, pmagic);
         const int c0 = (int)(i - row * P) * 8;
-        emit(i, *reinterpret_cast<const u32x4 *>((c0 >= C1) ? b2 + row * C2 + (c0 - C1) : b1 + row * C1 + c0));
+        emit(i, *reinterpret_cast<const u32x4 *>(gn_piece_ptr(b1, C1, b2, C2, row, c0)));
     }
     GG_GSTAMP(6);
 }
@@ -584,7 +520,6 @@ __global__ __launch_bounds__(256) void gn_apply_acc_lean_kernel(const bf16_t *__
     s1 = gg_pin(s1); C1 = gg_pin(C1); acc1 = gg_pin(acc1); s2 = gg_pin(s2); C2 = gg_pin(C2); acc2 = gg_pin(acc2); S = gg_pin(S);
     C_logical = gg_pin(C_logical); gamma = gg_pin(gamma); beta = gg_pin(beta); pmagic = gg_pin(pmagic);
     GG_GSTAMP(0);
-    typedef __attribute__((ext_vector_type(2))) long long i64x2;
     const int C = C1 + C2, P = C >> 3;
     const int tid = threadIdx.x, n = blockIdx.y;
     const int pieces = S * P;
@@ -602,7 +537,7 @@ __global__ __launch_bounds__(256) void gn_apply_acc_lean_kernel(const bf16_t *__
     const bool logical = live && c0 < C_logical;                                // (C_logical % 32 == 0: a piece is all logical or all padding)
     const unsigned e1 = (unsigned)n * (unsigned)S * (unsigned)C1, e2 = (unsigned)n * (unsigned)S * (unsigned)C2;   // < 2^31 elements (host gate)
     u32x4 pv = u32x4{0u, 0u, 0u, 0u};
-    if (live) pv = *reinterpret_cast<const u32x4 *>((c0 >= C1) ? s2 + e2 + (unsigned)row * (unsigned)C2 + (unsigned)(c0 - C1) : s1 + e1 + (unsigned)row * (unsigned)C1 + (unsigned)c0);
+    if (live) pv = *reinterpret_cast<const u32x4 *>(gn_piece_ptr(s1 + e1, C1, s2 + e2, C2, (unsigned)row, c0));
     f32x4 g0 = f32x4{0.f, 0.f, 0.f, 0.f}, g1 = g0, b0 = g0, b1 = g0;
     if (logical) {
         g0 = *reinterpret_cast<const f32x4 *>(gamma + c0); g1 = *reinterpret_cast<const f32x4 *>(gamma + c0 + 4);
@@ -613,12 +548,12 @@ __global__ __launch_bounds__(256) void gn_apply_acc_lean_kernel(const bf16_t *__
     for (int k = 0; k < CPT; ++k) {
         const int c = tid + 256 * k;
         if (c < C_logical) {
+            // (gn_acc_index of stripe 0, spelled out: through the function the sample offset becomes a signed 32-bit multiply here)
             const long long *q = (c < C1) ? acc1 + ((long long)n * GG_ACC_STRIPES * C1 + c) * 2 : acc2 + ((long long)n * GG_ACC_STRIPES * C2 + (c - C1)) * 2;
             const long long cs = (c < C1) ? (long long)C1 * 2 : (long long)C2 * 2;
-            i64x2 a = *reinterpret_cast<const i64x2 *>(q);
-#pragma unroll
-            for (int st = 1; st < GG_ACC_STRIPES; ++st) a += *reinterpret_cast<const i64x2 *>(q + st * cs);
-            csum[c] = a;
+            long long a = 0, b = 0;
+            gn_acc_fold_channel(q, cs, a, b);
+            csum[c] = i64x2{a, b};
         }
     }
     const int cpg = C_logical >> 5;
@@ -628,14 +563,7 @@ __global__ __launch_bounds__(256) void gn_apply_acc_lean_kernel(const bf16_t *__
     if (tid < 32) {
         i64x2 t = i64x2{0, 0};
         for (int j = 0; j < cpg; ++j) t += csum[tid * cpg + j];
-        const double a = (double)t[0] * (1.0 / GG_ACC_SUM_SCALE_D);
-        const double b = (double)t[1] * (1.0 / GG_ACC_SQ_SCALE_D);
-        const double cnt = (double)S * (double)cpg; double inv = (double)(1.0f / (float)cnt); inv = inv * (2.0 - cnt * inv);      // (as gn_apply_acc_kernel)
-        const double mean = a * inv;
-        double var = b * inv - mean * mean;
-        if (var < 0.0) var = 0.0;
-        gmean[tid] = (float)mean;
-        grstd[tid] = rsqrtf((float)var + eps);
+        gn_moments_fast(gn_acc_to_f64(t[0], 0), gn_acc_to_f64(t[1], 1), (double)S * (double)cpg, eps, gmean[tid], grstd[tid]);
         GG_GSTAMP(3);
     }
     __syncthreads();
@@ -649,12 +577,10 @@ __global__ __launch_bounds__(256) void gn_apply_acc_lean_kernel(const bf16_t *__
         float sc = 0.f, sh = 0.f;
         if (logical) {
             const int g = gg_div_small(c0 + j, rcpg);
-            sc = grstd[g] * (j < 4 ? g0[j & 3] : g1[j & 3]);
-            sh = (j < 4 ? b0[j & 3] : b1[j & 3]) - gmean[g] * sc;
+            sc = gn_scale(grstd[g], j < 4 ? g0[j & 3] : g1[j & 3]);
+            sh = gn_shift(j < 4 ? b0[j & 3] : b1[j & 3], gmean[g], sc);
         }
-        float t = (float)v[j] * sc + sh;
-        if (act) t = gg_silu(t);
-        y[j] = (bf16_t)t;
+        y[j] = (bf16_t)gn_affine((float)v[j], sc, sh, act);
     }
     *reinterpret_cast<bf16x8 *>(out + ((unsigned)n * (unsigned)S + (unsigned)row) * (unsigned)C + (unsigned)c0) = y;
     GG_GSTAMP(5);
@@ -666,11 +592,8 @@ extern "C" int gg_groupnorm_apply_acc(const void *src1, int32_t C1, const int64_
 {
     hipStream_t stream = (hipStream_t)stream_;
     const int C = C1 + C2;
-    if (C1 <= 0 || C1 % 32 || C2 % 32 || C2 < 0) GG_FAIL(GG_ERR_BAD_SHAPE, "groupnorm_apply_acc: C1/C2 must be multiples of 32");
-    if (C_logical % 32 || C_logical > C || C_logical <= 0) GG_FAIL(GG_ERR_BAD_SHAPE, "groupnorm_apply_acc: logical channels %d not divisible by 32 groups", C_logical);
-    if (C > 2048) GG_FAIL(GG_ERR_UNSUPPORTED, "groupnorm_apply_acc: C > 2048");
-    if (!src1 || !acc1 || (C2 && (!src2 || !acc2)) || !gamma || !beta || !out || N <= 0 || S <= 0)
-        GG_FAIL(GG_ERR_BAD_SHAPE, "groupnorm_apply_acc: null pointer / empty");
+    GN_CHECK("groupnorm_apply_acc", C1, C2, C_logical, GN_LOGICAL_TEXT, true,
+             src1 && acc1 && (!C2 || (src2 && acc2)) && gamma && beta && out && N > 0 && S > 0, "null pointer / empty");
     const long long pieces = (long long)S * (C / 8);
     long long blocks = (pieces + 255) / 256;   // one piece per thread (256 / 512 / 1024 pieces per block: 1477 / 1496 / 1545 us per latent-UNet forward: the parallelism is worth more than the per-block fold)
     if (blocks < 1) blocks = 1;
@@ -712,7 +635,6 @@ __global__ __launch_bounds__(256) void gn_scale_shift_acc_kernel(const long long
     float gmm = 0.f, bta = 0.f;
     if (tid < cpg) { gmm = gamma[g * cpg + tid]; bta = beta[g * cpg + tid]; }
     __syncthreads();
-    typedef __attribute__((ext_vector_type(2))) long long i64x2;
     const int smax = stripes1 > stripes2 ? stripes1 : stripes2;
     long long sa = 0, sb = 0;
     const float rcpg = __builtin_amdgcn_rcpf((float)cpg);
@@ -721,7 +643,7 @@ __global__ __launch_bounds__(256) void gn_scale_shift_acc_kernel(const long long
         const bool first = c < C1;
         const int st = first ? stripes1 : stripes2, Cs = first ? C1 : C2, cc = first ? c : c - C1;
         if (k < st) {
-            const i64x2 v = *reinterpret_cast<const i64x2 *>((first ? acc1 : acc2) + (((long long)n * st + k) * Cs + cc) * 2);
+            const i64x2 v = *reinterpret_cast<const i64x2 *>((first ? acc1 : acc2) + gn_acc_index(n, st, k, Cs, cc));
             sa += v[0];
             sb += v[1];
         }
@@ -729,23 +651,15 @@ __global__ __launch_bounds__(256) void gn_scale_shift_acc_kernel(const long long
     atomicAdd(&gacc[0], (unsigned long long)sa);
     atomicAdd(&gacc[1], (unsigned long long)sb);
     __syncthreads();
-    const double a = (double)(long long)gacc[0] * (1.0 / GG_ACC_SUM_SCALE_D);
-    const double b = (double)(long long)gacc[1] * (1.0 / GG_ACC_SQ_SCALE_D);
-    // (as gn_apply_acc_kernel: fp32 reciprocal of the exact count + one Newton step in fp64, v_rsq_f32; the fp64 divisions and the fp64
-    //  square root were ~150 instructions on the critical path of a 7 us kernel, 27-29 launches per CCDM forward / AE pass)
-    const double cnt = (double)S * (double)cpg; double inv = (double)(1.0f / (float)cnt); inv = inv * (2.0 - cnt * inv);
-    const double mean = a * inv;
-    double var = b * inv - mean * mean;
-    if (var < 0.0) var = 0.0;
-    const float fmean = (float)mean, frstd = rsqrtf((float)var + eps);
+    float fmean, frstd;
+    gn_moments_fast(gn_acc_to_f64((long long)gacc[0], 0), gn_acc_to_f64((long long)gacc[1], 1), (double)S * (double)cpg, eps, fmean, frstd);
     if (tid < cpg) {
         const int c = g * cpg + tid;
-        const float sc = frstd * gmm;
+        const float sc = gn_scale(frstd, gmm);
         scale[(long long)n * C + c] = sc;
-        shift[(long long)n * C + c] = bta - fmean * sc;
+        shift[(long long)n * C + c] = gn_shift(bta, fmean, sc);
     }
-    if (g == 0)   // zero the pad lanes once
-        for (int c = C_logical + tid; c < C; c += 256) { scale[(long long)n * C + c] = 0.f; shift[(long long)n * C + c] = 0.f; }
+    if (g == 0) gn_zero_pad_lanes(scale, shift, n, C, C_logical, tid);   // once
 }
 
 extern "C" int gg_groupnorm_scale_shift_acc(const int64_t *acc1, int32_t stripes1, int32_t C1, const int64_t *acc2, int32_t stripes2,
@@ -753,10 +667,8 @@ extern "C" int gg_groupnorm_scale_shift_acc(const int64_t *acc1, int32_t stripes
                                             float eps, float *scale_out, float *shift_out, void *stream_)
 {
     hipStream_t stream = (hipStream_t)stream_;
-    if (C1 <= 0 || C1 % 32 || C2 % 32 || C2 < 0) GG_FAIL(GG_ERR_BAD_SHAPE, "groupnorm_scale_shift_acc: C1/C2 must be multiples of 32");
-    if (C_logical <= 0 || C_logical % 32 || C_logical > C1 + C2) GG_FAIL(GG_ERR_BAD_SHAPE, "groupnorm_scale_shift_acc: C_logical must be a multiple of 32 groups");
-    if (!acc1 || (C2 && !acc2) || !gamma || !beta || !scale_out || !shift_out || N <= 0 || S <= 0 || stripes1 <= 0 || (C2 && stripes2 <= 0))
-        GG_FAIL(GG_ERR_BAD_SHAPE, "groupnorm_scale_shift_acc: null pointer / empty");
+    GN_CHECK("groupnorm_scale_shift_acc", C1, C2, C_logical, "%s: C_logical must be a multiple of 32 groups", false,
+             acc1 && (!C2 || acc2) && gamma && beta && scale_out && shift_out && N > 0 && S > 0 && stripes1 > 0 && (!C2 || stripes2 > 0), "null pointer / empty");
     hipLaunchKernelGGL(gn_scale_shift_acc_kernel, dim3(32, (unsigned)N), dim3(256), 0, stream, (const long long *)acc1, stripes1, C1,
                        (const long long *)acc2, stripes2, C2, (long long)S, C_logical, gamma, beta, eps, scale_out, shift_out);
     GG_CHECK_LAUNCH();
@@ -784,9 +696,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const bf16_t *__restrict
             for (int j = 0; j < 8; ++j) s += v[k][j];
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    const float mean = s / (float)C;
+    const float mean = gg_wave_sum_f32(s) / (float)C;
     float q = 0.f;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -796,9 +706,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const bf16_t *__restrict
             for (int j = 0; j < 8; ++j) { float d = v[k][j] - mean; q += d * d; }
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o);
-    const float rstd = rsqrtf(q / (float)C + eps);
+    const float rstd = rsqrtf(gg_wave_sum_f32(q) / (float)C + eps);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         int piece = lane + 64 * k;
@@ -807,7 +715,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const bf16_t *__restrict
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 int c = piece * 8 + j;
-                o[j] = (bf16_t)((v[k][j] - mean) * rstd * gamma[c] + beta[c]);
+                o[j] = (bf16_t)ln_normalise(v[k][j], mean, rstd, gamma[c], beta[c]);
             }
             *reinterpret_cast<bf16x8 *>(out + row * C + piece * 8) = o;
         }

@@ -7,7 +7,7 @@
 //   film_fold_kernel    scale' = scale * (1 + s), shift' = shift * (1 + s) + t for the ResBlock's per-sample FiLM row [s | t] (unet.py:254-257)
 //
 // Memory-bound: one thread per output position and 8 channels, 16-byte channel vectors (bf16; two per fp32 vector), fp32 arithmetic.
-#include "gg_common.h"
+#include "gg_norm.h"
 
 template <class T> struct Vec8;
 template <> struct Vec8<bf16_t> {
@@ -59,10 +59,7 @@ __global__ __launch_bounds__(256) void resample2x_kernel(const T *__restrict__ s
         auto pro = [&](f32x8 v) {
             if (scale) {
 #pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    float y = v[j] * a[j] + b[j];
-                    v[j] = act ? gg_silu(y) : y;
-                }
+                for (int j = 0; j < 8; ++j) v[j] = gn_affine(v[j], a[j], b[j], act);
             }
             return v;
         };

@@ -425,15 +425,21 @@ def _gn_sources(src1: CL, src2: Optional[CL], padded_first: str = "raise"):
     return src1.N, src1.S, src1.Cpad, src2.Cpad, src1.C + src2.C, src2.t.data_ptr()
 
 
+def _gn_out(src1: CL, Ct: int, dtype=torch.bfloat16) -> torch.Tensor:       # a GroupNorm's output: src1's positions, Ct channels
+    return torch.empty(tuple(src1.t.shape[:4]) + (Ct,), dtype=dtype, device=src1.t.device)
+
+
+def _gn_tables(src1: CL, N: int, Ct: int):                                   # per-(n, c) fp32 (scale, shift)
+    return tuple(torch.empty((N, Ct), dtype=torch.float32, device=src1.t.device) for _ in range(2))
+
+
 def groupnorm_stats(src1: CL, gamma: torch.Tensor, beta: torch.Tensor, eps: float, src2: Optional[CL] = None):
     """Returns per-(n, c) fp32 (scale, shift) with y = x*scale + shift == GroupNorm(32, C)(x)."""
     lib = _lib.load()
     N, S, C1, C2, c_log, p2 = _gn_sources(src1, src2)
-    Ct = C1 + C2
-    ws_bytes = lib.gg_groupnorm_workspace_bytes(N, S, Ct)
+    ws_bytes = lib.gg_groupnorm_workspace_bytes(N, S, C1 + C2)
     ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=src1.t.device)
-    scale = torch.empty((N, Ct), dtype=torch.float32, device=src1.t.device)
-    shift = torch.empty_like(scale)
+    scale, shift = _gn_tables(src1, N, C1 + C2)
     check(lib.gg_groupnorm_stats(src1.t.data_ptr(), C1, p2, C2, N, S, c_log,
                                  gamma.data_ptr(), beta.data_ptr(), eps, scale.data_ptr(), shift.data_ptr(), ws.data_ptr(),
                                  ws_bytes, _stream()), "gg_groupnorm_stats")
@@ -441,55 +447,46 @@ def groupnorm_stats(src1: CL, gamma: torch.Tensor, beta: torch.Tensor, eps: floa
 
 
 def groupnorm_apply(src1: CL, scale: torch.Tensor, shift: torch.Tensor, act: bool, src2: Optional[CL] = None) -> CL:
-    lib = _lib.load()
     N, S, C1, C2, c_log, p2 = _gn_sources(src1, src2, "ignore")       # per-(n, c) tables: padding lanes of the first source have their own rows
-    out = torch.empty(tuple(src1.t.shape[:4]) + (C1 + C2,), dtype=torch.bfloat16, device=src1.t.device)
-    check(lib.gg_groupnorm_apply(src1.t.data_ptr(), C1, p2, C2, N, S, scale.data_ptr(),
-                                 shift.data_ptr(), 1 if act else 0, out.data_ptr(), _stream()), "gg_groupnorm_apply")
+    out = _gn_out(src1, C1 + C2)
+    check(_lib.load().gg_groupnorm_apply(src1.t.data_ptr(), C1, p2, C2, N, S, scale.data_ptr(),
+                                         shift.data_ptr(), 1 if act else 0, out.data_ptr(), _stream()), "gg_groupnorm_apply")
     return CL(out, c_log)
 
 
 def groupnorm_fused_ok(src1: CL, src2: Optional[CL] = None) -> bool:
-    if is_f32(src1.t):
-        return False
-    hdr = _gn_sources(src1, src2, "none")
-    if hdr is None:
-        return False
-    N, S, C1, C2, c_log, p2 = hdr
-    return bool(_lib.load().gg_groupnorm_fused_supported(S, C1, C2, c_log))
+    hdr = None if is_f32(src1.t) else _gn_sources(src1, src2, "none")
+    return hdr is not None and bool(_lib.load().gg_groupnorm_fused_supported(hdr[1], hdr[2], hdr[3], hdr[4]))
 
 
 def groupnorm_fused(src1: CL, gamma: torch.Tensor, beta: torch.Tensor, eps: float, act: bool, src2: Optional[CL] = None) -> CL:
     """act(GroupNorm(32)(cat[src1, src2])) in one launch (small tensors: see groupnorm_fused_ok)."""
-    lib = _lib.load()
     N, S, C1, C2, c_log, p2 = _gn_sources(src1, src2, "ignore")       # the caller asked groupnorm_fused_ok
-    out = torch.empty(tuple(src1.t.shape[:4]) + (C1 + C2,), dtype=torch.bfloat16, device=src1.t.device)
-    check(lib.gg_groupnorm_fused(src1.t.data_ptr(), C1, p2, C2, N, S, c_log, gamma.data_ptr(),
-                                 beta.data_ptr(), eps, 1 if act else 0, out.data_ptr(), _stream()), "gg_groupnorm_fused")
+    out = _gn_out(src1, C1 + C2)
+    check(_lib.load().gg_groupnorm_fused(src1.t.data_ptr(), C1, p2, C2, N, S, c_log, gamma.data_ptr(),
+                                         beta.data_ptr(), eps, 1 if act else 0, out.data_ptr(), _stream()), "gg_groupnorm_fused")
     return CL(out, c_log)
 
 
 def groupnorm_f32(src1: CL, gamma: torch.Tensor, beta: torch.Tensor, eps: float, act: bool, src2: Optional[CL] = None) -> CL:
     """fp32 validation path: act(GroupNorm(32)(cat[src1, src2])) on fp32 CL tensors (fp64 statistics, ATen's fp32 affine order)."""
-    lib = _lib.load()
     N, S, C1, C2, c_log, p2 = _gn_sources(src1, src2)
-    out = torch.empty(tuple(src1.t.shape[:4]) + (C1 + C2,), dtype=torch.float32, device=src1.t.device)
+    out = _gn_out(src1, C1 + C2, torch.float32)
     ws = torch.empty(64 * N, dtype=torch.float32, device=src1.t.device)
-    check(lib.gg_groupnorm_f32(src1.t.data_ptr(), C1, p2, C2, N, S, c_log, gamma.data_ptr(), beta.data_ptr(),
-                               eps, 1 if act else 0, out.data_ptr(), ws.data_ptr(), _stream()), "gg_groupnorm_f32")
+    check(_lib.load().gg_groupnorm_f32(src1.t.data_ptr(), C1, p2, C2, N, S, c_log, gamma.data_ptr(), beta.data_ptr(),
+                                       eps, 1 if act else 0, out.data_ptr(), ws.data_ptr(), _stream()), "gg_groupnorm_f32")
     return CL(out, c_log)
 
 
 def groupnorm_f32_film(src: CL, gamma: torch.Tensor, beta: torch.Tensor, eps: float, film: torch.Tensor, act: bool) -> CL:
     """fp32 validation path of a FiLM out-norm: act(GroupNorm(32)(src) * (1 + s) + t) in the reference's order, with s = film[n, :C] and
     t = film[n, C:2C] (film fp32 [N, >= 2C], row-strided)."""
-    lib = _lib.load()
     N, S = src.N, src.S
     _check_film(film, N, src.C)
-    out = torch.empty_like(src.t)
+    out = _gn_out(src, src.Cpad, torch.float32)
     ws = torch.empty(64 * N, dtype=torch.float32, device=src.t.device)
-    check(lib.gg_groupnorm_f32_film(src.t.data_ptr(), src.Cpad, N, S, src.C, gamma.data_ptr(), beta.data_ptr(), eps, film.data_ptr(),
-                                    film.stride(0), 1 if act else 0, out.data_ptr(), ws.data_ptr(), _stream()), "gg_groupnorm_f32_film")
+    check(_lib.load().gg_groupnorm_f32_film(src.t.data_ptr(), src.Cpad, N, S, src.C, gamma.data_ptr(), beta.data_ptr(), eps, film.data_ptr(),
+                                            film.stride(0), 1 if act else 0, out.data_ptr(), ws.data_ptr(), _stream()), "gg_groupnorm_f32_film")
     return CL(out, src.C)
 
 
@@ -525,12 +522,11 @@ def resample2x(src: CL, up: bool, resample_d: bool, prologue: Optional[Tuple[tor
 
 def groupnorm_apply_acc(src1: CL, gamma: torch.Tensor, beta: torch.Tensor, eps: float, act: bool, src2: Optional[CL] = None) -> CL:
     """act(GroupNorm(32)(cat[src1, src2])) with the statistics taken from the accumulators the producing convs left in CL.acc."""
-    lib = _lib.load()
     N, S, C1, C2, c_log, p2 = _gn_sources(src1, src2)
-    out = torch.empty(tuple(src1.t.shape[:4]) + (C1 + C2,), dtype=torch.bfloat16, device=src1.t.device)
-    check(lib.gg_groupnorm_apply_acc(src1.t.data_ptr(), C1, src1.acc.data_ptr(), p2, C2,
-                                     src2.acc.data_ptr() if src2 is not None else None, N, S, c_log, gamma.data_ptr(),
-                                     beta.data_ptr(), eps, 1 if act else 0, out.data_ptr(), _stream()), "gg_groupnorm_apply_acc")
+    out = _gn_out(src1, C1 + C2)
+    check(_lib.load().gg_groupnorm_apply_acc(src1.t.data_ptr(), C1, src1.acc.data_ptr(), p2, C2,
+                                             src2.acc.data_ptr() if src2 is not None else None, N, S, c_log, gamma.data_ptr(),
+                                             beta.data_ptr(), eps, 1 if act else 0, out.data_ptr(), _stream()), "gg_groupnorm_apply_acc")
     return CL(out, c_log)
 
 
@@ -547,13 +543,11 @@ def has_any_stats(src1: CL, src2: Optional[CL] = None) -> bool:
 
 def groupnorm_scale_shift_acc(src1: CL, gamma: torch.Tensor, beta: torch.Tensor, eps: float, src2: Optional[CL] = None):
     """Per-(n, c) fp32 (scale, shift) of GroupNorm(32)(cat[src1, src2]) from the accumulators in CL.acc (no pass over the tensors)."""
-    lib = _lib.load()
     N, S, C1, C2, c_log, p2 = _gn_sources(src1, src2)
-    scale = torch.empty((N, C1 + C2), dtype=torch.float32, device=src1.t.device)
-    shift = torch.empty_like(scale)
-    check(lib.gg_groupnorm_scale_shift_acc(src1.acc.data_ptr(), src1.acc.shape[1], C1, src2.acc.data_ptr() if src2 is not None else None,
-                                           src2.acc.shape[1] if src2 is not None else 0, C2, N, S, c_log, gamma.data_ptr(), beta.data_ptr(),
-                                           eps, scale.data_ptr(), shift.data_ptr(), _stream()), "gg_groupnorm_scale_shift_acc")
+    scale, shift = _gn_tables(src1, N, C1 + C2)
+    check(_lib.load().gg_groupnorm_scale_shift_acc(src1.acc.data_ptr(), src1.acc.shape[1], C1, src2.acc.data_ptr() if src2 is not None else None,
+                                                   src2.acc.shape[1] if src2 is not None else 0, C2, N, S, c_log, gamma.data_ptr(), beta.data_ptr(),
+                                                   eps, scale.data_ptr(), shift.data_ptr(), _stream()), "gg_groupnorm_scale_shift_acc")
     return scale, shift
 
 

@@ -73,17 +73,17 @@ def _f32(x: float) -> torch.Tensor:
 
 # ------------------------------------------------------------------------------------------------ host gates (Python mirrors)
 def magic_u32(nmax: int, d: int) -> int:
-    """gg_magic_u32 (gg_common.h:76-79)"""
+    """gg_magic_u32 (gg_common.h)"""
     return ((1 << 32) + d - 1) // d if (d > 1 and nmax * d < (1 << 32)) else 0
 
 
 def stats_kernel(S: int, C_: int) -> str:
-    """gg_groupnorm_stats (gg_norm.hip:355): the single-launch statistics kernel up to S * C == 2^19"""
+    """gg_groupnorm_stats (gg_norm.hip, the gate in front of gn_stats_small_kernel): the single-launch statistics kernel up to S * C == 2^19"""
     return "small" if S * C_ <= (1 << 19) else "partial"
 
 
 def gn_nblk(N: int, S: int) -> int:
-    """gn_nblk (gg_norm.hip:333-343)"""
+    """gn_nblk (gg_norm.hip)"""
     want, maxb = (2048 + N - 1) // N, (S + 63) // 64
     return max(1, min(want, maxb, 1024))
 
@@ -94,7 +94,7 @@ def fused_np(C_: int) -> int:
 
 
 def fused_small_ok(S: int, C1: int, C2: int, c_log: int) -> bool:
-    """gn_fused_small_ok + the entry point's own checks (gg_norm.hip:294-312)"""
+    """gn_fused_small_ok + the checks of gg_groupnorm_fused_supported (gg_norm.hip)"""
     C_ = C1 + C2
     if not (C1 > 0 and C1 % 32 == 0 and C2 >= 0 and C2 % 32 == 0):
         return False
@@ -104,7 +104,7 @@ def fused_small_ok(S: int, C1: int, C2: int, c_log: int) -> bool:
 
 
 def apply_acc_kernel(N: int, S: int, C_: int, c_log: int) -> str:
-    """gg_groupnorm_apply_acc (gg_norm.hip:674-691): lean<CPT> (one piece per thread) or the general kernel"""
+    """gg_groupnorm_apply_acc (gg_norm.hip, its gate between the two kernels): lean<CPT> (one piece per thread) or the general kernel"""
     pieces = S * (C_ // 8)
     blocks = min(max((pieces + 255) // 256, 1), 4096)
     pm = magic_u32(pieces, C_ // 8)
