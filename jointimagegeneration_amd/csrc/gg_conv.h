@@ -6,8 +6,7 @@ struct ConvParams {
     int N, D, H, W, C1, C2, Cout, Cout_pad;
     int kd, kh, kw, stride, pad, upsample;
     int Do, Ho, Wo, out_dtype, prologue_act;
-    int path_hint;            // gg_conv_desc.path_hint (1: tests force the halo kernel below the grid-fill gate)
-                              // (box kernel: GG_BOX_HINT_GENERIC / GG_BOX_HINT_SPEC_ONLY, gg_conv_box_spec.hip)
+    int path_hint;            // gg_conv_desc.path_hint (0: production; halo kernel: GG_HALO_HINT_*; box kernel: GG_BOX_HINT_*, below)
     int nchunk1, nchunk, ntaps;
     long long M;              // N*Do*Ho*Wo
     long long bias_stride;
@@ -49,6 +48,13 @@ struct ConvParams {
 // that has no shape-specialised kernel
 #define GG_BOX_HINT_GENERIC 10
 #define GG_BOX_HINT_SPEC_ONLY 11
+// path_hint values of the halo-tile kernel (tests, A/B; 0 is production).  The first four lift the grid-fill gate, so that small shapes run
+// on the kernel; the BOX ones also fix the box size wherever that size is instantiated.
+#define GG_HALO_HINT_BOX512 1
+#define GG_HALO_HINT_BOX256 4
+#define GG_HALO_HINT_BOX1024 6
+#define GG_HALO_HINT_TEAM 7        /* the team kernel (gg_conv_halo3.hip) wherever its envelope allows */
+#define GG_HALO_HINT_NO_TEAM 8     /* production dispatch without the team kernel */
 
 // fixed-point scales of the GroupNorm accumulators: |sum| < 2^35, sumsq < 2^43 per channel and sample
 #define GG_ACC_SUM_SCALE 268435456.0f   /* 2^28 */

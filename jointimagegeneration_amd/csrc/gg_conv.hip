@@ -932,7 +932,7 @@ extern "C" int gg_conv_forward(const gg_conv_desc *d, void *stream_)
     }
 #endif
 #ifdef GG_H3_STAMPS
-    if (d->path_hint == 7 && d->workspace) p.ws = (float *)d->workspace;      // diagnostic build: phase stamps of the team halo kernel
+    if (d->path_hint == GG_HALO_HINT_TEAM && d->workspace) p.ws = (float *)d->workspace;      // diagnostic build: phase stamps of the team halo kernel
 #endif
     int rc = gg_conv_halo_try(p, stream);
 #ifdef GG_H3_STAMPS

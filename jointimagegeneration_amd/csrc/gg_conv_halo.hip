@@ -32,57 +32,61 @@
 #ifndef GG_HALO_W16_2D
 #define GG_HALO_W16_2D 1
 #endif
-#ifndef GG_HALO_W16_3D
-#define GG_HALO_W16_3D 0
-#endif
-#define GG_HALO_W16(D3, NT, HB) ((GG_HALO_W16_2D && !(D3) && (NT) >= 3 && (HB) != 1) || (GG_HALO_W16_3D && (D3) && ((HB) == 2 || (NT) >= 3)))
-#ifndef GG_HALO_DMA_UPPER
-#define GG_HALO_DMA_UPPER 0
-#endif
-#ifndef GG_HALO_PRIO_UPPER
-#define GG_HALO_PRIO_UPPER 0
-#endif
-#ifndef GG_HALO_WPS
-#define GG_HALO_WPS(NT) 2      /* measured: 4 waves/SIMD forces scratch spills (NT=2) and is not faster */
-#endif
+// The output box of a workgroup, for the kernel and for the host plan.  HB 0: 512 positions 4x8x16 (2-D: 1x32x16); 1: 256 positions 4x4x16
+// (under-filled 3-D grids; 2-D: 1x16x16 for grids that 512-position tiles leave under-filled at the widest cout tile, AE 512 / 384 channels
+// @128x128: 128 / 96 workgroups on 256 CUs); 2: 1024 positions 8x8x16, one 8-wave workgroup per CU (halo redundancy 1.76x instead of 2.1x)
+struct HaloBox { int TD, TH, TW; };
+constexpr HaloBox halo_box(bool d3, int hb) { return d3 ? HaloBox{hb == 2 ? 8 : 4, hb == 1 ? 4 : 8, 16} : HaloBox{1, hb == 1 ? 16 : 32, 16}; }
 
-template <int D3, int NT, int UP, int HB, int POST = 0>
-__global__ __launch_bounds__((GG_HALO_W16(D3, NT, HB) ? 1024 : (NT <= 2 && HB != 2) ? 256 : 512), (GG_HALO_W16(D3, NT, HB) ? 4 : (HB == 1 && D3) ? 3 : 2)) void conv_halo_kernel(const ConvParams p, const int tiles_d, const int tiles_h, const int tiles_w)
-{
-    // HB 0: 512-position box 4x8x16 (2-D: 1x32x16); 1: 256 positions 4x4x16 (under-filled 3-D grids); 2: 1024 positions 8x8x16, one
-    // 8-wave workgroup per CU (halo redundancy 1.76x instead of 2.1x: less staging work per output)
-    // 2-D, HB 1: 256 positions 1x16x16 for grids that 512-position tiles leave under-filled at the widest cout tile (AE 512 / 384 channels
-    // @128x128: 128 / 96 workgroups on 256 CUs); 8 waves x 2 position tiles
-    constexpr int TD = D3 ? (HB == 2 ? 8 : 4) : 1, TH = D3 ? (HB == 1 ? 4 : 8) : (HB == 1 ? 16 : 32), TW = 16;
+// Everything that __launch_bounds__, the kernel body and launch_halo derive from <D3, NT, UP, HB>, stated ONCE and with its assumptions asserted:
+// the weight DMA and the epilogue scratches write LDS at offsets computed from these, so a copy that fell behind would be a fault, not a failed test.
+template <int D3, int NT, int UP, int HB>
+struct HaloGeom {
+    static constexpr int TD = halo_box(D3, HB).TD, TH = halo_box(D3, HB).TH, TW = halo_box(D3, HB).TW;
     // NT <= 2: 4 waves x 8 position-tiles (128 pos x 32*NT couts per wave, 2 workgroups per CU overlap staging and MFMA);
-    // NT >= 3: 8 waves x 4 position-tiles (the accumulator would not fit otherwise)
+    // NT >= 3 and the 1024-position box: 8 waves x 4 (8) position-tiles (the accumulator would not fit otherwise)
     // 2-D, NT >= 3 (AE convs at 512^2 / 256^2: 9 taps per staged chunk, one workgroup per CU): 16 waves x 2 position tiles = 4 waves per SIMD
     // at <= 64 accumulator registers each, so that staging round trips and operand reads of one wave hide behind the others' MFMAs
-    // (same-box A/B at NT 4: AE decode 3.75 -> 3.60-3.68 ms)
-    constexpr int NWAVE = GG_HALO_W16(D3, NT, HB) ? 16 : (NT <= 2 && HB != 2) ? 4 : 8;
-    constexpr int TPW = (TD * TH) / NWAVE;
-    constexpr int NTHR = NWAVE * 64;
-    constexpr int KD = D3 ? 3 : 1;
-    constexpr int NTAPS = KD * 9;
-    constexpr int HD = D3 ? (UP ? TD / 2 + 2 : TD + 2) : 1;
-    constexpr int HH = UP ? TH / 2 + 2 : TH + 2;
-    constexpr int HW = UP ? TW / 2 + 2 : TW + 2;
-    constexpr int NROWS = HD * HH * HW;
-    constexpr int NPIECE = NROWS * 4;
-    constexpr int JMAX = (NPIECE + NTHR - 1) / NTHR;
-    constexpr int XBYTES = ((NROWS * 64 + 1023) / 1024) * 1024;
-    constexpr int WBYTES = NT * 2048;                    // one tap: 32*NT cout rows x 64 B
+    // (same-box A/B at NT 4: AE decode 3.75 -> 3.60-3.68 ms); 2-D, HB 1: 8 waves x 2 position tiles
+    static constexpr bool W16 = GG_HALO_W16_2D && !D3 && NT >= 3 && HB != 1;
+    static constexpr int NWAVE = W16 ? 16 : (NT <= 2 && HB != 2) ? 4 : 8, NTHR = NWAVE * 64;
+    static constexpr int LB_MIN = W16 ? 4 : (HB == 1 && D3) ? 3 : 2;       // second argument of __launch_bounds__
+    static constexpr int TPW = (TD * TH) / NWAVE;                           // position tiles (W-rows of 16 outputs) per wave
+    static constexpr int HD = D3 ? (UP ? TD / 2 + 2 : TD + 2) : 1, HH = UP ? TH / 2 + 2 : TH + 2, HW = UP ? TW / 2 + 2 : TW + 2;
+    static constexpr int NROWS = HD * HH * HW;                              // 64-byte rows of the staged input box
+    static constexpr int XBYTES = ((NROWS * 64 + 1023) / 1024) * 1024;
+    static constexpr int WBYTES = NT * 2048;                                // one tap: 32*NT cout rows x 64 B
     // G3: the three kw taps of a (kd, kh) line share ONE barrier and ONE weight DMA round (3 tiles, double-buffered: 6 * WBYTES), where
     // the workgroup is alone on its CU anyway (3-D, 8 waves: the 1024-position boxes and NT >= 3), so the extra LDS costs no residency:
     // 9 instead of 27 barriers per chunk (same-box A/B, CCDM forward @128^3: 16.54 -> 16.42 ms).  Hand-ordered software pipelines of the
     // tap loop on top of it (fragments of tap s+1 requested under the MFMAs of tap s; one or two register sets; immediate-offset
     // addressing) were NOT faster: 21.6 / 16.75 / 18.7 ms, see tools/experiments/README.md and gg_conv_halo_tap_pipeline.hip.txt.
-    constexpr bool G3 = (GG_HALO_G3 && D3 && (HB == 2 || (GG_HALO_G3_HB1 && HB == 1) || NT >= 3)) || (GG_HALO_G3_2D && !D3 && NT >= 3);
-    constexpr int GSZ = G3 ? 3 : 1;                      // taps per weight slot
-    extern __shared__ __attribute__((aligned(1024))) char smem[];      // XBYTES + 2 * GSZ * WBYTES (launch_halo)
-    char *xs = smem;
-    char *wsm = smem + XBYTES;
+    static constexpr bool G3 = (GG_HALO_G3 && D3 && (HB == 2 || (GG_HALO_G3_HB1 && HB == 1) || NT >= 3)) || (GG_HALO_G3_2D && !D3 && NT >= 3);
+    static constexpr int GSZ = G3 ? 3 : 1;                                  // taps per weight slot
+    static constexpr int LDSB = XBYTES + 2 * GSZ * WBYTES;                  // dynamic LDS: the box image, then two weight slots
+    // Epilogue (box and weights are dead): the statistics exchange [NWAVE][32 * NT][2] fp32 at 0; the per-wave scratches from SCR0 on
+    static constexpr int SCR0 = 8192, STAT_BYTES = NWAVE * 32 * NT * 2 * 4;
+    static constexpr bool TS = GG_HALO_TSTORE && D3 && HB == 2 && !W16;     // transposed stores (see the epilogue)
+    static constexpr int TS_RS = 64 * NT + 16, TS_END = SCR0 + NWAVE * 16 * TS_RS;
+    static constexpr int POST_END = SCR0 + NWAVE * TPW * 16 * 16 * 4;       // fused posterior: [TPW * 16 positions][16 logits] fp32 per wave
+    static_assert((TD * TH) % NWAVE == 0, "every wave owns the same number of position tiles");
+    static_assert(LDSB <= 160 * 1024, "box image + weight slots exceed the LDS of a CU");
+    static_assert(STAT_BYTES <= (TS ? SCR0 : LDSB), "statistics exchange runs into the scratch behind it");      // (16-wave kernels: 12 / 16 KiB, no scratch follows)
+    static_assert(!TS || TS_END <= LDSB, "transposed-store scratch ends outside the LDS allocation");
+};
 
+template <int D3, int NT, int UP, int HB, int POST = 0>
+__global__ __launch_bounds__((HaloGeom<D3, NT, UP, HB>::NTHR), (HaloGeom<D3, NT, UP, HB>::LB_MIN)) void conv_halo_kernel(const ConvParams p, const int tiles_d, const int tiles_h, const int tiles_w)
+{
+    using G = HaloGeom<D3, NT, UP, HB>;
+    constexpr int TD = G::TD, TH = G::TH, TW = G::TW, NWAVE = G::NWAVE, TPW = G::TPW, NTHR = G::NTHR, HH = G::HH, HW = G::HW;
+    constexpr int NROWS = G::NROWS, XBYTES = G::XBYTES, WBYTES = G::WBYTES, GSZ = G::GSZ;
+    constexpr bool G3 = G::G3;
+    static_assert(!POST || (NT == 1 && !G::W16 && (TPW * 16) % 64 == 0 && G::POST_END <= G::LDSB), "fused posterior: one 32-cout group, 64-lane position groups, scratch inside the LDS allocation");
+    constexpr int KD = D3 ? 3 : 1, NTAPS = KD * 9;
+    constexpr int NPIECE = NROWS * 4, JMAX = (NPIECE + NTHR - 1) / NTHR;
+    extern __shared__ __attribute__((aligned(1024))) char smem[];      // G::LDSB bytes
+    char *xs = smem, *wsm = smem + XBYTES;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // provably wave-uniform: tile rows live in SGPRs
     const int fr = lane & 15, fq = lane >> 4;
@@ -132,13 +136,10 @@ __global__ __launch_bounds__((GG_HALO_W16(D3, NT, HB) ? 1024 : (NT <= 2 && HB !=
     auto issue_w = [&](int ks, int buf) {               // ks: tap index (GSZ == 1) or index of the first tap of a line (GSZ == 3)
         const int chunk = ks / NTAPS, tap0 = ks - chunk * NTAPS;
         constexpr int NP = GSZ * NT * 2;                // 1 KiB pieces of the slot
-        // GG_HALO_DMA_UPPER: only the upper half of the waves (the SIMD partners of waves 0 .. NWAVE/2-1) issue the weight DMAs, so the
-        // two waves of a SIMD are not in lockstep after the barrier: one starts its operand reads at once, the other a few DMAs later
-        constexpr int DW = (GG_HALO_DMA_UPPER && G3) ? NWAVE / 2 : NWAVE, DW0 = NWAVE - DW;
 #pragma unroll
-        for (int i = 0; i < (NP + DW - 1) / DW; ++i) {
-            const int piece = (wave - DW0) + DW * i;
-            if (wave >= DW0 && piece < NP) {
+        for (int i = 0; i < (NP + NWAVE - 1) / NWAVE; ++i) {
+            const int piece = wave + NWAVE * i;
+            if (wave >= 0 && piece < NP) {      // wave >= 0 always holds; unstated, every kernel's assembly changes (tile % TH stops being a bit-field extract)
                 const int u = piece / (NT * 2), piece1k = piece - u * (NT * 2);
                 const int g = piece1k >> 1, half = piece1k & 1;
                 const bf16_t *src = p.weight + ((((long long)(g0 + g) * NTAPS + tap0 + u) * p.nchunk + chunk) << 10) + half * 512 + lane * 8;
@@ -148,8 +149,13 @@ __global__ __launch_bounds__((GG_HALO_W16(D3, NT, HB) ? 1024 : (NT <= 2 && HB !=
         }
     };
 
+    // tile tt of this wave is one W-row of 16 output positions: its (od, oh) inside the box, and the output position index of its column pw
+    auto tile_at = [&](int tt, int pw, int &od, int &oh) __attribute__((always_inline)) -> long long {
+        const int tile = wave * TPW + tt;
+        od = D3 ? tile / TH : 0; oh = D3 ? tile % TH : tile;
+        return (((long long)n * p.Do + (d0 + od)) * p.Ho + (h0 + oh)) * p.Wo + (w0 + pw);
+    };
     const int KS = p.nchunk * NTAPS;
-    if (GG_HALO_PRIO_UPPER && G3 && wave >= NWAVE / 2) __builtin_amdgcn_s_setprio(1);      // static priority for the younger half (MI355X_MICROARCH.md, two waves per SIMD, item 4)
     issue_w(0, 0);
 
     for (int chunk = 0; chunk < p.nchunk; ++chunk) {
@@ -246,9 +252,9 @@ __global__ __launch_bounds__((GG_HALO_W16(D3, NT, HB) ? 1024 : (NT <= 2 && HB !=
                     bf16x8 xf[TPW];
 #pragma unroll
                     for (int tt = 0; tt < TPW; ++tt) {
-                        const int tile = wave * TPW + tt;             // one W-row of 16 output positions
-                        const int od = D3 ? tile / TH : 0, oh = D3 ? tile % TH : tile;
-                        const int hd = D3 ? (UP ? ((od + kd + 1) >> 1) : od + kd) : 0;
+                        int od, oh;
+                        tile_at(tt, 0, od, oh);
+                        const int hd =D3 ? (UP ? ((od + kd + 1) >> 1) : od + kd) : 0;
                         const int hh = UP ? ((oh + kh + 1) >> 1) : oh + kh;
                         xf[tt] = *reinterpret_cast<const bf16x8 *>(xs + (hd * HH + hh) * (HW * 64) + lane_off[kw]);
                     }
@@ -285,9 +291,8 @@ __global__ __launch_bounds__((GG_HALO_W16(D3, NT, HB) ? 1024 : (NT <= 2 && HB !=
         // ===== fused CCDM reverse step (gg_conv_desc.post_xt): the logits never leave the CU =====
         // The accumulator layout gives a lane 4 of a position's K <= 16 logits; through LDS (the box image is dead) every lane gets ALL
         // logits of two of the wave's 16 TPW positions and runs gg_posterior.h on them: the very function of the stand-alone sampler kernel.
-        static_assert(NT == 1 && !GG_HALO_W16(D3, NT, HB) && (TPW * 16) % 64 == 0, "fused posterior: one 32-cout group, 64-lane position groups");
         const f32x4 bv = brow ? *reinterpret_cast<const f32x4 *>(brow + g0 * 32 + fq * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
-        float *scrp = reinterpret_cast<float *>(smem + 8192) + wave * (TPW * 16 * 16);        // [TPW * 16 positions][16 logits] fp32
+        float *scrp = reinterpret_cast<float *>(smem + G::SCR0) + wave * (TPW * 16 * 16);     // [TPW * 16 positions][16 logits] fp32, ends at G::POST_END
 #pragma unroll
         for (int tt = 0; tt < TPW; ++tt) {
             f32x4 v = acc[tt][0];
@@ -302,10 +307,9 @@ __global__ __launch_bounds__((GG_HALO_W16(D3, NT, HB) ? 1024 : (NT <= 2 && HB !=
         const long long mbase = p.post_seeds ? (long long)n * p.post_rows_per_sample : 0;
 #pragma unroll 1
         for (int r = 0; r < TPW * 16 / 64; ++r) {
-            const int pp = r * 64 + lane, tt = pp >> 4, pw = pp & 15;
-            const int tile = wave * TPW + tt;
-            const int od = D3 ? tile / TH : 0, oh = D3 ? tile % TH : tile;
-            const long long m = (((long long)n * p.Do + (d0 + od)) * p.Ho + (h0 + oh)) * p.Wo + (w0 + pw);
+            const int pp = r * 64 + lane;
+            int od, oh;
+            const long long m = tile_at(pp >> 4, pp & 15, od, oh);
             const int x = p.post_xt[m];
             float p0[16];
 #pragma unroll
@@ -323,15 +327,15 @@ __global__ __launch_bounds__((GG_HALO_W16(D3, NT, HB) ? 1024 : (NT <= 2 && HB !=
         }
         return;
     }
-    if constexpr (!GG_HALO_W16(D3, NT, HB)) {
+    // The per-value step (bias, residual, pad-lane zero, round to bf16, statistics) keeps its text in both arms below: shared through a
+    // lambda, this arm's NT 3 and 1024-position NT 2 kernels compile to other code
+    if constexpr (!G::W16) {
         f32x4 bvec[2 * NT];
 #pragma unroll
         for (int ct = 0; ct < 2 * NT; ++ct) bvec[ct] = brow ? *reinterpret_cast<const f32x4 *>(brow + g0 * 32 + ct * 16 + fq * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
         auto out_off = [&](int tt) -> long long {
-            const int tile = wave * TPW + tt;
-            const int od = D3 ? tile / TH : 0, oh = D3 ? tile % TH : tile;
-            const long long m = (((long long)n * p.Do + (d0 + od)) * p.Ho + (h0 + oh)) * p.Wo + (w0 + fr);
-            return m * p.Cout_pad + g0 * 32 + fq * 4;
+            int od, oh;
+            return tile_at(tt, fr, od, oh) * p.Cout_pad + g0 * 32 + fq * 4;
         };
         // all residual pieces of the wave's tiles in flight at once (TPW x 2 NT x 2 registers: 64 where the wave owns 128 positions x 64
         // couts; the operand fragments are dead by now): ONE memory round trip in front of the stores instead of one per tile row
@@ -343,9 +347,9 @@ __global__ __launch_bounds__((GG_HALO_W16(D3, NT, HB) ? 1024 : (NT <= 2 && HB !=
         // 2 KiB run where the wave owns all couts).  Scratch rows are padded by 16 B: conflict-free 8-byte writes for NT 1..4.
         // Measured (same-box A/B): 64->64 @128^3 with residual 566 -> 530 us, without 487 -> 476; on the 512-position boxes (NT 3 / 4) and
         // in 2-D it is 1-2 % SLOWER (shorter epilogues, and NT 3 spills 50 registers), so only the 1024-position boxes take it.
-        constexpr bool TS = GG_HALO_TSTORE && D3 && HB == 2;
-        constexpr int TS_PPR = 4 * NT, TS_RS = 64 * NT + 16;
-        char *scr = smem + 8192 + wave * (16 * TS_RS);      // the first 8 KiB take the statistics exchange below
+        constexpr bool TS = G::TS;
+        constexpr int TS_PPR = 4 * NT, TS_RS = G::TS_RS;
+        char *scr = smem + G::SCR0 + wave * (16 * TS_RS);   // ends at G::TS_END; the first 8 KiB take the statistics exchange below
         constexpr bool ALLRES = NT <= 2;
         constexpr int RD = ALLRES ? TPW : 2;
         // the residual comes in the same way: NT 16-byte pieces per lane in memory order, redistributed to the accumulator layout
@@ -428,11 +432,9 @@ __global__ __launch_bounds__((GG_HALO_W16(D3, NT, HB) ? 1024 : (NT <= 2 && HB !=
         constexpr int NTILE = TPW * 2 * NT;
         auto tile_off = [&](int k, long long &o, int &co) {
             const int tt = k / (2 * NT), ct = k - tt * (2 * NT);
-            const int tile = wave * TPW + tt;
-            const int od = D3 ? tile / TH : 0, oh = D3 ? tile % TH : tile;
-            const long long m = (((long long)n * p.Do + (d0 + od)) * p.Ho + (h0 + oh)) * p.Wo + (w0 + fr);
+            int od, oh;
             co = g0 * 32 + ct * 16 + fq * 4;
-            o = m * p.Cout_pad + co;
+            o = tile_at(tt, fr, od, oh) * p.Cout_pad + co;
         };
         f32x4 bnx = f32x4{0.f, 0.f, 0.f, 0.f};
         bf16x4 rnx = bf16x4{(bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f};
@@ -508,39 +510,49 @@ __global__ __launch_bounds__((GG_HALO_W16(D3, NT, HB) ? 1024 : (NT <= 2 && HB !=
     }
 }
 
+// What the host decides for one conv (halo_plan below): the kernel instantiation and its grid
+struct HaloPlan {
+    bool family, ok;          // 3x3(x3) stride-1 pad-1 conv (the team kernel may be asked) / inside the envelope and past the grid-fill gate
+    int d3, NT, HB, up, post;
+    int tiles_d, tiles_h, tiles_w;      // boxes of size HB per sample
+    long long blocks;         // workgroups at the 512-position box: the figure that the gate and the box-size rules were fitted on
+};
+
 template <int D3, int NT, int UP, int HB = 0, int POST = 0>
-static int launch_halo(const ConvParams &p, hipStream_t stream)
+static int launch_halo(const ConvParams &p, const HaloPlan &pl, hipStream_t stream)
 {
-    constexpr int TD = D3 ? (HB == 2 ? 8 : 4) : 1, TH = D3 ? (HB == 1 ? 4 : 8) : (HB == 1 ? 16 : 32), TW = 16;
-    constexpr int HD = D3 ? (UP ? TD / 2 + 2 : TD + 2) : 1, HH = UP ? TH / 2 + 2 : TH + 2, HW = UP ? TW / 2 + 2 : TW + 2;
-    constexpr bool G3 = (GG_HALO_G3 && D3 && (HB == 2 || (GG_HALO_G3_HB1 && HB == 1) || NT >= 3)) || (GG_HALO_G3_2D && !D3 && NT >= 3);
-    constexpr int LDSB = ((HD * HH * HW * 64 + 1023) / 1024) * 1024 + (G3 ? 6 : 2) * NT * 2048;
+    using G = HaloGeom<D3, NT, UP, HB>;
     // the attribute is per device: one bit per device ordinal (setting it twice from two threads is harmless)
     static std::atomic<unsigned long long> attr_mask{0};
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return GG_ERR_HIP;
     const unsigned long long dev_bit = 1ull << (dev & 63);
     if (!(attr_mask.load(std::memory_order_acquire) & dev_bit)) {
-        if (hipFuncSetAttribute((const void *)conv_halo_kernel<D3, NT, UP, HB, POST>, hipFuncAttributeMaxDynamicSharedMemorySize, LDSB) != hipSuccess)
-            return GG_ERR_UNSUPPORTED;
+        if (hipFuncSetAttribute((const void *)conv_halo_kernel<D3, NT, UP, HB, POST>, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDSB) != hipSuccess) return GG_ERR_UNSUPPORTED;
         attr_mask.fetch_or(dev_bit, std::memory_order_release);
     }
-    const int tiles_d = p.Do / TD, tiles_h = p.Ho / TH, tiles_w = p.Wo / TW;
-    dim3 grid((unsigned)(p.N * tiles_d * tiles_h * tiles_w), (unsigned)(p.Cout_pad / (32 * NT)));
-    hipLaunchKernelGGL((conv_halo_kernel<D3, NT, UP, HB, POST>), grid, dim3(GG_HALO_W16(D3, NT, HB) ? 1024 : (NT <= 2 && HB != 2) ? 256 : 512), LDSB, stream, p, tiles_d, tiles_h, tiles_w);
+    dim3 grid((unsigned)(p.N * pl.tiles_d * pl.tiles_h * pl.tiles_w), (unsigned)(p.Cout_pad / (32 * NT)));
+    hipLaunchKernelGGL((conv_halo_kernel<D3, NT, UP, HB, POST>), grid, dim3(G::NTHR), G::LDSB, stream, p, pl.tiles_d, pl.tiles_h, pl.tiles_w);
     GG_CHECK_LAUNCH();
     return GG_OK;
 }
 
-template <int D3, int UP>
-static int dispatch_nt(const ConvParams &p, int NT, hipStream_t stream)
+// The 27 instantiations of the library; a plan outside them (a fused posterior off the 1024-position box) has no kernel
+constexpr int halo_key(int d3, int nt, int up, int hb, int post) { return (((d3 * 8 + nt) * 2 + up) * 4 + hb) * 2 + post; }
+static int halo_dispatch(const ConvParams &p, const HaloPlan &pl, hipStream_t stream)
 {
-    switch (NT) {
-        case 4: return launch_halo<D3, 4, UP>(p, stream);
-        case 3: return launch_halo<D3, 3, UP>(p, stream);
-        case 2: return launch_halo<D3, 2, UP>(p, stream);
-        default: return launch_halo<D3, 1, UP>(p, stream);
+#define GG_HALO_CASE(D3, NT, UP, HB, POST) case halo_key(D3, NT, UP, HB, POST): return launch_halo<D3, NT, UP, HB, POST>(p, pl, stream);
+    switch (halo_key(pl.d3, pl.NT, pl.up, pl.HB, pl.post)) {
+        GG_HALO_CASE(1, 2, 0, 2, 0) GG_HALO_CASE(1, 1, 0, 2, 1) GG_HALO_CASE(1, 1, 0, 2, 0)      // (the kernels sit in the code object in this order)
+        GG_HALO_CASE(1, 2, 1, 1, 0) GG_HALO_CASE(1, 2, 0, 1, 0) GG_HALO_CASE(1, 1, 1, 1, 0) GG_HALO_CASE(1, 1, 0, 1, 0)
+        GG_HALO_CASE(1, 4, 1, 0, 0) GG_HALO_CASE(1, 3, 1, 0, 0) GG_HALO_CASE(1, 2, 1, 0, 0) GG_HALO_CASE(1, 1, 1, 0, 0)
+        GG_HALO_CASE(1, 4, 0, 0, 0) GG_HALO_CASE(1, 3, 0, 0, 0) GG_HALO_CASE(1, 2, 0, 0, 0) GG_HALO_CASE(1, 1, 0, 0, 0)
+        GG_HALO_CASE(0, 4, 1, 1, 0) GG_HALO_CASE(0, 4, 0, 1, 0) GG_HALO_CASE(0, 3, 1, 1, 0) GG_HALO_CASE(0, 3, 0, 1, 0)
+        GG_HALO_CASE(0, 4, 1, 0, 0) GG_HALO_CASE(0, 3, 1, 0, 0) GG_HALO_CASE(0, 2, 1, 0, 0) GG_HALO_CASE(0, 1, 1, 0, 0)
+        GG_HALO_CASE(0, 4, 0, 0, 0) GG_HALO_CASE(0, 3, 0, 0, 0) GG_HALO_CASE(0, 2, 0, 0, 0) GG_HALO_CASE(0, 1, 0, 0, 0)
+        default: return GG_ERR_UNSUPPORTED;
     }
+#undef GG_HALO_CASE
 }
 
 // team kernel for filled 3-D grids (gg_conv_halo3.hip); same contract
@@ -560,6 +572,41 @@ static int halo_pick_nt(bool d3, int G, long long tiles)
     return 1;
 }
 
+// Every envelope test, the grid-fill gate and the box-size rules.  The figures are filled in whatever the tests say (the predicates below
+// read them for shapes that their callers have vetted); .ok says whether the kernel takes the conv.
+static HaloPlan halo_plan(const ConvParams &p)
+{
+    HaloPlan pl{};
+    const int hint = p.path_hint;
+    const bool prod = hint == 0 || hint == GG_HALO_HINT_NO_TEAM;
+    pl.d3 = (p.kd == 3); pl.up = p.upsample ? 1 : 0; pl.post = p.post_xt ? 1 : 0;
+    const HaloBox b0 = halo_box(pl.d3, 0);
+    const int G = p.Cout_pad / 32;
+    const long long tiles = (long long)p.N * (p.Do / b0.TD) * (p.Ho / b0.TH) * (p.Wo / b0.TW);
+    pl.NT = halo_pick_nt(pl.d3, G, tiles);
+    pl.blocks = tiles * (G / pl.NT);
+    // 3-D grids that still give every CU a workgroup with 1024-position boxes (8x8x16, one 8-wave workgroup per CU, 124 KiB of LDS):
+    // the halo redundancy drops from 2.1x to 1.76x, i.e. less staging (loads, GroupNorm*SiLU, LDS writes) per output.  Same-box A/B at
+    // 128^3 with the fused prologue: 64->64 500 -> 468 us, 192->64 1338 -> 1240 us, 32->64 300 -> 280 us (bit-identical results);
+    // 256->256 @32^3 would lose (177 vs 156 us: half the workgroups), hence the grid condition.
+    // 3-D grids of at most one 512-position workgroup per CU: 256-position boxes (4x4x16, three workgroups per CU) double the
+    // grid; same-box A/B 256->256 @32^3: 141 vs 156 us.  On filled grids the two box sizes are within +-3 % (64->64 @128^3
+    // 525-534 vs 519-571 us, 192->64 1464-1467 vs 1370-1442 us), so those keep the box with the smaller halo.
+    // 2-D grids that the 512-position tiles under-fill at the widest cout tile: 256-position boxes, twice the workgroups.
+    // Hints (tests): BOX512 = always the 512-position box, BOX256 = the 256-position box wherever it is instantiated, BOX1024 = the 1024-one.
+    if (pl.d3 && pl.NT <= 2 && !pl.up && (p.Do % 8) == 0 && (hint == GG_HALO_HINT_BOX1024 || (prod && pl.blocks >= 512))) pl.HB = 2;
+    else if (pl.d3 && pl.NT <= 2 && (hint == GG_HALO_HINT_BOX256 || (prod && pl.blocks <= 256))) pl.HB = 1;
+    else if (!pl.d3 && GG_HALO_2D_HB1 && pl.NT >= 3 && (hint == GG_HALO_HINT_BOX256 || (prod && pl.blocks < 224))) pl.HB = 1;
+    const HaloBox b = halo_box(pl.d3, pl.HB);
+    pl.tiles_d = p.Do / b.TD; pl.tiles_h = p.Ho / b.TH; pl.tiles_w = p.Wo / b.TW;
+    pl.family = p.kh == 3 && p.kw == 3 && (p.kd == 3 || p.kd == 1) && p.stride == 1 && p.pad == 1 && (pl.d3 || p.D == 1);
+    // under-filled grids: the box / split-K gather paths are faster (2-D under one workgroup per CU: AE 512->512 @64x64 is 136 us
+    // here at 128 workgroups); the test hints lift the gate so that small shapes run on this kernel
+    const bool gate = hint != GG_HALO_HINT_BOX512 && hint != GG_HALO_HINT_BOX256 && hint != GG_HALO_HINT_BOX1024 && hint != GG_HALO_HINT_TEAM;
+    pl.ok = pl.family && !(p.Wo % b0.TW || p.Ho % b0.TH || p.Do % b0.TD) && !(gate && pl.blocks < ((pl.d3 || pl.NT > 1) ? 128 : 256));
+    return pl;
+}
+
 // Whether GroupNorm * SiLU in front of this conv is cheaper as its OWN pass than fused into the staging pass (the caller has checked
 // that gg_conv_halo_try takes the shape).  Fused, every staged element costs ~25 vector instructions incl. two transcendentals, once per
 // cout group and per box that holds it (halo redundancy 1.2x in 2-D, 2.1x for the 512-position 3-D boxes, 1.76x for the 1024-position
@@ -573,85 +620,37 @@ static int halo_pick_nt(bool d3, int G, long long tiles)
 // 128 channels @64^3 / @32^3) look like wins above (-4 %), but IN the captured CCDM forward the rule applied to them lost: 15.47 -> 15.55 ms
 // (their apply pass reads a tensor the memory-side cache no longer holds); they stay fused.  With the rule as it is (captured, same box):
 // AE decode 3.51 -> 3.44 ms, cond-encode 1.458 -> 1.423 ms.
+// The rule counts groups with the NT of the plan, i.e. from the tiles of the 512-position box whatever HB the plan then chooses: it was fitted so
 bool gg_conv_halo_prefers_separate_norm(const ConvParams &p)
 {
-    const bool d3 = (p.kd == 3);
-    const int TD = d3 ? 4 : 1, TH = d3 ? 8 : 32, TW = 16;
-    const int G = p.Cout_pad / 32;
-    const long long tiles = (long long)p.N * (p.Do / TD) * (p.Ho / TH) * (p.Wo / TW);
-    const int NT = halo_pick_nt(d3, G, tiles);
-    const int groups = G / NT;
-    return groups >= 3 || (groups == 2 && NT == 4);
-}
-
-static bool halo_uses_1024_box(const ConvParams &p, bool d3, int NT, long long blocks)
-{
-    return d3 && NT <= 2 && !p.upsample && (p.Do % 8) == 0 && (p.path_hint == 6 || ((p.path_hint == 0 || p.path_hint == 8) && blocks >= 512));
+    const HaloPlan pl = halo_plan(p);
+    const int groups = p.Cout_pad / 32 / pl.NT;
+    return groups >= 3 || (groups == 2 && pl.NT == 4);
 }
 
 // The CCDM reverse step as the epilogue of the head conv: the 1024-position 3-D box kernel with ONE 32-cout group holding all K <= 16 classes
 bool gg_conv_halo_fuses_posterior(const ConvParams &p)
 {
-    if (!(p.kd == 3 && p.kh == 3 && p.kw == 3) || p.stride != 1 || p.pad != 1 || p.upsample) return false;
     if (p.Cout > 16 || p.Cout_pad != 32 || p.out_dtype != GG_F32 || p.residual || p.gn_acc) return false;
-    if (p.Wo % 16 || p.Ho % 8 || p.Do % 8) return false;
-    const long long tiles = (long long)p.N * (p.Do / 4) * (p.Ho / 8) * (p.Wo / 16);
-    if (p.path_hint != 6 && tiles < 128) return false;      // (the under-filled-grid gate of gg_conv_halo_try)
-    return halo_uses_1024_box(p, true, 1, tiles);
+    const HaloPlan pl = halo_plan(p);
+    return pl.ok && pl.HB == 2;
 }
 
 // Returns GG_ERR_UNSUPPORTED (silently, no error text) when the shape is outside the envelope: the caller then uses the
 // generic gather kernel.  stream == (hipStream_t)-1: dry run (only answers whether the halo kernel would be used).
 int gg_conv_halo_try(const ConvParams &p, hipStream_t stream)
 {
-    const bool d3 = (p.kd == 3);
-    if (!(p.kh == 3 && p.kw == 3 && (p.kd == 3 || p.kd == 1))) return GG_ERR_UNSUPPORTED;
-    if (p.stride != 1 || p.pad != 1) return GG_ERR_UNSUPPORTED;
-    if (!d3 && p.D != 1) return GG_ERR_UNSUPPORTED;
-    // path_hint 7 (tests, A/B probes): the team kernel wherever its envelope allows; 8: production dispatch WITHOUT the team kernel.
-    // GG_HALO3_DEFAULT decides what production (path_hint 0) does.
+    const HaloPlan pl = halo_plan(p);
+    if (!pl.family) return GG_ERR_UNSUPPORTED;
+    // the team kernel where a hint asks for it (gg_conv.h); GG_HALO3_DEFAULT decides what production (path_hint 0) does
 #ifndef GG_HALO3_DEFAULT
 #define GG_HALO3_DEFAULT 0
 #endif
-    if (d3 && !p.post_xt && ((GG_HALO3_DEFAULT && p.path_hint == 0) || p.path_hint == 7)) {
+    if (pl.d3 && !p.post_xt && ((GG_HALO3_DEFAULT && p.path_hint == 0) || p.path_hint == GG_HALO_HINT_TEAM)) {
         const int rc3 = gg_conv_halo3_try(p, stream);
         if (rc3 != GG_ERR_UNSUPPORTED) return rc3;
     }
-    const int TD = d3 ? 4 : 1, TH = d3 ? 8 : 32, TW = 16;
-    if (p.Wo % TW || p.Ho % TH || p.Do % TD) return GG_ERR_UNSUPPORTED;
-    const int G = p.Cout_pad / 32;
-    const long long tiles = (long long)p.N * (p.Do / TD) * (p.Ho / TH) * (p.Wo / TW);
-    constexpr int wide2d = 1;
-    const int NT = halo_pick_nt(d3, G, tiles);
-    const long long blocks = tiles * (G / NT);
-    // under-filled grids: the box / split-K gather paths are faster (2-D under one workgroup per CU: AE 512->512 @64x64 is 136 us
-    // here at 128 workgroups); path_hint 1 / 4 / 6 (tests) lift the gate so that small shapes run on this kernel
-    const long long min_blocks = (d3 || (wide2d && NT > 1)) ? 128 : 256;
-    if (p.path_hint != 1 && p.path_hint != 4 && p.path_hint != 6 && p.path_hint != 7 && blocks < min_blocks) return GG_ERR_UNSUPPORTED;
+    if (!pl.ok) return GG_ERR_UNSUPPORTED;
     if (stream == (hipStream_t)-1) return GG_OK;
-    // 3-D grids of at most one 512-position workgroup per CU: 256-position boxes (HB: 4x4x16, three workgroups per CU) double the
-    // grid; same-box A/B 256->256 @32^3: 141 vs 156 us.  On filled grids the two box sizes are within +-3 % (64->64 @128^3
-    // 525-534 vs 519-571 us, 192->64 1464-1467 vs 1370-1442 us), so those keep the box with the smaller halo.
-    // path_hint (tests): 1 = always the 512-position box, 4 = the 256-position box wherever it is instantiated (NT <= 2), 6 = the 1024-one.
-    // 3-D grids that still give every CU a workgroup with 1024-position boxes (8x8x16, one 8-wave workgroup per CU, 124 KiB of LDS):
-    // the halo redundancy drops from 2.1x to 1.76x, i.e. less staging (loads, GroupNorm*SiLU, LDS writes) per output.  Same-box A/B at
-    // 128^3 with the fused prologue: 64->64 500 -> 468 us, 192->64 1338 -> 1240 us, 32->64 300 -> 280 us (bit-identical results);
-    // 256->256 @32^3 would lose (177 vs 156 us: half the workgroups), hence the grid condition.  path_hint 6 (tests) forces it.
-    if (halo_uses_1024_box(p, d3, NT, blocks)) {
-        if (NT == 2) return launch_halo<1, 2, 0, 2>(p, stream);
-        if (p.post_xt) return launch_halo<1, 1, 0, 2, 1>(p, stream);       // UNet head with the CCDM reverse step as its epilogue
-        return launch_halo<1, 1, 0, 2>(p, stream);
-    }
-    if (p.post_xt) return GG_ERR_UNSUPPORTED;      // (gg_conv_forward has asked gg_conv_fuses_posterior: not reached)
-    if (d3 && NT <= 2 && (p.path_hint == 4 || ((p.path_hint == 0 || p.path_hint == 8) && blocks <= 256))) {
-        if (NT == 2) return p.upsample ? launch_halo<1, 2, 1, 1>(p, stream) : launch_halo<1, 2, 0, 1>(p, stream);
-        return p.upsample ? launch_halo<1, 1, 1, 1>(p, stream) : launch_halo<1, 1, 0, 1>(p, stream);
-    }
-    if (d3) return p.upsample ? dispatch_nt<1, 1>(p, NT, stream) : dispatch_nt<1, 0>(p, NT, stream);
-    // 2-D grids that the 512-position tiles under-fill at the widest cout tile: 256-position boxes, twice the workgroups (path_hint 4: tests)
-    if (GG_HALO_2D_HB1 && NT >= 3 && (p.path_hint == 4 || ((p.path_hint == 0 || p.path_hint == 8) && blocks < 224))) {
-        if (NT == 4) return p.upsample ? launch_halo<0, 4, 1, 1>(p, stream) : launch_halo<0, 4, 0, 1>(p, stream);
-        return p.upsample ? launch_halo<0, 3, 1, 1>(p, stream) : launch_halo<0, 3, 0, 1>(p, stream);
-    }
-    return p.upsample ? dispatch_nt<0, 1>(p, NT, stream) : dispatch_nt<0, 0>(p, NT, stream);
+    return halo_dispatch(p, pl, stream);
 }

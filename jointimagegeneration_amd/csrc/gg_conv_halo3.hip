@@ -498,7 +498,7 @@ int gg_conv_halo3_try(const ConvParams &p, hipStream_t stream)
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return GG_ERR_HIP;
     // persistent: one workgroup per CU; under-filled grids (fewer items than ~3/4 of the CUs) stay on the 256-position boxes of conv_halo_kernel
-    if (p.path_hint != 7 && items < (long long)cus * 3 / 4) return GG_ERR_UNSUPPORTED;
+    if (p.path_hint != GG_HALO_HINT_TEAM && items < (long long)cus * 3 / 4) return GG_ERR_UNSUPPORTED;
     if (stream == (hipStream_t)-1) return GG_OK;
     static std::atomic<unsigned long long> attr_mask{0};
     const unsigned long long dev_bit = 1ull << (dev & 63);
