@@ -263,6 +263,14 @@ int64_t gg_attention_workspace_bytes(const gg_attention_desc *desc);
  * workspace is handed in (1: never), in-workgroup key split 0/1, K/V tiles staged by LDS-DMA 0/1}.  Pointers are not read and
  * nothing is launched; gg_attention_forward takes its decisions from the same function. */
 int gg_attention_plan(const gg_attention_desc *desc, int32_t plan[4]);
+/* Attention under a padding mask that is a prefix of ones (BERT): sample n attends to keys [0, kv_len[n]) only.  kv_len: int32 [N] on
+ * the DEVICE, 1 <= kv_len[n] <= Tkv (the caller checks the host values it uploaded; the kernel clamps a value outside the range into
+ * it and never reads past row Tkv - 1).  Keys j >= kv_len[n] have weight exactly 0 and their K / V rows are not read; whole key tiles
+ * past the length are not walked.  All Tq query rows are computed; Tkv stays the row stride of the K / V buffers.  Runs the plain
+ * register-staged kernel (no key split of either kind, desc->workspace is ignored): head_dim 32, 64 or 128, others
+ * GG_ERR_UNSUPPORTED.  With kv_len[n] == Tkv for all n the result equals gg_attention_forward's wherever that runs the plain kernel.
+ * Like every entry point here it reads no device memory on the host, allocates nothing and never synchronises (capture-safe). */
+int gg_attention_forward_kvlen(const gg_attention_desc *desc, const int32_t *kv_len, void *stream);
 
 /* LayerNorm over the last dim (nn.LayerNorm eps 1e-5, attention.py:203-205), bf16 rows -> bf16 rows. */
 int gg_layernorm(const void *x, int64_t rows, int32_t C, const float *gamma, const float *beta, float eps,
@@ -493,6 +501,16 @@ int gg_minmax_normalise_scatter(const float *src, int32_t N, int64_t n_per_sampl
  * reads neither table (the callers check the range on the host; the kernel never reads out of bounds). */
 int gg_embed_rows(const int32_t *ids, int64_t rows, int32_t T, const float *tok, int32_t V, int32_t D, const float *pos, int32_t P,
                   void *out, int32_t out_dtype, int32_t out_stride, void *stream);
+/* transformers' BertEmbeddings in one launch: out[r, :] = LayerNorm((word[ids[r]] + type[type_ids[r]]) + pos[r % T]), rows = B * T.
+ * word fp32 [V, D], pos fp32 [P, D] (T <= P), type fp32 [NT, D], gamma / beta fp32 [D]; type_ids NULL: type 0 everywhere.  Sums and
+ * statistics in fp32 (mean, then the centred sum of squares; biased variance; eps from the model's config), one rounding to bf16.
+ * out: bf16 rows of out_stride >= D elements, lanes [D, out_stride) written as zeros.  ids_host / type_ids_host: optional HOST copies
+ * of the ids (they come from a host tokenizer); an id outside its table there returns GG_ERR_BAD_SHAPE before anything is launched.
+ * The device copies are never read back: without the host copies an id outside its table gives a zero row and reads no table, as in
+ * gg_embed_rows. */
+int gg_bert_embed(const int32_t *ids, const int32_t *type_ids, int64_t rows, int32_t T, const float *word, int32_t V, const float *pos,
+                  int32_t P, const float *type, int32_t NT, int32_t D, const float *gamma, const float *beta, float eps, void *out,
+                  int32_t out_stride, const int32_t *ids_host, const int32_t *type_ids_host, void *stream);
 /* Elementwise erf-form GELU (nn.GELU, F.gelu): bf16 in, bf16 out, fp32 arithmetic, 0.5 x erfc(-x / sqrt 2) (the left tail keeps its
  * relative accuracy).  n > 0 elements, any n; x and out 16-byte aligned. */
 int gg_gelu(const void *x, int64_t n, void *out, void *stream);
@@ -600,6 +618,8 @@ int gg_groupnorm_f32(const float *src1, int32_t C1, const float *src2, int32_t C
 int gg_groupnorm_f32_film(const float *src, int32_t C_pad, int32_t N, int64_t S, int32_t C_logical, const float *gamma, const float *beta,
                           float eps, const float *film, int64_t film_stride, int32_t act, float *out, float *workspace, void *stream);
 int gg_attention_forward_f32(const gg_attention_desc *desc, void *stream);
+/* gg_attention_forward_kvlen on the fp32 validation kernel (head_dim <= 64): the key loop of sample n ends at kv_len[n]. */
+int gg_attention_forward_kvlen_f32(const gg_attention_desc *desc, const int32_t *kv_len, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * On-box peak measurements for the benchmark's roofline (gg_ubench.hip; SURVEY.md 8d, BASELINE.md 3: fractions are quoted against

@@ -67,6 +67,7 @@ SIGNATURES = {
     "gg_attention_forward": (C.c_int, [C.POINTER(AttentionDesc), vp]),
     "gg_attention_workspace_bytes": (i64, [C.POINTER(AttentionDesc)]),
     "gg_attention_plan": (C.c_int, [C.POINTER(AttentionDesc), C.POINTER(i32)]),
+    "gg_attention_forward_kvlen": (C.c_int, [C.POINTER(AttentionDesc), vp, vp]),
     "gg_layernorm": (C.c_int, [vp, i64, i32, vp, vp, f32, vp, vp]),
     "gg_geglu": (C.c_int, [vp, i64, i32, vp, vp]),
     "gg_add": (C.c_int, [vp, vp, i64, vp, vp]),
@@ -96,6 +97,7 @@ SIGNATURES = {
     "gg_conv_forward_f32": (C.c_int, [C.POINTER(ConvDesc), vp]),
     "gg_groupnorm_f32": (C.c_int, [vp, i32, vp, i32, i32, i64, i32, vp, vp, f32, i32, vp, vp, vp]),
     "gg_attention_forward_f32": (C.c_int, [C.POINTER(AttentionDesc), vp]),
+    "gg_attention_forward_kvlen_f32": (C.c_int, [C.POINTER(AttentionDesc), vp, vp]),
     "gg_groupnorm_f32_film": (C.c_int, [vp, i32, i32, i64, i32, vp, vp, f32, vp, i64, i32, vp, vp, vp]),
     "gg_resample2x": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp]),
     "gg_film_fold": (C.c_int, [vp, vp, i32, i32, i32, vp, i64, vp]),
@@ -103,6 +105,7 @@ SIGNATURES = {
     "gg_mask_to_cond_slices": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp, i32, vp]),
     "gg_minmax_normalise_scatter": (C.c_int, [vp, i32, i64, vp, vp, i32, vp, i32, i32, vp, vp]),
     "gg_embed_rows": (C.c_int, [vp, i64, i32, vp, i32, i32, vp, i32, vp, i32, i32, vp]),
+    "gg_bert_embed": (C.c_int, [vp, vp, i64, i32, vp, i32, vp, i32, vp, i32, i32, vp, vp, f32, vp, i32, vp, vp, vp]),
     "gg_gelu": (C.c_int, [vp, i64, vp, vp]),
     "gg_layernorm_rows": (C.c_int, [vp, i64, i32, i32, vp, vp, f32, vp, vp]),
     "gg_interpolate2d_f32": (C.c_int, [vp, i64, i32, i32, i32, i32, f32, f32, i32, vp, vp]),

@@ -30,6 +30,8 @@ TARGET_ALIASES = {
     "ldm.modules.encoders.modules.TransformerEmbedder": "jointimagegeneration_amd.cond.TransformerEmbedder",
     "ldm.modules.encoders.modules.BERTEmbedder": "jointimagegeneration_amd.cond.BERTEmbedder",
     "ldm.modules.encoders.modules.SpatialRescaler": "jointimagegeneration_amd.cond.SpatialRescaler",
+    "ldm.modules.encoders.modules.FrozenBERTEmbedder": "jointimagegeneration_amd.cond.FrozenBERTEmbedder",
+    "ddpm.models.encoder.FrozenBERTEmbedder": "jointimagegeneration_amd.encoder.FrozenBERTEmbedder",
     "ldm.models.diffusion.ddim.DDIMSampler": "jointimagegeneration_amd.ldm.DDIMSampler",
     "ldm.models.diffusion.plms.PLMSSampler": "jointimagegeneration_amd.ldm.PLMSSampler",
     "torch.nn.Identity": "torch.nn.Identity",

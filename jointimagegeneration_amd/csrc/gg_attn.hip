@@ -22,6 +22,8 @@ struct AttnParams {
     // (o fp32 [.., D], m, l) in the workspace; attn_merge_kernel combines the states.  ksplit == 1: plain kernel.
     int ksplit, kchunk;
     float *ws_o, *ws_ml;
+    // per-sample key lengths (attn_kernel<.., KVLEN = true> only): sample n attends to keys [0, kv_len[n]); Tkv stays the row stride
+    const int *kv_len;
 };
 
 typedef __attribute__((ext_vector_type(4))) short s16x4;
@@ -39,10 +41,15 @@ __device__ __forceinline__ int swz_row(int row, int chunk)
 // K/V tiles of their own, and merge their online-softmax states through LDS at the end.  For under-filled grids with long key loops (the
 // latent UNet's 32x32 attention at batch 1: 160 workgroups, T = 1024: 8 softmax steps of 128 keys per wave, the kernel is bound by that
 // serial chain): half the steps per wave for the same staging work per thread.
-template <int D, int KT, int WS = 1>
+//
+// KVLEN: per-sample key lengths (a padding mask that is a prefix of ones: BERT).  The key range of sample n ends at kv_len[n] instead of
+// Tkv: whole tiles past it are not walked, the ragged tile is masked by the code that masks the tail past Tkv, rows past the length are
+// staged as zeros and never read from memory.  All Tq query rows are computed.  Plain register-staged kernel only.
+template <int D, int KT, int WS = 1, bool KVLEN = false>
 __global__ __launch_bounds__(256 * WS) void attn_kernel(const AttnParams p)
 {
     static_assert(WS == 1 || (WS == 2 && D < 256), "in-workgroup key split: register-staged tiles only");
+    static_assert(!KVLEN || (WS == 1 && D < 256), "key lengths: the plain register-staged kernel only");
     constexpr int CH = D / 8;          // 16-byte chunks per row
     constexpr int ROWB = D * 2;
     constexpr int KS = D / 32;         // k-steps of the S^T product
@@ -63,6 +70,11 @@ __global__ __launch_bounds__(256 * WS) void attn_kernel(const AttnParams p)
     const int qt = p.ksplit > 1 ? blockIdx.x / p.ksplit : blockIdx.x, ksp = p.ksplit > 1 ? blockIdx.x - qt * p.ksplit : 0;
     const int q0 = qt * 64 + wave * 16;
     int kbeg = ksp * p.kchunk, kend = (p.ksplit > 1 && kbeg + p.kchunk < p.Tkv) ? kbeg + p.kchunk : p.Tkv;     // kchunk % KT == 0
+    if constexpr (KVLEN) {                                         // (ksplit == 1: kbeg = 0) a length outside [1, Tkv] is clamped into it
+        const int len = p.kv_len[n];
+        kend = len < 1 ? 1 : (len < p.Tkv ? len : p.Tkv);
+    }
+    const int kfetch = KVLEN ? kend : p.Tkv;                       // rows from here on are staged as zeros
     int ntile = (kend - kbeg + KT - 1) / KT;                       // tiles of this workgroup's key range
     if constexpr (WS == 2) {                                       // both groups walk the SAME number of tiles (whole-workgroup barriers)
         ntile = (ntile + 1) >> 1;
@@ -101,7 +113,7 @@ __global__ __launch_bounds__(256 * WS) void attn_kernel(const AttnParams p)
             const int r = i / CH, c = i - r * CH;
             kreg[j] = u32x4{0u, 0u, 0u, 0u};
             vreg[j] = u32x4{0u, 0u, 0u, 0u};
-            if (i < KT * CH && key0 + r < p.Tkv) {
+            if (i < KT * CH && key0 + r < kfetch) {
                 kreg[j] = *reinterpret_cast<const u32x4 *>(kbase + (long long)(key0 + r) * p.ldk + c * 8);
                 vreg[j] = *reinterpret_cast<const u32x4 *>(vbase + (long long)(key0 + r) * p.ldv + c * 8);
             }
@@ -390,6 +402,16 @@ static int launch_attn(AttnParams p, const gg_attention_desc *d, const AttnPlan 
     return GG_OK;
 }
 
+// Key lengths: always the plain kernel (no key split of either kind), whatever attn_plan says for the shape.
+template <int D, int KT>
+static int launch_attn_kvlen(AttnParams p, hipStream_t stream)
+{
+    const dim3 grid((unsigned)((p.Tq + 63) / 64), (unsigned)p.heads, (unsigned)p.N);
+    hipLaunchKernelGGL((attn_kernel<D, KT, 1, true>), grid, dim3(256), 0, stream, p);
+    GG_CHECK_LAUNCH();
+    return GG_OK;
+}
+
 extern "C" int gg_attention_plan(const gg_attention_desc *d, int32_t plan[4])
 {
     AttnPlan pl;
@@ -407,9 +429,11 @@ extern "C" int64_t gg_attention_workspace_bytes(const gg_attention_desc *d)
     return pl.ksplit > 1 ? (int64_t)d->N * d->heads * pl.ksplit * d->Tq * (d->head_dim + 2) * 4 : 0;
 }
 
-extern "C" int gg_attention_forward(const gg_attention_desc *d, void *stream_)
+// kv_len == nullptr: gg_attention_forward.  with_len: gg_attention_forward_kvlen (kv_len is a device pointer and is not read here).
+static int attention_forward(const gg_attention_desc *d, bool with_len, const int32_t *kv_len, void *stream_)
 {
     hipStream_t stream = (hipStream_t)stream_;
+    if (with_len && !kv_len) GG_FAIL(GG_ERR_BAD_SHAPE, "attention_kvlen: null kv_len");
     if (!d || !d->q || !d->k || !d->v || !d->out) GG_FAIL(GG_ERR_BAD_SHAPE, "attention: null pointer");
     if (d->N <= 0 || d->heads <= 0 || d->Tq <= 0 || d->Tkv <= 0) GG_FAIL(GG_ERR_BAD_SHAPE, "attention: empty extent");
     auto al8 = [](long long x) { return (x % 8) == 0; };
@@ -421,6 +445,15 @@ extern "C" int gg_attention_forward(const gg_attention_desc *d, void *stream_)
     p.scale_log2 = d->scale * 1.4426950408889634f;
     p.q = (const bf16_t *)d->q; p.k = (const bf16_t *)d->k; p.v = (const bf16_t *)d->v; p.out = (bf16_t *)d->out;
     p.ksplit = 1; p.kchunk = d->Tkv; p.ws_o = nullptr; p.ws_ml = nullptr;
+    p.kv_len = kv_len;
+    if (with_len) {
+        switch (d->head_dim) {
+            case 32: return launch_attn_kvlen<32, 256>(p, stream);
+            case 64: return launch_attn_kvlen<64, 64>(p, stream);
+            case 128: return launch_attn_kvlen<128, 64>(p, stream);
+            default: GG_FAIL(GG_ERR_UNSUPPORTED, "attention_kvlen: head_dim %d not in {32,64,128} (key lengths run on the register-staged kernel only)", d->head_dim);
+        }
+    }
     AttnPlan pl;
     if (!attn_plan(d, &pl)) GG_FAIL(GG_ERR_UNSUPPORTED, "attention: head_dim %d not in {32,64,128,256,384,512}", d->head_dim);
     switch (d->head_dim) {
@@ -431,4 +464,11 @@ extern "C" int gg_attention_forward(const gg_attention_desc *d, void *stream_)
         case 384: return launch_attn<384, 32>(p, d, pl, stream);
         default: return launch_attn<512, 32>(p, d, pl, stream);
     }
+}
+
+extern "C" int gg_attention_forward(const gg_attention_desc *d, void *stream) { return attention_forward(d, false, nullptr, stream); }
+
+extern "C" int gg_attention_forward_kvlen(const gg_attention_desc *d, const int32_t *kv_len, void *stream)
+{
+    return attention_forward(d, true, kv_len, stream);
 }

@@ -3,6 +3,7 @@
 //
 //   embed_rows_kernel       out[r, d] = tok[ids[r], d] (+ pos[r % T, d]): nn.Embedding, and token + absolute positional embedding
 //                           (x_transformer.py:25-36,609-610), as fp32 rows or as the bf16 channels-last token rows the convs read
+//   bert_embed_kernel       LayerNorm(word[ids] + type[tt] + pos[t]) of transformers' BertEmbeddings as bf16 token rows, one launch
 //   gelu_kernel             erf-form GELU (nn.GELU) between the two Linears of x_transformer.FeedForward (x_transformer.py:194-211)
 //   layernorm_rows_kernel   LayerNorm over the C logical lanes of rows `stride` lanes apart (gg_layernorm normalises whole rows: C == stride)
 //   interpolate2d_kernel    F.interpolate(x, scale_factor=s, mode=nearest | bilinear | bicubic | area) on NCHW fp32 planes
@@ -46,6 +47,56 @@ extern "C" int gg_embed_rows(const int32_t *ids, int64_t rows, int32_t T, const 
         hipLaunchKernelGGL(embed_rows_kernel<bf16_t>, g, b, 0, (hipStream_t)stream_, ids, (long long)rows, T, tok, V, D, pos, (bf16_t *)out, out_stride);
     else
         hipLaunchKernelGGL(embed_rows_kernel<float>, g, b, 0, (hipStream_t)stream_, ids, (long long)rows, T, tok, V, D, pos, (float *)out, out_stride);
+    GG_CHECK_LAUNCH();
+    return GG_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------ BERT embeddings
+// out[r, :] = LayerNorm(word[ids[r]] + type[tt[r]] + pos[r % T]) (transformers' BertEmbeddings, in its order of additions): one wave per
+// row, four rows per workgroup, the statistics of layernorm_rows_kernel (mean, then the centred sum of squares, biased variance) on the
+// fp32 sums, ONE rounding to bf16.  The three table rows are re-read per pass (they are in L2; the kernel runs once per text).
+// An id outside its table: a zero row, nothing is read.
+__global__ __launch_bounds__(256) void bert_embed_kernel(const int32_t *__restrict__ ids, const int32_t *__restrict__ tts, long long rows, int T_len,
+                                                         const float *__restrict__ word, int V, const float *__restrict__ pos,
+                                                         const float *__restrict__ type, int NT, int D, const float *__restrict__ gamma,
+                                                         const float *__restrict__ beta, float eps, bf16_t *__restrict__ out, int stride)
+{
+    const int lane = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;                               // whole waves leave: the shuffles below see full waves
+    bf16_t *orow = out + row * stride;
+    const int id = ids[row], tt = tts ? tts[row] : 0;
+    if (id < 0 || id >= V || tt < 0 || tt >= NT) {         // wave-uniform
+        for (int c = lane; c < stride; c += 64) orow[c] = (bf16_t)0.f;
+        return;
+    }
+    const float *w = word + (long long)id * D, *ty = type + (long long)tt * D, *po = pos + (row % T_len) * D;
+    float s = 0.f;
+    for (int c = lane; c < D; c += 64) s += (w[c] + ty[c]) + po[c];
+    const float mean = gg_wave_sum_f32(s) / (float)D;
+    float q = 0.f;
+    for (int c = lane; c < D; c += 64) { const float d = ((w[c] + ty[c]) + po[c]) - mean; q += d * d; }
+    const float rstd = rsqrtf(gg_wave_sum_f32(q) / (float)D + eps);
+    for (int c = lane; c < stride; c += 64)
+        orow[c] = c < D ? (bf16_t)ln_normalise((w[c] + ty[c]) + po[c], mean, rstd, gamma[c], beta[c]) : (bf16_t)0.f;
+}
+
+extern "C" int gg_bert_embed(const int32_t *ids, const int32_t *type_ids, int64_t rows, int32_t T, const float *word, int32_t V,
+                             const float *pos, int32_t P, const float *type, int32_t NT, int32_t D, const float *gamma, const float *beta,
+                             float eps, void *out, int32_t out_stride, const int32_t *ids_host, const int32_t *type_ids_host, void *stream_)
+{
+    if (rows <= 0 || T <= 0 || rows % T) GG_FAIL(GG_ERR_BAD_SHAPE, "bert_embed: %lld rows are not whole sequences of %d", (long long)rows, T);
+    if (V <= 0 || NT <= 0 || D <= 0 || out_stride < D) GG_FAIL(GG_ERR_BAD_SHAPE, "bert_embed: bad tables [%d | %d, %d] or row stride %d", V, NT, D, out_stride);
+    if (T > P) GG_FAIL(GG_ERR_BAD_SHAPE, "bert_embed: sequence length %d exceeds the %d positions of the table", T, P);
+    if (!ids || !word || !pos || !type || !gamma || !beta || !out) GG_FAIL(GG_ERR_BAD_SHAPE, "bert_embed: null pointer");
+    // the caller's HOST copies of the ids (they come from a host tokenizer): checked here, the device copies are never read back
+    for (int64_t r = 0; ids_host && r < rows; ++r)
+        if (ids_host[r] < 0 || ids_host[r] >= V) GG_FAIL(GG_ERR_BAD_SHAPE, "bert_embed: token id %d at row %lld is outside the table's [0, %d)", ids_host[r], (long long)r, V);
+    for (int64_t r = 0; type_ids_host && r < rows; ++r)
+        if (type_ids_host[r] < 0 || type_ids_host[r] >= NT)
+            GG_FAIL(GG_ERR_BAD_SHAPE, "bert_embed: token type %d at row %lld is outside the table's [0, %d)", type_ids_host[r], (long long)r, NT);
+    hipLaunchKernelGGL(bert_embed_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream_, ids, type_ids, (long long)rows, T,
+                       word, V, pos, type, NT, D, gamma, beta, eps, (bf16_t *)out, out_stride);
     GG_CHECK_LAUNCH();
     return GG_OK;
 }

@@ -267,10 +267,12 @@ extern "C" int gg_groupnorm_f32_film(const float *src, int32_t C_pad, int32_t N,
 // ---------------------------------------------------------------------------------------------------------------- attention
 // One thread per query, online softmax in fp32; q and k are each multiplied by a = sqrt(scale) first, as QKVAttentionLegacy does
 // with a = ch^-1/4 (unet.py:349-354).  All threads of a wave read the same key / value row: broadcast loads.
+// kv_len (nullable): sample n attends to keys [0, kv_len[n]) clamped into [1, Tkv]; Tkv stays the row stride (gg_attention_forward_kvlen).
 template <int DMAX>
 __global__ __launch_bounds__(64) void attn_f32_kernel(const float *__restrict__ q, const float *__restrict__ k, const float *__restrict__ v,
                                                       float *__restrict__ out, int heads, int D, int Tq, int Tkv, long long ldq, long long hsq,
-                                                      long long ldk, long long hsk, long long ldv, long long hsv, long long ldo, long long hso, float a)
+                                                      long long ldk, long long hsk, long long ldv, long long hsv, long long ldo, long long hso, float a,
+                                                      const int *__restrict__ kv_len)
 {
     const int t = blockIdx.x * 64 + threadIdx.x, h = blockIdx.y, n = blockIdx.z;
     if (t >= Tq) return;
@@ -279,7 +281,9 @@ __global__ __launch_bounds__(64) void attn_f32_kernel(const float *__restrict__ 
 #pragma unroll
     for (int d = 0; d < DMAX; ++d) { qr[d] = d < D ? qp[d] * a : 0.f; o[d] = 0.f; }
     float m = -INFINITY, l = 0.f;
-    for (int j = 0; j < Tkv; ++j) {
+    int kend = Tkv;
+    if (kv_len) { const int len = kv_len[n]; kend = len < 1 ? 1 : (len < Tkv ? len : Tkv); }
+    for (int j = 0; j < kend; ++j) {
         const float *kp = k + ((long long)n * Tkv + j) * ldk + h * hsk;
         const float *vp = v + ((long long)n * Tkv + j) * ldv + h * hsv;
         float s = 0.f;
@@ -300,7 +304,7 @@ __global__ __launch_bounds__(64) void attn_f32_kernel(const float *__restrict__ 
         if (d < D) op[d] = o[d] / l;
 }
 
-extern "C" int gg_attention_forward_f32(const gg_attention_desc *d, void *stream_)
+static int attention_forward_f32(const gg_attention_desc *d, const int32_t *kv_len, void *stream_)
 {
     hipStream_t stream = (hipStream_t)stream_;
     if (!d || !d->q || !d->k || !d->v || !d->out) GG_FAIL(GG_ERR_BAD_SHAPE, "attention_f32: null pointer");
@@ -310,10 +314,18 @@ extern "C" int gg_attention_forward_f32(const gg_attention_desc *d, void *stream
     dim3 grid((unsigned)((d->Tq + 63) / 64), (unsigned)d->heads, (unsigned)d->N);
     if (d->head_dim <= 32)
         hipLaunchKernelGGL(attn_f32_kernel<32>, grid, dim3(64), 0, stream, (const float *)d->q, (const float *)d->k, (const float *)d->v, (float *)d->out,
-                           d->heads, d->head_dim, d->Tq, d->Tkv, d->ldq, d->hsq, d->ldk, d->hsk, d->ldv, d->hsv, d->ldo, d->hso, a);
+                           d->heads, d->head_dim, d->Tq, d->Tkv, d->ldq, d->hsq, d->ldk, d->hsk, d->ldv, d->hsv, d->ldo, d->hso, a, kv_len);
     else
         hipLaunchKernelGGL(attn_f32_kernel<64>, grid, dim3(64), 0, stream, (const float *)d->q, (const float *)d->k, (const float *)d->v, (float *)d->out,
-                           d->heads, d->head_dim, d->Tq, d->Tkv, d->ldq, d->hsq, d->ldk, d->hsk, d->ldv, d->hsv, d->ldo, d->hso, a);
+                           d->heads, d->head_dim, d->Tq, d->Tkv, d->ldq, d->hsq, d->ldk, d->hsk, d->ldv, d->hsv, d->ldo, d->hso, a, kv_len);
     GG_CHECK_LAUNCH();
     return GG_OK;
+}
+
+extern "C" int gg_attention_forward_f32(const gg_attention_desc *d, void *stream) { return attention_forward_f32(d, nullptr, stream); }
+
+extern "C" int gg_attention_forward_kvlen_f32(const gg_attention_desc *d, const int32_t *kv_len, void *stream)
+{
+    if (!kv_len) GG_FAIL(GG_ERR_BAD_SHAPE, "attention_kvlen_f32: null kv_len");
+    return attention_forward_f32(d, kv_len, stream);
 }

@@ -5,8 +5,9 @@ Mirrors `PreloadedBERTEncoder` (ccdm/ddpm/models/encoder.py:103-123): `depth` Ba
 features `[b, embed_dim, length]`, residual `inputs + outputs`.  Same constructor arguments and state_dict keys, so the
 `feature_cond_encoder` entry of an ignite checkpoint (trainer.py:444-463) loads unchanged.  It is built by the reference's
 `feature_cond_encoder: {type: "selfattn", embed_dim, n_heads, model_depth, d_head, dropout}` yaml block
-(condition_encoder.py:84-99).  The frozen BERT itself (`FrozenBERTEmbedder`, encoder.py:21-100) needs weights that do not
-exist offline and is out of scope: the encoder's input is the feature tensor the reference's datasets cache.
+(condition_encoder.py:84-99).  The frozen BERT that produces those features (`FrozenBERTEmbedder`, encoder.py:21-100) lives in
+cond.py, loads from a local Hugging Face directory and is re-exported here under the reference's module path;
+`python -m jointimagegeneration_amd.cond --bert DIR --text ... --out feats.npy` writes the feature tensor the reference's datasets cache.
 The shipped CCDM UNet has no SpatialTransformer and therefore ignores `context`; the LDM UNet with
 `use_spatial_transformer` consumes it through the `crossattn` / `hybrid` conditioning keys.
 """
@@ -19,6 +20,7 @@ import torch.nn as nn
 
 from . import ops
 from .blocks import BasicTransformerBlock
+from .cond import FrozenBERTEmbedder  # noqa: F401  (ddpm.models.encoder.FrozenBERTEmbedder)
 from .ops import CL, pad32
 
 

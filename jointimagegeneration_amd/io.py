@@ -9,6 +9,8 @@ Checkpoints are read with torch.load(weights_only=True) only.
 from __future__ import annotations
 
 import gzip
+import json
+import os
 import struct
 import zlib
 
@@ -103,3 +105,67 @@ def write_png(path: str, img: np.ndarray) -> None:
 def load_checkpoint(path: str) -> dict:
     """Safe loader only (executes nothing from the file)."""
     return torch.load(path, map_location="cpu", weights_only=True)
+
+
+# ----------------------------------------------------------------------------------------------- local Hugging Face model directory
+# What FrozenBERTEmbedder needs of a directory saved by transformers' save_pretrained (config.json, vocab.txt, tokenizer_config.json and
+# model.safetensors or pytorch_model.bin), read without transformers, tokenizers or safetensors.
+_SAFETENSORS_DTYPES = {"F32": torch.float32, "F16": torch.float16, "BF16": torch.bfloat16}
+_SAFETENSORS_HEADER_MAX = 100 * 1024 * 1024
+
+
+def read_safetensors(path: str) -> dict:
+    """{name: tensor} of a .safetensors file: 8-byte little-endian header length, a JSON header {name: {dtype, shape, data_offsets}}
+    (plus "__metadata__"), then the tensors' raw little-endian bytes.  F32 / F16 / BF16 only; every offset is checked against the file."""
+    with open(path, "rb") as f:
+        raw = f.read()
+    if len(raw) < 8:
+        raise ValueError(f"{path}: too short for a safetensors header")
+    (n,) = struct.unpack("<Q", raw[:8])
+    if n > _SAFETENSORS_HEADER_MAX or 8 + n > len(raw):
+        raise ValueError(f"{path}: safetensors header length {n} does not fit the file ({len(raw)} bytes)")
+    header = json.loads(raw[8:8 + n].decode("utf-8"))
+    data = memoryview(raw)[8 + n:]
+    out = {}
+    for name, e in header.items():
+        if name == "__metadata__":
+            continue
+        if e["dtype"] not in _SAFETENSORS_DTYPES:
+            raise NotImplementedError(f"{path}: tensor {name!r} has dtype {e['dtype']} (F32, F16 and BF16 are supported)")
+        dt = _SAFETENSORS_DTYPES[e["dtype"]]
+        shape = [int(v) for v in e["shape"]]
+        b0, b1 = (int(v) for v in e["data_offsets"])
+        numel = int(np.prod(shape, dtype=np.int64)) if shape else 1
+        if not (0 <= b0 <= b1 <= len(data)) or b1 - b0 != numel * dt.itemsize:
+            raise ValueError(f"{path}: tensor {name!r} {shape} {e['dtype']} does not match its byte range [{b0}, {b1}) of {len(data)}")
+        # little-endian host assumed, as everywhere in this package (NIfTI writer above)
+        out[name] = torch.frombuffer(bytearray(data[b0:b1]), dtype=dt).reshape(shape) if numel else torch.zeros(shape, dtype=dt)
+    return out
+
+
+def load_hf_dir(path: str):
+    """(config dict, state_dict, vocab list, tokenizer config dict) of a local Hugging Face model directory.  Weights come from
+    model.safetensors if present, else from pytorch_model.bin through the safe loader; nothing outside `path` is touched."""
+    if not os.path.isdir(path):
+        raise FileNotFoundError(f"{path}: not a directory (a local Hugging Face model directory is expected; nothing is downloaded)")
+
+    def need(name):
+        p = os.path.join(path, name)
+        if not os.path.exists(p):
+            raise FileNotFoundError(f"{p}: missing from the model directory")
+        return p
+
+    with open(need("config.json"), "r", encoding="utf-8") as f:
+        config = json.load(f)
+    with open(need("vocab.txt"), "r", encoding="utf-8") as f:
+        vocab = [line.rstrip("\n") for line in f]
+    while vocab and vocab[-1] == "":
+        vocab.pop()
+    tok_cfg = {}
+    p = os.path.join(path, "tokenizer_config.json")
+    if os.path.exists(p):
+        with open(p, "r", encoding="utf-8") as f:
+            tok_cfg = json.load(f)
+    st = os.path.join(path, "model.safetensors")
+    sd = read_safetensors(st) if os.path.exists(st) else load_checkpoint(need("pytorch_model.bin"))
+    return config, sd, vocab, tok_cfg

@@ -610,6 +610,33 @@ def embed_rows(ids: torch.Tensor, tok: torch.Tensor, pos: Optional[torch.Tensor]
     return out
 
 
+def bert_embed(ids: torch.Tensor, type_ids: Optional[torch.Tensor], word: torch.Tensor, pos: torch.Tensor, type_tab: torch.Tensor,
+               gamma: torch.Tensor, beta: torch.Tensor, eps: float, ids_host: Optional[torch.Tensor] = None,
+               type_ids_host: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """transformers' BertEmbeddings in one launch (gg_bert_embed): ids int32 [B, T] on the device (type_ids likewise, or None for type 0),
+    fp32 tables word [V, D], pos [P, D], type_tab [NT, D], gamma / beta [D] -> LayerNorm(word[ids] + type[tt] + pos[t]) as channels-last
+    token rows bf16 [B, 1, 1, T, pad32(D)] (pad lanes zero).  ids_host / type_ids_host: the int32 CPU tensors the device ids were made
+    from; the library checks them against the tables before it launches.  Nothing is read back from the device."""
+    require_gpu(ids, "bert_embed")
+    for name, t in (("ids", ids), ("type_ids", type_ids)):
+        if t is not None and (t.dtype != torch.int32 or t.dim() != 2 or not t.is_contiguous() or t.shape != ids.shape or t.device != ids.device):
+            raise ValueError(f"bert_embed: {name} must be a contiguous int32 tensor [B, T] on {ids.device}, got {t.dtype} {tuple(t.shape)}")
+    for name, t in (("ids_host", ids_host), ("type_ids_host", type_ids_host)):
+        if t is not None and (t.dtype != torch.int32 or t.is_cuda or not t.is_contiguous() or t.shape != ids.shape):
+            raise ValueError(f"bert_embed: {name} must be a contiguous int32 CPU tensor of shape {tuple(ids.shape)}")
+    D = int(word.shape[1])
+    for name, t in (("word", word), ("pos", pos), ("type_tab", type_tab), ("gamma", gamma.view(1, -1)), ("beta", beta.view(1, -1))):
+        if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != D or not t.is_contiguous() or t.device != ids.device:
+            raise ValueError(f"bert_embed: {name} must be a contiguous fp32 table of width {D} on {ids.device}")
+    B, T = (int(v) for v in ids.shape)
+    out = torch.empty((B, 1, 1, T, pad32(D)), dtype=torch.bfloat16, device=ids.device)
+    check(_lib.load().gg_bert_embed(ids.data_ptr(), _ptr(type_ids), B * T, T, word.data_ptr(), int(word.shape[0]), pos.data_ptr(),
+                                    int(pos.shape[0]), type_tab.data_ptr(), int(type_tab.shape[0]), D, gamma.data_ptr(), beta.data_ptr(),
+                                    float(eps), out.data_ptr(), out.shape[-1], _ptr(ids_host), _ptr(type_ids_host), _stream()),
+          "gg_bert_embed")
+    return out
+
+
 def gelu(x: torch.Tensor) -> torch.Tensor:
     """Elementwise erf-form GELU of a contiguous bf16 tensor (gg_gelu)."""
     require_gpu(x, "gelu")
@@ -665,9 +692,16 @@ def interpolate2d(x: torch.Tensor, scale_factor: float, mode: str) -> torch.Tens
 
 # ----------------------------------------------------------------------------------------------- attention
 def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, N: int, heads: int, head_dim: int, Tq: int,
-              Tkv: int, ld_hs_q, ld_hs_k, ld_hs_v, ld_hs_o, scale: float, q_off=0, k_off=0, v_off=0) -> None:
-    """q/k/v/out are bf16 tensors; element (n,t,h,d) at base + off + (n*T+t)*ld + h*hs + d."""
+              Tkv: int, ld_hs_q, ld_hs_k, ld_hs_v, ld_hs_o, scale: float, q_off=0, k_off=0, v_off=0,
+              kv_len: Optional[torch.Tensor] = None) -> None:
+    """q/k/v/out are bf16 tensors; element (n,t,h,d) at base + off + (n*T+t)*ld + h*hs + d.
+    kv_len: int32 device tensor [N]; sample n then attends to keys [0, kv_len[n]) only (gg_attention_forward_kvlen).  It is not read
+    back: the caller checks 1 <= kv_len[n] <= Tkv on the host values it built the tensor from."""
     lib = _lib.load()
+    if kv_len is not None and (not isinstance(kv_len, torch.Tensor) or kv_len.dtype != torch.int32 or tuple(kv_len.shape) != (N,)
+                               or not kv_len.is_contiguous() or kv_len.device != q.device):
+        what = f"{kv_len.dtype} {tuple(kv_len.shape)} on {kv_len.device}" if isinstance(kv_len, torch.Tensor) else type(kv_len).__name__
+        raise ValueError(f"attention: kv_len must be a contiguous int32 tensor [{N}] on {q.device}, got {what}")
     d = AttentionDesc()
     d.N, d.heads, d.head_dim, d.Tq, d.Tkv = N, heads, head_dim, Tq, Tkv
     d.ldq, d.hsq = ld_hs_q
@@ -680,6 +714,10 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tens
     d.k = k.data_ptr() + esz * k_off
     d.v = v.data_ptr() + esz * v_off
     d.out = out.data_ptr()
+    if kv_len is not None:                          # key lengths: the plain kernel, no workspace
+        fn = "gg_attention_forward_kvlen_f32" if is_f32(q) else "gg_attention_forward_kvlen"
+        check(getattr(lib, fn)(C.byref(d), kv_len.data_ptr(), _stream()), fn)
+        return
     if is_f32(q):                                   # fp32 validation path
         check(lib.gg_attention_forward_f32(C.byref(d), _stream()), "gg_attention_forward_f32")
         return
