@@ -321,6 +321,17 @@ int gg_ccdm_posterior_sample_seeds(const float *head, int32_t head_stride, int32
                                    const float *E, const uint64_t *philox_seeds_dev, int64_t rows_per_sample,
                                    const int64_t *philox_offset_dev, int32_t draw, const float *scalars_dev, int32_t K, int64_t M,
                                    int32_t *labels_out, float *probs_out, void *onehot_out, int32_t onehot_stride, void *stream);
+/* The tape of a Philox run: what the kernels above (and gg_ccdm_q_sample, and the fused head conv) draw when E == NULL, so that the run
+ * can be replayed teacher-forced (E = the first K columns of E_out's rows, repacked to [M, K]) here or elsewhere.
+ *   Row m draws kmax / 4 Philox4x32-10 blocks; block q4 has counter (row lo, row hi, q4, LOW 32 BITS of philox_offset_dev[0], 0 when
+ *   NULL) and key (seed lo, seed hi); its four words are the classes 4 * q4 .. 4 * q4 + 3.  philox_seeds_dev == NULL: key philox_seed,
+ *   row = m (gg_ccdm_posterior_sample); else key philox_seeds_dev[m / rows_per_sample], row = m % rows_per_sample (M a multiple).
+ *   A word w gives u = ((w >> 8) + 1) * 2^-24 in (0, 1] and E = -log(u) + 1e-30 (hardware logarithm).
+ *   kmax: 16 (the kernels' draw at K <= 16) or 32 (K > 16): the first 16 columns of the two agree.
+ *   bits_in: uint32 [M, kmax] or NULL; given, those words are mapped instead of drawn (keys and offset unused).
+ * Outputs, either may be NULL but not both: bits_out uint32 [M, kmax] the words; E_out fp32 [M, kmax] the exponentials. */
+int gg_ccdm_draw_tape(uint64_t philox_seed, const uint64_t *philox_seeds_dev, int64_t rows_per_sample, const int64_t *philox_offset_dev,
+                      int32_t kmax, int64_t M, const uint32_t *bits_in, uint32_t *bits_out, float *E_out, void *stream);
 /* labels -> one-hot bf16 CL rows (x_T assembly; evaluator.py:135-136 + unet.py:774-775 concat with zeros). */
 int gg_labels_to_onehot(const int32_t *labels, int64_t M, int32_t K, void *onehot_out, int32_t stride, void *stream);
 

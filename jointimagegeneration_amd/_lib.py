@@ -77,6 +77,7 @@ SIGNATURES = {
     "gg_cl_to_nchw_f32": (C.c_int, [vp, i32, i32, i32, i64, i32, vp, vp]),
     "gg_ccdm_posterior_sample": (C.c_int, [vp, i32, i32, vp, vp, u64, vp, i32, vp, i32, i64, vp, vp, vp, i32, vp]),
     "gg_ccdm_posterior_sample_seeds": (C.c_int, [vp, i32, i32, vp, vp, vp, i64, vp, i32, vp, i32, i64, vp, vp, vp, i32, vp]),
+    "gg_ccdm_draw_tape": (C.c_int, [u64, vp, i64, vp, i32, i64, vp, vp, vp, vp]),
     "gg_labels_to_onehot": (C.c_int, [vp, i64, i32, vp, i32, vp]),
     "gg_ddim_step": (C.c_int, [vp, vp, i32, vp, vp, i64, i32, vp, vp, i32, vp]),
     "gg_minmax_normalise": (C.c_int, [vp, i64, vp, vp, vp]),

@@ -127,19 +127,8 @@ __global__ __launch_bounds__(LS_THREADS) void ccdm_q_sample_kernel(const int *__
     if (E) {
 #pragma unroll
         for (int c = 0; c < KMAX; ++c) Ev[c] = (c < K) ? E[m * K + c] : 1.f;
-    } else {                                   // the counter layout of gg_ccdm_posterior_sample_seeds: (row lo, row hi, draw index, step offset)
-        const unsigned long long key = seeds[n];
-        const long long off = offset_dev ? offset_dev[0] : 0;
-#pragma unroll
-        for (int q4 = 0; q4 < KMAX / 4; ++q4) {
-            uint32_t ctr[4] = {(uint32_t)row, (uint32_t)(row >> 32), (uint32_t)q4, (uint32_t)off};
-            philox4x32_10(ctr, (uint32_t)key, (uint32_t)(key >> 32));
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float uu = (float)((ctr[j] >> 8) + 1u) * 5.9604644775390625e-8f;   // (0, 1]
-                Ev[q4 * 4 + j] = -__logf(uu) + 1e-30f;
-            }
-        }
+    } else {                                   // the draw of gg_ccdm_posterior_sample_seeds (gg_posterior.h): key seeds[n], the row within the sample
+        ccdm_draw_row<KMAX>(Ev, seeds[n], row, offset_dev ? offset_dev[0] : 0);
     }
     int best = 0;
     float bestv = -1.0f;

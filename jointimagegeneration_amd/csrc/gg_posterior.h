@@ -25,6 +25,34 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32
     }
 }
 
+// One Philox word -> one Exp(1) draw: the top 24 bits + 1 scaled by 2^-24 is a uniform in (0, 1] that fp32 holds exactly, the hardware
+// logarithm of it is <= 0 (0 at u == 1), and the 1e-30f keeps the divisor of the race positive.
+__device__ __forceinline__ float ccdm_word_to_exp(const uint32_t w)
+{
+    const float uu = (float)((w >> 8) + 1u) * 5.9604644775390625e-8f;   // (0, 1]
+    return -__logf(uu) + 1e-30f;
+}
+
+// The KMAX exponentials of one row: call q4 draws with counter (row lo, row hi, q4, low 32 bits of the step offset) and key (seed lo,
+// seed hi), and its four words are the classes 4 * q4 .. 4 * q4 + 3.  This is THE draw of the CCDM kernels: the reverse step here, the fused
+// head-conv epilogue (through ccdm_posterior_voxel), gg_ccdm_q_sample and gg_ccdm_draw_tape all call it.  words: the raw words out, or
+// nullptr.
+template <int KMAX>
+__device__ __forceinline__ void ccdm_draw_row(float (&Ev)[KMAX], const uint64_t key, const long long row, const long long off,
+                                              uint32_t *__restrict__ words = nullptr)
+{
+#pragma unroll
+    for (int q4 = 0; q4 < KMAX / 4; ++q4) {
+        uint32_t ctr[4] = {(uint32_t)row, (uint32_t)(row >> 32), (uint32_t)q4, (uint32_t)off};
+        philox4x32_10(ctr, (uint32_t)key, (uint32_t)(key >> 32));
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (words) words[q4 * 4 + j] = ctr[j];
+            Ev[q4 * 4 + j] = ccdm_word_to_exp(ctr[j]);
+        }
+    }
+}
+
 // p0: the head's K values of voxel m (logits or probabilities), overwritten; x: the voxel's current label; a / abar: the step's scalars
 // (alpha_t, cumulative alpha of t - 1); E_row: K exponentials of a tape or nullptr (then Philox draws them); probs_row: K normalised
 // posterior probabilities out, or nullptr.  Returns the new label.
@@ -90,16 +118,7 @@ __device__ __forceinline__ int ccdm_posterior_voxel(float (&p0)[KMAX], const int
 #pragma unroll
             for (int c = 0; c < KMAX; ++c) Ev[c] = (c < K) ? E_row[c] : 1.f;
         } else {
-#pragma unroll
-            for (int q4 = 0; q4 < KMAX / 4; ++q4) {
-                uint32_t ctr[4] = {(uint32_t)m, (uint32_t)(m >> 32), (uint32_t)q4, (uint32_t)off};
-                philox4x32_10(ctr, (uint32_t)seed, (uint32_t)(seed >> 32));
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    float uu = (float)((ctr[j] >> 8) + 1u) * 5.9604644775390625e-8f;   // (0, 1]
-                    Ev[q4 * 4 + j] = -__logf(uu) + 1e-30f;
-                }
-            }
+            ccdm_draw_row<KMAX>(Ev, seed, m, off);
         }
     }
     int best = 0;

@@ -88,6 +88,61 @@ extern "C" int gg_ccdm_posterior_sample_seeds(const float *head, int32_t head_st
                                     probs_out, onehot_out, onehot_stride, philox_seeds_dev, rows_per_sample, (hipStream_t)stream_);
 }
 
+// The tape of a Philox run, one row per thread: the words and exponentials ccdm_draw_row gives row m under the key / counter rule of
+// ccdm_posterior_kernel (seeds != nullptr: the per-sample rule), or with bits_in the exponentials of those words instead.
+template <int KMAX>
+__global__ __launch_bounds__(256) void ccdm_draw_tape_kernel(uint64_t seed, const unsigned long long *__restrict__ seeds, long long rows_per_sample,
+                                                             const long long *__restrict__ offset_dev, long long M,
+                                                             const uint32_t *__restrict__ bits_in, uint32_t *__restrict__ bits_out,
+                                                             float *__restrict__ E_out)
+{
+    const long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= M) return;
+    uint32_t w[KMAX];
+    float Ev[KMAX];
+    if (bits_in) {
+#pragma unroll
+        for (int c = 0; c < KMAX; ++c) { w[c] = bits_in[m * KMAX + c]; Ev[c] = ccdm_word_to_exp(w[c]); }
+    } else {
+        uint64_t key = seed;
+        long long row = m;
+        if (seeds) {
+            const long long n = m / rows_per_sample;
+            key = seeds[n];
+            row = m - n * rows_per_sample;
+        }
+        ccdm_draw_row<KMAX>(Ev, key, row, offset_dev ? offset_dev[0] : 0, w);
+    }
+#pragma unroll
+    for (int c = 0; c < KMAX; ++c) {
+        if (bits_out) bits_out[m * KMAX + c] = w[c];
+        if (E_out) E_out[m * KMAX + c] = Ev[c];
+    }
+}
+
+extern "C" int gg_ccdm_draw_tape(uint64_t philox_seed, const uint64_t *philox_seeds_dev, int64_t rows_per_sample,
+                                 const int64_t *philox_offset_dev, int32_t kmax, int64_t M, const uint32_t *bits_in, uint32_t *bits_out,
+                                 float *E_out, void *stream_)
+{
+    if (!bits_out && !E_out) GG_FAIL(GG_ERR_BAD_SHAPE, "ccdm_draw_tape: no output");
+    if (kmax != 16 && kmax != 32) GG_FAIL(GG_ERR_UNSUPPORTED, "ccdm_draw_tape: kmax=%d is neither 16 nor 32", kmax);
+    if (M < 0) GG_FAIL(GG_ERR_BAD_SHAPE, "ccdm_draw_tape: M=%lld", (long long)M);
+    if (philox_seeds_dev && !bits_in && (rows_per_sample <= 0 || M % rows_per_sample))
+        GG_FAIL(GG_ERR_BAD_SHAPE, "ccdm_draw_tape: M=%lld is not a multiple of rows_per_sample=%lld", (long long)M, (long long)rows_per_sample);
+    if (M == 0) return GG_OK;
+    const long long blocks = (M + 255) / 256;
+    if (blocks > 0x7fffffffLL) GG_FAIL(GG_ERR_UNSUPPORTED, "ccdm_draw_tape: M=%lld rows exceed the grid", (long long)M);
+    const unsigned long long *sd = (const unsigned long long *)philox_seeds_dev;
+    if (kmax == 16)
+        hipLaunchKernelGGL(ccdm_draw_tape_kernel<16>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, philox_seed, sd,
+                           (long long)rows_per_sample, (const long long *)philox_offset_dev, (long long)M, bits_in, bits_out, E_out);
+    else
+        hipLaunchKernelGGL(ccdm_draw_tape_kernel<32>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, philox_seed, sd,
+                           (long long)rows_per_sample, (const long long *)philox_offset_dev, (long long)M, bits_in, bits_out, E_out);
+    GG_CHECK_LAUNCH();
+    return GG_OK;
+}
+
 __global__ __launch_bounds__(256) void labels_to_onehot_kernel(const int *__restrict__ labels, long long M, int K,
                                                                bf16_t *__restrict__ out, int stride)
 {

@@ -791,6 +791,39 @@ def philox_seed_tensor(seeds: Sequence[int], device) -> torch.Tensor:
     return torch.tensor([int(s) - (1 << 64) if int(s) >= (1 << 63) else int(s) for s in seeds], dtype=torch.int64, device=device)
 
 
+def ccdm_draw_tape(M: int, kmax: int, *, philox_seed: int = 0, philox_seeds: Optional[torch.Tensor] = None,
+                   philox_offset: Optional[torch.Tensor] = None, bits_in: Optional[torch.Tensor] = None, want_bits: bool = True,
+                   want_E: bool = True, device=None) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """The tape of a Philox run (gg_ccdm_draw_tape): (words int32 [M, kmax] holding the uint32 bit patterns, E fp32 [M, kmax]) as
+    ccdm_posterior_sample / ccdm_q_sample / the fused head conv draw them for the same philox_seed (or philox_seeds: device int64 [N], M a
+    multiple of N) and philox_offset; kmax is 16 for K <= 16 and 32 above.  E[:, :K].contiguous() is the tape `E` of those calls.
+    bits_in: device int32 [M, kmax] words to map instead of drawing."""
+    lib = _lib.load()
+    if bits_in is not None:
+        if bits_in.dtype != torch.int32 or not bits_in.is_cuda or not bits_in.is_contiguous() or bits_in.numel() != M * kmax:
+            raise ValueError(f"ccdm_draw_tape: bits_in must be a contiguous device int32 [{M}, {kmax}] tensor")
+        device = bits_in.device
+    elif philox_seeds is not None:
+        device = philox_seeds.device
+    elif philox_offset is not None:
+        device = philox_offset.device
+    if device is None:
+        device = torch.device("cuda")
+    if not (want_bits or want_E):
+        raise ValueError("ccdm_draw_tape: neither the words nor the exponentials are asked for")
+    Ns, rps = 0, 0
+    if philox_seeds is not None and bits_in is None:
+        Ns = philox_seeds.numel()
+        if Ns < 1 or M % Ns:
+            raise ValueError(f"ccdm_draw_tape: {M} rows do not split into {Ns} samples")
+        rps = M // Ns
+    bits = torch.empty((M, kmax), dtype=torch.int32, device=device) if want_bits else None
+    E = torch.empty((M, kmax), dtype=torch.float32, device=device) if want_E else None
+    check(lib.gg_ccdm_draw_tape(int(philox_seed) & ((1 << 64) - 1), _seeds_ptr(philox_seeds, Ns) if Ns else None, rps, _ptr(philox_offset),
+                                kmax, M, _ptr(bits_in), _ptr(bits), _ptr(E), _stream()), "gg_ccdm_draw_tape")
+    return bits, E
+
+
 def labels_to_onehot(labels: torch.Tensor, K: int, out: torch.Tensor) -> None:
     lib = _lib.load()
     if is_f32(out):                                 # fp32 validation path: index scatter (plumbing)
