@@ -611,6 +611,43 @@ int gg_ccdm_step_loss(const float *logits, int32_t logits_stride, const int32_t 
                       int64_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The first stage's held-out objective, forward only (gg_patchgan.hip): what LPIPSWithDiscriminator of
+ * ldm/modules/losses/contperceptual.py needs beyond gg_lpips_tap and gg_loss_rows.  Same rules as above: the caller's stream,
+ * caller-owned buffers and workspace, no allocation, no readback, no floating-point atomics; the reductions are two-stage fp64 sums in
+ * a fixed order (two runs give the same bits).
+ * ------------------------------------------------------------------------------------------------ */
+/* PatchGAN convolution (NLayerDiscriminator / NLayerDiscriminator3D, contperceptual.py:296-406): kernel extent 4 on H and W, and on D when
+ * kd == 4 (kd == 1: 2-D, the D axis is a batch axis), zero padding 2 on both sides of every 4-wide axis, one stride in {1, 2} on them:
+ * Ho = H / stride + 1 (Wo, and Do for kd == 4, alike; Do = D for kd == 1).  src: channels-last bf16 [N, D, H, W, Cin_pad], Cin_pad % 32 == 0;
+ * weight: gg_conv_pack_weight with ntaps = 16 * kd; out: channels-last [N, Do, Ho, Wo, pad32(Cout)] of out_dtype, pad lanes zero.
+ * bf16 MFMA with fp32 accumulation, then in fp32, each step rounded once: y = acc * alpha[c] + beta[c] (alpha NULL: y = acc + beta[c]),
+ * y = y >= 0 ? y : y * slope (slope == 1: none).  alpha, beta: fp32 [pad32(Cout)], the conv bias and the eval-mode BatchNorm folded by
+ * the caller: alpha = gamma / sqrt(running_var + eps), beta = (bias - running_mean) * alpha + beta_bn.
+ * The _f32 form (validation mode) takes fp32 src, fp32 weight [taps][Cin_pad][pad32(Cout)] and accumulates with fp32 FMA, taps outer,
+ * channels inner.  A wrong extent, Cin_pad % 32, a stride outside {1, 2}, kd outside {1, 4}, a null pointer: GG_ERR_* before any launch. */
+int gg_patch_conv_forward(const void *src, const void *weight, const float *alpha, const float *beta, float slope, int32_t N, int32_t D,
+                          int32_t H, int32_t W, int32_t Cin_pad, int32_t Cout, int32_t kd, int32_t stride, int32_t Do, int32_t Ho, int32_t Wo,
+                          void *out, int32_t out_dtype, void *stream);
+int gg_patch_conv_forward_f32(const float *src, const float *weight, const float *alpha, const float *beta, float slope, int32_t N, int32_t D,
+                              int32_t H, int32_t W, int32_t Cin_pad, int32_t Cout, int32_t kd, int32_t stride, int32_t Do, int32_t Ho,
+                              int32_t Wo, float *out, void *stream);
+/* DiagonalGaussianDistribution.kl() (distributions.py:44-51): out[n] (fp64) = 0.5 * sum over the C * S elements of sample n of
+ * m^2 + exp(lv) - 1 - lv, lv clamped to [-30, 20], every term in fp32 (left to right, nothing contracted; exp rounded to fp32 from its
+ * fp64 value).  moments: fp32 channels-last rows [N * S, stride], mean in lanes [0, C), logvar in lanes [C, 2C).
+ * workspace: gg_loss_workspace_bytes(N, S). */
+int gg_gauss_kl_rows(const float *moments, int32_t stride, int32_t N, int32_t C, int64_t S, double *out, void *workspace,
+                     int64_t workspace_bytes, void *stream);
+/* DiagonalGaussianDistribution.sample() (distributions.py:35-37): z = m + exp(0.5 * lv) * noise with the same clamp, each step rounded to
+ * fp32.  moments as above; noise fp32 [N, C, S].  out: fp32 [N, C, S] or NULL; z_in: channels [0, C) of a channels-last
+ * [N * S, z_in_stride] buffer of z_in_dtype (GG_BF16, or GG_F32 in validation mode) or NULL, other lanes untouched.  At least one output. */
+int gg_gauss_sample_rows(const float *moments, int32_t stride, const float *noise, int32_t N, int32_t C, int64_t S, float *out, void *z_in,
+                         int32_t z_in_dtype, int32_t z_in_stride, void *stream);
+/* out fp64 [5] = means over the M logits l of  l, relu(1 - l), relu(1 + l), softplus(-l), softplus(l)  (hinge_d_loss / vanilla_d_loss /
+ * g_loss of contperceptual.py:14-25,140; softplus as F.softplus: x > 20 ? x : log1p(exp(x))).  logits: lane 0 of fp32 rows [M, stride].
+ * Each term in fp32.  workspace: 5 doubles per workgroup; gg_loss_workspace_bytes(3, M) is enough. */
+int gg_logit_stats(const float *logits, int32_t stride, int64_t M, double *out, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * fp32 VALIDATION mode of the CCDM path (gg_f32.hip): the same network functions on fp32 channels-last tensors with fp32 weights
  * and fp32 FMA accumulation in a fixed order, so that integer outputs (labels) can be compared exactly with the fp32 CPU
  * reference (the reference's own precision switch: ccdm/ddpm/models/unet_openai/unet.py:447,742-756).  Not a fast path.

@@ -117,6 +117,11 @@ SIGNATURES = {
     "gg_loss_rows": (C.c_int, [vp, i32, vp, vp, vp, i32, i32, i32, i64, vp, vp, i64, vp]),
     "gg_ccdm_q_sample": (C.c_int, [vp, vp, i64, i32, vp, vp, vp, i64, vp, vp, i32, vp]),
     "gg_ccdm_step_loss": (C.c_int, [vp, i32, vp, vp, vp, i64, vp, i32, i64, vp, vp, i64, vp]),
+    "gg_patch_conv_forward": (C.c_int, [vp, vp, vp, vp, f32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp]),
+    "gg_patch_conv_forward_f32": (C.c_int, [vp, vp, vp, vp, f32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
+    "gg_gauss_kl_rows": (C.c_int, [vp, i32, i32, i32, i64, vp, vp, i64, vp]),
+    "gg_gauss_sample_rows": (C.c_int, [vp, i32, vp, i32, i32, i64, vp, vp, i32, i32, vp]),
+    "gg_logit_stats": (C.c_int, [vp, i32, i64, vp, vp, i64, vp]),
     "gg_ubench_mfma_bf16": (C.c_int, [i32, i32, i32, vp, C.POINTER(C.c_double), vp]),
     "gg_ubench_stream_copy": (C.c_int, [vp, vp, i64, vp]),
 }

@@ -66,18 +66,50 @@ def split_cond(conditioning, conditioning_key):
 
 # ================================================================================================ autoencoder
 class DiagonalGaussianDistribution:
-    """moments = [mean | logvar] on dim 1; logvar clamped to [-30, 20] (distributions.py:24-33)."""
+    """moments = [mean | logvar] on dim 1; logvar clamped to [-30, 20] (distributions.py:24-33).  rows: the same moments as fp32
+    channels-last rows [N, *sp, stride >= 2 C] where the producer has them (AutoencoderKL.encode), so that kl() and sample() read them
+    without a layout copy."""
 
-    def __init__(self, parameters: torch.Tensor, deterministic=False):
+    def __init__(self, parameters: torch.Tensor, deterministic=False, rows: Optional[torch.Tensor] = None):
         self.parameters = parameters
         self.mean, self.logvar = torch.chunk(parameters, 2, dim=1)
         self.logvar = torch.clamp(self.logvar, -30.0, 20.0)
         self.deterministic = deterministic
         self.std = torch.exp(0.5 * self.logvar)
         self.var = torch.exp(self.logvar)
+        self._rows = rows
 
-    def sample(self):
-        return self.mean + self.std * torch.randn(self.mean.shape, device=self.parameters.device)
+    def rows(self) -> torch.Tensor:
+        if self._rows is None:
+            self._rows = nc_to_rows(self.parameters.detach().float()).contiguous()                  # plumbing: layout copy
+        return self._rows
+
+    def sample(self, noise: Optional[torch.Tensor] = None):
+        """mean + std * noise.  Device tensors: gg_gauss_sample_rows; noise (this package's addition, fp32 of the latent's shape) replays
+        a recorded draw, None draws torch.randn on the device."""
+        if not self.parameters.is_cuda:
+            if noise is None:
+                noise = torch.randn(self.mean.shape, device=self.parameters.device)
+            return self.mean + self.std * noise
+        if noise is None:
+            noise = torch.randn(tuple(self.mean.shape), device=self.parameters.device)
+        if tuple(noise.shape) != tuple(self.mean.shape):
+            raise ValueError(f"DiagonalGaussianDistribution.sample: noise {tuple(noise.shape)} is not the latent's shape {tuple(self.mean.shape)}")
+        return ops.gauss_sample_rows(self.rows(), int(self.mean.shape[1]), noise.to(self.parameters.device).float().contiguous())
+
+    def kl_rows(self) -> torch.Tensor:
+        """fp64 [N]: 0.5 * sum(mean^2 + var - 1 - logvar) per sample (gg_gauss_kl_rows)."""
+        if self.deterministic:
+            raise NotImplementedError("DiagonalGaussianDistribution.kl: deterministic=True is not supported")
+        ops.require_gpu(self.parameters, "DiagonalGaussianDistribution.kl")
+        return ops.gauss_kl_rows(self.rows(), int(self.mean.shape[1]))
+
+    def kl(self, other=None):
+        """distributions.py:44-51 against the standard normal: fp32 [N] per-sample sums.  (The reference sums dims 1..3 only, which
+        leaves a volume's last axis; every caller sums the result, and so does this.)"""
+        if other is not None:
+            raise NotImplementedError("DiagonalGaussianDistribution.kl(other) is not supported (no caller in the reference's sampling or validation)")
+        return self.kl_rows().float()
 
     def mode(self):
         return self.mean
@@ -218,6 +250,14 @@ def first_stage_dims(who, ddconfig, dims) -> int:
     return dims
 
 
+AE_LOSS_TARGETS = ("ldm.modules.losses.LPIPSWithDiscriminator", "ldm.modules.losses.contperceptual.LPIPSWithDiscriminator",
+                   "jointimagegeneration_amd.aeloss.LPIPSWithDiscriminator")
+
+
+def is_ae_loss_config(lossconfig) -> bool:
+    return isinstance(lossconfig, dict) and lossconfig.get("target") in AE_LOSS_TARGETS
+
+
 def check_rank(who, x, dims) -> None:
     """Host-side refusal of a tensor whose rank is not the model's: a [N, C, H, W] tensor given to a dims = 3 model would otherwise run
     as a one-slice volume (to_cl pads D to 1), and a volume given to a dims = 2 model as a stack the 2-D kernels misread."""
@@ -238,7 +278,9 @@ class AutoencoderKL(nn.Module):
         self.image_key = image_key
         self.encoder = Encoder(**ddconfig)
         self.decoder = Decoder(**ddconfig)
-        self.loss = nn.Identity()                       # lossconfig is torch.nn.Identity in the shipped yaml; training is out of scope
+        # the held-out objective (aeloss.py) where the config names it; any other target, or none, stays Identity: training is out of scope
+        self.loss = instantiate_from_config(lossconfig) if is_ae_loss_config(lossconfig) else nn.Identity()
+        self.global_step = 0                            # LightningModule.global_step: the checkpoint's, for disc_start (ae_eval sets it)
         self.quant_conv = conv_nd(self.dims, 2 * ddconfig["z_channels"], 2 * embed_dim, 1)
         self.post_quant_conv = conv_nd(self.dims, embed_dim, ddconfig["z_channels"], 1)
         self.embed_dim = embed_dim
@@ -276,12 +318,54 @@ class AutoencoderKL(nn.Module):
         check_rank("AutoencoderKL.encode", x, self.dims)
         ops.require_gpu(x, "AutoencoderKL.encode")
         m = self.encode_moments_cl(ops.to_cl(x))
-        return DiagonalGaussianDistribution(ops.from_cl(m, self.dims))
+        return DiagonalGaussianDistribution(ops.from_cl(m, self.dims), rows=m.t)
 
     def decode(self, z: torch.Tensor) -> torch.Tensor:
         check_rank("AutoencoderKL.decode", z, self.dims)
         ops.require_gpu(z, "AutoencoderKL.decode")
         return ops.from_cl(self.decode_cl(ops.to_cl(z)), self.dims)
+
+    # ---- held-out objective (autoencoder.py:353-416), forward only
+    def forward(self, input: torch.Tensor, sample_posterior=True, noise: Optional[torch.Tensor] = None):
+        """(reconstruction, posterior).  noise: fp32 of the latent's shape, this package's addition so that a recorded draw can be
+        replayed; None draws torch.randn on the device."""
+        posterior = self.encode(input)
+        z = posterior.sample(noise) if sample_posterior else posterior.mode()
+        return self.decode(z.contiguous()), posterior
+
+    def latent_shape(self, x_shape) -> tuple:
+        """Shape of the posterior's mean for an input of x_shape: every Downsample (model.py:75-79) halves each spatial extent, rounding down."""
+        sp = tuple(int(e) for e in x_shape[2:])
+        for _ in range(self.encoder.num_resolutions - 1):
+            sp = tuple(e // 2 for e in sp)
+        return (int(x_shape[0]), self.embed_dim) + sp
+
+    def get_input(self, batch, k):
+        x = batch[k]
+        if x.ndim == self.dims + 1:
+            x = x[..., None]
+        return x.permute((0, self.dims + 1) + tuple(range(1, self.dims + 1))).to(memory_format=torch.contiguous_format).float()
+
+    @torch.no_grad()
+    def validation_losses(self, x: torch.Tensor, noise: Optional[torch.Tensor] = None, global_step: Optional[int] = None) -> Dict[str, torch.Tensor]:
+        """validation_step on a tensor: one forward, then the loss module's autoencoder pass (optimizer_idx 0) and discriminator pass (1)
+        with split "val"; the union of the two dicts, every value a 0-dim fp32 device tensor."""
+        if isinstance(self.loss, nn.Identity):
+            raise NotImplementedError("AutoencoderKL.validation_losses: the model was built without an objective (loss is nn.Identity); give a "
+                                      "lossconfig whose target is ldm.modules.losses.LPIPSWithDiscriminator")
+        if self.training:
+            raise NotImplementedError("AutoencoderKL.validation_losses: training mode is not supported (forward only; call .eval())")
+        if next(self.parameters()).device.type != "cuda":
+            raise RuntimeError(f"AutoencoderKL.validation_losses: the model is on {next(self.parameters()).device}; the GuideGen engine runs on "
+                               "MI355X only (no CPU fallback)")
+        step = self.global_step if global_step is None else global_step
+        rec, posterior = self.forward(x, noise=noise)
+        _, log_ae = self.loss(x, rec, posterior, 0, step, last_layer=None, split="val")
+        _, log_disc = self.loss(x, rec, posterior, 1, step, last_layer=None, split="val")
+        return {**log_ae, **log_disc}
+
+    def validation_step(self, batch, batch_idx):
+        return self.validation_losses(self.get_input(batch, self.image_key).to(next(self.parameters()).device))
 
 
 class VectorQuantizer(nn.Module):

@@ -1361,3 +1361,100 @@ def ccdm_step_loss(logits: torch.Tensor, xt: torch.Tensor, x0: torch.Tensor, sca
     check(lib.gg_ccdm_step_loss(logits.data_ptr(), stride, xt.data_ptr(), x0.data_ptr(), scalars.data_ptr(), M // N, class_weights.data_ptr(),
                                 K, M, out.data_ptr(), workspace.data_ptr(), workspace.numel() * 8, _stream()), "gg_ccdm_step_loss")
     return out
+
+
+# ----------------------------------------------------------------------------------------------- first-stage objective (gg_patchgan.hip)
+def patch_conv_out_extent(in_sp: Sequence[int], kd: int, stride: int) -> Tuple[int, int, int]:
+    """Output extent of a kernel-4, padding-2 convolution over (D, H, W); kd == 1: 2-D, D is carried through."""
+    D, H, W = in_sp
+    return (D if kd == 1 else D // stride + 1, H // stride + 1, W // stride + 1)
+
+
+def patch_conv(src: CL, weight: torch.Tensor, alpha: Optional[torch.Tensor], beta: torch.Tensor, cout: int, kd: int, stride: int,
+               slope: float = 0.2, out_f32: bool = False) -> CL:
+    """One PatchGAN convolution (gg_patch_conv_forward, or the fp32 kernel for fp32 inputs): kernel 4, padding 2, then
+    y = acc * alpha + beta and LeakyReLU(slope) (slope 1: none).  weight: pack_conv_weight of the OI[D]HW weight; alpha (or None) and
+    beta: fp32 [pad32(cout)], the folded conv bias and eval-mode BatchNorm."""
+    lib = _lib.load()
+    require_gpu(src.t, "patch_conv")
+    N, D, H, W, cin = src.t.shape
+    Do, Ho, Wo = patch_conv_out_extent((D, H, W), kd, stride)
+    cp = pad32(cout)
+    for name, t in (("alpha", alpha), ("beta", beta)):
+        if t is not None:
+            _f32_dev(t, cp, f"patch_conv: {name}")
+    if is_f32(src.t):
+        if weight.dtype != torch.float32 or tuple(weight.shape) != (16 * kd, cin, cp):
+            raise ValueError(f"patch_conv: fp32 input needs an fp32 weight [{16 * kd}, {cin}, {cp}], got {weight.dtype} {tuple(weight.shape)}")
+        out = torch.empty((N, Do, Ho, Wo, cp), dtype=torch.float32, device=src.t.device)
+        check(lib.gg_patch_conv_forward_f32(src.t.data_ptr(), weight.data_ptr(), _ptr(alpha), beta.data_ptr(), slope, N, D, H, W, cin, cout, kd,
+                                            stride, Do, Ho, Wo, out.data_ptr(), _stream()), "gg_patch_conv_forward_f32")
+        return CL(out, cout)
+    if src.t.dtype != torch.bfloat16 or weight.dtype != torch.bfloat16 or weight.numel() != cp * 16 * kd * cin:
+        raise ValueError(f"patch_conv: bf16 input needs a packed bf16 weight of {cp * 16 * kd * cin} elements, got {src.t.dtype} input, "
+                         f"{weight.dtype} weight of {weight.numel()}")
+    out = torch.empty((N, Do, Ho, Wo, cp), dtype=torch.float32 if out_f32 else torch.bfloat16, device=src.t.device)
+    check(lib.gg_patch_conv_forward(src.t.data_ptr(), weight.data_ptr(), _ptr(alpha), beta.data_ptr(), slope, N, D, H, W, cin, cout, kd, stride,
+                                    Do, Ho, Wo, out.data_ptr(), GG_F32 if out_f32 else GG_BF16, _stream()), "gg_patch_conv_forward")
+    return CL(out, cout)
+
+
+def _moment_rows(moments: torch.Tensor, C: int, what: str) -> Tuple[int, int]:
+    stride = int(moments.shape[-1])
+    require_gpu(moments, what)
+    if moments.dtype != torch.float32 or not moments.is_contiguous() or stride < 2 * C:
+        raise ValueError(f"{what}: moments must be contiguous fp32 channels-last rows of >= {2 * C} lanes, got {moments.dtype} {tuple(moments.shape)}")
+    N = int(moments.shape[0])
+    return N, moments.numel() // (N * stride)
+
+
+def gauss_kl_rows(moments: torch.Tensor, C: int, out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp64 [N] = DiagonalGaussianDistribution.kl() (gg_gauss_kl_rows) of fp32 channels-last moments [N, ..., stride]: mean lanes [0, C),
+    logvar lanes [C, 2C)."""
+    lib = _lib.load()
+    N, S = _moment_rows(moments, C, "gauss_kl_rows")
+    if out is None:
+        out = torch.empty(N, dtype=torch.float64, device=moments.device)
+    if workspace is None:
+        workspace = loss_workspace(N, S, moments.device)
+    check(lib.gg_gauss_kl_rows(moments.data_ptr(), int(moments.shape[-1]), N, C, S, out.data_ptr(), workspace.data_ptr(), workspace.numel() * 8,
+                               _stream()), "gg_gauss_kl_rows")
+    return out
+
+
+def gauss_sample_rows(moments: torch.Tensor, C: int, noise: torch.Tensor, out: Optional[torch.Tensor] = None,
+                      z_in: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+    """z = mean + exp(0.5 * logvar) * noise (gg_gauss_sample_rows): moments as in gauss_kl_rows, noise fp32 [N, C, *spatial].
+    out: fp32 like noise; z_in: channels-last [N, ..., Cpad] bf16 (or fp32 in validation mode), channels [0, C) written."""
+    lib = _lib.load()
+    N, S = _moment_rows(moments, C, "gauss_sample_rows")
+    _f32_dev(noise, N * C * S, "gauss_sample_rows: noise")
+    if out is None and z_in is None:
+        out = torch.empty_like(noise)
+    if out is not None:
+        _f32_dev(out, N * C * S, "gauss_sample_rows: out")
+    dt, stride = GG_BF16, 0
+    if z_in is not None:
+        stride = int(z_in.shape[-1])
+        if z_in.dtype not in (torch.bfloat16, torch.float32) or not z_in.is_cuda or not z_in.is_contiguous() or z_in.numel() != N * S * stride or stride < C:
+            raise ValueError(f"gauss_sample_rows: z_in {z_in.dtype} {tuple(z_in.shape)} is not a channels-last device buffer of {N * S} rows, >= {C} lanes")
+        dt = GG_F32 if is_f32(z_in) else GG_BF16
+    check(lib.gg_gauss_sample_rows(moments.data_ptr(), int(moments.shape[-1]), noise.data_ptr(), N, C, S, _ptr(out), _ptr(z_in), dt, stride,
+                                   _stream()), "gg_gauss_sample_rows")
+    return out
+
+
+def logit_stats(logits: torch.Tensor, out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp64 [5] = means over all logits l of (l, relu(1 - l), relu(1 + l), softplus(-l), softplus(l)) (gg_logit_stats); logits: lane 0
+    of fp32 channels-last rows [..., stride] (a discriminator's last convolution with out_f32)."""
+    lib = _lib.load()
+    require_gpu(logits, "logit_stats")
+    stride = int(logits.shape[-1])
+    M = logits.numel() // stride
+    _f32_dev(logits, M * stride, "logit_stats: logits")
+    if out is None:
+        out = torch.empty(5, dtype=torch.float64, device=logits.device)
+    if workspace is None:
+        workspace = loss_workspace(3, M, logits.device)
+    check(lib.gg_logit_stats(logits.data_ptr(), stride, M, out.data_ptr(), workspace.data_ptr(), workspace.numel() * 8, _stream()), "gg_logit_stats")
+    return out
