@@ -78,9 +78,23 @@ static inline unsigned gg_magic_u32(long long nmax, int d)
     return (d > 1 && nmax * (long long)d < (1LL << 32)) ? (unsigned)(((1ULL << 32) + (unsigned)d - 1) / (unsigned)d) : 0u;
 }
 
-// SiLU with the hardware reciprocal (v_rcp_f32, 1 ulp), as the conv prologues compute it: an IEEE division is ~10 VALU instructions per
-// element, 16 elements per thread in the launch-bound GroupNorm kernels
-__device__ __forceinline__ float gg_silu(float y) { return y * __builtin_amdgcn_rcpf(1.0f + __expf(-y)); }
+// SiLU with the hardware exp2 and reciprocal (v_exp_f32, v_rcp_f32: 1 ulp each), the one definition every bf16 site calls (GroupNorm
+// kernels, resample, every conv staging pass): an IEEE division is ~10 VALU instructions per element, 16 elements per thread in the
+// launch-bound GroupNorm kernels.
+// Written as (y / 2) * rcp((1 + exp(-y)) / 2): v_rcp_f32 flushes a subnormal RESULT to zero, so y * rcp(1 + exp(-y)) returned 0 once
+// exp(-y) passed 2^126 (y = -87.5: SiLU = -8.7e-37, a normal number; found by the exhaustive sweep of tests/test_act_sweep_gpu.py).
+// With the halves the reciprocal stays normal up to exp(-y) < 2^127 (y > -88.03; below that |SiLU| < 5.3e-37).  Every other result is,
+// bit for bit, that of the plain form: the exponential is the same instruction pair, fma(e, 0.5, 0.5) is round(1 + e) / 2 exactly,
+// and a power of two moves through the reciprocal and the products without touching a rounding (only y below 2^-125 can lose a bit
+// in y / 2; q * (-2 log2 e) below rounds as y * (-log2 e) does in __expf(-y)).  gg_silu is one multiply longer than the plain form.
+// gg_silu_of_half takes q = y / 2 and is as long as the plain form: a staging pass whose scale / shift stay in registers over many
+// elements halves them once, x * (scale / 2) + shift / 2 is y / 2 exactly, and every result equals gg_silu(y) bit for bit.
+__device__ __forceinline__ float gg_silu_of_half(float q)
+{
+    const float half_d = fmaf(__builtin_amdgcn_exp2f(q * (-2.0f * 1.4426950408889634f)), 0.5f, 0.5f);      // (1 + exp(-y)) / 2
+    return q * __builtin_amdgcn_rcpf(half_d);
+}
+__device__ __forceinline__ float gg_silu(float y) { return gg_silu_of_half(0.5f * y); }
 
 __device__ __forceinline__ f32x8 gg_bf16x8_to_f32(bf16x8 v)
 {

@@ -135,8 +135,8 @@ __global__ __launch_bounds__(256) void conv_gather_kernel(const ConvParams p)
                 for (int j = 0; j < 4; ++j) {
                     float y0 = (float)xb8[j] * s0[j] + h0[j], y1 = (float)xb8[j + 4] * s1[j] + h1[j];
                     if (p.prologue_act == 1) {
-                        y0 = y0 * __builtin_amdgcn_rcpf(1.0f + __expf(-y0));
-                        y1 = y1 * __builtin_amdgcn_rcpf(1.0f + __expf(-y1));
+                        y0 = gg_silu(y0);
+                        y1 = gg_silu(y1);
                     }
                     yb[j] = (bf16_t)y0;
                     yb[j + 4] = (bf16_t)y1;
@@ -407,8 +407,8 @@ __global__ __launch_bounds__(256) void conv_gather5_kernel(const ConvParams p)
                 for (int j = 0; j < 4; ++j) {
                     float y0 = (float)xb8[j] * s0[j] + h0[j], y1 = (float)xb8[j + 4] * s1[j] + h1[j];
                     if (p.prologue_act == 1) {
-                        y0 = y0 * __builtin_amdgcn_rcpf(1.0f + __expf(-y0));
-                        y1 = y1 * __builtin_amdgcn_rcpf(1.0f + __expf(-y1));
+                        y0 = gg_silu(y0);
+                        y1 = gg_silu(y1);
                     }
                     yb[j] = (bf16_t)y0;
                     yb[j + 4] = (bf16_t)y1;

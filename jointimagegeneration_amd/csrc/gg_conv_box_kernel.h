@@ -498,8 +498,8 @@ __global__ __launch_bounds__(GG_BOX_NW * 64) void conv_box2d_kernel(const ConvPa
                 for (int e = 0; e < 4; ++e) {
                     float y0 = (float)xb[e] * sc0[e] + sh0[e], y1 = (float)xb[e + 4] * sc1[e] + sh1[e];
                     if (p.prologue_act == 1) {
-                        y0 = y0 * __builtin_amdgcn_rcpf(1.0f + __expf(-y0));
-                        y1 = y1 * __builtin_amdgcn_rcpf(1.0f + __expf(-y1));
+                        y0 = gg_silu(y0);
+                        y1 = gg_silu(y1);
                     }
                     yb[e] = (bf16_t)y0;
                     yb[e + 4] = (bf16_t)y1;

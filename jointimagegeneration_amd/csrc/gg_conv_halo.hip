@@ -170,6 +170,9 @@ __global__ __launch_bounds__((HaloGeom<D3, NT, UP, HB>::NTHR), (HaloGeom<D3, NT,
                 const long long so = (long long)n * (p.C1 + p.C2) + chunk * 32 + xq * 8;
                 s0 = *reinterpret_cast<const f32x4 *>(p.gn_scale + so); s1 = *reinterpret_cast<const f32x4 *>(p.gn_scale + so + 4);
                 b0 = *reinterpret_cast<const f32x4 *>(p.gn_shift + so); b1 = *reinterpret_cast<const f32x4 *>(p.gn_shift + so + 4);
+                // SiLU: the coefficients serve the whole chunk, so they are halved here, once, and the affine below yields y / 2 (exactly),
+                // which is what gg_silu_of_half takes
+                if (p.prologue_act == 1) { s0 *= 0.5f; s1 *= 0.5f; b0 *= 0.5f; b1 *= 0.5f; }
             }
             constexpr int JG = 3;                                   // pieces in flight per thread (bounds the VGPR footprint)
             // The piece of step j is box row (tid >> 2) + (NTHR / 4) j: its (hd, hh, hw) is decoded once per chunk and then stepped
@@ -214,8 +217,8 @@ __global__ __launch_bounds__((HaloGeom<D3, NT, UP, HB>::NTHR), (HaloGeom<D3, NT,
                         for (int e = 0; e < 4; ++e) {
                             float y0 = (float)xb[e] * s0[e] + b0[e], y1 = (float)xb[e + 4] * s1[e] + b1[e];
                             if (p.prologue_act == 1) {
-                                y0 = y0 * __builtin_amdgcn_rcpf(1.0f + __expf(-y0));
-                                y1 = y1 * __builtin_amdgcn_rcpf(1.0f + __expf(-y1));
+                                y0 = gg_silu_of_half(y0);
+                                y1 = gg_silu_of_half(y1);
                             }
                             yb[e] = (bf16_t)y0;
                             yb[e + 4] = (bf16_t)y1;

@@ -171,8 +171,8 @@ __global__ __launch_bounds__(512, 2) void conv_halo3_team_kernel(const ConvParam
                         for (int e = 0; e < 4; ++e) {
                             float y0 = (float)q.x[e] * q.s0[e] + q.b0[e], y1 = (float)q.x[e + 4] * q.s1[e] + q.b1[e];
                             if constexpr (PRO == 1) {
-                                y0 = y0 * __builtin_amdgcn_rcpf(1.0f + __expf(-y0));
-                                y1 = y1 * __builtin_amdgcn_rcpf(1.0f + __expf(-y1));
+                                y0 = gg_silu(y0);
+                                y1 = gg_silu(y1);
                             }
                             yb[e] = (bf16_t)y0;
                             yb[e + 4] = (bf16_t)y1;
