@@ -601,6 +601,27 @@ int gg_loss_rows(const float *pred, int32_t pred_stride, const float *target, co
 int gg_ccdm_q_sample(const int32_t *x0, const float *mix_dev, int64_t rows_per_sample, int32_t K, const float *E,
                      const uint64_t *philox_seeds_dev, const int64_t *philox_offset_dev, int64_t M, int32_t *labels_out, void *onehot_out,
                      int32_t onehot_stride, void *stream);
+/* Mask editing of the CCDM reverse chain (the blend of ldm/models/diffusion/ddim.py:144-148 with the categorical operands of
+ * diffusion_denoising.py:82-89): every row m with keep[m] != 0 takes labels[m] = a draw of q(x_t | x_0 = known[m]), formed and drawn
+ * exactly as gg_ccdm_q_sample does (same expressions, same order, first maximum on a tie); a row with keep[m] == 0 is not written at
+ * all, neither its label nor its one-hot row.
+ *   labels     int32 [M], in/out: only rows with keep != 0 are written, none is read
+ *   known      int32 [M] in 0 .. K-1 (the caller's check; a value outside reads nothing out of bounds).  known may be the labels buffer
+ *              itself: a row reads its known label before it writes, so kept rows are then re-noised in place
+ *   keep       uint8 [M], non-zero = keep the known value
+ *   mix_dev    fp32 [N, 2] = (keep, unif) of sample n = m / rows_per_sample, read on the device: (cumalphas[t-1], 1 - cumalphas[t-1]) at
+ *              step t; (1, 0) returns known on the kept rows whatever is drawn
+ *   E          fp32 [M, K] exponentials (rows with keep == 0 unused), or NULL: Philox4x32-10 with gg_ccdm_draw_tape's counter and
+ *              philox_offset_dev[0] (0 when NULL); philox_seeds_dev == NULL: key philox_seed, row = m (gg_ccdm_posterior_sample's rule);
+ *              else key philox_seeds_dev[n], row = m % rows_per_sample (gg_ccdm_posterior_sample_seeds' rule)
+ *   onehot_out bf16 rows [M, onehot_stride] or NULL: channels [0, K) of the kept rows written, channels >= K never
+ * 2 <= K <= 32 (16 or 32 exponentials drawn per row, as the posterior kernel).  No allocation, no synchronisation: one launch that a
+ * captured step can hold, since the mix row and the offset are read from device memory.
+ * GG_ERR_BAD_SHAPE: labels, known, keep or mix_dev NULL; K outside [2, 32]; M < 1, rows_per_sample < 1 or M not a multiple of
+ * rows_per_sample; onehot_out with onehot_stride < K, an odd onehot_stride or rows that are not 4-byte aligned. */
+int gg_ccdm_inpaint_blend(int32_t *labels, const int32_t *known, const uint8_t *keep, const float *mix_dev, int64_t rows_per_sample,
+                          int32_t K, const float *E, uint64_t philox_seed, const uint64_t *philox_seeds_dev,
+                          const int64_t *philox_offset_dev, int64_t M, void *onehot_out, int32_t onehot_stride, void *stream);
 /* out fp64 [N, 2] = per-sample sums over the voxels of (class_weights[x0] * KL, CE), trainer.py:305-320 with its quirks kept:
  *   p = softmax(logits);  q_pred = max(theta_post_prob(xt, p), 1e-12) NOT renormalised;  q_true = theta_post(xt, x0);
  *   KL = sum_c (q_true > 0 ? q_true * log(q_true) : 0) - q_true * log(q_pred);  CE = cross_entropy(p, x0) on the PROBABILITIES.

@@ -116,6 +116,7 @@ SIGNATURES = {
     "gg_q_sample_rows": (C.c_int, [vp, vp, vp, i32, i32, i64, vp, vp, i32, i32, vp]),
     "gg_loss_rows": (C.c_int, [vp, i32, vp, vp, vp, i32, i32, i32, i64, vp, vp, i64, vp]),
     "gg_ccdm_q_sample": (C.c_int, [vp, vp, i64, i32, vp, vp, vp, i64, vp, vp, i32, vp]),
+    "gg_ccdm_inpaint_blend": (C.c_int, [vp, vp, vp, vp, i64, i32, vp, u64, vp, vp, i64, vp, i32, vp]),
     "gg_ccdm_step_loss": (C.c_int, [vp, i32, vp, vp, vp, i64, vp, i32, i64, vp, vp, i64, vp]),
     "gg_patch_conv_forward": (C.c_int, [vp, vp, vp, vp, f32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp]),
     "gg_patch_conv_forward_f32": (C.c_int, [vp, vp, vp, vp, f32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp]),

@@ -110,6 +110,16 @@ class DiffusionModel(nn.Module):
         abar = torch.where(one, torch.ones_like(a), self.cumalphas[(t - 2).clamp(min=0)])
         return torch.stack([a, abar], 1).float().contiguous()
 
+    def known_mix(self, t_values: Sequence[int]) -> Tensor:
+        """fp32 [S, 2] = (cumalphas[t-1], 1 - cumalphas[t-1]): the operands of q(x_t | x_0) as `q_xt_given_x0` forms them, one row per step."""
+        ca = self.cumalphas[torch.tensor(list(t_values), dtype=torch.long, device=self.cumalphas.device) - 1]
+        return torch.stack([ca, 1 - ca], 1).float().contiguous()
+
+    def renoise_mix(self, t_values: Sequence[int]) -> Tensor:
+        """fp32 [S, 2] = (1 - betas[t-1], betas[t-1]): the operands of q(x_t | x_{t-1}) as `q_xt_given_xtm1` forms them, one row per step."""
+        betas = self.betas[torch.tensor(list(t_values), dtype=torch.long, device=self.betas.device) - 1]
+        return torch.stack([1 - betas, betas], 1).float().contiguous()
+
     def _mix_rows(self, keep: Tensor, unif: Tensor, x: Tensor, who: str) -> "CategoricalBCHW":
         ops.require_gpu(x, who)
         if x.shape[1] != self.num_classes:
@@ -166,13 +176,15 @@ class DenoisingModel(nn.Module):
         return self.diffusion.time_steps
 
     def forward(self, x: Tensor, condition: Tensor, feature_condition: Tensor = None, t: Optional[Tensor] = None,
-                label_ref_logits: Optional[Tensor] = None, validation: bool = False, context=None, rng_tapes=None) -> dict:
+                label_ref_logits: Optional[Tensor] = None, validation: bool = False, context=None, rng_tapes=None,
+                known: Optional[Tensor] = None, keep: Optional[Tensor] = None, resample: int = 1) -> dict:
         if self.training:
             raise RuntimeError("this engine implements sampling only (training is out of scope, SURVEY.md 2.1 row 5)")
         if validation:
             return self.forward_step(x, condition, feature_condition, t, context=context)
         init_t = None if t is None else cast(int, int(t.item()))
-        return self.forward_denoising(x, condition, feature_condition, init_t, label_ref_logits, context=context, rng_tapes=rng_tapes)
+        return self.forward_denoising(x, condition, feature_condition, init_t, label_ref_logits, context=context, rng_tapes=rng_tapes,
+                                      known=known, keep=keep, resample=resample)
 
     def forward_step(self, x, condition, feature_condition, t, context=None):
         return self.unet(x, condition, feature_condition=feature_condition, timesteps=t, context=context)
@@ -190,14 +202,15 @@ class DenoisingModel(nn.Module):
 
     @torch.no_grad()
     def forward_denoising(self, x: Tensor, condition: Tensor, feature_condition: Tensor = None, init_t: Optional[int] = None,
-                          label_ref_logits: Optional[Tensor] = None, context: Tensor = None, rng_tapes=None) -> dict:
+                          label_ref_logits: Optional[Tensor] = None, context: Tensor = None, rng_tapes=None,
+                          known: Optional[Tensor] = None, keep: Optional[Tensor] = None, resample: int = 1) -> dict:
         if label_ref_logits is not None:
             raise NotImplementedError("label_ref_logits guidance is dead code in the reference (undefined guidance_fn)")
         if feature_condition is not None:
             raise NotImplementedError("feature_condition is always None on the shipped path (evaluator.py:169)")
         ops.require_gpu(x, "DenoisingModel.forward_denoising")
         labels = x.argmax(dim=1).to(torch.int32).contiguous()                   # x_T one-hot -> labels (plumbing)
-        lab, probs = self.sample_labels(labels, condition, init_t, rng_tapes)
+        lab, probs = self.sample_labels(labels, condition, init_t, rng_tapes, known=known, keep=keep, resample=resample)
         K = self.diffusion.num_classes
         nd = x.ndim
         inv = (0, nd - 1) + tuple(range(1, nd - 1))
@@ -209,12 +222,51 @@ class DenoisingModel(nn.Module):
             raise ValueError(f"step_T_sample={self.step_T_sample}")
         return {"diffusion_out": out}
 
+    def check_edit(self, shape, known: Optional[Tensor], keep: Optional[Tensor], resample: int = 1):
+        """The refusals of mask editing, each by name; returns (known int32 [M], keep uint8 [M]) or (None, None) without a mask.  The
+        label range is checked where the labels are (one readback for a device tensor)."""
+        if isinstance(resample, bool) or not isinstance(resample, int) or resample < 1:
+            raise ValueError(f"sample_labels: resample={resample!r} must be an integer >= 1")
+        if resample > 256:
+            raise ValueError(f"sample_labels: resample={resample} exceeds 256, the repetitions the Philox offset word can number")
+        if (known is None) != (keep is None):
+            raise ValueError(f"sample_labels: {'keep' if known is None else 'known'} given without {'known' if known is None else 'keep'}; "
+                             "mask editing needs both")
+        if (known is not None or resample > 1) and self.time_steps >= (1 << 16):
+            raise ValueError(f"sample_labels: time_steps={self.time_steps} >= 65536 does not fit the 16 bits the Philox offset word gives t")
+        K = self.diffusion.num_classes
+        if resample > 1 and K > 16:
+            raise NotImplementedError(f"sample_labels: resample > 1 re-noises with gg_ccdm_q_sample, which takes K <= 16 (K = {K})")
+        if known is None:
+            return None, None
+        for name, v in (("known", known), ("keep", keep)):
+            if tuple(v.shape) != tuple(shape):
+                raise ValueError(f"sample_labels: {name} has shape {tuple(v.shape)}, the labels {tuple(shape)}")
+        if known.dtype.is_floating_point or known.dtype == torch.bool:
+            raise ValueError(f"sample_labels: known must hold integer labels, got {known.dtype}")
+        if keep.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f"sample_labels: keep must be bool or uint8, got {keep.dtype}")
+        lo, hi = torch.stack([known.min(), known.max()]).tolist()
+        if lo < 0 or hi > K - 1:
+            raise ValueError(f"sample_labels: known holds labels {lo}..{hi} outside 0..{K - 1}")
+        return known.to(torch.int32).contiguous().view(-1), (keep != 0).to(torch.uint8).contiguous().view(-1)
+
     @torch.no_grad()
     def sample_labels(self, labels: Tensor, condition: Optional[Tensor], init_t: Optional[int] = None, rng_tapes=None,
-                      trace: Optional[list] = None, philox_seeds: Optional[Sequence[int]] = None) -> Tuple[Tensor, Tensor]:
+                      trace: Optional[list] = None, philox_seeds: Optional[Sequence[int]] = None, known: Optional[Tensor] = None,
+                      keep: Optional[Tensor] = None, resample: int = 1) -> Tuple[Tensor, Tensor]:
         """labels int32 [N, (D,) H, W] on the GPU -> (final labels int32, final normalised posterior fp32 [M, K]).
         philox_seeds (N keys): sample n draws with its own Philox key and its own voxel index as the counter, so that its chain does not
-        depend on its batch slot or its neighbours (independent volumes in one batch); None: `self.philox_seed` over the whole batch."""
+        depend on its batch slot or its neighbours (independent volumes in one batch); None: `self.philox_seed` over the whole batch.
+        known / keep (mask editing): integer labels in 0..K-1 and a bool / uint8 mask, both of labels' shape.  At the top of
+        every step the voxels with keep != 0 are replaced by a draw of q(x_t | x_0 = known) (one `gg_ccdm_inpaint_blend` launch in front
+        of the UNet), and after the last step they hold known exactly.  resample R: every step runs R times, re-noised one step with
+        q(x_t | x_{t-1}) in between (RePaint's resampling, jump length 1).  The Philox offset word is `ops.philox_offset_word(t, j, purpose)`.
+        rng_tapes: per (t, j) the blend tape (with a mask), the posterior tape (t > 1), the re-noise tape (j < R - 1), in that order.
+        trace entries: t, j, labels, probs and, with a mask, x_in (the labels after the blend, the UNet's input)."""
+        known_f, keep_f = self.check_edit(labels.shape, known, keep, resample)
+        masked = known_f is not None
+        edit = masked or resample > 1
         dev = labels.device
         K = self.diffusion.num_classes
         unet = self.unet
@@ -261,30 +313,95 @@ class DenoisingModel(nn.Module):
             if not bf16_in:                                           # fp32 validation mode: the one-hot input is refreshed by an index scatter
                 ops.labels_to_onehot(lab, K, xin.view(M, -1))
 
+        bf16_state = xin.dtype == torch.bfloat16
+        if masked:
+            known_f, keep_f = known_f.to(dev), keep_f.to(dev)
+            kmix = self.diffusion.known_mix(tv).to(dev)
+            cur_kmix = torch.empty((N, 2), dtype=torch.float32, device=dev)
+            cur_koff = torch.zeros(1, dtype=torch.int64, device=dev)
+        if resample > 1:
+            rmix = self.diffusion.renoise_mix(tv).to(dev)
+            cur_rmix = torch.empty((N, 2), dtype=torch.float32, device=dev)
+            cur_roff = torch.zeros(1, dtype=torch.int64, device=dev)
+            # gg_ccdm_q_sample draws per sample; the single-key stream (key philox_seed, counter = the row of the batch) is its one-sample case
+            rkeys = seeds if seeds is not None else ops.philox_seed_tensor([self.philox_seed], dev)
+
+        def blend(E=None, final=False):
+            # x_t <- a draw of q(x_t | x_0 = known) where keep != 0, into the labels and the one-hot UNet input (operands (1, 0): known itself)
+            ops.ccdm_inpaint_blend(lab, known_f, keep_f, cur_kmix, K, E=E, philox_seed=self.philox_seed, philox_seeds=seeds,
+                                   philox_offset=cur_koff, onehot_out=xin.view(M, -1) if (bf16_state and not final) else None)
+            if not bf16_state and not final:
+                ops.labels_to_onehot(lab, K, xin.view(M, -1))
+
+        def renoise(E=None):
+            # x_t <- a draw of q(x_t | x_{t-1}) on every voxel, in place
+            mix = cur_rmix if (seeds is not None or E is not None) else cur_rmix[:1]
+            ops.ccdm_q_sample(lab, mix, K, E=E, philox_seeds=None if E is not None else rkeys, philox_offset=cur_roff, labels_out=lab,
+                              onehot_out=xin.view(M, -1) if bf16_state else None)
+            if not bf16_state:
+                ops.labels_to_onehot(lab, K, xin.view(M, -1))
+
+        def masked_step():
+            blend()
+            step(True)
+
         if rng_tapes is not None:
-            need = sum(1 for t in tv if t > 1)                        # one exponential tape per DRAWING step (t = 1 takes the argmax)
+            # per (t, j): the blend tape with a mask, the posterior tape of a DRAWING step (t = 1 takes the argmax), the re-noise tape
+            need = sum(resample * (int(masked) + int(t > 1)) + (resample - 1) for t in tv)
             if len(rng_tapes) < need:
-                raise ValueError(f"sample_labels: {need} drawing steps (t = {tv[0]} .. 2) need {need} rng tapes, got {len(rng_tapes)}")
+                what = f"{need} drawing steps (t = {tv[0]} .. 2)" if not edit else \
+                    f"{S} steps (t = {tv[0]} .. {tv[-1]}) x {resample} repetitions{' with a mask' if masked else ''}"
+                raise ValueError(f"sample_labels: {what} need {need} rng tapes, got {len(rng_tapes)}")
         use_graph = self.use_graph and rng_tapes is None and trace is None and S > 3 and not ops.FP32
         graph, warmed, ti = None, False, 0
+
+        def tape():
+            nonlocal ti
+            if rng_tapes is None:
+                return None
+            ti += 1
+            return rng_tapes[ti - 1].to(dev).contiguous()
+
         for i, t in enumerate(tv):
-            cur_bias.copy_(table[i]); cur_scal.copy_(scal[i]); cur_off.fill_(t)
-            last, draw = (i == S - 1), (t > 1)
-            if use_graph and draw and not last:
-                if not warmed:
-                    step(True)                                   # eager warm-up: fills the weight-repack cache
-                    warmed = True
+            cur_bias.copy_(table[i]); cur_scal.copy_(scal[i])
+            if masked:
+                cur_kmix.copy_(kmix[i])
+            if resample > 1:
+                cur_rmix.copy_(rmix[i])
+            for j in range(resample):
+                cur_off.fill_(ops.philox_offset_word(t, j, ops.PHILOX_POSTERIOR) if edit else t)
+                if masked:
+                    cur_koff.fill_(ops.philox_offset_word(t, j, ops.PHILOX_KNOWN))
+                last, draw = (i == S - 1 and j == resample - 1), (t > 1)
+                x_in = None
+                if use_graph and draw and not last:
+                    if not warmed:
+                        masked_step() if masked else step(True)      # eager warm-up: fills the weight-repack cache
+                        warmed = True
+                    else:
+                        if graph is None:                            # capture the fixed-shape step once (hipGraph)
+                            graph = ops.capture_graph(masked_step if masked else (lambda: step(True)))
+                        graph.replay()
                 else:
-                    if graph is None:                            # capture the fixed-shape step once (hipGraph)
-                        graph = ops.capture_graph(lambda: step(True))
-                    graph.replay()
-            else:
-                E = None
-                if rng_tapes is not None and draw:
-                    E = rng_tapes[ti].to(dev).contiguous(); ti += 1
-                step(draw, E, want_probs=last or trace is not None)
-            if trace is not None:
-                trace.append(dict(t=t, labels=lab.clone().view(labels.shape), probs=probs.clone()))
+                    if masked:
+                        blend(tape())
+                        if trace is not None:
+                            x_in = lab.clone().view(labels.shape)
+                    step(draw, tape() if draw else None, want_probs=last or trace is not None)
+                if trace is not None:
+                    entry = dict(t=t, j=j, labels=lab.clone().view(labels.shape), probs=probs.clone())
+                    if masked:
+                        entry["x_in"] = x_in
+                    trace.append(entry)
+                if j < resample - 1:                                 # between two repetitions, outside the captured step
+                    cur_roff.fill_(ops.philox_offset_word(t, j, ops.PHILOX_RENOISE))
+                    renoise(tape())
+        if masked:
+            # the labels are discrete and kept anatomy must come back unchanged: one more blend with operands (1, 0), whose race has one
+            # non-zero class, and the returned posterior rows of the kept voxels are the one-hot of known (an index select: plumbing)
+            cur_kmix.copy_(torch.tensor([1.0, 0.0], dtype=torch.float32, device=dev))
+            blend(final=True)
+            probs = torch.where(keep_f.view(-1, 1) != 0, torch.nn.functional.one_hot(known_f.long(), K).to(probs.dtype), probs)
         return lab.view(labels.shape), probs
 
 

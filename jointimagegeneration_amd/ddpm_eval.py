@@ -15,6 +15,12 @@ the Hungarian-matched IoU.  Without these options the run writes exactly what it
 Objectives (trainer.py:298-327; losses.py): `--gt DIR --loss-t T1,T2,...` adds a `loss` block to metrics.json: per listed step t the
 KL, cross-entropy and their sum of the ground-truth volumes noised to t, averaged over the volumes.  The noise of volume v at step t
 comes from the Philox key (1024 + v) + (t << 32), so reruns agree and a volume's terms do not depend on the rank that scored it.
+
+Mask editing (DenoisingModel.sample_labels known / keep / resample): `--known DIR` holds `known_{vid:04d}.nii.gz` label volumes of the
+run's size, and exactly one of `--keep-classes a,b,c` (keep the voxels whose known label is listed) and `--keep-mask DIR`
+(`keep_{vid:04d}.nii.gz`, non-zero = keep) says which voxels come back unchanged; `--resample R` repeats every step R times.  With
+--samples S the S masks of a volume share one known / keep pair.  metrics.json (written with or without --gt) then holds an `edit`
+block: per volume the kept fraction and the count of kept voxels that differ from known, which is 0.
 """
 from __future__ import annotations
 
@@ -33,7 +39,7 @@ from . import distributed as ggd
 from . import metrics
 from .ccdm import build_model
 from .encoder import build_feature_cond_encoder
-from .io import load_checkpoint, write_nifti
+from .io import load_checkpoint, read_nifti, write_nifti
 from .losses import ccdm_step_losses
 from .synth import randomize_parameters
 
@@ -73,6 +79,36 @@ def loss_key(vid: int, t: int) -> int:
     return (1024 + vid) + (t << 32)
 
 
+def load_edit(args, vids, size, K: int):
+    """{vid: (known int32 [D, H, W], keep uint8 [D, H, W])} of --known with --keep-classes or --keep-mask; None without --known.
+    Host-side: a bad option or volume ends the run before any sampling."""
+    if args.known is None:
+        if args.keep_classes is not None or args.keep_mask is not None or args.resample != 1:
+            raise ValueError("--keep-classes / --keep-mask / --resample edit a known mask: give --known DIR")
+        return None
+    if (args.keep_classes is None) == (args.keep_mask is None):
+        raise ValueError("--known needs exactly one of --keep-classes a,b,c and --keep-mask DIR")
+    classes = None
+    if args.keep_classes is not None:
+        classes = [int(v) for v in args.keep_classes.split(",") if v.strip()]
+        if not classes or any(c < 0 or c >= K for c in classes):
+            raise ValueError(f"--keep-classes {args.keep_classes}: classes are 0..{K - 1}")
+    known = metrics.load_gt(args.known, vids, size, K, prefix="known")
+    out = {}
+    for vid in vids:
+        if classes is not None:
+            keep = np.isin(known[vid], classes)
+        else:
+            path = os.path.join(args.keep_mask, f"keep_{vid:04d}.nii.gz")
+            if not os.path.exists(path):
+                raise FileNotFoundError(f"{path}: no keep mask for volume {vid}")
+            keep = read_nifti(path) != 0
+            if tuple(keep.shape) != tuple(size):
+                raise ValueError(f"{path}: shape {tuple(keep.shape)}, the run samples {tuple(size)}")
+        out[vid] = (known[vid], np.ascontiguousarray(keep.astype(np.uint8)))
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("params_file", nargs="?", default="params_eval.yml")
@@ -86,7 +122,13 @@ def main(argv=None):
     ap.add_argument("--gt", default=None, help="directory of gt_{vid:04d}.nii.gz label volumes: score the run into metrics.json")
     ap.add_argument("--ignore-class", type=int, default=None, help="class left out of Dice (default: yaml ignore_class, else 0)")
     ap.add_argument("--loss-t", default=None, help="comma-separated steps t (1..time_steps): KL / CE / loss of the --gt volumes noised to t, into metrics.json")
+    ap.add_argument("--known", default=None, help="directory of known_{vid:04d}.nii.gz label volumes: mask editing, with one of the two keep options")
+    ap.add_argument("--keep-classes", default=None, help="comma-separated classes: keep the voxels whose known label is listed")
+    ap.add_argument("--keep-mask", default=None, help="directory of keep_{vid:04d}.nii.gz volumes, non-zero = keep the known label")
+    ap.add_argument("--resample", type=int, default=1, help="repetitions of every step of an edited chain (re-noised one step in between)")
     args = ap.parse_args(argv)
+    if args.resample < 1:
+        raise ValueError(f"--resample {args.resample}: at least one repetition per step")
     if args.samples < 1:
         raise ValueError(f"--samples {args.samples}: at least one mask per volume")
     loss_ts = [int(v) for v in args.loss_t.split(",") if v.strip()] if args.loss_t else []
@@ -103,6 +145,7 @@ def main(argv=None):
     S = args.samples
     ignore = args.ignore_class if args.ignore_class is not None else params.get("ignore_class", 0)      # ruijin's get_ignore_class: 0
     gts = metrics.load_gt(args.gt, vids, size, K) if args.gt else None           # a bad ground truth ends the run before any sampling
+    edits = load_edit(args, vids, size, K)
     if any(t < 1 or t > params["time_steps"] for t in loss_ts):
         raise ValueError(f"--loss-t {args.loss_t}: steps are 1..{params['time_steps']}")
     assert torch.cuda.is_available(), "the GuideGen engine needs an MI355X (no CPU fallback)"
@@ -146,21 +189,30 @@ def main(argv=None):
     L = len(loss_ts)
     loss_at = K * K + 4 * n_vol                                                       # then 3 fp64 (kl, ce, loss) per (volume, listed t)
     score_buf = torch.zeros(loss_at + 3 * L * n_vol, dtype=torch.int64, device=dev) if gts is not None else None
+    edit_buf = torch.zeros((n_vol, 2), dtype=torch.int64, device=dev) if edits is not None else None   # (kept voxels, kept voxels != known)
     for vid in vids:                                                                  # volumes are independent units
+        ed = {}
+        if edits is not None:                                                         # the S masks of a volume share one known / keep pair
+            known, keep = (torch.from_numpy(a).to(dev)[None].expand((S,) + size).contiguous() for a in edits[vid])
+            ed = dict(known=known, keep=keep, resample=args.resample)
         if S == 1:
             g = torch.Generator(device=dev).manual_seed(1024 + vid)
             x_T = torch.randint(0, K, (1,) + size, generator=g, device=dev, dtype=torch.int32)   # uniform categorical x_T
             model.philox_seed = 1024 + vid
-            labels, _ = model.sample_labels(x_T, torch.zeros((1, 1) + size, device=dev), init_t)
+            labels, _ = model.sample_labels(x_T, torch.zeros((1, 1) + size, device=dev), init_t, **ed)
             write_nifti(os.path.join(out_dir, f"pred_{vid:04d}.nii.gz"), labels[0].to(torch.uint8).cpu().numpy())
         else:                                                                         # the S masks of a volume: one batch, S independent chains
             seeds = [1024 + vid * S + j for j in range(S)]
             x_T = torch.cat([torch.randint(0, K, (1,) + size, generator=torch.Generator(device=dev).manual_seed(sd), device=dev, dtype=torch.int32)
                              for sd in seeds])
-            labels, _ = model.sample_labels(x_T, torch.zeros((S, 1) + size, device=dev), init_t, philox_seeds=seeds)
+            labels, _ = model.sample_labels(x_T, torch.zeros((S, 1) + size, device=dev), init_t, philox_seeds=seeds, **ed)
             host = labels.to(torch.uint8).cpu().numpy()
             for j in range(S):
                 write_nifti(os.path.join(out_dir, f"pred_{vid:04d}_s{j:02d}.nii.gz"), host[j])
+        if edits is not None:
+            kept = ed["keep"] != 0
+            edit_buf[vid, 0] = kept[0].sum()
+            edit_buf[vid, 1] = (kept & (labels != ed["known"])).sum()
         if gts is not None:
             cm, scores = metrics.score_case(labels, torch.from_numpy(gts[vid]).to(dev), K)
             score_buf[:K * K] += cm.reshape(-1)
@@ -174,6 +226,16 @@ def main(argv=None):
                 score_buf[at:at + 3] = torch.stack([r["loss_kl"], r["loss_ce"], r["loss"]]).view(torch.int64)
     torch.cuda.synchronize()
     print(f"[rank {rank}] sampled {len(vids)} volume(s) of {size} in {time.time() - t0:.1f}s -> {out_dir}", file=sys.stderr)
+    edit_doc = None
+    if edit_buf is not None:
+        if torch.distributed.is_available() and torch.distributed.is_initialized():
+            torch.distributed.all_reduce(edit_buf)                                    # a volume belongs to one rank, the others hold zeros
+        voxels = int(np.prod(size))
+        edit_doc = dict(resample=args.resample, keep_classes=args.keep_classes, keep_mask=args.keep_mask,
+                        volumes=[dict(id=v, kept_fraction=k / voxels, kept_differing=d) for v, (k, d) in enumerate(edit_buf.cpu().tolist())])
+        if rank == 0 and score_buf is None:
+            with open(os.path.join(out_dir, "metrics.json"), "w") as f:
+                json.dump(dict(edit=edit_doc), f, indent=1)
     if score_buf is not None:
         if torch.distributed.is_available() and torch.distributed.is_initialized():
             torch.distributed.all_reduce(score_buf)                                   # once, after the sampling loop: off the data path
@@ -188,6 +250,8 @@ def main(argv=None):
                 mean = lv.sum(0) / n_vol                                              # volume order: the same bits on every run
                 doc["loss"] = [dict(t=t, loss_kl=float(mean[j, 0]), loss_ce=float(mean[j, 1]), loss=float(mean[j, 2]), volumes=n_vol)
                                for j, t in enumerate(loss_ts)]
+            if edit_doc is not None:
+                doc["edit"] = edit_doc
             with open(os.path.join(out_dir, "metrics.json"), "w") as f:
                 json.dump(doc, f, indent=1)
             print(f"[rank 0] {metrics.summary_line(doc)} -> {os.path.join(out_dir, 'metrics.json')}", file=sys.stderr)

@@ -99,14 +99,14 @@ def hungarian_iou(labels_0: torch.Tensor, labels_1: torch.Tensor, K: int) -> flo
 
 
 # ------------------------------------------------------------------------------------------------ what the entry points report
-def load_gt(gt_dir: str, vids, size, K: int) -> Dict[int, np.ndarray]:
+def load_gt(gt_dir: str, vids, size, K: int, prefix: str = "gt") -> Dict[int, np.ndarray]:
     """gt_{vid:04d}.nii.gz of every volume id -> int32 [D, H, W].  A volume of another shape, or with a label outside [0, K), is a
-    ValueError (host-side: nothing has been sampled yet)."""
+    ValueError (host-side: nothing has been sampled yet).  prefix: the file stem of another set of label volumes ("known")."""
     out = {}
     for vid in vids:
-        path = os.path.join(gt_dir, f"gt_{vid:04d}.nii.gz")
+        path = os.path.join(gt_dir, f"{prefix}_{vid:04d}.nii.gz")
         if not os.path.exists(path):
-            raise FileNotFoundError(f"{path}: no ground truth for volume {vid}")
+            raise FileNotFoundError(f"{path}: no {'ground truth' if prefix == 'gt' else prefix + ' label volume'} for volume {vid}")
         arr = read_nifti(path)
         if size is not None and tuple(arr.shape) != tuple(size):
             raise ValueError(f"{path}: shape {tuple(arr.shape)}, the run samples {tuple(size)}")

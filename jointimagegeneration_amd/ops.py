@@ -1341,6 +1341,49 @@ def ccdm_q_sample(x0: torch.Tensor, mix: torch.Tensor, K: int, *, E: Optional[to
     return labels_out
 
 
+PHILOX_POSTERIOR, PHILOX_KNOWN, PHILOX_RENOISE = 0, 1, 2      # `purpose` of a CCDM chain draw (philox_offset_word)
+
+
+def philox_offset_word(t: int, j: int = 0, purpose: int = PHILOX_POSTERIOR) -> int:
+    """The 32-bit Philox offset word of a CCDM chain draw: t | (j << 16) | (purpose << 28), with t the 1-based timestep (< 2^16), j the
+    resampling repetition (< 256) and purpose 0 the posterior draw, 1 the known-region noising, 2 the resample re-noise.  At j = 0,
+    purpose 0 it is t, the offset of a chain without a mask."""
+    if not 0 <= int(t) < (1 << 16):
+        raise ValueError(f"philox_offset_word: t={t} does not fit the 16 bits of the offset word (time_steps must be < 65536)")
+    if not 0 <= int(j) < 256:
+        raise ValueError(f"philox_offset_word: repetition j={j} outside 0..255 (resample must be <= 256)")
+    if purpose not in (PHILOX_POSTERIOR, PHILOX_KNOWN, PHILOX_RENOISE):
+        raise ValueError(f"philox_offset_word: purpose={purpose} is none of 0 (posterior), 1 (known), 2 (re-noise)")
+    return int(t) | (int(j) << 16) | (int(purpose) << 28)
+
+
+def ccdm_inpaint_blend(labels: torch.Tensor, known: torch.Tensor, keep: torch.Tensor, mix: torch.Tensor, K: int, *,
+                       E: Optional[torch.Tensor] = None, philox_seed: int = 0, philox_seeds: Optional[torch.Tensor] = None,
+                       philox_offset: Optional[torch.Tensor] = None, onehot_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Mask editing of the CCDM chain state (gg_ccdm_inpaint_blend): labels int32 [M] of N equal samples, in place; rows with keep != 0
+    (uint8 [M]) take a draw of q(x_t | x_0 = known) with mix fp32 [N, 2] = (cumalphas[t - 1], 1 - cumalphas[t - 1]), every other row is
+    left as it is.  known int32 [M] may be `labels` itself.  E: fp32 [M, K] exponential tape; otherwise Philox with philox_seeds (device
+    int64 [N], one key per sample) or the single key philox_seed, at philox_offset (device int64 [1]).  onehot_out: bf16 rows
+    [M, stride], channels [0, K) of the kept rows written.  Returns labels."""
+    lib = _lib.load()
+    require_gpu(labels, "ccdm_inpaint_blend")
+    M, N = labels.numel(), mix.numel() // 2
+    if N < 1 or M % N:
+        raise ValueError(f"ccdm_inpaint_blend: {M} rows do not split into {N} samples")
+    _i32_dev(labels, M, "ccdm_inpaint_blend: labels"); _i32_dev(known, M, "ccdm_inpaint_blend: known"); _f32_dev(mix, 2 * N, "ccdm_inpaint_blend: mix")
+    if keep.dtype != torch.uint8 or not keep.is_cuda or not keep.is_contiguous() or keep.numel() != M:
+        raise ValueError(f"ccdm_inpaint_blend: keep must be a contiguous device uint8 tensor of {M} elements, got {keep.dtype} {tuple(keep.shape)} on {keep.device}")
+    if E is not None:
+        _f32_dev(E, M * K, "ccdm_inpaint_blend: E")
+    if onehot_out is not None and (onehot_out.dtype != torch.bfloat16 or not onehot_out.is_contiguous() or onehot_out.numel() != M * onehot_out.shape[-1]):
+        raise ValueError(f"ccdm_inpaint_blend: onehot_out must be contiguous bf16 rows [{M}, stride], got {onehot_out.dtype} {tuple(onehot_out.shape)}")
+    check(lib.gg_ccdm_inpaint_blend(labels.data_ptr(), known.data_ptr(), keep.data_ptr(), mix.data_ptr(), M // N, K, _ptr(E),
+                                    int(philox_seed) & ((1 << 64) - 1), _seeds_ptr(philox_seeds, N) if philox_seeds is not None else None,
+                                    _ptr(philox_offset), M, _ptr(onehot_out), onehot_out.shape[-1] if onehot_out is not None else 0,
+                                    _stream()), "gg_ccdm_inpaint_blend")
+    return labels
+
+
 def ccdm_step_loss(logits: torch.Tensor, xt: torch.Tensor, x0: torch.Tensor, scalars: torch.Tensor, class_weights: torch.Tensor, K: int, *,
                    out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
     """fp64 [N, 2] per-sample sums of (class-weighted KL, CE) of trainer.py:305-320 (gg_ccdm_step_loss): logits fp32 channels-last

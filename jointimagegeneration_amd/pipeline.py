@@ -110,27 +110,31 @@ class GuideGenPipeline:
 
     # ---- stage 1 ------------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def sample_mask(self, N: int, size: Tuple[int, int, int], seed: int, init_t: Optional[int] = None) -> torch.Tensor:
-        """x_T ~ uniform categorical one-hot (evaluator.py:135-136), condition = zeros; returns int32 labels [N,D,H,W]."""
+    def sample_mask(self, N: int, size: Tuple[int, int, int], seed: int, init_t: Optional[int] = None, known: Optional[torch.Tensor] = None,
+                    keep: Optional[torch.Tensor] = None, resample: int = 1) -> torch.Tensor:
+        """x_T ~ uniform categorical one-hot (evaluator.py:135-136), condition = zeros; returns int32 labels [N,D,H,W].
+        known / keep / resample: mask editing, as `DenoisingModel.sample_labels` takes them ([N, D, H, W])."""
         dev = self.ccdm.diffusion.betas.device
         K = self.ccdm.diffusion.num_classes
         g = torch.Generator(device=dev).manual_seed(seed)
         x_T = torch.randint(0, K, (N,) + tuple(size), generator=g, device=dev, dtype=torch.int32)
         self.ccdm.philox_seed = seed
         cond = torch.zeros((N, 1) + tuple(size), device=dev)
-        labels, _ = self.ccdm.sample_labels(x_T, cond, init_t)
+        labels, _ = self.ccdm.sample_labels(x_T, cond, init_t, known=known, keep=keep, resample=resample)
         return labels
 
     @torch.no_grad()
-    def sample_masks(self, seeds: Sequence[int], size: Tuple[int, int, int], init_t: Optional[int] = None) -> torch.Tensor:
+    def sample_masks(self, seeds: Sequence[int], size: Tuple[int, int, int], init_t: Optional[int] = None,
+                     known: Optional[torch.Tensor] = None, keep: Optional[torch.Tensor] = None, resample: int = 1) -> torch.Tensor:
         """Independent volumes in one batch: volume i is sample_mask(1, size, seeds[i]) -- its own x_T generator and its own Philox key
-        (per-sample key of the reverse step), so that it depends on nothing its neighbours hold.  Returns int32 labels [B, D, H, W]."""
+        (per-sample key of the reverse step), so that it depends on nothing its neighbours hold.  Returns int32 labels [B, D, H, W].
+        known / keep / resample: mask editing, as `DenoisingModel.sample_labels` takes them ([B, D, H, W])."""
         dev = self.ccdm.diffusion.betas.device
         K = self.ccdm.diffusion.num_classes
         x_T = torch.cat([torch.randint(0, K, (1,) + tuple(size), generator=torch.Generator(device=dev).manual_seed(int(s)), device=dev,
                                        dtype=torch.int32) for s in seeds])
         cond = torch.zeros((len(seeds), 1) + tuple(size), device=dev)
-        labels, _ = self.ccdm.sample_labels(x_T, cond, init_t, philox_seeds=[int(s) for s in seeds])
+        labels, _ = self.ccdm.sample_labels(x_T, cond, init_t, philox_seeds=[int(s) for s in seeds], known=known, keep=keep, resample=resample)
         return labels
 
     def _slice_engine(self, N: int, hw: int, dev, st) -> Dict:
