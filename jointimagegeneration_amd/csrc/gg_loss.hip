@@ -2,7 +2,7 @@
 //   gg_q_sample_rows    q_sample with per-sample scalars (ldm/models/diffusion/ddpm.py:275-278), into fp32 NC(D)HW and / or the UNet input
 //   gg_loss_rows        per-sample mean of (target - pred)^2, |target - pred| (ddpm.py:280-293,1040) or the prior-KL integrand (ddpm.py:1011-1023)
 //   gg_ccdm_q_sample    q_xt_given_x0(x0, t).sample() on labels (ccdm/ddpm/models/diffusion_denoising.py:82-89, one_hot_categorical.py)
-//   gg_ccdm_inpaint_blend  the same draw around known labels, written into the reverse chain's state where keep != 0 (mask editing)
+//   gg_ccdm_inpaint_blend  the same kernel around known labels, written into the reverse chain's state where keep != 0 (mask editing)
 //   gg_ccdm_step_loss   per-sample sums of the weighted KL and the cross-entropy of ccdm/ddpm/trainer.py:305-327
 // Reductions use NO floating-point atomics and are two-stage: every fp32 term is added into an fp64 per-thread sum in a fixed (grid-stride)
 // order, the 256 sums of a workgroup are combined by a fixed shuffle tree and a fixed loop over its 4 waves, one fp64 partial per workgroup
@@ -72,92 +72,28 @@ __global__ __launch_bounds__(LS_THREADS) void loss_rows_kernel(const float *__re
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// categorical forward noising, one voxel per thread
-// ------------------------------------------------------------------------------------------------------------
-template <int KMAX>
-__global__ __launch_bounds__(LS_THREADS) void ccdm_q_sample_kernel(const int *__restrict__ x0, const float *__restrict__ mix,
-                                                                   long long rows_per_sample, int K, const float *__restrict__ E,
-                                                                   const unsigned long long *__restrict__ seeds,
-                                                                   const long long *__restrict__ offset_dev, long long M,
-                                                                   int *__restrict__ labels_out, bf16_t *__restrict__ onehot_out, int onehot_stride)
-{
-#pragma clang fp contract(off)
-    const long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (m >= M) return;
-    const long long n = m / rows_per_sample;
-    const long long row = m - n * rows_per_sample;
-    const float ca = mix[2 * n];
-    const float v = mix[2 * n + 1] / (float)K;
-    const float pd = ca * 1.0f + v, po = ca * 0.0f + v;
-    const int lab = x0[m];
-    float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < KMAX; ++c) if (c < K) s = s + (c == lab ? pd : po);
-    float Ev[KMAX];
-    if (E) {
-#pragma unroll
-        for (int c = 0; c < KMAX; ++c) Ev[c] = (c < K) ? E[m * K + c] : 1.f;
-    } else {                                   // the draw of gg_ccdm_posterior_sample_seeds (gg_posterior.h): key seeds[n], the row within the sample
-        ccdm_draw_row<KMAX>(Ev, seeds[n], row, offset_dev ? offset_dev[0] : 0);
-    }
-    int best = 0;
-    float bestv = -1.0f;
-#pragma unroll
-    for (int c = 0; c < KMAX; ++c) if (c < K) {
-        const float pn = (c == lab ? pd : po) / s;
-        const float r = pn / Ev[c];
-        if (r > bestv) { bestv = r; best = c; }
-    }
-    labels_out[m] = best;
-    if (onehot_out) ccdm_onehot_row<KMAX, 0>(onehot_out + m * onehot_stride, best, K);
-}
-
-// ------------------------------------------------------------------------------------------------------------
-// mask editing: the rows with keep != 0 take a draw of q(x_t | x_0 = known), expression for expression ccdm_q_sample_kernel's; every other
-// row returns before it writes anything.  One row per thread, and a row's known label is read before its label is written, so known may
-// be the labels buffer itself.  PS: the key rule of ccdm_posterior_kernel (0: key seed, counter m; 1: key seeds[n], row within the sample).
+// categorical forward noising, one voxel per thread: labels[m] takes a draw of q(x_t | x_0 = known[m]).  keep: only the rows with
+// keep[m] != 0 are drawn (mask editing), every other row returns before it writes anything; nullptr: every row.  A row's known label is read
+// before its label is written, so known may be the labels buffer itself (no __restrict__ on either).  PS: ccdm_key_row's.
 // ------------------------------------------------------------------------------------------------------------
 template <int KMAX, int PS>
-__global__ __launch_bounds__(LS_THREADS) void ccdm_inpaint_blend_kernel(int *__restrict__ labels, const int *known,
-                                                                        const unsigned char *__restrict__ keep, const float *__restrict__ mix,
-                                                                        long long rows_per_sample, int K, const float *__restrict__ E,
-                                                                        uint64_t seed, const unsigned long long *__restrict__ seeds,
-                                                                        const long long *__restrict__ offset_dev, long long M,
-                                                                        bf16_t *__restrict__ onehot_out, int onehot_stride)
+__global__ __launch_bounds__(LS_THREADS) void ccdm_q_sample_kernel(int *labels, const int *known, const unsigned char *__restrict__ keep,
+                                                                   const float *__restrict__ mix, long long rows_per_sample, int K,
+                                                                   const float *__restrict__ E, uint64_t seed,
+                                                                   const unsigned long long *__restrict__ seeds,
+                                                                   const long long *__restrict__ offset_dev, long long M,
+                                                                   bf16_t *__restrict__ onehot_out, int onehot_stride)
 {
-#pragma clang fp contract(off)
     const long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (m >= M) return;
-    if (keep[m] == 0) return;
+    if (keep && keep[m] == 0) return;
     const long long n = m / rows_per_sample;
-    const float ca = mix[2 * n];
-    const float v = mix[2 * n + 1] / (float)K;
-    const float pd = ca * 1.0f + v, po = ca * 0.0f + v;
-    const int lab = known[m];
-    float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < KMAX; ++c) if (c < K) s = s + (c == lab ? pd : po);
+    uint64_t key = 0;
+    long long row = 0;
+    if (!E) ccdm_key_row<PS>(seed, seeds, rows_per_sample, m, key, row);      // with a tape there may be no keys to load
     float Ev[KMAX];
-    if (E) {
-#pragma unroll
-        for (int c = 0; c < KMAX; ++c) Ev[c] = (c < K) ? E[m * K + c] : 1.f;
-    } else {
-        uint64_t key = seed;
-        long long row = m;
-        if constexpr (PS) {
-            key = seeds[n];
-            row = m - n * rows_per_sample;
-        }
-        ccdm_draw_row<KMAX>(Ev, key, row, offset_dev ? offset_dev[0] : 0);
-    }
-    int best = 0;
-    float bestv = -1.0f;
-#pragma unroll
-    for (int c = 0; c < KMAX; ++c) if (c < K) {
-        const float pn = (c == lab ? pd : po) / s;
-        const float r = pn / Ev[c];
-        if (r > bestv) { bestv = r; best = c; }
-    }
+    ccdm_exp_row<KMAX>(Ev, E ? E + m * K : nullptr, K, key, row, (!E && offset_dev) ? offset_dev[0] : 0);
+    const int best = ccdm_q_sample_voxel<KMAX>(known[m], mix[2 * n], mix[2 * n + 1], K, Ev);
     labels[m] = best;
     if (onehot_out) ccdm_onehot_row<KMAX, 0>(onehot_out + m * onehot_stride, best, K);
 }
@@ -266,15 +202,11 @@ extern "C" int gg_ccdm_q_sample(const int32_t *x0, const float *mix_dev, int64_t
     if (!x0 || !mix_dev || !labels_out) GG_FAIL(GG_ERR_BAD_SHAPE, "ccdm_q_sample: null pointer");
     if (!E && !philox_seeds_dev) GG_FAIL(GG_ERR_BAD_SHAPE, "ccdm_q_sample: neither a tape nor Philox keys");
     if (K < 2 || K > 16) GG_FAIL(GG_ERR_UNSUPPORTED, "ccdm_q_sample: K=%d outside [2, 16]", K);
-    if (M < 1 || rows_per_sample < 1 || M % rows_per_sample)
-        GG_FAIL(GG_ERR_BAD_SHAPE, "ccdm_q_sample: M=%lld is not a multiple of rows_per_sample=%lld", (long long)M, (long long)rows_per_sample);
-    if (onehot_out && onehot_stride < K) GG_FAIL(GG_ERR_BAD_SHAPE, "ccdm_q_sample: onehot_stride < K");
-    if (onehot_out && ((onehot_stride & 1) || ((uintptr_t)onehot_out & 3))) GG_FAIL(GG_ERR_BAD_SHAPE, "ccdm_q_sample: onehot rows must be 4-byte aligned (even stride)");
-    const long long blocks = (M + LS_THREADS - 1) / LS_THREADS;
-    if (blocks > 0x7fffffffLL) GG_FAIL(GG_ERR_UNSUPPORTED, "ccdm_q_sample: M=%lld voxels exceed the grid", (long long)M);
-    hipLaunchKernelGGL(ccdm_q_sample_kernel<16>, dim3((unsigned)blocks), dim3(LS_THREADS), 0, (hipStream_t)stream_, x0, mix_dev,
-                       (long long)rows_per_sample, K, E, (const unsigned long long *)philox_seeds_dev, (const long long *)philox_offset_dev,
-                       (long long)M, labels_out, (bf16_t *)onehot_out, onehot_stride);
+    if (int rc = ccdm_check_rows("ccdm_q_sample", M, 1, rows_per_sample, K, onehot_out, onehot_stride)) return rc;
+    hipLaunchKernelGGL((ccdm_q_sample_kernel<16, 1>), dim3((unsigned)((M + LS_THREADS - 1) / LS_THREADS)), dim3(LS_THREADS), 0, (hipStream_t)stream_,
+                       labels_out, x0, (const unsigned char *)nullptr, mix_dev, (long long)rows_per_sample, K, E, (uint64_t)0,
+                       (const unsigned long long *)philox_seeds_dev, (const long long *)philox_offset_dev, (long long)M, (bf16_t *)onehot_out,
+                       onehot_stride);
     GG_CHECK_LAUNCH();
     return GG_OK;
 }
@@ -285,14 +217,10 @@ extern "C" int gg_ccdm_inpaint_blend(int32_t *labels, const int32_t *known, cons
 {
     if (!labels || !known || !keep || !mix_dev) GG_FAIL(GG_ERR_BAD_SHAPE, "ccdm_inpaint_blend: null pointer");
     if (K < 2 || K > 32) GG_FAIL(GG_ERR_BAD_SHAPE, "ccdm_inpaint_blend: K=%d outside [2, 32]", K);
-    if (M < 1 || rows_per_sample < 1 || M % rows_per_sample)
-        GG_FAIL(GG_ERR_BAD_SHAPE, "ccdm_inpaint_blend: M=%lld is not a multiple of rows_per_sample=%lld", (long long)M, (long long)rows_per_sample);
-    if (onehot_out && onehot_stride < K) GG_FAIL(GG_ERR_BAD_SHAPE, "ccdm_inpaint_blend: onehot_stride < K");
-    if (onehot_out && ((onehot_stride & 1) || ((uintptr_t)onehot_out & 3))) GG_FAIL(GG_ERR_BAD_SHAPE, "ccdm_inpaint_blend: onehot rows must be 4-byte aligned (even stride)");
+    if (int rc = ccdm_check_rows("ccdm_inpaint_blend", M, 1, rows_per_sample, K, onehot_out, onehot_stride)) return rc;
     const long long blocks = (M + LS_THREADS - 1) / LS_THREADS;
-    if (blocks > 0x7fffffffLL) GG_FAIL(GG_ERR_UNSUPPORTED, "ccdm_inpaint_blend: M=%lld voxels exceed the grid", (long long)M);
 #define IB_CASE(KMAX_, PS_)                                                                                                              \
-    hipLaunchKernelGGL((ccdm_inpaint_blend_kernel<KMAX_, PS_>), dim3((unsigned)blocks), dim3(LS_THREADS), 0, (hipStream_t)stream_, labels, \
+    hipLaunchKernelGGL((ccdm_q_sample_kernel<KMAX_, PS_>), dim3((unsigned)blocks), dim3(LS_THREADS), 0, (hipStream_t)stream_, labels,      \
                        known, keep, mix_dev, (long long)rows_per_sample, K, E, philox_seed,                                             \
                        (const unsigned long long *)philox_seeds_dev, (const long long *)philox_offset_dev, (long long)M,                \
                        (bf16_t *)onehot_out, onehot_stride)
@@ -310,8 +238,7 @@ extern "C" int gg_ccdm_step_loss(const float *logits, int32_t logits_stride, con
     if (!logits || !xt || !x0 || !scalars_dev || !class_weights || !out || !workspace) GG_FAIL(GG_ERR_BAD_SHAPE, "ccdm_step_loss: null pointer");
     if (K < 2 || K > 16) GG_FAIL(GG_ERR_UNSUPPORTED, "ccdm_step_loss: K=%d outside [2, 16]", K);
     if (logits_stride < K) GG_FAIL(GG_ERR_BAD_SHAPE, "ccdm_step_loss: logits_stride < K");
-    if (M < 1 || rows_per_sample < 1 || M % rows_per_sample)
-        GG_FAIL(GG_ERR_BAD_SHAPE, "ccdm_step_loss: M=%lld is not a multiple of rows_per_sample=%lld", (long long)M, (long long)rows_per_sample);
+    if (int rc = ccdm_check_rows("ccdm_step_loss", M, 1, rows_per_sample, K, nullptr, 0)) return rc;
     const long long N = M / rows_per_sample;
     if (N > 65535) GG_FAIL(GG_ERR_UNSUPPORTED, "ccdm_step_loss: %lld samples exceed the grid", N);
     const int blocks = ls_blocks(rows_per_sample);

@@ -6,8 +6,7 @@
 // ------------------------------------------------------------------------------------------------------------
 // CCDM reverse step, one voxel per thread (gg_posterior.h holds the arithmetic).
 // ------------------------------------------------------------------------------------------------------------
-// PS (per-sample key): row m belongs to sample n = m / rows_per_sample and draws with key seeds[n] and counter row m - n * rows_per_sample,
-// so that a sample's labels do not depend on its slot in the batch; PS == 0 is the single-key mode (key seed, counter m).
+// PS: ccdm_key_row's (0: the single key `seed`; 1: one key per sample of rows_per_sample rows).
 template <int KMAX, int KS = 0, int PS = 0>
 __global__ __launch_bounds__(256) void ccdm_posterior_kernel(const float *__restrict__ head, int head_stride, int is_logits,
                                                              const int *__restrict__ xt, const float *__restrict__ E,
@@ -24,13 +23,9 @@ __global__ __launch_bounds__(256) void ccdm_posterior_kernel(const float *__rest
 #pragma unroll
     for (int c = 0; c < KMAX; ++c) p0[c] = (c < (KS > 0 ? KS : K)) ? hp[c] : 0.f;
     const long long off = (draw && !E && offset_dev) ? offset_dev[0] : 0;
-    uint64_t key = seed;
-    long long row = m;
-    if constexpr (PS) {
-        const long long n = m / rows_per_sample;
-        key = seeds[n];
-        row = m - n * rows_per_sample;
-    }
+    uint64_t key;
+    long long row;
+    ccdm_key_row<PS>(seed, seeds, rows_per_sample, m, key, row);
     const int best = ccdm_posterior_voxel<KMAX, KS>(p0, is_logits, xt[m], scalars[0], scalars[1], K, row, draw, E ? E + m * K : nullptr, key, off,
                                                 probs_out ? probs_out + m * K : nullptr);
     labels_out[m] = best;
@@ -46,8 +41,8 @@ static int ccdm_posterior_launch(const float *head, int32_t head_stride, int32_t
     if (!head || !xt || !scalars_dev || !labels_out) GG_FAIL(GG_ERR_BAD_SHAPE, "ccdm_posterior_sample: null pointer");
     if (K < 2 || K > 32) GG_FAIL(GG_ERR_UNSUPPORTED, "ccdm_posterior_sample: K=%d outside [2, 32]", K);
     if (head_stride < K) GG_FAIL(GG_ERR_BAD_SHAPE, "ccdm_posterior_sample: head_stride < K");
-    if (onehot_out && onehot_stride < K) GG_FAIL(GG_ERR_BAD_SHAPE, "ccdm_posterior_sample: onehot_stride < K");
-    if (onehot_out && ((onehot_stride & 1) || ((uintptr_t)onehot_out & 3))) GG_FAIL(GG_ERR_BAD_SHAPE, "ccdm_posterior_sample: onehot rows must be 4-byte aligned (even stride)");
+    // no least row count: M <= 0 is an empty launch, below
+    if (int rc = ccdm_check_rows("ccdm_posterior_sample", M, INT64_MIN, PS ? rows_per_sample : 1, K, onehot_out, onehot_stride)) return rc;
     if (M <= 0) return GG_OK;
     const unsigned long long *sd = (const unsigned long long *)seeds;
     dim3 grid((unsigned)((M + 255) / 256));
@@ -82,14 +77,13 @@ extern "C" int gg_ccdm_posterior_sample_seeds(const float *head, int32_t head_st
                                               int32_t *labels_out, float *probs_out, void *onehot_out, int32_t onehot_stride, void *stream_)
 {
     if (!philox_seeds_dev) GG_FAIL(GG_ERR_BAD_SHAPE, "ccdm_posterior_sample_seeds: null seeds");
-    if (rows_per_sample <= 0 || M % rows_per_sample) GG_FAIL(GG_ERR_BAD_SHAPE, "ccdm_posterior_sample_seeds: M=%lld is not a multiple of rows_per_sample=%lld",
-                                                             (long long)M, (long long)rows_per_sample);
+    if (int rc = ccdm_check_rows("ccdm_posterior_sample_seeds", M, INT64_MIN, rows_per_sample, K, nullptr, 0)) return rc;
     return ccdm_posterior_launch<1>(head, head_stride, head_is_logits, xt, E, 0, philox_offset_dev, draw, scalars_dev, K, M, labels_out,
                                     probs_out, onehot_out, onehot_stride, philox_seeds_dev, rows_per_sample, (hipStream_t)stream_);
 }
 
-// The tape of a Philox run, one row per thread: the words and exponentials ccdm_draw_row gives row m under the key / counter rule of
-// ccdm_posterior_kernel (seeds != nullptr: the per-sample rule), or with bits_in the exponentials of those words instead.
+// The tape of a Philox run, one row per thread: the words and exponentials ccdm_draw_row gives row m under ccdm_key_row's rule (seeds !=
+// nullptr: the per-sample one), or with bits_in the exponentials of those words instead.
 template <int KMAX>
 __global__ __launch_bounds__(256) void ccdm_draw_tape_kernel(uint64_t seed, const unsigned long long *__restrict__ seeds, long long rows_per_sample,
                                                              const long long *__restrict__ offset_dev, long long M,
@@ -104,13 +98,10 @@ __global__ __launch_bounds__(256) void ccdm_draw_tape_kernel(uint64_t seed, cons
 #pragma unroll
         for (int c = 0; c < KMAX; ++c) { w[c] = bits_in[m * KMAX + c]; Ev[c] = ccdm_word_to_exp(w[c]); }
     } else {
-        uint64_t key = seed;
-        long long row = m;
-        if (seeds) {
-            const long long n = m / rows_per_sample;
-            key = seeds[n];
-            row = m - n * rows_per_sample;
-        }
+        uint64_t key;
+        long long row;
+        if (seeds) ccdm_key_row<1>(seed, seeds, rows_per_sample, m, key, row);
+        else ccdm_key_row<0>(seed, seeds, rows_per_sample, m, key, row);
         ccdm_draw_row<KMAX>(Ev, key, row, offset_dev ? offset_dev[0] : 0, w);
     }
 #pragma unroll

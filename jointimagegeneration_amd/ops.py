@@ -763,21 +763,35 @@ def ccdm_posterior_sample(head: torch.Tensor, head_is_logits: bool, xt: torch.Te
     M = head.numel() // stride
     if labels_out is None:
         labels_out = torch.empty(M, dtype=torch.int32, device=head.device)
+    oh_stride = _onehot_stride(onehot_out, M, "ccdm_posterior_sample")
     if philox_seeds is not None:
         Ns = philox_seeds.numel()
-        if Ns < 1 or M % Ns:
-            raise ValueError(f"ccdm_posterior_sample: {M} rows do not split into {Ns} samples")
+        rps = _rows_per_sample(M, Ns, "ccdm_posterior_sample")
         check(lib.gg_ccdm_posterior_sample_seeds(head.data_ptr(), stride, 1 if head_is_logits else 0, xt.data_ptr(), _ptr(E),
-                                                 _seeds_ptr(philox_seeds, Ns), M // Ns, _ptr(philox_offset), 1 if draw else 0,
+                                                 _seeds_ptr(philox_seeds, Ns), rps, _ptr(philox_offset), 1 if draw else 0,
                                                  scalars.data_ptr(), K, M, labels_out.data_ptr(), _ptr(probs_out), _ptr(onehot_out),
-                                                 onehot_out.shape[-1] if onehot_out is not None else 0, _stream()),
-              "gg_ccdm_posterior_sample_seeds")
+                                                 oh_stride, _stream()), "gg_ccdm_posterior_sample_seeds")
         return labels_out
     check(lib.gg_ccdm_posterior_sample(head.data_ptr(), stride, 1 if head_is_logits else 0, xt.data_ptr(), _ptr(E), philox_seed,
                                        _ptr(philox_offset), 1 if draw else 0, scalars.data_ptr(), K, M, labels_out.data_ptr(),
-                                       _ptr(probs_out), _ptr(onehot_out), onehot_out.shape[-1] if onehot_out is not None else 0,
-                                       _stream()), "gg_ccdm_posterior_sample")
+                                       _ptr(probs_out), _ptr(onehot_out), oh_stride, _stream()), "gg_ccdm_posterior_sample")
     return labels_out
+
+
+def _rows_per_sample(M: int, N: int, what: str) -> int:
+    """M rows split into N equal samples: the rows of one."""
+    if N < 1 or M % N:
+        raise ValueError(f"{what}: {M} rows do not split into {N} samples")
+    return M // N
+
+
+def _onehot_stride(onehot_out: Optional[torch.Tensor], M: int, what: str) -> int:
+    """onehot_out is contiguous bf16 rows [M, stride], or None: the stride (0)."""
+    if onehot_out is None:
+        return 0
+    if onehot_out.dtype != torch.bfloat16 or not onehot_out.is_contiguous() or onehot_out.numel() != M * onehot_out.shape[-1]:
+        raise ValueError(f"{what}: onehot_out must be contiguous bf16 rows [{M}, stride], got {onehot_out.dtype} {tuple(onehot_out.shape)}")
+    return int(onehot_out.shape[-1])
 
 
 def _seeds_ptr(seeds: torch.Tensor, N: int) -> int:
@@ -814,9 +828,7 @@ def ccdm_draw_tape(M: int, kmax: int, *, philox_seed: int = 0, philox_seeds: Opt
     Ns, rps = 0, 0
     if philox_seeds is not None and bits_in is None:
         Ns = philox_seeds.numel()
-        if Ns < 1 or M % Ns:
-            raise ValueError(f"ccdm_draw_tape: {M} rows do not split into {Ns} samples")
-        rps = M // Ns
+        rps = _rows_per_sample(M, Ns, "ccdm_draw_tape")
     bits = torch.empty((M, kmax), dtype=torch.int32, device=device) if want_bits else None
     E = torch.empty((M, kmax), dtype=torch.float32, device=device) if want_E else None
     check(lib.gg_ccdm_draw_tape(int(philox_seed) & ((1 << 64) - 1), _seeds_ptr(philox_seeds, Ns) if Ns else None, rps, _ptr(philox_offset),
@@ -1322,8 +1334,7 @@ def ccdm_q_sample(x0: torch.Tensor, mix: torch.Tensor, K: int, *, E: Optional[to
     lib = _lib.load()
     require_gpu(x0, "ccdm_q_sample")
     M, N = x0.numel(), mix.numel() // 2
-    if N < 1 or M % N:
-        raise ValueError(f"ccdm_q_sample: {M} rows do not split into {N} samples")
+    rps = _rows_per_sample(M, N, "ccdm_q_sample")
     _i32_dev(x0, M, "ccdm_q_sample: x0"); _f32_dev(mix, 2 * N, "ccdm_q_sample: mix")
     if (E is None) == (philox_seeds is None):
         raise ValueError("ccdm_q_sample: give either an exponential tape E or philox_seeds")
@@ -1332,12 +1343,10 @@ def ccdm_q_sample(x0: torch.Tensor, mix: torch.Tensor, K: int, *, E: Optional[to
     if labels_out is None:
         labels_out = torch.empty(M, dtype=torch.int32, device=x0.device)
     _i32_dev(labels_out, M, "ccdm_q_sample: labels_out")
-    if onehot_out is not None and (onehot_out.dtype != torch.bfloat16 or not onehot_out.is_contiguous() or onehot_out.numel() != M * onehot_out.shape[-1]):
-        raise ValueError(f"ccdm_q_sample: onehot_out must be contiguous bf16 rows [{M}, stride], got {onehot_out.dtype} {tuple(onehot_out.shape)}")
-    check(lib.gg_ccdm_q_sample(x0.data_ptr(), mix.data_ptr(), M // N, K, _ptr(E),
+    oh_stride = _onehot_stride(onehot_out, M, "ccdm_q_sample")
+    check(lib.gg_ccdm_q_sample(x0.data_ptr(), mix.data_ptr(), rps, K, _ptr(E),
                                _seeds_ptr(philox_seeds, N) if philox_seeds is not None else None, _ptr(philox_offset), M,
-                               labels_out.data_ptr(), _ptr(onehot_out), onehot_out.shape[-1] if onehot_out is not None else 0, _stream()),
-          "gg_ccdm_q_sample")
+                               labels_out.data_ptr(), _ptr(onehot_out), oh_stride, _stream()), "gg_ccdm_q_sample")
     return labels_out
 
 
@@ -1368,19 +1377,16 @@ def ccdm_inpaint_blend(labels: torch.Tensor, known: torch.Tensor, keep: torch.Te
     lib = _lib.load()
     require_gpu(labels, "ccdm_inpaint_blend")
     M, N = labels.numel(), mix.numel() // 2
-    if N < 1 or M % N:
-        raise ValueError(f"ccdm_inpaint_blend: {M} rows do not split into {N} samples")
+    rps = _rows_per_sample(M, N, "ccdm_inpaint_blend")
     _i32_dev(labels, M, "ccdm_inpaint_blend: labels"); _i32_dev(known, M, "ccdm_inpaint_blend: known"); _f32_dev(mix, 2 * N, "ccdm_inpaint_blend: mix")
     if keep.dtype != torch.uint8 or not keep.is_cuda or not keep.is_contiguous() or keep.numel() != M:
         raise ValueError(f"ccdm_inpaint_blend: keep must be a contiguous device uint8 tensor of {M} elements, got {keep.dtype} {tuple(keep.shape)} on {keep.device}")
     if E is not None:
         _f32_dev(E, M * K, "ccdm_inpaint_blend: E")
-    if onehot_out is not None and (onehot_out.dtype != torch.bfloat16 or not onehot_out.is_contiguous() or onehot_out.numel() != M * onehot_out.shape[-1]):
-        raise ValueError(f"ccdm_inpaint_blend: onehot_out must be contiguous bf16 rows [{M}, stride], got {onehot_out.dtype} {tuple(onehot_out.shape)}")
-    check(lib.gg_ccdm_inpaint_blend(labels.data_ptr(), known.data_ptr(), keep.data_ptr(), mix.data_ptr(), M // N, K, _ptr(E),
+    oh_stride = _onehot_stride(onehot_out, M, "ccdm_inpaint_blend")
+    check(lib.gg_ccdm_inpaint_blend(labels.data_ptr(), known.data_ptr(), keep.data_ptr(), mix.data_ptr(), rps, K, _ptr(E),
                                     int(philox_seed) & ((1 << 64) - 1), _seeds_ptr(philox_seeds, N) if philox_seeds is not None else None,
-                                    _ptr(philox_offset), M, _ptr(onehot_out), onehot_out.shape[-1] if onehot_out is not None else 0,
-                                    _stream()), "gg_ccdm_inpaint_blend")
+                                    _ptr(philox_offset), M, _ptr(onehot_out), oh_stride, _stream()), "gg_ccdm_inpaint_blend")
     return labels
 
 
@@ -1393,15 +1399,14 @@ def ccdm_step_loss(logits: torch.Tensor, xt: torch.Tensor, x0: torch.Tensor, sca
     stride = int(logits.shape[-1])
     M = logits.numel() // stride
     N = scalars.numel() // 2
-    if N < 1 or M % N:
-        raise ValueError(f"ccdm_step_loss: {M} rows do not split into {N} samples")
+    rps = _rows_per_sample(M, N, "ccdm_step_loss")
     _f32_dev(logits, M * stride, "ccdm_step_loss: logits"); _i32_dev(xt, M, "ccdm_step_loss: xt"); _i32_dev(x0, M, "ccdm_step_loss: x0")
     _f32_dev(scalars, 2 * N, "ccdm_step_loss: scalars"); _f32_dev(class_weights, K, "ccdm_step_loss: class_weights")
     if out is None:
         out = torch.empty((N, 2), dtype=torch.float64, device=logits.device)
     if workspace is None:
-        workspace = loss_workspace(N, M // N, logits.device)
-    check(lib.gg_ccdm_step_loss(logits.data_ptr(), stride, xt.data_ptr(), x0.data_ptr(), scalars.data_ptr(), M // N, class_weights.data_ptr(),
+        workspace = loss_workspace(N, rps, logits.device)
+    check(lib.gg_ccdm_step_loss(logits.data_ptr(), stride, xt.data_ptr(), x0.data_ptr(), scalars.data_ptr(), rps, class_weights.data_ptr(),
                                 K, M, out.data_ptr(), workspace.data_ptr(), workspace.numel() * 8, _stream()), "gg_ccdm_step_loss")
     return out
 

@@ -133,6 +133,39 @@ def test_blend_kernel_refusals(dev):
     torch.cuda.synchronize()
 
 
+@pytest.mark.parametrize("K", [2, 14, 16])
+@pytest.mark.parametrize("mode", ["tape", "philox"])
+def test_q_sample_equals_the_blend_with_every_row_kept(dev, K, mode):
+    """The invariant the edited chain relies on: gg_ccdm_q_sample is gg_ccdm_inpaint_blend with keep all-one.  2 samples of 389 rows: four
+    workgroups of 256 with a partial last one, and the sample boundary falls inside a workgroup and inside a wave."""
+    from jointimagegeneration_amd import ops
+    N, R, stride, sentinel = 2, 389, 32, 7.0
+    M = N * R
+    x0 = torch.randint(0, K, (M,), generator=gen(50 + K), dtype=torch.int32).to(dev)
+    mix = torch.tensor([[0.75, 0.25], [0.25, 0.75]], device=dev)
+    keep = torch.ones(M, dtype=torch.uint8, device=dev)
+    if mode == "tape":
+        draw = dict(E=torch.empty(M, K).exponential_(1, generator=gen(60 + K)).to(dev))
+    else:
+        draw = dict(philox_seeds=ops.philox_seed_tensor((1, 2 ** 63 + 5), dev),
+                    philox_offset=torch.tensor([ops.philox_offset_word(7, 3, ops.PHILOX_RENOISE)], dtype=torch.int64, device=dev))
+    oh_q = torch.full((M, stride), sentinel, dtype=torch.bfloat16, device=dev)
+    oh_b = oh_q.clone()
+    lab_q = ops.ccdm_q_sample(x0, mix, K, onehot_out=oh_q, **draw)
+    lab_b = torch.randint(0, K, (M,), generator=gen(70 + K), dtype=torch.int32).to(dev)
+    ops.ccdm_inpaint_blend(lab_b, x0, keep, mix, K, onehot_out=oh_b, **draw)
+    assert torch.equal(lab_q, lab_b)
+    assert torch.equal(oh_q[:, :K], oh_b[:, :K])
+    assert torch.equal(oh_q[:, :K].float(), torch.nn.functional.one_hot(lab_q.long(), K).float())
+    for oh in (oh_q, oh_b):                                           # channels >= K keep the sentinel they were filled with
+        assert torch.equal(oh[:, K:], torch.full((M, stride - K), sentinel, dtype=torch.bfloat16, device=dev))
+    assert not torch.equal(lab_q, x0) and int(lab_q.min()) >= 0 and int(lab_q.max()) < K
+    # the re-noise step's call: labels_out is x0 itself
+    buf = x0.clone()
+    assert ops.ccdm_q_sample(buf, mix, K, labels_out=buf, **draw).data_ptr() == buf.data_ptr()
+    assert torch.equal(buf, lab_q)
+
+
 # ------------------------------------------------------------------------------------------------ 2. Philox mode equals tape mode
 @pytest.mark.parametrize("K", [14, 17])
 @pytest.mark.parametrize("tjp", [(7, 0, 1), (7, 3, 2)])
