@@ -502,6 +502,28 @@ int gg_mask_to_cond_slices(const int32_t *labels, int32_t N, int32_t Dm, int32_t
 int gg_minmax_normalise_scatter(const float *src, int32_t N, int64_t n_per_sample, float *workspace2n, const int32_t *schedule_dev,
                                 int32_t iterations, int32_t *iter_dev, int32_t advance, int32_t depth, float *volume, void *stream);
 
+/* CT editing in the batched slice loop: the schedule, the counter and the volume layout of the two calls above.
+ * known fp32 and keep uint8 are volumes [D][N][H*W] like `volume`; keep != 0 keeps the known voxel.  All three: vector loads and stores
+ * where the extents allow, no atomics on floats, no allocation, no synchronisation, capturable.
+ * gg_ct_edit_glue: for each sample n at its own slice, (a) image_cl, the bf16 channels-last first-stage input [N][H*W][stride]: channel 0
+ * = the known slice, every other lane 0; (b) latent_keep fp32 [N][lat][lat]: cell (i, j) is 1 iff every pixel of
+ * [f (i - margin), f (i + 1 + margin)) x [f (j - margin), f (j + 1 + margin)) that lies inside the image is kept, f = H / lat (pixels
+ * outside the image count as kept), else 0.  An inactive row gives a zero image and mask 0.  A counter outside [0, iterations) writes
+ * nothing.  H == W, H % lat == 0, f (2 margin + 1) <= H, else GG_ERR_BAD_SHAPE / GG_ERR_UNSUPPORTED.
+ * gg_minmax_normalise_keep_scatter: gg_minmax_normalise_scatter with the pixel composite -- the min / max are taken over all of the
+ * sample's values as there; of the active row's slice, kept pixels receive known bit for bit, the others the normalised value, bit-equal
+ * to gg_minmax_normalise on that sample alone.  advance as there.
+ * gg_label_keep_volume: keep[d][n][i][j] = 1 iff the stage glue's label (order-0 zoom of [N,Dm,Hm,Wm] to (D,H,W) by the index rule of
+ * gg_mask_to_cond_slice, then rot90(k=3)) of new_labels equals that of old_labels, else 0; the device function of the glue, not a copy. */
+int gg_ct_edit_glue(const float *known, const uint8_t *keep, int32_t N, int32_t D, int32_t H, int32_t W, int32_t lat, int32_t margin,
+                    const int32_t *schedule_dev, int32_t iterations, const int32_t *iter_dev, void *image_cl, int32_t stride,
+                    float *latent_keep, void *stream);
+int gg_minmax_normalise_keep_scatter(const float *src, int32_t N, int64_t n_per_sample, float *workspace2n, const int32_t *schedule_dev,
+                                     int32_t iterations, int32_t *iter_dev, int32_t advance, int32_t depth, const float *known,
+                                     const uint8_t *keep, float *volume, void *stream);
+int gg_label_keep_volume(const int32_t *old_labels, const int32_t *new_labels, int32_t N, int32_t Dm, int32_t Hm, int32_t Wm, int32_t D,
+                         int32_t H, int32_t W, uint8_t *keep, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Cond stages (ldm/modules/encoders/modules.py:22-136: ClassEmbedder, TransformerEmbedder / BERTEmbedder, SpatialRescaler), gg_cond.hip.
  * All four: no allocation, no synchronisation, capturable; a refused shape is GG_ERR_BAD_SHAPE.

@@ -105,6 +105,9 @@ SIGNATURES = {
     "gg_mask_to_cond_slice": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp]),
     "gg_mask_to_cond_slices": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp, i32, vp]),
     "gg_minmax_normalise_scatter": (C.c_int, [vp, i32, i64, vp, vp, i32, vp, i32, i32, vp, vp]),
+    "gg_ct_edit_glue": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp, i32, vp, vp]),
+    "gg_minmax_normalise_keep_scatter": (C.c_int, [vp, i32, i64, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp]),
+    "gg_label_keep_volume": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
     "gg_embed_rows": (C.c_int, [vp, i64, i32, vp, i32, i32, vp, i32, vp, i32, i32, vp]),
     "gg_bert_embed": (C.c_int, [vp, vp, i64, i32, vp, i32, vp, i32, vp, i32, i32, vp, vp, f32, vp, i32, vp, vp, vp]),
     "gg_gelu": (C.c_int, [vp, i64, vp, vp]),

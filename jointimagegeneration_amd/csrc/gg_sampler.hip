@@ -492,15 +492,21 @@ struct MaskGrid {             // the label volume [N][Dm][Hm][Wm], the slice ext
     double zd, zh, zw;
 };
 
-// One conditioning row: pixel r = i * W + j of sample n's slice `slice`; pv: that pixel of the previous generated slice.  Writes the
-// whole padded row and returns the mask value.
-__device__ __forceinline__ float mask_to_cond_row(const MaskGrid &g, int n, int slice, long long r, float pv, bf16_t *__restrict__ row, int stride)
+// The zoomed, rotated label of pixel r = i * W + j of sample n's slice `slice` (the one place the glue's index rule and rotation stand).
+__device__ __forceinline__ int glue_label(const MaskGrid &g, int n, int slice, long long r)
 {
     const int sd = zoom0_index(slice, g.zd, g.Dm);
     const int j = (int)(r % g.W), i = (int)(r / g.W);
     const int y = g.H - 1 - j, x = i;                     // rot90(k=3) on (H, W): out[i][j] = up[H-1-j][i]  (H == W)
     const int sy = zoom0_index(y, g.zh, g.Hm), sx = zoom0_index(x, g.zw, g.Wm);
-    const int lab = g.labels[(((long long)n * g.Dm + sd) * g.Hm + sy) * g.Wm + sx];
+    return g.labels[(((long long)n * g.Dm + sd) * g.Hm + sy) * g.Wm + sx];
+}
+
+// One conditioning row: pixel r = i * W + j of sample n's slice `slice`; pv: that pixel of the previous generated slice.  Writes the
+// whole padded row and returns the mask value.
+__device__ __forceinline__ float mask_to_cond_row(const MaskGrid &g, int n, int slice, long long r, float pv, bf16_t *__restrict__ row, int stride)
+{
+    const int lab = glue_label(g, n, slice, r);
     const float mv = (float)lab / 255.0f;
     bf16x8 o = {(bf16_t)pv, (bf16_t)mv, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f};
     *reinterpret_cast<bf16x8 *>(row) = o;
@@ -621,6 +627,178 @@ extern "C" int gg_minmax_normalise_scatter(const float *src, int32_t N, int64_t 
     hipLaunchKernelGGL(minmax_seg_scatter_kernel, dim3(bx, (unsigned)N), dim3(256), 0, stream, src, N, (long long)n_per_sample,
                        (const uint32_t *)workspace2n, schedule_dev, iterations, iter_dev, depth, volume);
     if (advance) hipLaunchKernelGGL(schedule_advance_kernel, dim3(1), dim3(1), 0, stream, iter_dev);
+    GG_CHECK_LAUNCH();
+    return GG_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// CT editing (GuideGenPipeline.sample_ct_volumes with known_ct / keep): the same schedule and counter as above.
+// known fp32 / keep uint8 [D][N][H*W] in the layout of `volume`; keep != 0 keeps the known voxel.
+// ------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool keep4_all(uint32_t w) { return (w & 0xFFu) && (w & 0xFF00u) && (w & 0xFF0000u) && (w & 0xFF000000u); }
+
+// Per sample n at its own slice: (a) the first-stage input row of every pixel, channel 0 = the known slice, other lanes 0; (b) the latent
+// keep mask: cell (i, j) is 1 iff every pixel of [f (i - r), f (i + 1 + r)) x [f (j - r), f (j + 1 + r)) inside the image is kept.  An
+// inactive row gives a zero image and mask 0.  vec4: the window's row pieces are read as aligned 4-byte words (f % 4 == 0, H % 4 == 0).
+__global__ __launch_bounds__(256) void ct_edit_glue_kernel(const float *__restrict__ known, const uint8_t *__restrict__ keep, int N, int D, int H,
+                                                           int lat, int f, int margin, const int *__restrict__ sched, int iterations,
+                                                           const int *__restrict__ iter_dev, bf16_t *__restrict__ img, int stride,
+                                                           float *__restrict__ mask, int vec4)
+{
+    const int it = iter_dev[0];
+    if (it < 0 || it >= iterations) return;                // a schedule overrun writes nothing
+    const long long HW = (long long)H * H, total = (long long)N * HW;
+    const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x, step = (long long)gridDim.x * blockDim.x;
+    const int *rows = sched + (long long)it * N * 3;
+    const bf16x8 z = {(bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f};
+    for (long long t = tid; t < total; t += step) {
+        const int n = (int)(t / HW);
+        const long long r = t - n * HW;
+        const int slice = min(max(rows[3 * n], 0), D - 1);
+        const float kv = rows[3 * n + 2] ? known[((long long)slice * N + n) * HW + r] : 0.f;
+        bf16x8 o = z;
+        o[0] = (bf16_t)kv;
+        bf16_t *row = img + t * stride;
+        *reinterpret_cast<bf16x8 *>(row) = o;
+        for (int c = 8; c < stride; c += 8) *reinterpret_cast<bf16x8 *>(row + c) = z;
+    }
+    const int LL = lat * lat;
+    for (long long c = tid; c < (long long)N * LL; c += step) {
+        const int n = (int)(c / LL), q = (int)(c - (long long)n * LL);
+        const int i = q / lat, j = q - i * lat;
+        bool all = rows[3 * n + 2] != 0;
+        if (all) {
+            const int slice = min(max(rows[3 * n], 0), D - 1);
+            const uint8_t *kp = keep + ((long long)slice * N + n) * HW;
+            const int y0 = max(f * (i - margin), 0), y1 = min(f * (i + 1 + margin), H);
+            const int x0 = max(f * (j - margin), 0), x1 = min(f * (j + 1 + margin), H);
+            for (int y = y0; y < y1 && all; ++y) {
+                const uint8_t *p = kp + (long long)y * H;
+                if (vec4) {
+                    for (int x = x0; x < x1; x += 4) all = all && keep4_all(*reinterpret_cast<const uint32_t *>(p + x));
+                } else {
+                    for (int x = x0; x < x1; ++x) all = all && p[x] != 0;
+                }
+            }
+        }
+        mask[c] = all ? 1.0f : 0.0f;
+    }
+}
+
+extern "C" int gg_ct_edit_glue(const float *known, const uint8_t *keep, int32_t N, int32_t D, int32_t H, int32_t W, int32_t lat, int32_t margin,
+                               const int32_t *schedule_dev, int32_t iterations, const int32_t *iter_dev, void *image_cl, int32_t stride,
+                               float *latent_keep, void *stream_)
+{
+    if (!known || !keep || !schedule_dev || !iter_dev || !image_cl || !latent_keep) GG_FAIL(GG_ERR_BAD_SHAPE, "ct_edit_glue: null pointer");
+    if (H != W) GG_FAIL(GG_ERR_UNSUPPORTED, "ct_edit_glue: the slice must be square, got %d x %d", H, W);
+    if (stride % 8 || stride < 8) GG_FAIL(GG_ERR_BAD_SHAPE, "ct_edit_glue: stride");
+    if (N < 1 || D < 1 || H < 1 || iterations < 1 || lat < 1 || H % lat) GG_FAIL(GG_ERR_BAD_SHAPE, "ct_edit_glue: bad extent (H=%d, lat=%d)", H, lat);
+    const int f = H / lat;
+    if (margin < 0 || (long long)f * (2LL * margin + 1) > H) GG_FAIL(GG_ERR_BAD_SHAPE, "ct_edit_glue: margin %d: the window is wider than the image", margin);
+    const int vec4 = (f % 4 == 0 && H % 4 == 0 && ((uintptr_t)keep & 3) == 0) ? 1 : 0;
+    const unsigned blocks = gg_blocks256((long long)N * H * W, 4096);
+    hipLaunchKernelGGL(ct_edit_glue_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, known, keep, N, D, H, lat, f, margin, schedule_dev,
+                       iterations, iter_dev, (bf16_t *)image_cl, stride, latent_keep, vec4);
+    GG_CHECK_LAUNCH();
+    return GG_OK;
+}
+
+// minmax_seg_scatter_kernel with the pixel composite: kept pixels receive the known value, the others the normalised one (the same
+// operands and rounding, so bit-equal to gg_minmax_normalise on that sample alone).  vec4: 16-byte rows (n_per % 4 == 0, aligned bases).
+__global__ __launch_bounds__(256) void minmax_seg_keep_scatter_kernel(const float *__restrict__ src, int N, long long n_per, const uint32_t *ws,
+                                                                      const int *__restrict__ sched, int iterations,
+                                                                      const int *__restrict__ iter_dev, int depth,
+                                                                      const float *__restrict__ known, const uint8_t *__restrict__ keep,
+                                                                      float *__restrict__ volume, int vec4)
+{
+#pragma clang fp contract(off)
+    const int n = blockIdx.y;
+    const int it = iter_dev[0];
+    if (it < 0 || it >= iterations) return;
+    const int *row = sched + ((long long)it * N + n) * 3;
+    if (!row[2]) return;
+    const int slice = row[0];
+    if (slice < 0 || slice >= depth) return;
+    const float mn = ord2f(ws[2 * n]), mx = ord2f(ws[2 * n + 1]);
+    const float den = mx - mn;
+    const float *s = src + (long long)n * n_per;
+    const long long off = ((long long)slice * N + n) * n_per;
+    const float *kn = known + off;
+    const uint8_t *kp = keep + off;
+    float *d = volume + off;
+    const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x, step = (long long)gridDim.x * blockDim.x;
+    if (vec4) {
+        for (long long i = tid; i < n_per / 4; i += step) {
+            const f32x4 sv = *reinterpret_cast<const f32x4 *>(s + 4 * i);
+            const f32x4 kv = *reinterpret_cast<const f32x4 *>(kn + 4 * i);
+            const uint32_t kb = *reinterpret_cast<const uint32_t *>(kp + 4 * i);
+            f32x4 o;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) o[c] = ((kb >> (8 * c)) & 0xFFu) ? kv[c] : (sv[c] - mn) / den;
+            *reinterpret_cast<f32x4 *>(d + 4 * i) = o;
+        }
+    } else {
+        for (long long i = tid; i < n_per; i += step) d[i] = kp[i] ? kn[i] : (s[i] - mn) / den;
+    }
+}
+
+extern "C" int gg_minmax_normalise_keep_scatter(const float *src, int32_t N, int64_t n_per_sample, float *workspace2n, const int32_t *schedule_dev,
+                                                int32_t iterations, int32_t *iter_dev, int32_t advance, int32_t depth, const float *known,
+                                                const uint8_t *keep, float *volume, void *stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!src || !workspace2n || !schedule_dev || !iter_dev || !known || !keep || !volume)
+        GG_FAIL(GG_ERR_BAD_SHAPE, "minmax_normalise_keep_scatter: null pointer");
+    if (N < 1 || N > 65535 || n_per_sample <= 0 || depth < 1 || iterations < 1) GG_FAIL(GG_ERR_BAD_SHAPE, "minmax_normalise_keep_scatter: bad extent");
+    const auto al = [](const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; };
+    const int vec4 = (n_per_sample % 4 == 0 && al(src, 16) && al(known, 16) && al(volume, 16) && al(keep, 4)) ? 1 : 0;
+    const unsigned bx = gg_blocks256(n_per_sample, 2048 / N > 1 ? 2048 / N : 1);       // the grid of gg_minmax_normalise_scatter
+    hipLaunchKernelGGL(minmax_seg_init_kernel, dim3(1), dim3(256), 0, stream, (uint32_t *)workspace2n, N);
+    hipLaunchKernelGGL(minmax_seg_reduce_kernel, dim3(bx, (unsigned)N), dim3(256), 0, stream, src, (long long)n_per_sample,
+                       (uint32_t *)workspace2n);
+    hipLaunchKernelGGL(minmax_seg_keep_scatter_kernel, dim3(bx, (unsigned)N), dim3(256), 0, stream, src, N, (long long)n_per_sample,
+                       (const uint32_t *)workspace2n, schedule_dev, iterations, iter_dev, depth, known, keep, volume, vec4);
+    if (advance) hipLaunchKernelGGL(schedule_advance_kernel, dim3(1), dim3(1), 0, stream, iter_dev);
+    GG_CHECK_LAUNCH();
+    return GG_OK;
+}
+
+// keep[d][n][i][j] = (the glue's zoomed, rotated label of the new volume == that of the old one): glue_label on both volumes.
+__global__ __launch_bounds__(256) void label_keep_volume_kernel(const int *__restrict__ old_labels, const int *__restrict__ new_labels, int N, int Dm,
+                                                                int Hm, int Wm, int D, int H, int W, double zd, double zh, double zw,
+                                                                uint8_t *__restrict__ keep, int vec4)
+{
+    const MaskGrid go{old_labels, Dm, Hm, Wm, H, W, zd, zh, zw}, gn{new_labels, Dm, Hm, Wm, H, W, zd, zh, zw};
+    const long long HW = (long long)H * W, total = (long long)D * N * HW;
+    const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x, step = (long long)gridDim.x * blockDim.x;
+    const int per = vec4 ? 4 : 1;                          // HW % 4 == 0: the 4 pixels of a word lie in one slice of one sample
+    for (long long t = tid * per; t < total; t += step * per) {
+        const int d = (int)(t / (N * HW));
+        const long long rem = t - (long long)d * N * HW;
+        const int n = (int)(rem / HW);
+        const long long r = rem - n * HW;
+        if (vec4) {
+            uint32_t w = 0;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) w |= (glue_label(go, n, d, r + c) == glue_label(gn, n, d, r + c) ? 1u : 0u) << (8 * c);
+            *reinterpret_cast<uint32_t *>(keep + t) = w;
+        } else {
+            keep[t] = glue_label(go, n, d, r) == glue_label(gn, n, d, r) ? 1 : 0;
+        }
+    }
+}
+
+extern "C" int gg_label_keep_volume(const int32_t *old_labels, const int32_t *new_labels, int32_t N, int32_t Dm, int32_t Hm, int32_t Wm, int32_t D,
+                                    int32_t H, int32_t W, uint8_t *keep, void *stream_)
+{
+    if (!old_labels || !new_labels || !keep) GG_FAIL(GG_ERR_BAD_SHAPE, "label_keep_volume: null pointer");
+    if (H != W) GG_FAIL(GG_ERR_UNSUPPORTED, "label_keep_volume: rot90 needs H == W");
+    if (N < 1 || Dm < 1 || Hm < 1 || Wm < 1 || D < 1 || H < 1) GG_FAIL(GG_ERR_BAD_SHAPE, "label_keep_volume: empty extent");
+    const long long HW = (long long)H * W, total = (long long)D * N * HW;
+    const int vec4 = (HW % 4 == 0 && ((uintptr_t)keep & 3) == 0) ? 1 : 0;
+    const unsigned blocks = gg_blocks256(vec4 ? total / 4 : total, 4096);
+    hipLaunchKernelGGL(label_keep_volume_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, old_labels, new_labels, N, Dm, Hm, Wm, D, H, W,
+                       zoom0_factor(Dm, D), zoom0_factor(Hm, H), zoom0_factor(Wm, W), keep, vec4);
     GG_CHECK_LAUNCH();
     return GG_OK;
 }

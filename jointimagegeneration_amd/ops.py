@@ -1190,6 +1190,79 @@ def minmax_normalise_scatter(src: torch.Tensor, schedule: torch.Tensor, it: torc
           "gg_minmax_normalise_scatter")
 
 
+def _check_edit_volumes(who: str, known: torch.Tensor, keep: torch.Tensor, shape: Tuple[int, ...], device) -> None:
+    if tuple(known.shape) != tuple(shape) or known.dtype != torch.float32 or not known.is_contiguous() or known.device != device:
+        raise ValueError(f"{who}: known must be a contiguous fp32 {tuple(shape)} tensor on {device}, got {known.dtype} {tuple(known.shape)}")
+    if tuple(keep.shape) != tuple(shape) or keep.dtype != torch.uint8 or not keep.is_contiguous() or keep.device != device:
+        raise ValueError(f"{who}: keep must be a contiguous uint8 {tuple(shape)} tensor on {device}, got {keep.dtype} {tuple(keep.shape)}")
+
+
+def ct_edit_glue(known: torch.Tensor, keep: torch.Tensor, schedule: torch.Tensor, it: torch.Tensor, margin: int, image: torch.Tensor,
+                 latent_keep: torch.Tensor) -> None:
+    """CT editing glue of independent volumes: known fp32 / keep uint8 [D, N, H, W]; sample n at its own slice schedule[it[0], n, 0] ->
+    image bf16 CL [N,1,H,W,stride] (channel 0 the known slice, other lanes 0) and latent_keep fp32 [N*lat*lat, 1]: 1 iff every in-image
+    pixel of the cell's window, grown by `margin` cells on each side, is kept.  Inactive rows: zero image, mask 0."""
+    lib = _lib.load()
+    if known.dim() != 4:
+        raise ValueError(f"ct_edit_glue: known must be [D, N, H, W], got {tuple(known.shape)}")
+    D, N, H, W = (int(v) for v in known.shape)
+    require_gpu(known, "ct_edit_glue")
+    _check_edit_volumes("ct_edit_glue", known, keep, (D, N, H, W), known.device)
+    _check_schedule(schedule, N, it)
+    if image.dtype != torch.bfloat16 or not image.is_contiguous() or tuple(image.shape[:-1]) != (N, 1, H, W) or image.shape[-1] % 8:
+        raise ValueError(f"ct_edit_glue: image must be a contiguous bf16 {(N, 1, H, W)} + (stride,) tensor, stride a multiple of 8, got "
+                         f"{image.dtype} {tuple(image.shape)}")
+    cells = latent_keep.numel() // N
+    lat = int(round(cells ** 0.5))
+    if latent_keep.dtype != torch.float32 or not latent_keep.is_contiguous() or lat * lat * N != latent_keep.numel() or lat < 1 or H % lat or H != W:
+        raise ValueError(f"ct_edit_glue: latent_keep must be a contiguous fp32 tensor of {N} x lat x lat values with lat dividing H = W = {H}, "
+                         f"got {latent_keep.dtype} {tuple(latent_keep.shape)}")
+    if int(margin) < 0 or (H // lat) * (2 * int(margin) + 1) > H:
+        raise ValueError(f"ct_edit_glue: margin = {margin}: the window of {(H // lat) * (2 * int(margin) + 1)} pixels must fit the {H} x {W} slice")
+    check(lib.gg_ct_edit_glue(known.data_ptr(), keep.data_ptr(), N, D, H, W, lat, int(margin), schedule.data_ptr(), schedule.shape[0],
+                              it.data_ptr(), image.data_ptr(), image.shape[-1], latent_keep.data_ptr(), _stream()), "gg_ct_edit_glue")
+
+
+def minmax_normalise_keep_scatter(src: torch.Tensor, schedule: torch.Tensor, it: torch.Tensor, known: torch.Tensor, keep: torch.Tensor,
+                                  volume: torch.Tensor, advance: bool = True, workspace: Optional[torch.Tensor] = None) -> None:
+    """minmax_normalise_scatter with the pixel composite: known fp32 / keep uint8 of volume's shape [depth, N, ...]; of the active row's
+    slice, kept pixels receive known bit for bit, the others the normalised value (bit-equal to minmax_normalise on that sample)."""
+    lib = _lib.load()
+    N = src.shape[0]
+    require_gpu(src, "minmax_normalise_keep_scatter")
+    _check_schedule(schedule, N, it)
+    n_per = src.numel() // N
+    if src.dtype != torch.float32 or not src.is_contiguous():
+        raise ValueError("minmax_normalise_keep_scatter: src must be contiguous fp32")
+    if volume.dtype != torch.float32 or not volume.is_contiguous() or volume.shape[1] != N or volume[0, 0].numel() != n_per:
+        raise ValueError(f"minmax_normalise_keep_scatter: volume must be contiguous fp32 [depth, {N}, ...] of {n_per} values per slice")
+    _check_edit_volumes("minmax_normalise_keep_scatter", known, keep, tuple(volume.shape), volume.device)
+    if workspace is None:
+        workspace = torch.empty(2 * N, dtype=torch.float32, device=src.device)
+    check(lib.gg_minmax_normalise_keep_scatter(src.data_ptr(), N, n_per, workspace.data_ptr(), schedule.data_ptr(), schedule.shape[0],
+                                               it.data_ptr(), 1 if advance else 0, volume.shape[0], known.data_ptr(), keep.data_ptr(),
+                                               volume.data_ptr(), _stream()), "gg_minmax_normalise_keep_scatter")
+
+
+def label_keep_volume(old_labels: torch.Tensor, new_labels: torch.Tensor, D: int, H: int, W: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int32 label volumes [N, Dm, Hm, Wm] -> keep uint8 [D, N, H, W]: 1 where the stage glue's zoomed, rotated label of new_labels equals
+    that of old_labels (the index rule and rot90(k=3) of mask_to_cond_slice)."""
+    lib = _lib.load()
+    require_gpu(old_labels, "label_keep_volume")
+    for name, t in (("old_labels", old_labels), ("new_labels", new_labels)):
+        if t.dim() != 4 or t.dtype != torch.int32 or not t.is_contiguous() or t.shape != old_labels.shape or t.device != old_labels.device:
+            raise ValueError(f"label_keep_volume: {name} must be a contiguous int32 [N, Dm, Hm, Wm] tensor, both of one shape and device, got "
+                             f"{t.dtype} {tuple(t.shape)}")
+    N, Dm, Hm, Wm = (int(v) for v in old_labels.shape)
+    if out is None:
+        out = torch.empty((D, N, H, W), dtype=torch.uint8, device=old_labels.device)
+    elif tuple(out.shape) != (D, N, H, W) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != old_labels.device:
+        raise ValueError(f"label_keep_volume: out must be a contiguous uint8 {(D, N, H, W)} tensor on {old_labels.device}")
+    check(lib.gg_label_keep_volume(old_labels.data_ptr(), new_labels.data_ptr(), N, Dm, Hm, Wm, D, H, W, out.data_ptr(), _stream()),
+          "gg_label_keep_volume")
+    return out
+
+
 def _check_schedule(schedule: torch.Tensor, N: int, it: torch.Tensor) -> None:
     if schedule.dtype != torch.int32 or schedule.dim() != 3 or schedule.shape[1:] != (N, 3) or not schedule.is_contiguous():
         raise ValueError(f"schedule must be a contiguous int32 [iterations, {N}, 3] tensor")

@@ -256,12 +256,14 @@ class GuideGenPipeline:
             samples[mm].copy_(sg["ds"])
         return samples.permute(1, 0, 2, 3)
 
-    def _volume_engine(self, B: int, hw: int, depth: int, lab_shape: Tuple[int, ...], dev, st) -> Dict:
+    def _volume_engine(self, B: int, hw: int, depth: int, lab_shape: Tuple[int, ...], dev, st, edit_margin: Optional[int] = None) -> Dict:
         """Static buffers + the ONE per-slice hipGraph of the batched slice loop of B independent volumes: batched glue (schedule row of the
-        device iteration counter), cond-encode, the S DDIM steps, decode, per-volume normalise + scatter (advances the counter)."""
+        device iteration counter), cond-encode, the S DDIM steps, decode, per-volume normalise + scatter (advances the counter).
+        edit_margin (an int): the engine of the editing loop, under its own key -- `st` is then an inpainting state; the
+        known / keep volumes, the first-stage input and the edit glue + first-stage encode join the iteration, and the scatter composites."""
         ldm = self.ldm
         lat, Cz = hw // self.latent_factor, ldm.channels
-        key = (B, hw, depth, tuple(lab_shape), str(dev))
+        key = (B, hw, depth, tuple(lab_shape), str(dev)) + ((("edit", int(edit_margin)),) if edit_margin is not None else ())
         token = (id(st), ops.weights_token(ldm.cond_stage_model), ops.weights_token(ldm.first_stage_model))
         ve = self._volume_graphs.get(key)
         if ve is not None and ve["token"] == token:
@@ -274,37 +276,193 @@ class GuideGenPipeline:
                   z=torch.zeros((B, 1, lat, lat, 32), dtype=torch.bfloat16, device=dev),
                   ds=torch.empty((B, hw, hw), dtype=torch.float32, device=dev), graph=None, warmed=False)
 
+        if edit_margin is not None:
+            ve.update(known=torch.zeros((depth, B, hw, hw), dtype=torch.float32, device=dev),
+                      keep=torch.zeros((depth, B, hw, hw), dtype=torch.uint8, device=dev),
+                      fs_in=torch.empty((B, 1, hw, hw, 32), dtype=torch.bfloat16, device=dev))
+
         def glue():
             ops.mask_to_cond_slices(ve["labels"], depth, hw, hw, ve["sched"], ve["it"], ve["samples"], ve["cond_in"])
+            if edit_margin is not None:                # the known slice as first-stage input, the latent keep mask into the chain's state
+                ops.ct_edit_glue(ve["known"], ve["keep"], ve["sched"], ve["it"], int(edit_margin), ve["fs_in"], st["ip_mask"].view(-1, 1))
 
         def encode():
             mom = ldm.cond_stage_model.encode_moments_cl(CL(ve["cond_in"], 2))
             st["unet_in"][..., Cz:2 * Cz].copy_(mom.t[..., :Cz])
+            if edit_margin is not None:                # x0 = scale_factor * posterior mean: the mode, no draw
+                mom = ldm.first_stage_model.encode_moments_cl(CL(ve["fs_in"], 1))
+                st["ip_x0"].copy_(mom.t[..., :Cz] * ldm.scale_factor)
 
         def decode():
             ve["z"][..., :Cz].copy_(st["x"] * (1.0 / ldm.scale_factor))
             dec = ldm.first_stage_model.decode_cl(CL(ve["z"], Cz))
             ve["ds"].copy_(dec.t[..., 0].reshape(B, hw, hw))
-            ops.minmax_normalise_scatter(ve["ds"], ve["sched"], ve["it"], ve["samples"], advance=True, workspace=ve["ws"])
+            if edit_margin is None:
+                ops.minmax_normalise_scatter(ve["ds"], ve["sched"], ve["it"], ve["samples"], advance=True, workspace=ve["ws"])
+            else:
+                ops.minmax_normalise_keep_scatter(ve["ds"], ve["sched"], ve["it"], ve["known"], ve["keep"], ve["samples"], advance=True,
+                                                  workspace=ve["ws"])
 
         ve["glue"], ve["encode"], ve["decode"] = glue, encode, decode
         self._volume_graphs[key] = ve
         return ve
 
+    def _check_edit(self, B: int, depth: int, hw: int, known_ct, keep, edit_margin, q_noise_tapes) -> None:
+        """Host-side refusals of the editing loop, by name, before any launch."""
+        who = "sample_ct_volumes"
+        ldm = self.ldm
+        if (known_ct is None) != (keep is None):
+            raise ValueError(f"{who}: known_ct= and keep= go together (got only {'known_ct' if keep is None else 'keep'})")
+        if known_ct is None:
+            if q_noise_tapes is not None or edit_margin != 0:
+                raise ValueError(f"{who}: edit_margin / q_noise_tapes edit a known CT: give known_ct= and keep=")
+            return
+        if hasattr(ldm, "split_input_params"):
+            raise NotImplementedError(f"{who}: CT editing with split_input_params (patch-wise evaluation) is not supported")
+        if getattr(ldm, "dims", 2) != 2 or getattr(ldm.first_stage_model, "dims", 2) != 2:
+            raise NotImplementedError(f"{who}: CT editing is a 2-D slice loop; 3-D latents (dims = 3) are not supported")
+        if ldm.model.conditioning_key != "concat":
+            raise NotImplementedError(f"{who}: CT editing needs conditioning_key 'concat', got '{ldm.model.conditioning_key}'")
+        if type(self.sampler) is not DDIMSampler or any(float(s) != 0.0 for s in self.sampler.ddim_sigmas):
+            raise NotImplementedError(f"{who}: CT editing runs the DDIM sampler at eta = 0, got {type(self.sampler).__name__} with "
+                                      f"sigmas up to {max(float(s) for s in self.sampler.ddim_sigmas):g}")
+        shape = (B, depth, hw, hw)
+        if not isinstance(known_ct, torch.Tensor) or tuple(known_ct.shape) != shape or known_ct.dtype != torch.float32:
+            raise ValueError(f"{who}: known_ct must be an fp32 {shape} tensor, got {getattr(known_ct, 'dtype', type(known_ct).__name__)} "
+                             f"{tuple(getattr(known_ct, 'shape', ()))}")
+        if not isinstance(keep, torch.Tensor) or tuple(keep.shape) != shape or keep.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f"{who}: keep must be a bool or uint8 {shape} tensor, got {getattr(keep, 'dtype', type(keep).__name__)} "
+                             f"{tuple(getattr(keep, 'shape', ()))}")
+        if not isinstance(edit_margin, int) or isinstance(edit_margin, bool) or edit_margin < 0:
+            raise ValueError(f"{who}: edit_margin must be an int >= 0, got {edit_margin!r}")
+        if hw % self.latent_factor or self.latent_factor * (2 * edit_margin + 1) > hw:
+            raise ValueError(f"{who}: edit_margin = {edit_margin}: the window of {self.latent_factor * (2 * edit_margin + 1)} pixels is wider "
+                             f"than the {hw} x {hw} slice")
+        if q_noise_tapes is not None and len(q_noise_tapes) != B:
+            raise ValueError(f"{who}: q_noise_tapes holds {len(q_noise_tapes)} lists, the batch has {B} volumes")
+        lo, hi = torch.stack([known_ct.min(), known_ct.max()]).tolist()                # the one host check of the values
+        if not (lo >= 0.0 and hi <= 1.0):
+            raise ValueError(f"{who}: known_ct holds values {lo:g}..{hi:g} outside [0, 1]")
+
+    @torch.no_grad()
+    def _sample_ct_volumes_edit(self, labels, depth, hw, seeds, max_slices, x_T_tapes, known_ct, keep, edit_margin, q_noise_tapes):
+        """The editing loop of sample_ct_volumes."""
+        ldm, sampler, S = self.ldm, self.sampler, self.ddim_steps
+        dev = labels.device
+        B = labels.shape[0]
+        lat, Cz = hw // self.latent_factor, ldm.channels
+        known_d = known_ct.to(dev).permute(1, 0, 2, 3).contiguous()                   # slice-major, as `samples`
+        keep_d = (keep.to(dev) != 0).permute(1, 0, 2, 3).contiguous()
+        kept_all = keep_d.flatten(2).all(-1).cpu()                                     # [depth, B]
+        kept_any = keep_d.flatten(2).any(-1).cpu()
+        unkept_px = (~keep_d).flatten(2).sum(-1).cpu()
+        windows, mixed, skipped, outside = [], [], 0, 0
+        for i in range(B):
+            win = slice_window(labels[i], depth, max_slices)
+            visit = [m for m in win if not bool(kept_all[m % depth, i])]
+            skipped += len(win) - len(visit)
+            inside = {m % depth for m in win}
+            outside += int(sum(int(unkept_px[d, i]) for d in range(depth) if d not in inside))
+            windows.append(visit)
+            mixed.append([bool(kept_any[m % depth, i]) for m in visit])
+        n_mixed = [sum(mx) for mx in mixed]
+        for name, tapes, want in (("x_T_tapes", x_T_tapes, [len(w) for w in windows]), ("q_noise_tapes", q_noise_tapes, n_mixed)):
+            if tapes is not None:
+                for i in range(B):
+                    if len(tapes[i]) != want[i]:
+                        raise ValueError(f"sample_ct_volumes: {name}[{i}] holds {len(tapes[i])} tensors, volume {i} "
+                                         f"{'visits' if name == 'x_T_tapes' else 'has'} {want[i]} {'slices' if name == 'x_T_tapes' else 'mixed slices'}")
+        if q_noise_tapes is not None:
+            for i in range(B):
+                for k, t in enumerate(q_noise_tapes[i]):
+                    if tuple(t.shape) != (S, 1, Cz, lat, lat):
+                        raise ValueError(f"sample_ct_volumes: q_noise_tapes[{i}][{k}] has shape {tuple(t.shape)}, a mixed slice takes {(S, 1, Cz, lat, lat)}")
+        self.stats.update(slices_visited=sum(len(w) for w in windows), slices_skipped_kept=skipped, slices_mixed=sum(n_mixed),
+                          unkept_outside_window=outside)
+        start = torch.where(keep_d, known_d, torch.zeros_like(known_d))
+        iters = max(len(w) for w in windows)
+        if iters == 0:                                                                 # every slice of every window is kept: no iteration
+            self.stats["wasted_slot_fraction"] = 0.0
+            return start.permute(1, 0, 2, 3).contiguous()
+        sched, wasted = volume_schedule(windows, depth)
+        self.stats["wasted_slot_fraction"] = wasted
+        gens = [torch.Generator(device=dev).manual_seed(int(s)) for s in seeds]
+        st = sampler.prepare_state(B, Cz, (lat, lat), dev, Cz, mask_C=1)
+        ve = self._volume_engine(B, hw, depth, tuple(labels.shape), dev, st, edit_margin=edit_margin)
+        ve["labels"].copy_(labels)
+        ve["known"].copy_(known_d)
+        ve["keep"].copy_(keep_d)
+        ve["samples"].copy_(start)
+        ve["sched"].zero_()
+        ve["sched"][:iters].copy_(sched)
+        ve["it"].zero_()
+        glue, encode, decode = ve["glue"], ve["encode"], ve["decode"]
+        q_used = [0] * B
+
+        t_last = time.time()
+        for it in range(iters):
+            if time.time() - t_last > self.progress_every_s:
+                _log(f"LDM edited slice {it}/{iters} (batch of {B})")
+                t_last = time.time()
+            x_T = torch.zeros((B, Cz, lat, lat), dtype=torch.float32, device=dev)
+            q = torch.zeros((S, B, Cz, lat, lat), dtype=torch.float32, device=dev)     # rows of free or inactive volumes stay zero
+            for i in range(B):
+                if it < len(windows[i]):                                               # the x_T draw of the un-edited loop, then the q-sample noise
+                    x_T[i] = (x_T_tapes[i][it].to(dev).float().reshape(Cz, lat, lat) if x_T_tapes is not None
+                              else torch.randn((1, Cz, lat, lat), generator=gens[i], device=dev)[0])
+                    if mixed[i][it]:
+                        q[:, i] = (q_noise_tapes[i][q_used[i]].to(dev).float() if q_noise_tapes is not None
+                                   else torch.randn((S, 1, Cz, lat, lat), generator=gens[i], device=dev))[:, 0]
+                        q_used[i] += 1
+            x_T = x_T.permute(0, 2, 3, 1).reshape(B, 1, lat, lat, Cz)
+            st["x"].copy_(x_T)
+            st["unet_in"][..., :Cz].copy_(x_T)
+            st["ip_noise"].copy_(q.permute(0, 1, 3, 4, 2).reshape(st["ip_noise"].shape))
+            if not (self.use_graph and sampler.chain_graphable(st)):
+                glue()
+                encode()
+                sampler.run_steps(st, None, 0.0, None)
+                decode()
+            elif not ve["warmed"]:
+                glue()
+                encode()                                                               # eager once: fills the repack caches
+                sampler.chain(st)
+                decode()
+                ve["warmed"] = True
+            else:
+                if ve["graph"] is None:
+                    ve["graph"] = ops.capture_graph(lambda: (glue(), encode(), sampler.chain(st), decode()))
+                ve["graph"].replay()
+        return ve["samples"].clone().permute(1, 0, 2, 3)
+
     @torch.no_grad()
     def sample_ct_volumes(self, labels: torch.Tensor, depth: int, hw: int, seeds: Sequence[int], max_slices: Optional[int] = None,
-                          x_T_tapes=None) -> torch.Tensor:
+                          x_T_tapes=None, known_ct: Optional[torch.Tensor] = None, keep: Optional[torch.Tensor] = None, edit_margin: int = 0,
+                          q_noise_tapes=None) -> torch.Tensor:
         """labels int32 [B,Dm,Hm,Wm] of B INDEPENDENT volumes -> CT fp32 [B, depth, hw, hw]: volume i is sample_ct(labels[i:i+1], depth,
         hw, seeds[i], max_slices) -- its own slice window, its own min-max normalisation, its own x_T generator -- up to the bf16 rounding
         of batch-size-dependent kernel plans, and bit for bit independent of the other volumes at a fixed B.  The batch is static: a volume
         whose window has ended keeps computing on a discarded row.  One graph replay per slice iteration; the host's share is one x_T
         draw per ACTIVE volume (so every volume's generator stream is its solo one).  `x_T_tapes` (parity runs): per volume, one
-        [1, Cz, lat, lat] start latent per generated slice in loop order.  self.stats["wasted_slot_fraction"] reports the discarded work."""
+        [1, Cz, lat, lat] start latent per generated slice in loop order.  self.stats["wasted_slot_fraction"] reports the discarded work.
+        CT editing: known_ct fp32 [B, depth, hw, hw] in [0, 1] (the loop's own output convention) with keep bool / uint8
+        of that shape (1 keeps the known voxel, 0 is generated).  Kept voxels come back bit for bit; a slice of the window all of whose
+        pixels are kept is not visited (it feeds the next slice as the previous one); a visited slice with kept pixels ("mixed") runs the
+        DDIM chain with the sampler's inpainting blend around x0 = scale_factor * mean of the first stage's encoding of the known slice
+        (the mode, no draw), the latent keep mask being 1 where every pixel of the cell's window, grown by `edit_margin` cells on each
+        side, is kept; the decoded slice is normalised as always and composited per pixel.  A mixed slice draws, after its x_T, one
+        [S, 1, Cz, lat, lat] of q-sample noise from the volume's generator (`q_noise_tapes`: per volume, one such tensor per mixed slice in
+        loop order); a slice with no kept pixel draws nothing more, so an all-zero keep leaves the volume's stream, and its result, those
+        of its un-edited run.  self.stats gains slices_visited / slices_skipped_kept / slices_mixed / unkept_outside_window (un-kept
+        pixels on slices outside the window stay 0).  A call without known_ct takes the state, graph and launches it took before."""
         ldm, sampler = self.ldm, self.sampler
         dev = labels.device
         B = labels.shape[0]
         if len(seeds) != B or (x_T_tapes is not None and len(x_T_tapes) != B):
             raise ValueError(f"sample_ct_volumes: {B} volumes need {B} seeds (and {B} tapes)")
+        self._check_edit(B, depth, hw, known_ct, keep, edit_margin, q_noise_tapes)
+        if known_ct is not None:
+            return self._sample_ct_volumes_edit(labels, depth, hw, seeds, max_slices, x_T_tapes, known_ct, keep, edit_margin, q_noise_tapes)
         lat, Cz = hw // self.latent_factor, ldm.channels
         windows = [slice_window(labels[i], depth, max_slices) for i in range(B)]
         sched, wasted = volume_schedule(windows, depth)
@@ -365,6 +523,47 @@ class GuideGenPipeline:
         _log(f"{len(seeds)} volumes done: CCDM {t1 - t0:.1f}s, LDM {time.time() - t1:.1f}s, "
              f"wasted slots {self.stats['wasted_slot_fraction']:.3f}")
         return labels, ct
+
+    @torch.no_grad()
+    def ct_keep_from_labels(self, old_labels: torch.Tensor, new_labels: torch.Tensor, depth: int, hw: int) -> torch.Tensor:
+        """The CT keep volume of an edited mask: uint8 [B, depth, hw, hw], 1 where the stage glue's zoomed, rotated label of new_labels
+        equals that of old_labels (both int [B, Dm, Hm, Wm]), i.e. where the slice loop is conditioned as the known CT was."""
+        if old_labels.shape != new_labels.shape or old_labels.dim() != 4:
+            raise ValueError(f"ct_keep_from_labels: two label volumes [B, Dm, Hm, Wm] of one shape, got {tuple(old_labels.shape)} and "
+                             f"{tuple(new_labels.shape)}")
+        dev = new_labels.device
+        keep = ops.label_keep_volume(old_labels.to(device=dev, dtype=torch.int32).contiguous(), new_labels.to(torch.int32).contiguous(), depth, hw, hw)
+        return keep.permute(1, 0, 2, 3).contiguous()
+
+    @torch.no_grad()
+    def edit_volumes(self, known_labels: torch.Tensor, known_ct: torch.Tensor, seeds: Sequence[int], label_keep: Optional[torch.Tensor] = None,
+                     keep_classes: Optional[Sequence[int]] = None, resample: int = 1, edit_margin: int = 0, ccdm_init_t: Optional[int] = None,
+                     max_slices: Optional[int] = None):
+        """Edit B known volumes through both stages: known_labels int [B, Dm, Hm, Wm] with exactly one of label_keep (bool / uint8 of that
+        shape, 1 keeps the known label) and keep_classes (keep the voxels whose known label is listed); known_ct fp32 [B, depth, hw, hw].
+        Stage 1 samples the un-kept labels (sample_masks(known=, keep=, resample=), seed seeds[i]); the CT keep volume is where the new
+        labels condition the slice loop as the old ones did (ct_keep_from_labels); stage 2 regenerates the rest of the CT
+        (sample_ct_volumes(known_ct=, keep=, edit_margin=), seed seeds[i] + 1).  Returns (labels, ct, ct_keep)."""
+        if (label_keep is None) == (keep_classes is None):
+            raise ValueError("edit_volumes: give exactly one of label_keep= and keep_classes=")
+        if known_labels.dim() != 4 or known_ct.dim() != 4 or known_ct.shape[0] != known_labels.shape[0] or len(seeds) != known_labels.shape[0]:
+            raise ValueError(f"edit_volumes: known_labels [B, Dm, Hm, Wm], known_ct [B, depth, hw, hw] and B seeds, got "
+                             f"{tuple(known_labels.shape)}, {tuple(known_ct.shape)} and {len(seeds)} seeds")
+        dev = self.ccdm.diffusion.betas.device
+        depth, hw = int(known_ct.shape[1]), int(known_ct.shape[2])
+        known_labels = known_labels.to(device=dev, dtype=torch.int32).contiguous()
+        if keep_classes is not None:
+            label_keep = torch.isin(known_labels, torch.tensor([int(c) for c in keep_classes], dtype=torch.int32, device=dev))
+        t0 = time.time()
+        labels = self.sample_masks(seeds, tuple(known_labels.shape[1:]), ccdm_init_t, known=known_labels, keep=label_keep.to(dev), resample=resample)
+        ct_keep = self.ct_keep_from_labels(known_labels, labels, depth, hw)
+        torch.cuda.synchronize()
+        t1 = time.time()
+        ct = self.sample_ct_volumes(labels, depth, hw, [int(s) + 1 for s in seeds], max_slices, known_ct=known_ct, keep=ct_keep,
+                                    edit_margin=edit_margin)
+        torch.cuda.synchronize()
+        self.stats.update({"ccdm_s": t1 - t0, "ldm_s": time.time() - t1})
+        return labels, ct, ct_keep
 
     @torch.no_grad()
     def run_volume(self, N: int = 1, mask_size=(128, 128, 128), depth: int = 256, hw: int = 512, seed: int = 1024,

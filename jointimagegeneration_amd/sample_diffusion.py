@@ -15,6 +15,10 @@ timesteps, one row per sample (ddpm.py:539-549) -- is written as `<stem>_progres
 `layers/*.png` and the private datasets are out of scope; the mask comes from `--inputs <dir>` (the
 `pred_*.nii.gz` label volumes the stage-1 entry point ddpm_eval writes: the hand-off of README.md:21, one CT volume per mask),
 from --mask (.npy label volume [D,H,W]) or is synthetic.
+CT editing (this package's addition): with `--inputs DIR --known-ct DIR` and one of `--known-mask DIR` (the original label
+volumes) and `--keep-mask DIR` (explicit keep volumes), all paired by stem, each volume runs through
+`GuideGenPipeline.sample_ct_volumes(known_ct=, keep=, edit_margin=--edit-margin)`: kept voxels of the known CT come back bit for bit, the
+rest is regenerated, and metrics.json gains an `edit` block.
 """
 from __future__ import annotations
 
@@ -62,6 +66,13 @@ def get_parser():
     p.add_argument("--progress-png", default=False, action="store_true", help="with -v: sample the last generated slice with "
                    "progressive_denoising and write its denoise row (decoded x_0 predictions at the logged timesteps) as <stem>_progress.png")
     p.add_argument("--log-every-t", type=int, default=None, help="with --progress-png: log every K-th timestep (default: the model's log_every_t)")
+    p.add_argument("--known-ct", type=str, default=None, help="CT editing (with --inputs): directory of known CT volumes (NIfTI, fp32 in [0, 1], already "
+                   "--slices x --size x --size; nothing is resampled), paired with the --inputs label volumes by stem.  Kept voxels come back bit for bit")
+    p.add_argument("--known-mask", type=str, default=None, help="with --known-ct: directory of the ORIGINAL label volumes (same stems): a voxel is kept "
+                   "where the edited and the original label condition the slice loop alike")
+    p.add_argument("--keep-mask", type=str, default=None, help="with --known-ct: directory of explicit uint8 keep volumes (same stems, --slices x --size x "
+                   "--size, non-zero = keep), instead of --known-mask")
+    p.add_argument("--edit-margin", type=int, default=0, help="with --known-ct: latent cells within R cells of an un-kept pixel are regenerated too")
     return p
 
 
@@ -149,6 +160,71 @@ def sample_cond(model, instance, n_samples=1, ddim_steps=50, ddim_eta=0.0, noise
         return torch.cat([samples, gen_mask], dim=1)
 
 
+def check_edit_options(opt) -> bool:
+    """The CT editing flags, checked by name before a model is loaded.  True when the run edits."""
+    if opt.known_ct is None:
+        if opt.known_mask is not None or opt.keep_mask is not None or opt.edit_margin != 0:
+            raise SystemExit("--known-mask / --keep-mask / --edit-margin edit a known CT: give --known-ct DIR")
+        return False
+    if not opt.inputs:
+        raise SystemExit("--known-ct pairs known CT volumes with the label volumes of --inputs DIR")
+    if (opt.known_mask is None) == (opt.keep_mask is None):
+        raise SystemExit("--known-ct needs exactly one of --known-mask DIR and --keep-mask DIR")
+    for name in ("known_ct", "known_mask", "keep_mask"):
+        d = getattr(opt, name)
+        if d is not None and not os.path.isdir(d):
+            raise SystemExit(f"--{name.replace('_', '-')} {d!r} is not a directory")
+    if opt.edit_margin < 0:
+        raise SystemExit(f"--edit-margin {opt.edit_margin}: must be >= 0")
+    if opt.vanilla_sample:
+        raise SystemExit("--known-ct: -v / --vanilla_sample is not supported (CT editing runs the DDIM sampler at eta 0)")
+    if opt.plms:
+        raise SystemExit("--known-ct: --plms is not supported (CT editing runs the DDIM sampler at eta 0)")
+    if opt.eta > 0:
+        raise SystemExit(f"--known-ct: eta = {opt.eta} is not supported (CT editing runs the DDIM sampler at eta 0)")
+    if opt.n_samples > 1:
+        raise SystemExit(f"--known-ct: n_samples = {opt.n_samples} is not supported (one edited CT per known volume)")
+    return True
+
+
+def _paired_volume(directory: str, stem: str, flag: str) -> np.ndarray:
+    found = [f for f in (os.path.join(directory, stem + ext) for ext in (".nii.gz", ".nii")) if os.path.exists(f)]
+    if not found:
+        raise SystemExit(f"{flag} {directory!r}: no volume named {stem}.nii.gz / {stem}.nii (volumes pair with --inputs by stem)")
+    return np.ascontiguousarray(read_nifti(found[0]))
+
+
+@torch.no_grad()
+def edit_volume(pipe, opt, stem: str, labels: np.ndarray, seed: int):
+    """One edited volume of --known-ct: (ct fp32 [slices, size, size] on the device, its entry of metrics.json's edit block)."""
+    shape = (opt.slices, opt.size, opt.size)
+    known = _paired_volume(opt.known_ct, stem, "--known-ct")
+    if tuple(known.shape) != shape:
+        raise SystemExit(f"--known-ct: {stem} has shape {tuple(known.shape)}, --slices x --size x --size is {shape} (nothing is resampled)")
+    known = torch.from_numpy(known.astype(np.float32))
+    if not (float(known.min()) >= 0.0 and float(known.max()) <= 1.0):
+        raise SystemExit(f"--known-ct: {stem} holds values {float(known.min()):g}..{float(known.max()):g} outside [0, 1]")
+    lab = torch.as_tensor(np.ascontiguousarray(labels)).to(device="cuda", dtype=torch.int32)[None].contiguous()
+    if opt.keep_mask is not None:
+        keep = _paired_volume(opt.keep_mask, stem, "--keep-mask")
+        if tuple(keep.shape) != shape:
+            raise SystemExit(f"--keep-mask: {stem} has shape {tuple(keep.shape)}, --slices x --size x --size is {shape}")
+        keep = (torch.from_numpy(keep) != 0).to(device="cuda", dtype=torch.uint8)[None]
+    else:
+        old = _paired_volume(opt.known_mask, stem, "--known-mask")
+        if tuple(old.shape) != tuple(lab.shape[1:]):
+            raise SystemExit(f"--known-mask: {stem} has shape {tuple(old.shape)}, the edited label volume {tuple(lab.shape[1:])}")
+        keep = pipe.ct_keep_from_labels(torch.as_tensor(old).to(device="cuda", dtype=torch.int32)[None].contiguous(), lab, opt.slices, opt.size)
+    known = known.cuda()[None]
+    ct = pipe.sample_ct_volumes(lab, opt.slices, opt.size, [seed], known_ct=known, keep=keep, edit_margin=opt.edit_margin)[0]
+    kb = keep[0] != 0
+    diff = float((ct[kb] - known[0][kb]).abs().max()) if bool(kb.any()) else 0.0
+    doc = dict(volume=stem, kept_fraction=float(kb.float().mean()), slices_visited=int(pipe.stats["slices_visited"]),
+               slices_skipped_kept=int(pipe.stats["slices_skipped_kept"]), slices_mixed=int(pipe.stats["slices_mixed"]),
+               unkept_outside_window=int(pipe.stats["unkept_outside_window"]), kept_max_abs_diff=diff)
+    return ct, doc
+
+
 def render_input(x: torch.Tensor) -> torch.Tensor:
     """One sampled volume [2, D, H, W] = (CT, label / 255) as render.combine_mask_and_im takes it: (CT, label / 11).  The reference
     renders `pred` as it is (sample_diffusion.py:257); label / 255 * 11 truncates to 0 for every label, so nothing would be painted."""
@@ -164,6 +240,7 @@ def main(argv=None):
         raise SystemExit("--progress-png goes with -v / --vanilla_sample (the denoise row comes from progressive_denoising)")
     if opt.log_every_t is not None and not opt.progress_png:
         raise SystemExit("--log-every-t goes with --progress-png")
+    editing = check_edit_options(opt)
     scorer = None
     if all(scoring):                         # weights and directory are checked before anything is sampled
         from .lpips import LPIPS
@@ -197,14 +274,33 @@ def main(argv=None):
         files = sorted(f for f in glob.glob(os.path.join(opt.inputs, "*.nii*")) if f.endswith((".nii", ".nii.gz")))
         if not files:
             raise SystemExit(f"--inputs {opt.inputs!r}: no *.nii / *.nii.gz label volumes found")
+        label_volumes = {os.path.basename(f).split(".nii")[0]: read_nifti(f) for f in files} if editing else None
         jobs = [(os.path.basename(f).split(".nii")[0], stage1_mask_to_wholemask(read_nifti(f), opt.slices, opt.size), opt.seed + i) for i, f in enumerate(files)]
     else:
         lab = torch.from_numpy(np.load(opt.mask)).long() if opt.mask else synth_mask_volume(opt.slices, opt.size, opt.size)
         jobs = [("sample", lab.float() / 255.0, opt.seed)]
     written = []
+    edit_docs = []
+    if editing:
+        if getattr(model, "no_first_stage", False):
+            raise SystemExit("--known-ct: a model without a first stage is not supported (the known slice is encoded by the first stage)")
+        from .pipeline import GuideGenPipeline
+        pipe = GuideGenPipeline(None, model, opt.custom_steps)
     for stem, wholemask, seed in jobs:
         instance = {"wholemask": wholemask[None, ..., None]}
         t0 = time.time()
+        if editing:
+            with model.ema_scope():
+                ct, doc = edit_volume(pipe, opt, stem, label_volumes[stem], seed)
+            torch.cuda.synchronize()
+            edit_docs.append(doc)
+            write_nifti(os.path.join(out_dir, f"{stem}_0000.nii.gz"), ct.float().cpu().numpy())
+            written.append(os.path.join(out_dir, f"{stem}_0000.nii.gz"))
+            if opt.png:
+                volume_png(render_input(torch.stack([ct, wholemask.to(ct.device)])), os.path.join(out_dir, f"{stem}_0000.png"))
+            print(f"edited {tuple(ct.shape)} in {time.time() - t0:.1f}s ({doc['slices_visited']} slices visited, {doc['slices_skipped_kept']} kept "
+                  f"whole) -> {out_dir}/{stem}_0000.nii.gz", file=sys.stderr)
+            continue
         progress = dict(log_every_t=opt.log_every_t) if opt.progress_png else None
         pred = sample_cond(model, instance, n_samples=opt.n_samples, ddim_steps=opt.custom_steps, ddim_eta=opt.eta, noise_seed=seed,
                            vanilla=opt.vanilla_sample, plms=opt.plms, progress=progress)
@@ -217,12 +313,17 @@ def main(argv=None):
             if opt.png:
                 volume_png(render_input(x), os.path.join(out_dir, f"{stem}_{ix:04d}.png"))
         print(f"sampled {tuple(pred.shape)} in {time.time() - t0:.1f}s -> {out_dir}/{stem}_*.nii.gz", file=sys.stderr)
-    if scorer is not None:
+    if scorer is not None or editing:
         import json
-        from .lpips import score_directory
-        doc = score_directory(scorer.cuda(), written, opt.gt, torch.device("cuda"))
+        doc = {}
+        if scorer is not None:
+            from .lpips import score_directory
+            doc = score_directory(scorer.cuda(), written, opt.gt, torch.device("cuda"))
+        if editing:
+            doc["edit"] = dict(edit_margin=opt.edit_margin, known_mask=opt.known_mask, keep_mask=opt.keep_mask, volumes=edit_docs)
         with open(os.path.join(out_dir, "metrics.json"), "w") as f:
             json.dump(doc, f, indent=1)
+    if scorer is not None:
         print(f"mean LPIPS {doc['mean_lpips']:.5f} over {len(written)} volume(s) -> {out_dir}/metrics.json", file=sys.stderr)
 
 
