@@ -172,6 +172,10 @@ int gg_conv_fuses_prologue(const gg_conv_desc *desc);
 int gg_conv_fuses_posterior(const gg_conv_desc *desc);
 /* 1 if gg_conv_forward(desc) runs this shape on the halo-tile kernel (3x3(x3), stride 1, filled grid). Pointers are not read. */
 int gg_conv_runs_halo_tile(const gg_conv_desc *desc);
+/* 1 if gg_conv_forward(desc) runs this shape on the streaming 1x1 tile kernel (stride 1, one or two power-of-two sources, Cout_pad 64 /
+ * 128, bf16 output, no prologue / residual / fused epilogue, at least 64^3 positions), else 0.  path_hint 12 (tests, A/B) is production
+ * dispatch with this kernel switched off: the gather kernel then runs these shapes, with byte-identical results.  Pointers are not read. */
+int gg_conv_runs_tile(const gg_conv_desc *desc);
 /* 0 if gg_conv_forward(desc) will not fill desc->gn_acc, else the number of stripes S of the [N][S][Cout_pad][2] accumulator it fills
  * (1 for the box / 160-step kernels, 32 for the halo-tile kernel); pointers are not read. */
 int gg_conv_emits_stats(const gg_conv_desc *desc);

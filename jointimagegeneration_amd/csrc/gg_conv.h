@@ -55,6 +55,10 @@ struct ConvParams {
 #define GG_HALO_HINT_BOX1024 6
 #define GG_HALO_HINT_TEAM 7        /* the team kernel (gg_conv_halo3.hip) wherever its envelope allows */
 #define GG_HALO_HINT_NO_TEAM 8     /* production dispatch without the team kernel */
+// path_hint of the tile kernels (gg_conv_tile.hip; tests, A/B): production dispatch in every other respect, but the tile kernels decline,
+// so that their shapes run on the gather kernel as they did before
+#define GG_CONV_HINT_GATHER 12
+static inline bool gg_hint_is_production(int hint) { return hint == 0 || hint == GG_CONV_HINT_GATHER; }
 
 // fixed-point scales of the GroupNorm accumulators: |sum| < 2^35, sumsq < 2^43 per channel and sample
 #define GG_ACC_SUM_SCALE 268435456.0f   /* 2^28 */
@@ -84,3 +88,30 @@ __device__ __forceinline__ float gg_row16_sum(float x)
     x += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0x140, 0xF, 0xF, true));   // row_mirror
     return x;
 }
+
+// ---- the bf16 / fp32 epilogue value of the single-pass kernels (conv_gather_kernel, gg_conv_tile.hip), stated once so that the two cannot
+// drift: accumulator + bias row (+ residual), channels beyond Cout zeroed; then round-to-nearest-even to bf16.
+__device__ __forceinline__ f32x4 gg_conv_epi_value(f32x4 acc, bool has_bias, f32x4 bv, bool has_res, bf16x4 res, int co, int Cout)
+{
+    f32x4 v = acc;
+    if (has_bias) v += bv;
+    if (has_res) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] += (float)res[j];
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (co + j >= Cout) v[j] = 0.f;
+    return v;
+}
+__device__ __forceinline__ bf16x4 gg_conv_epi_bf16(f32x4 v)
+{
+    bf16x4 ob;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ob[j] = (bf16_t)v[j];
+    return ob;
+}
+
+// streaming 1x1 tile kernel (gg_conv_tile.hip); same contract as gg_conv_halo_try.  gg_conv_tile_family: 0 = declines, 1 = streaming 1x1
+int gg_conv_tile_try(const ConvParams &p, hipStream_t stream);
+int gg_conv_tile_family(const ConvParams &p);

@@ -266,24 +266,12 @@ __global__ __launch_bounds__(256) void conv_gather_kernel(const ConvParams p)
 #pragma unroll
         for (int ct = 0; ct < 2 * NT; ++ct) {
             int co = (g0 * 32) + ct * 16 + fq * 4;
-            f32x4 v = acc[pt][ct];
-            if (p.bias) v += bv[pt][ct];
+            const f32x4 v = gg_conv_epi_value(acc[pt][ct], p.bias != nullptr, bv[pt][ct], p.residual != nullptr, resv[pt][ct], co, p.Cout);
             long long o = m * p.Cout_pad + co;
-            if (p.residual) {
-                const bf16x4 r = resv[pt][ct];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] += (float)r[j];
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (co + j >= p.Cout) v[j] = 0.f;
             if (p.out_dtype == GG_F32) {
                 *reinterpret_cast<f32x4 *>((float *)p.out + o) = v;
             } else {
-                bf16x4 ob;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) ob[j] = (bf16_t)v[j];
-                *reinterpret_cast<bf16x4 *>((bf16_t *)p.out + o) = ob;
+                *reinterpret_cast<bf16x4 *>((bf16_t *)p.out + o) = gg_conv_epi_bf16(v);
             }
         }
     }
@@ -787,7 +775,7 @@ extern "C" int gg_conv_fuses_prologue(const gg_conv_desc *d)
     ConvParams p;
     fill_params(d, p);
     // halo-tile convs CAN always fuse it; the answer is whether they should (measured rule in gg_conv_halo.hip)
-    if (halo_try_dry(p)) return (GG_HALO_SEPARATE_NORM && d->path_hint == 0 && gg_conv_halo_prefers_separate_norm(p)) ? 0 : 1;
+    if (halo_try_dry(p)) return (GG_HALO_SEPARATE_NORM && gg_hint_is_production(d->path_hint) && gg_conv_halo_prefers_separate_norm(p)) ? 0 : 1;
     if (box_try_dry(p)) return gg_conv_box_fuses_prologue(p) ? 1 : 0;
     // GroupNorm*SiLU inside the 160-step gather loop was measured slower (26 vs 16.6 us per conv: SiLU on the load -> LDS critical
     // path once per tap), so the gather kernels never fuse the prologue
@@ -853,6 +841,16 @@ extern "C" int gg_conv_emits_stats(const gg_conv_desc *d)
     if (gg_conv_tiny_plan(p.M, p.Cout_pad, p.ntaps * p.nchunk, p.prologue_act)) return 0;
     const long long osp = (long long)d->Do * d->Ho * d->Wo;
     return (plan_gather5(p.M, p.C1, p.C2, p.Cout_pad, p.ntaps) == 1 && osp % 64 == 0) ? GG_ACC_STRIPES : 0;
+}
+
+// 0: gg_conv_forward does not run this descriptor on a tile kernel (gg_conv_tile.hip); 1: the streaming 1x1 kernel.
+extern "C" int gg_conv_runs_tile(const gg_conv_desc *d)
+{
+    if (!desc_channels_ok(d) || d->epilogue_geglu || d->skip_C1 || d->ddim_x || d->post_xt) return 0;
+    ConvParams p;
+    fill_params(d, p);
+    if (halo_try_dry(p) || box_try_dry(p)) return 0;
+    return gg_conv_tile_family(p);
 }
 
 #ifdef GG_EXP_WPREFETCH
@@ -948,6 +946,10 @@ extern "C" int gg_conv_forward(const gg_conv_desc *d, void *stream_)
 #ifdef GG_BOX_STAMPS
     p.ws = nullptr;
 #endif
+    if (rc != GG_ERR_UNSUPPORTED) return rc;
+
+    // streaming 1x1 on big grids (gg_conv_tile.hip): byte-identical to the gather kernel, which takes whatever it declines
+    rc = gg_conv_tile_try(p, stream);
     if (rc != GG_ERR_UNSUPPORTED) return rc;
 
     if (int tsk = gg_conv_tiny_plan(p.M, p.Cout_pad, p.ntaps * p.nchunk, p.prologue_act)) {

@@ -581,7 +581,7 @@ static HaloPlan halo_plan(const ConvParams &p)
 {
     HaloPlan pl{};
     const int hint = p.path_hint;
-    const bool prod = hint == 0 || hint == GG_HALO_HINT_NO_TEAM;
+    const bool prod = gg_hint_is_production(hint) || hint == GG_HALO_HINT_NO_TEAM;
     pl.d3 = (p.kd == 3); pl.up = p.upsample ? 1 : 0; pl.post = p.post_xt ? 1 : 0;
     const HaloBox b0 = halo_box(pl.d3, 0);
     const int G = p.Cout_pad / 32;
