@@ -176,6 +176,16 @@ int gg_conv_runs_halo_tile(const gg_conv_desc *desc);
  * 128, bf16 output, no prologue / residual / fused epilogue, at least 64^3 positions), else 0.  path_hint 12 (tests, A/B) is production
  * dispatch with this kernel switched off: the gather kernel then runs these shapes, with byte-identical results.  Pointers are not read. */
 int gg_conv_runs_tile(const gg_conv_desc *desc);
+/* 0 if gg_conv_forward(desc) does not run this shape on the split halo path, else its number of K slabs (the gather plan's split, so
+ * gg_conv_workspace_bytes(desc) == slabs * M * Cout_pad * 4 as before): 3x3x3, stride 1, pad 1, extents multiples of the 4x4x16 box, a grid
+ * too small for the halo-tile gate, no prologue / upsample / fused epilogue, whole chunks per slab.  path_hint 13 (tests, A/B) is production
+ * dispatch with this path switched off: the split gather kernel then runs these shapes, with byte-identical results.  Pointers are not read. */
+int gg_conv_runs_halo_split(const gg_conv_desc *desc);
+/* 1 if gg_conv_forward(desc) runs this shape on the stride-2 3x3x3 tile kernel: pad 1, even input extents, output extents multiples of the
+ * 2x4x16 tile, Cout_pad 128, no prologue / upsample / fused epilogue, and a grid that the gather kernel runs without a K split.
+ * path_hint 14 (or 12; tests, A/B) is production dispatch with this kernel switched off: the gather kernel then runs these shapes, with
+ * byte-identical results; path_hint 15 (tests only) lifts the grid condition.  Pointers are not read. */
+int gg_conv_runs_tile_s2(const gg_conv_desc *desc);
 /* 0 if gg_conv_forward(desc) will not fill desc->gn_acc, else the number of stripes S of the [N][S][Cout_pad][2] accumulator it fills
  * (1 for the box / 160-step kernels, 32 for the halo-tile kernel); pointers are not read. */
 int gg_conv_emits_stats(const gg_conv_desc *desc);

@@ -54,6 +54,8 @@ SIGNATURES = {
     "gg_conv_runs_halo_tile": (C.c_int, [C.POINTER(ConvDesc)]),
     "gg_conv_emits_stats": (C.c_int, [C.POINTER(ConvDesc)]),
     "gg_conv_runs_tile": (C.c_int, [C.POINTER(ConvDesc)]),
+    "gg_conv_runs_halo_split": (C.c_int, [C.POINTER(ConvDesc)]),
+    "gg_conv_runs_tile_s2": (C.c_int, [C.POINTER(ConvDesc)]),
     "gg_conv_prologue_from_acc": (C.c_int, [C.POINTER(ConvDesc)]),
     "gg_conv_fuses_skip": (C.c_int, [C.POINTER(ConvDesc)]),
     "gg_conv_fuses_ddim": (C.c_int, [C.POINTER(ConvDesc)]),

@@ -58,7 +58,17 @@ struct ConvParams {
 // path_hint of the tile kernels (gg_conv_tile.hip; tests, A/B): production dispatch in every other respect, but the tile kernels decline,
 // so that their shapes run on the gather kernel as they did before
 #define GG_CONV_HINT_GATHER 12
-static inline bool gg_hint_is_production(int hint) { return hint == 0 || hint == GG_CONV_HINT_GATHER; }
+// path_hint of the split halo path (gg_conv_runs_halo_split; tests, A/B): production dispatch in every other respect, but that path declines,
+// so that its shapes run on the split gather kernel as they did before
+#define GG_CONV_HINT_NO_HALO_SPLIT 13
+// path_hint of the stride-2 tile kernel (gg_conv_runs_tile_s2; tests, A/B): production dispatch with that kernel switched off (12 does the same)
+#define GG_CONV_HINT_NO_TILE_S2 14
+// tests only: the stride-2 tile kernel wherever its shape envelope allows, whatever the gather plan says (small shapes for the fp64 exact regimes)
+#define GG_CONV_HINT_TILE_S2 15
+static inline bool gg_hint_is_production(int hint)
+{
+    return hint == 0 || hint == GG_CONV_HINT_GATHER || hint == GG_CONV_HINT_NO_HALO_SPLIT || hint == GG_CONV_HINT_NO_TILE_S2;
+}
 
 // fixed-point scales of the GroupNorm accumulators: |sum| < 2^35, sumsq < 2^43 per channel and sample
 #define GG_ACC_SUM_SCALE 268435456.0f   /* 2^28 */
@@ -115,3 +125,9 @@ __device__ __forceinline__ bf16x4 gg_conv_epi_bf16(f32x4 v)
 // streaming 1x1 tile kernel (gg_conv_tile.hip); same contract as gg_conv_halo_try.  gg_conv_tile_family: 0 = declines, 1 = streaming 1x1
 int gg_conv_tile_try(const ConvParams &p, hipStream_t stream);
 int gg_conv_tile_family(const ConvParams &p);
+// stride-2 3x3x3 tile kernel (gg_conv_tile.hip): the shape envelope, and the launch for a shape that plan_tile_s2 (gg_conv.hip) has vetted
+bool gg_conv_tile_s2_family(const ConvParams &p);
+int gg_conv_tile_s2_launch(const ConvParams &p, hipStream_t stream);
+// one K slab per blockIdx.z on the 256-position 3-D halo box (gg_conv_halo.hip): p.splitk slabs of whole chunks into p.ws, no epilogue
+bool gg_conv_halo_split_box_fits(const ConvParams &p);
+int gg_conv_halo_split_launch(const ConvParams &p, hipStream_t stream);

@@ -853,6 +853,53 @@ extern "C" int gg_conv_runs_tile(const gg_conv_desc *d)
     return gg_conv_tile_family(p);
 }
 
+// The 3x3x3 stride-1 convs of 3-D grids too small for the halo-tile gate (CCDM 16^3 level at batch 1) ran on the split gather kernel, where every
+// workgroup gathers its activation rows again for each of the 27 taps.  The halo kernel's 256-position box stages a chunk once for all taps;
+// with the gather plan's own K split as a grid axis (whole chunks per slab: splitk | nchunk) it fills the chip as well, and because both kernels
+// walk chunk-outer / tap-inner with the same MFMA, the slabs hold the same fp32 partials and the fixed-order reduce gives the same bytes.
+// Returns the K split (that of plan_gather, so gg_conv_workspace_bytes stays what it was), 0 where the path declines.
+#ifndef GG_HALO_SPLIT
+#define GG_HALO_SPLIT 1        /* A/B switch: 0 = these shapes stay on the split gather kernel */
+#endif
+static int plan_halo_split(const gg_conv_desc *d, const ConvParams &p)
+{
+    if (!GG_HALO_SPLIT || !gg_hint_is_production(p.path_hint) || p.path_hint == GG_CONV_HINT_NO_HALO_SPLIT) return 0;
+    if (p.kd != 3 || p.kh != 3 || p.kw != 3 || p.stride != 1 || p.pad != 1 || p.upsample || p.prologue_act) return 0;
+    if (d->epilogue_geglu || d->post_xt || d->ddim_x || d->skip_C1) return 0;
+    if (halo_try_dry(p) || box_try_dry(p) || !gg_conv_halo_split_box_fits(p)) return 0;
+    if (gg_conv_tiny_plan(p.M, p.Cout_pad, p.ntaps * p.nchunk, p.prologue_act) || plan_gather5(p.M, p.C1, p.C2, p.Cout_pad, p.ntaps)) return 0;
+    const GatherPlan pl = plan_gather(p.M, p.Cout_pad, p.ntaps * p.nchunk);
+    return (pl.NT == 1 && pl.splitk >= 2 && p.nchunk % pl.splitk == 0) ? pl.splitk : 0;
+}
+
+// 0: gg_conv_forward does not run this descriptor on the split halo path; else its number of K slabs (= workspace bytes / (M * Cout_pad * 4)).
+extern "C" int gg_conv_runs_halo_split(const gg_conv_desc *d)
+{
+    if (!desc_channels_ok(d)) return 0;
+    ConvParams p;
+    fill_params(d, p);
+    return plan_halo_split(d, p);
+}
+
+// The stride-2 3x3x3 convs that the gather kernel runs in ONE pass (plan_gather: no K split -- with a split it is no bit reference for a
+// one-pass kernel) on the tile kernel of gg_conv_tile.hip, 128 couts only.  32^3 -> 16^3 and deeper split K and stay where they are.
+static bool plan_tile_s2(const gg_conv_desc *d, const ConvParams &p)
+{
+    if (!gg_conv_tile_s2_family(p) || halo_try_dry(p) || box_try_dry(p)) return false;
+    if (p.path_hint == GG_CONV_HINT_TILE_S2) return true;          // tests: small shapes, compared with fp64 only
+    if (gg_conv_tiny_plan(p.M, p.Cout_pad, p.ntaps * p.nchunk, p.prologue_act) || plan_gather5(p.M, p.C1, p.C2, p.Cout_pad, p.ntaps)) return false;
+    return plan_gather(p.M, p.Cout_pad, p.ntaps * p.nchunk).splitk == 1;
+}
+
+// 1 if gg_conv_forward runs this descriptor on the stride-2 tile kernel, else 0.
+extern "C" int gg_conv_runs_tile_s2(const gg_conv_desc *d)
+{
+    if (!desc_channels_ok(d)) return 0;
+    ConvParams p;
+    fill_params(d, p);
+    return plan_tile_s2(d, p) ? 1 : 0;
+}
+
 #ifdef GG_EXP_WPREFETCH
 __global__ __launch_bounds__(256) void exp_wprefetch_kernel(const u32x4 *w, long long n16, unsigned *sink)
 {
@@ -951,6 +998,16 @@ extern "C" int gg_conv_forward(const gg_conv_desc *d, void *stream_)
     // streaming 1x1 on big grids (gg_conv_tile.hip): byte-identical to the gather kernel, which takes whatever it declines
     rc = gg_conv_tile_try(p, stream);
     if (rc != GG_ERR_UNSUPPORTED) return rc;
+
+    // stride-2 3x3x3 on big grids: byte-identical to the one-pass gather kernel
+    if (plan_tile_s2(d, p)) return gg_conv_tile_s2_launch(p, stream);
+
+    // K split as a grid axis of the halo-tile kernel: byte-identical to the split gather kernel, which takes whatever this declines
+    if (int hs = plan_halo_split(d, p)) {
+        if ((rc = take_splitk_workspace(d, p, hs)) != GG_OK) return rc;
+        if ((rc = gg_conv_halo_split_launch(p, stream)) != GG_OK) return rc;
+        return launch_splitk_reduce(p, stream, true);
+    }
 
     if (int tsk = gg_conv_tiny_plan(p.M, p.Cout_pad, p.ntaps * p.nchunk, p.prologue_act)) {
         if ((rc = take_splitk_workspace(d, p, tsk)) != GG_OK) return rc;

@@ -75,9 +75,13 @@ struct HaloGeom {
     static_assert(!TS || TS_END <= LDSB, "transposed-store scratch ends outside the LDS allocation");
 };
 
-template <int D3, int NT, int UP, int HB, int POST = 0>
+// EPI: 0 = the bias / residual / statistics epilogue, 1 = the fused CCDM reverse step (POST), 2 = one K slab of a split conv (SPLIT):
+// blockIdx.z owns the chunks [nchunk * z / splitk, nchunk * (z + 1) / splitk) and leaves its raw fp32 accumulators in the gather kernel's
+// slab layout p.ws[z][m][co] for conv_splitk_reduce_kernel -- no bias, residual or statistics here.
+template <int D3, int NT, int UP, int HB, int EPI = 0>
 __global__ __launch_bounds__((HaloGeom<D3, NT, UP, HB>::NTHR), (HaloGeom<D3, NT, UP, HB>::LB_MIN)) void conv_halo_kernel(const ConvParams p, const int tiles_d, const int tiles_h, const int tiles_w)
 {
+    constexpr bool POST = EPI == 1, SPLIT = EPI == 2;
     using G = HaloGeom<D3, NT, UP, HB>;
     constexpr int TD = G::TD, TH = G::TH, TW = G::TW, NWAVE = G::NWAVE, TPW = G::TPW, NTHR = G::NTHR, HH = G::HH, HW = G::HW;
     constexpr int NROWS = G::NROWS, XBYTES = G::XBYTES, WBYTES = G::WBYTES, GSZ = G::GSZ;
@@ -155,10 +159,12 @@ __global__ __launch_bounds__((HaloGeom<D3, NT, UP, HB>::NTHR), (HaloGeom<D3, NT,
         od = D3 ? tile / TH : 0; oh = D3 ? tile % TH : tile;
         return (((long long)n * p.Do + (d0 + od)) * p.Ho + (h0 + oh)) * p.Wo + (w0 + pw);
     };
-    const int KS = p.nchunk * NTAPS;
-    issue_w(0, 0);
+    const int c_begin = SPLIT ? (int)(p.nchunk * blockIdx.z) / p.splitk : 0;
+    const int c_end = SPLIT ? (int)(p.nchunk * (blockIdx.z + 1)) / p.splitk : p.nchunk;
+    const int KS = c_end * NTAPS;
+    issue_w(c_begin * NTAPS, SPLIT ? (c_begin * NTAPS / GSZ) & 1 : 0);      // (the slot of a tap or line is the parity of its index)
 
-    for (int chunk = 0; chunk < p.nchunk; ++chunk) {
+    for (int chunk = c_begin; chunk < c_end; ++chunk) {
         // ================= stage the input box of this chunk (all threads) =================
         {
             const bool second = chunk >= p.nchunk1;
@@ -276,6 +282,18 @@ __global__ __launch_bounds__((HaloGeom<D3, NT, UP, HB>::NTHR), (HaloGeom<D3, NT,
         }
     }
 
+    if constexpr (SPLIT) {
+        // ===== split-K slab: the accumulator layout gives a lane 4 consecutive couts of one position, as in conv_gather_kernel =====
+#pragma unroll
+        for (int tt = 0; tt < TPW; ++tt) {
+            int od, oh;
+            const long long m = tile_at(tt, fr, od, oh);
+#pragma unroll
+            for (int ct = 0; ct < 2 * NT; ++ct)
+                *reinterpret_cast<f32x4 *>(p.ws + ((long long)blockIdx.z * p.M + m) * p.Cout_pad + g0 * 32 + ct * 16 + fq * 4) = acc[tt][ct];
+        }
+        return;
+    }
     // ================= epilogue: + bias[n] (+ residual) -> bf16 / fp32 =================
     const float *brow = p.bias ? p.bias + (long long)n * p.bias_stride : nullptr;
     // GroupNorm statistics of the NEXT norm (gg_conv_desc.gn_acc): per output channel, sum and sum of squares of the bf16-rounded
@@ -521,7 +539,7 @@ struct HaloPlan {
     long long blocks;         // workgroups at the 512-position box: the figure that the gate and the box-size rules were fitted on
 };
 
-template <int D3, int NT, int UP, int HB = 0, int POST = 0>
+template <int D3, int NT, int UP, int HB = 0, int EPI = 0>
 static int launch_halo(const ConvParams &p, const HaloPlan &pl, hipStream_t stream)
 {
     using G = HaloGeom<D3, NT, UP, HB>;
@@ -531,11 +549,11 @@ static int launch_halo(const ConvParams &p, const HaloPlan &pl, hipStream_t stre
     if (hipGetDevice(&dev) != hipSuccess) return GG_ERR_HIP;
     const unsigned long long dev_bit = 1ull << (dev & 63);
     if (!(attr_mask.load(std::memory_order_acquire) & dev_bit)) {
-        if (hipFuncSetAttribute((const void *)conv_halo_kernel<D3, NT, UP, HB, POST>, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDSB) != hipSuccess) return GG_ERR_UNSUPPORTED;
+        if (hipFuncSetAttribute((const void *)conv_halo_kernel<D3, NT, UP, HB, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDSB) != hipSuccess) return GG_ERR_UNSUPPORTED;
         attr_mask.fetch_or(dev_bit, std::memory_order_release);
     }
-    dim3 grid((unsigned)(p.N * pl.tiles_d * pl.tiles_h * pl.tiles_w), (unsigned)(p.Cout_pad / (32 * NT)));
-    hipLaunchKernelGGL((conv_halo_kernel<D3, NT, UP, HB, POST>), grid, dim3(G::NTHR), G::LDSB, stream, p, pl.tiles_d, pl.tiles_h, pl.tiles_w);
+    dim3 grid((unsigned)(p.N * pl.tiles_d * pl.tiles_h * pl.tiles_w), (unsigned)(p.Cout_pad / (32 * NT)), EPI == 2 ? (unsigned)p.splitk : 1u);
+    hipLaunchKernelGGL((conv_halo_kernel<D3, NT, UP, HB, EPI>), grid, dim3(G::NTHR), G::LDSB, stream, p, pl.tiles_d, pl.tiles_h, pl.tiles_w);
     GG_CHECK_LAUNCH();
     return GG_OK;
 }
@@ -637,6 +655,23 @@ bool gg_conv_halo_fuses_posterior(const ConvParams &p)
     if (p.Cout > 16 || p.Cout_pad != 32 || p.out_dtype != GG_F32 || p.residual || p.gn_acc) return false;
     const HaloPlan pl = halo_plan(p);
     return pl.ok && pl.HB == 2;
+}
+
+// K split as a grid axis (gg_conv_runs_halo_split, gg_conv.hip): 3-D grids too small for the gate above run the 256-position box with one
+// cout group per workgroup and blockIdx.z = the slab of p.splitk whole-chunk ranges; the caller has vetted the shape (3x3x3 stride 1 pad 1,
+// extents multiples of the box, no prologue / upsample / fused epilogue, splitk | nchunk), taken the workspace and runs the reduce.
+bool gg_conv_halo_split_box_fits(const ConvParams &p)
+{
+    constexpr HaloBox b = halo_box(true, 1);
+    return p.Do % b.TD == 0 && p.Ho % b.TH == 0 && p.Wo % b.TW == 0;
+}
+int gg_conv_halo_split_launch(const ConvParams &p, hipStream_t stream)
+{
+    constexpr HaloBox b = halo_box(true, 1);
+    if (!gg_conv_halo_split_box_fits(p) || p.splitk < 2 || p.nchunk % p.splitk || !p.ws) return GG_ERR_UNSUPPORTED;
+    HaloPlan pl{};
+    pl.tiles_d = p.Do / b.TD; pl.tiles_h = p.Ho / b.TH; pl.tiles_w = p.Wo / b.TW;
+    return launch_halo<1, 1, 0, 1, 2>(p, pl, stream);
 }
 
 // Returns GG_ERR_UNSUPPORTED (silently, no error text) when the shape is outside the envelope: the caller then uses the

@@ -238,3 +238,207 @@ int gg_conv_tile_try(const ConvParams &p, hipStream_t stream)
     if (CT == 8 && p.nchunk == 8) return launch_tile1x1<8, 8>(p, stream);
     return GG_ERR_UNSUPPORTED;
 }
+
+// ------------------------------------------------------------------------------------------ stride-2 3x3x3 tile conv
+// The 128-cout Downsample conv of the CCDM UNet (128 -> 128 @64^3 -> 32^3), byte-identical to conv_gather_kernel without a K split.
+// (64 couts -- 64 -> 64 @128^3 -> 64^3 -- were measured a tie, 172 us on both kernels: 64-byte slices of 128-byte rows, fetched twice;
+// that width is not instantiated.)  One workgroup owns a 2x4x16 output tile and all couts.  Per 32-channel chunk the 5x9x33 input
+// rows that the tile's 27 taps touch are staged ONCE (all of a thread's pieces in flight together); the columns of a W-line are stored
+// de-interleaved by parity (17 even columns, then 16 odd ones), so that the 16 lanes of an operand read (outputs ow .. ow + 15 of tap kw:
+// input columns 2 ow + kw) take 16 CONSECUTIVE rows and swz64 keeps them conflict-free as in the gather kernel.  The three kw taps of a
+// (kd, kh) line share one weight round (global_load_lds into a double-buffered slot, as in conv_halo_kernel) and one barrier.
+// Bit-identity: chunk-outer, (kd, kh, kw)-inner from a zero accumulator, v_mfma_f32_16x16x32_bf16 with A = weights, zero rows for the
+// padding, then gg_conv_epi_value / gg_conv_epi_bf16: what conv_gather_kernel computes for splitk == 1.  No GroupNorm sums, as there.
+#ifndef GG_TILE_S2
+#define GG_TILE_S2 1          /* A/B switch: 0 = the stride-2 tile kernel declines everything (the gather kernel runs, as before) */
+#endif
+
+template <int NT>
+struct TileS2Geom {
+    static constexpr int TD = 2, TH = 4, TW = 16;                               // output tile
+    static constexpr int ID = 2 * TD + 1, IH = 2 * TH + 1, IW = 2 * TW + 1;    // input box: 5 x 9 x 33 rows of 64 B
+    static constexpr int WE = TW + 1;                                          // even columns of a W-line (17) come first, then the odd ones (16)
+    static constexpr int NROWS = ID * IH * IW;
+    static constexpr int XBYTES = ((NROWS * 64 + 1023) / 1024) * 1024;
+    static constexpr int WBYTES = NT * 2048;                                   // one tap: 32 NT cout rows x 64 B
+    static constexpr int LDSB = XBYTES + 2 * 3 * WBYTES;                       // the box image, then two slots of three taps
+    // eight waves, one W-row of 16 outputs each: with four (two rows each) a lone wave per SIMD issued the staging and operand-address
+    // instructions of a chunk at ~6 ticks each (128 -> 128 @64^3: 69 us; with eight 59 us; the gather kernel 89 us)
+    static constexpr int NTHR = 512, NWAVE = 8, TPW = TD * TH / NWAVE;
+    static constexpr int JMAX = (NROWS * 4 + NTHR - 1) / NTHR;                 // 16-byte pieces per thread and chunk
+    static_assert(TD * TH == NWAVE * TPW, "every wave owns the same number of position tiles");
+    static_assert(LDSB <= 160 * 1024, "box image + weight slots exceed the LDS of a CU");
+    // last operand row: input line (2 (TD - 1) + 2, 2 (TH - 1) + 2), tap kw 1 (odd columns), lane 15
+    static_assert(((ID - 1) * IH + IH - 1) * IW + WE + TW - 1 < NROWS && 1 + TW - 1 < WE, "operand rows inside the box image");
+    static_assert((2 * 3 - 1) * WBYTES + (NT * 2 - 1) * 1024 + 1024 <= 2 * 3 * WBYTES, "weight pieces inside the slots");
+};
+
+template <int NT>
+__global__ __launch_bounds__((TileS2Geom<NT>::NTHR), 1) void conv_tile_s2_kernel(const ConvParams p, const int tiles_d, const int tiles_h, const int tiles_w)
+{
+    using G = TileS2Geom<NT>;
+    constexpr int IH = G::IH, IW = G::IW, WE = G::WE, NROWS = G::NROWS, WBYTES = G::WBYTES, TPW = G::TPW, JMAX = G::JMAX;
+    extern __shared__ __attribute__((aligned(1024))) char smem[];      // G::LDSB bytes
+    char *xs = smem, *wsm = smem + G::XBYTES;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int fr = lane & 15, fq = lane >> 4;
+
+    int t = blockIdx.x;
+    const int tw = t % tiles_w; t /= tiles_w;
+    const int th = t % tiles_h; t /= tiles_h;
+    const int td = t % tiles_d;
+    const int n = t / tiles_d;
+    const int od0 = td * G::TD, oh0 = th * G::TH, ow0 = tw * G::TW;          // output-tile origin
+    const int id0 = 2 * od0 - 1, ih0 = 2 * oh0 - 1, iw0 = 2 * ow0 - 1;       // input coordinates of box row (0, 0, 0)
+    const int xq = tid & 3;
+
+    // weight round of line gl = chunk * 9 + (kd * 3 + kh): its three kw taps, NT contiguous 2 KiB groups each, strided by 27 * nchunk * 2 KiB
+    auto issue_w = [&](int gl, int buf) {
+        const int chunk = gl / 9, tap0 = (gl - chunk * 9) * 3;
+        constexpr int NP = 3 * NT * 2;                  // 1 KiB pieces of the slot
+#pragma unroll
+        for (int i = 0; i < (NP + G::NWAVE - 1) / G::NWAVE; ++i) {
+            const int piece = wave + G::NWAVE * i;
+            if (piece < NP) {
+                const int u = piece / (NT * 2), piece1k = piece - u * (NT * 2);
+                const int g = piece1k >> 1, half = piece1k & 1;
+                const bf16_t *src = p.weight + ((((long long)g * 27 + tap0 + u) * p.nchunk + chunk) << 10) + half * 512 + lane * 8;
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
+                                                 (__attribute__((address_space(3))) void *)(wsm + (buf * 3 + u) * WBYTES + piece1k * 1024), 16, 0, 0);
+            }
+        }
+    };
+
+    f32x4 acc[TPW][2 * NT];
+#pragma unroll
+    for (int a = 0; a < TPW; ++a)
+#pragma unroll
+        for (int b = 0; b < 2 * NT; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    const int KL = p.nchunk * 9;
+    issue_w(0, 0);
+    for (int chunk = 0; chunk < p.nchunk; ++chunk) {
+        // ================= stage the input box of this chunk: every piece of the thread requested before the first is written =================
+        {
+            const bool second = chunk >= p.nchunk1;
+            const bf16_t *src = second ? p.src2 : p.src1;
+            const int Cs = second ? p.C2 : p.C1;
+            const int coff = (second ? chunk - p.nchunk1 : chunk) * 32 + xq * 8;
+            const bf16_t *srcn = src + (long long)n * p.D * p.H * p.W * Cs + coff;
+            u32x4 v[JMAX];
+            int lrow[JMAX];                 // LDS row of the piece; -1: beyond the box (last round); bit 30: padding (stored as zeros)
+#pragma unroll
+            for (int j = 0; j < JMAX; ++j) {
+                const int row = (tid >> 2) + (G::NTHR / 4) * j;          // box rows in input order (hd, hh, column): a W-line is one contiguous run
+                const int hd = row / (IH * IW), rem = row - hd * (IH * IW), hh = rem / IW, iwl = rem - hh * IW;
+                const int id = id0 + hd, ih = ih0 + hh, iw = iw0 + iwl;
+                const bool in = row < NROWS;
+                const bool ok = in && (unsigned)id < (unsigned)p.D && (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W;
+                const unsigned pos = ok ? (unsigned)((id * p.H + ih) * p.W + iw) : 0u;      // (padding: a valid address, the value is dropped)
+                v[j] = *reinterpret_cast<const u32x4 *>(srcn + pos * (unsigned)Cs);
+                lrow[j] = in ? (((hd * IH + hh) * IW + (iwl & 1) * WE + (iwl >> 1)) | (ok ? 0 : (1 << 30))) : -1;
+            }
+#pragma unroll
+            for (int j = 0; j < JMAX; ++j) {
+                if (lrow[j] >= 0) {
+                    const int lr = lrow[j] & ~(1 << 30);
+                    const u32x4 val = (lrow[j] >> 30) ? u32x4{0u, 0u, 0u, 0u} : v[j];
+                    *reinterpret_cast<u32x4 *>(xs + lr * 64 + swz64(lr, xq) * 16) = val;
+                }
+            }
+        }
+        __syncthreads();          // box visible; the first weight round of the chunk has landed too
+
+#pragma unroll 1
+        for (int kd = 0; kd < 3; ++kd) {
+#pragma unroll 1
+            for (int kh = 0; kh < 3; ++kh) {
+                const int gl = chunk * 9 + kd * 3 + kh;
+                if (gl + 1 < KL) issue_w(gl + 1, (gl + 1) & 1);
+#pragma unroll
+                for (int kw = 0; kw < 3; ++kw) {
+                    const char *wb = wsm + ((gl & 1) * 3 + kw) * WBYTES;
+                    bf16x8 xf[TPW];
+#pragma unroll
+                    for (int tt = 0; tt < TPW; ++tt) {
+                        const int tile = wave * TPW + tt, od = tile / G::TH, oh = tile % G::TH;
+                        const int row = ((2 * od + kd) * IH + 2 * oh + kh) * IW + (kw == 1 ? WE : 0) + (kw == 2 ? 1 : 0) + fr;
+                        xf[tt] = *reinterpret_cast<const bf16x8 *>(xs + row * 64 + swz64(row, fq) * 16);
+                    }
+#pragma unroll
+                    for (int ct = 0; ct < 2 * NT; ++ct) {
+                        const int r = ct * 16 + fr;
+                        const bf16x8 wf = *reinterpret_cast<const bf16x8 *>(wb + r * 64 + swz64(r, fq) * 16);   // image pre-swizzled at pack time
+#pragma unroll
+                        for (int tt = 0; tt < TPW; ++tt)
+                            acc[tt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, xf[tt], acc[tt][ct], 0, 0, 0);
+                    }
+                }
+                __syncthreads();       // next line's weights landed; this line's slot / (after the last line) the box may be overwritten
+            }
+        }
+    }
+
+    // ================= epilogue: the gather kernel's; every bias / residual load in front of the first store =================
+    const float *brow = p.bias ? p.bias + (long long)n * p.bias_stride : nullptr;
+    f32x4 bv[2 * NT];
+    bf16x4 resv[TPW][2 * NT];
+    long long ob[TPW];
+#pragma unroll
+    for (int ct = 0; ct < 2 * NT; ++ct) bv[ct] = brow ? *reinterpret_cast<const f32x4 *>(brow + ct * 16 + fq * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int tt = 0; tt < TPW; ++tt) {
+        const int tile = wave * TPW + tt, od = tile / G::TH, oh = tile % G::TH;
+        const long long m = (((long long)n * p.Do + (od0 + od)) * p.Ho + (oh0 + oh)) * p.Wo + (ow0 + fr);
+        ob[tt] = m * p.Cout_pad + fq * 4;
+#pragma unroll
+        for (int ct = 0; ct < 2 * NT; ++ct)
+            if (p.residual) resv[tt][ct] = *reinterpret_cast<const bf16x4 *>(p.residual + ob[tt] + ct * 16);
+    }
+#pragma unroll
+    for (int tt = 0; tt < TPW; ++tt)
+#pragma unroll
+        for (int ct = 0; ct < 2 * NT; ++ct) {
+            const f32x4 val = gg_conv_epi_value(acc[tt][ct], p.bias != nullptr, bv[ct], p.residual != nullptr, resv[tt][ct], ct * 16 + fq * 4, p.Cout);
+            const long long o = ob[tt] + ct * 16;
+            if (p.out_dtype == GG_F32) *reinterpret_cast<f32x4 *>((float *)p.out + o) = val;
+            else *reinterpret_cast<bf16x4 *>((bf16_t *)p.out + o) = gg_conv_epi_bf16(val);
+        }
+}
+
+// shape envelope only; the caller (plan_tile_s2, gg_conv.hip) adds what the gather plan must say (no K split)
+bool gg_conv_tile_s2_family(const ConvParams &p)
+{
+    using G = TileS2Geom<4>;
+    if (!GG_TILE_S2 || p.path_hint == GG_CONV_HINT_GATHER || p.path_hint == GG_CONV_HINT_NO_TILE_S2 || !(gg_hint_is_production(p.path_hint) || p.path_hint == GG_CONV_HINT_TILE_S2)) return false;
+    if (p.kd != 3 || p.kh != 3 || p.kw != 3 || p.stride != 2 || p.pad != 1 || p.upsample) return false;
+    if (p.prologue_act || p.epi_geglu || p.post_xt || p.ddim_x || p.skip_C1) return false;
+    if (p.D != 2 * p.Do || p.H != 2 * p.Ho || p.W != 2 * p.Wo) return false;
+    if (p.Do % G::TD || p.Ho % G::TH || p.Wo % G::TW) return false;
+    return p.Cout_pad == 128;
+}
+
+template <int NT>
+static int launch_tile_s2(const ConvParams &p, hipStream_t stream)
+{
+    using G = TileS2Geom<NT>;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return GG_ERR_HIP;
+    static std::atomic<unsigned long long> attr_mask{0};
+    const unsigned long long dev_bit = 1ull << (dev & 63);
+    if (!(attr_mask.load(std::memory_order_acquire) & dev_bit)) {
+        if (hipFuncSetAttribute((const void *)conv_tile_s2_kernel<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDSB) != hipSuccess) return GG_ERR_UNSUPPORTED;
+        attr_mask.fetch_or(dev_bit, std::memory_order_release);
+    }
+    const int tiles_d = p.Do / G::TD, tiles_h = p.Ho / G::TH, tiles_w = p.Wo / G::TW;
+    hipLaunchKernelGGL((conv_tile_s2_kernel<NT>), dim3((unsigned)(p.N * tiles_d * tiles_h * tiles_w)), dim3(G::NTHR), G::LDSB, stream, p, tiles_d, tiles_h, tiles_w);
+    GG_CHECK_LAUNCH();
+    return GG_OK;
+}
+
+int gg_conv_tile_s2_launch(const ConvParams &p, hipStream_t stream)
+{
+    if (!gg_conv_tile_s2_family(p)) return GG_ERR_UNSUPPORTED;
+    return launch_tile_s2<4>(p, stream);
+}

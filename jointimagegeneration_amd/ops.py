@@ -55,6 +55,9 @@ def is_f32(t) -> bool:
 
 PATH_HINT = 0        # gg_conv_desc.path_hint: tests set 1 / 4 / 6 to run small shapes on the halo-tile kernel (production: 0)
 HINT_GATHER = 12     # production dispatch with the streaming 1x1 tile kernel switched off (tests, A/B)
+HINT_TILE_S2 = 15        # tests: the stride-2 tile kernel wherever its shape envelope allows (the grid condition lifted)
+HINT_NO_TILE_S2 = 14     # production dispatch with the stride-2 3x3x3 tile kernel (gg_conv_runs_tile_s2) switched off (tests, A/B)
+HINT_NO_HALO_SPLIT = 13     # production dispatch with the split halo path (gg_conv_runs_halo_split) switched off (tests, A/B)
 def weights_token(module) -> Tuple[int, int, int]:
     """Cheap identity of a module's current weights: (#tensors, sum of in-place version counters, sum of storage addresses).
     load_state_dict, LitEma.copy_to / restore and optimizer steps write in place (version bump); .to(device) moves storage.
