@@ -437,6 +437,47 @@ int gg_ddim_step_vq(float *x, const float *eps, int32_t eps_stride, const float 
 int gg_label_confusion(const int32_t *a, int32_t Sa, const int32_t *b, int32_t Sb, int64_t M, int32_t K, int64_t *cm_out,
                        int64_t *skipped_out, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Cleaning sampled label volumes (gg_components.hip).  gg_label_confusion's rules: labels are contiguous int32 on the
+ * device, memory and workspace are the caller's, all work is on the passed stream, no allocation, no host read-back, no
+ * synchronisation: capturable.  Integer atomics only: every output is exact and independent of scheduling.  No counterpart in the
+ * reference (it hands a raw sample to the CT stage).
+ * ------------------------------------------------------------------------------------------------ */
+/* Per-voxel vote of S samples: labels [S, M], 1 <= S <= 64, 1 <= K <= 32, 1 <= M < 2^31.
+ *   winner    int32 [M]  the most-voted label; on a tie the smallest label among the most voted
+ *   agreement int32 [M]  the winner's votes
+ *   entropy   fp32 [M]   H = ln S - (1 / S) sum_k c_k ln c_k over the vote counts c_k, formed as
+ *                        acc = 0; for k = 0 .. K-1: acc = fp32(acc + table[c_k]);  H = fp32(ln_s - fp32(acc * inv_s))
+ *                        (no contraction), with table_dev fp32 [S + 1] on the device, table[c] = fp32(c ln c) computed in fp64
+ *                        (table[0] = 0), ln_s = fp32(ln S), inv_s = fp32(1 / S): the caller's three operands, so that a host
+ *                        restatement in fp32 gives the same bits
+ *   skipped   int64 [1]  votes with a label outside [0, K): they are not cast
+ * A voxel with no valid vote gets winner 0, agreement 0, entropy 0. */
+int gg_label_vote(const int32_t *labels, int32_t S, int64_t M, int32_t K, const float *table_dev, float ln_s, float inv_s, int32_t *winner,
+                  int32_t *agreement, float *entropy, int64_t *skipped, void *stream);
+/* Connected components of labels [B, D, H, W] (M = D * H * W < 2^31, B <= 65535, 1 <= K <= 32) under connectivity 6 (faces) or 26
+ * (faces, edges, corners).  root int32 [B, M]: for a voxel whose label lies in [0, K) and is not `background` (-1: no background
+ * class) the smallest linear index, within its own volume, of its component -- the maximal set of equal-labelled voxels joined under
+ * the connectivity; -1 for every other voxel.  Volumes never join and rows never wrap.
+ * workspace: gg_label_components_workspace_bytes(B, M) bytes (the union-find's parent array).  status: one int32 on the device that
+ * the caller zeroed; a thread whose find or union reaches its bound of M steps (impossible unless the algorithm is wrong) sets it to a
+ * non-zero value and returns, and the caller reads it whenever it next reads results back. */
+int64_t gg_label_components_workspace_bytes(int32_t B, int64_t M);
+int gg_label_components(const int32_t *labels, int32_t B, int32_t D, int32_t H, int32_t W, int32_t K, int32_t connectivity,
+                        int32_t background, int32_t *root, void *workspace, int64_t workspace_bytes, int32_t *status, void *stream);
+/* From labels and gg_label_components' root (both [B, M]):
+ *   size  int32 [B, M]     the component's voxel count at its root position, 0 elsewhere
+ *   stats int64 [B, K, 4]  per class (components, voxels in components, size of the largest, root of the largest; -1 when none);
+ *                          among equal sizes the component with the smaller root is the largest */
+int gg_component_stats(const int32_t *labels, const int32_t *root, int32_t B, int64_t M, int32_t K, int32_t *size, int64_t *stats,
+                       void *stream);
+/* out_labels[v] = labels[v] when the class c of v is `background`, or when (keep_largest[c] == 0 or root[v] is the root of c's largest
+ * component) and size[root[v]] >= min_size[c]; `fill` (in [0, K)) otherwise, and for a label outside [0, K).  keep_largest, min_size:
+ * int32 [K] on the device.  kept uint8 [B, M]: 1 where the label was left as it was. */
+int gg_component_filter(const int32_t *labels, const int32_t *root, const int32_t *size, const int64_t *stats, int32_t B, int64_t M,
+                        int32_t K, const int32_t *keep_largest, const int32_t *min_size, int32_t background, int32_t fill,
+                        int32_t *out_labels, uint8_t *kept, void *stream);
+
 /* Three-view LPIPS of CT volumes (ldm/modules/losses/lpips.py; latentdiffusion/sample_diffusion.py:437-475), gg_lpips.hip: the kernels
  * around the VGG16 convolutions (which are gg_conv_forward / gg_conv_forward_f32 calls).  All three: the caller's stream, no allocation,
  * no synchronisation, capturable.

@@ -91,6 +91,11 @@ SIGNATURES = {
     "gg_vq_nearest": (C.c_int, [vp, i32, vp, i32, i32, i64, vp, vp, i32, vp]),
     "gg_ddim_step_vq": (C.c_int, [vp, vp, i32, vp, vp, i32, vp, i32, i64, i32, vp, vp, vp, i32, vp]),
     "gg_label_confusion": (C.c_int, [vp, i32, vp, i32, i64, i32, vp, vp, vp]),
+    "gg_label_vote": (C.c_int, [vp, i32, i64, i32, vp, f32, f32, vp, vp, vp, vp, vp]),
+    "gg_label_components_workspace_bytes": (i64, [i32, i64]),
+    "gg_label_components": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, i64, vp, vp]),
+    "gg_component_stats": (C.c_int, [vp, vp, i32, i64, i32, vp, vp, vp]),
+    "gg_component_filter": (C.c_int, [vp, vp, vp, vp, i32, i64, i32, vp, vp, i32, i32, vp, vp, vp]),
     "gg_volume_views_cl": (C.c_int, [vp, i32, i32, i32, i32, i32, i64, i64, vp, vp, vp, i32, vp]),
     "gg_relu_cl": (C.c_int, [vp, i32, i64, vp]),
     "gg_lpips_tap_workspace_bytes": (i64, [i32, i32, i32, i32, i32]),

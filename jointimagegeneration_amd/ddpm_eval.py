@@ -21,6 +21,13 @@ run's size, and exactly one of `--keep-classes a,b,c` (keep the voxels whose kno
 (`keep_{vid:04d}.nii.gz`, non-zero = keep) says which voxels come back unchanged; `--resample R` repeats every step R times.  With
 --samples S the S masks of a volume share one known / keep pair.  metrics.json (written with or without --gt) then holds an `edit`
 block: per volume the kept fraction and the count of kept voxels that differ from known, which is 0.
+
+Cleaning (postprocess.py; no counterpart in the reference): `--consensus` (with --samples S > 1) writes the per-voxel vote of a volume's
+S masks as `consensus_{vid:04d}.nii.gz` and its entropy in nats as `entropy_{vid:04d}.nii.gz`, and adds a `consensus` block to
+metrics.json.  `--largest-component all|a,b,c`, `--min-component V` and `--connectivity 6|26` clean the mask -- the consensus, or the
+single sample at --samples 1 -- into `clean_{vid:04d}.nii.gz` and add a `components` block: per volume and class the components, voxels
+and largest component before and after.  With --gt, `dice_consensus` / `dice_clean` (and their means) score the two new masks.  The
+existing keys and files are untouched (--keep-mask / --keep-classes belong to mask editing, hence the new names).
 """
 from __future__ import annotations
 
@@ -37,6 +44,7 @@ import yaml
 
 from . import distributed as ggd
 from . import metrics
+from . import postprocess
 from .ccdm import build_model
 from .encoder import build_feature_cond_encoder
 from .io import load_checkpoint, read_nifti, write_nifti
@@ -126,6 +134,8 @@ def main(argv=None):
     ap.add_argument("--keep-classes", default=None, help="comma-separated classes: keep the voxels whose known label is listed")
     ap.add_argument("--keep-mask", default=None, help="directory of keep_{vid:04d}.nii.gz volumes, non-zero = keep the known label")
     ap.add_argument("--resample", type=int, default=1, help="repetitions of every step of an edited chain (re-noised one step in between)")
+    ap.add_argument("--consensus", action="store_true", help="with --samples S > 1: write the per-voxel vote of the S masks and its entropy")
+    postprocess.add_cleanup_arguments(ap)
     args = ap.parse_args(argv)
     if args.resample < 1:
         raise ValueError(f"--resample {args.resample}: at least one repetition per step")
@@ -146,6 +156,11 @@ def main(argv=None):
     ignore = args.ignore_class if args.ignore_class is not None else params.get("ignore_class", 0)      # ruijin's get_ignore_class: 0
     gts = metrics.load_gt(args.gt, vids, size, K) if args.gt else None           # a bad ground truth ends the run before any sampling
     edits = load_edit(args, vids, size, K)
+    if args.consensus and not 2 <= S <= 64:
+        raise ValueError(f"--consensus votes over the masks of a volume: give --samples S with 2 <= S <= 64, got {S}")
+    clean_opts = postprocess.cleanup_options(args, K)
+    if clean_opts is not None and S > 1 and not args.consensus:
+        raise ValueError("--largest-component / --min-component clean ONE mask per volume: with --samples S > 1 give --consensus")
     if any(t < 1 or t > params["time_steps"] for t in loss_ts):
         raise ValueError(f"--loss-t {args.loss_t}: steps are 1..{params['time_steps']}")
     assert torch.cuda.is_available(), "the GuideGen engine needs an MI355X (no CPU fallback)"
@@ -190,6 +205,10 @@ def main(argv=None):
     loss_at = K * K + 4 * n_vol                                                       # then 3 fp64 (kl, ce, loss) per (volume, listed t)
     score_buf = torch.zeros(loss_at + 3 * L * n_vol, dtype=torch.int64, device=dev) if gts is not None else None
     edit_buf = torch.zeros((n_vol, 2), dtype=torch.int64, device=dev) if edits is not None else None   # (kept voxels, kept voxels != known)
+    # the cleaning blocks travel the same way: per volume 3 fp64 consensus means as bit patterns and the two [K, 4] component tables,
+    # then the [K, K] counts of the consensus and of the cleaned mask against the ground truth
+    post_vol = 3 + 8 * K
+    post_buf = torch.zeros(post_vol * n_vol + 2 * K * K, dtype=torch.int64, device=dev) if (args.consensus or clean_opts is not None) else None
     for vid in vids:                                                                  # volumes are independent units
         ed = {}
         if edits is not None:                                                         # the S masks of a volume share one known / keep pair
@@ -213,6 +232,26 @@ def main(argv=None):
             kept = ed["keep"] != 0
             edit_buf[vid, 0] = kept[0].sum()
             edit_buf[vid, 1] = (kept & (labels != ed["known"])).sum()
+        if post_buf is not None:
+            mask = labels[0]
+            at = post_vol * vid
+            if args.consensus:
+                mask, agreement, entropy = postprocess.consensus(labels, K)
+                cs = postprocess.consensus_summary(agreement, entropy, S)
+                post_buf[at:at + 3] = torch.tensor([cs["mean_entropy"], cs["mean_agreement"], cs["unanimous_fraction"]],
+                                                   dtype=torch.float64).view(torch.int64).to(dev)
+                write_nifti(os.path.join(out_dir, f"consensus_{vid:04d}.nii.gz"), mask.to(torch.uint8).cpu().numpy())
+                write_nifti(os.path.join(out_dir, f"entropy_{vid:04d}.nii.gz"), entropy.cpu().numpy())
+                if gts is not None:
+                    post_buf[post_vol * n_vol:post_vol * n_vol + K * K] += metrics.confusion_matrix(
+                        torch.from_numpy(gts[vid]).to(dev), mask, K).reshape(-1)
+            if clean_opts is not None:
+                cleaned, _ = postprocess.clean(mask, K, scores=False, **clean_opts)[:2]
+                tables = torch.stack([postprocess.components(m, K, clean_opts["connectivity"])[2][0] for m in (mask, cleaned)])
+                post_buf[at + 3:at + post_vol] = tables.reshape(-1)
+                write_nifti(os.path.join(out_dir, f"clean_{vid:04d}.nii.gz"), cleaned.to(torch.uint8).cpu().numpy())
+                if gts is not None:
+                    post_buf[post_vol * n_vol + K * K:] += metrics.confusion_matrix(torch.from_numpy(gts[vid]).to(dev), cleaned, K).reshape(-1)
         if gts is not None:
             cm, scores = metrics.score_case(labels, torch.from_numpy(gts[vid]).to(dev), K)
             score_buf[:K * K] += cm.reshape(-1)
@@ -226,6 +265,35 @@ def main(argv=None):
                 score_buf[at:at + 3] = torch.stack([r["loss_kl"], r["loss_ce"], r["loss"]]).view(torch.int64)
     torch.cuda.synchronize()
     print(f"[rank {rank}] sampled {len(vids)} volume(s) of {size} in {time.time() - t0:.1f}s -> {out_dir}", file=sys.stderr)
+    post_doc = {}
+    if post_buf is not None:
+        from .ops import check_component_status
+        check_component_status(dev)
+        if torch.distributed.is_available() and torch.distributed.is_initialized():
+            torch.distributed.all_reduce(post_buf)                                    # a volume belongs to one rank, the others hold zeros
+        host = post_buf.cpu()
+        per_vol = host[:post_vol * n_vol].reshape(n_vol, post_vol)
+        voxels = int(np.prod(size))
+        if args.consensus:
+            means = per_vol[:, :3].contiguous().view(torch.float64)
+            post_doc["consensus"] = dict(samples=S, mean_entropy=float(means[:, 0].sum() / n_vol), mean_agreement=float(means[:, 1].sum() / n_vol),
+                                         unanimous_fraction=float(means[:, 2].sum() / n_vol),
+                                         volumes=[dict(id=v, mean_entropy=float(means[v, 0]), mean_agreement=float(means[v, 1]),
+                                                       unanimous_fraction=float(means[v, 2])) for v in range(n_vol)])
+        if clean_opts is not None:
+            tables = per_vol[:, 3:].reshape(n_vol, 2, K, 4).numpy()
+            post_doc["components"] = dict(largest=clean_opts["largest"], min_size=clean_opts["min_size"], connectivity=clean_opts["connectivity"],
+                                          volumes=[dict(id=v, before=postprocess.scores_from_stats(tables[v, :1], voxels)[0],
+                                                        after=postprocess.scores_from_stats(tables[v, 1:], voxels)[0]) for v in range(n_vol)])
+        if gts is not None:
+            for j, (name, on) in enumerate((("consensus", args.consensus), ("clean", clean_opts is not None))):
+                if on:
+                    dice = metrics.dice_coefficient(host[post_vol * n_vol + j * K * K:post_vol * n_vol + (j + 1) * K * K].reshape(K, K), ignore)
+                    post_doc[f"dice_{name}"] = [float(v) for v in dice.tolist()]
+                    post_doc[f"mean_dice_{name}"] = float(dice.mean())
+        if rank == 0 and score_buf is None and edit_buf is None:
+            with open(os.path.join(out_dir, "metrics.json"), "w") as f:
+                json.dump(post_doc, f, indent=1)
     edit_doc = None
     if edit_buf is not None:
         if torch.distributed.is_available() and torch.distributed.is_initialized():
@@ -235,7 +303,7 @@ def main(argv=None):
                         volumes=[dict(id=v, kept_fraction=k / voxels, kept_differing=d) for v, (k, d) in enumerate(edit_buf.cpu().tolist())])
         if rank == 0 and score_buf is None:
             with open(os.path.join(out_dir, "metrics.json"), "w") as f:
-                json.dump(dict(edit=edit_doc), f, indent=1)
+                json.dump(dict(edit=edit_doc, **post_doc), f, indent=1)
     if score_buf is not None:
         if torch.distributed.is_available() and torch.distributed.is_initialized():
             torch.distributed.all_reduce(score_buf)                                   # once, after the sampling loop: off the data path
@@ -252,6 +320,7 @@ def main(argv=None):
                                for j, t in enumerate(loss_ts)]
             if edit_doc is not None:
                 doc["edit"] = edit_doc
+            doc.update(post_doc)
             with open(os.path.join(out_dir, "metrics.json"), "w") as f:
                 json.dump(doc, f, indent=1)
             print(f"[rank 0] {metrics.summary_line(doc)} -> {os.path.join(out_dir, 'metrics.json')}", file=sys.stderr)

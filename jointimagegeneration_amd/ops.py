@@ -1036,6 +1036,175 @@ def label_confusion(a: torch.Tensor, b: torch.Tensor, K: int) -> torch.Tensor:
     return cm
 
 
+# ----------------------------------------------------------------------------------- cleaning label volumes (gg_components.hip)
+def _labels_i32(t: torch.Tensor, what: str, name: str, dim: Optional[int] = None) -> None:
+    require_gpu(t, what)
+    if t.dtype != torch.int32 or not t.is_contiguous() or (dim is not None and t.dim() != dim):
+        shape = "" if dim is None else f" with {dim} dimensions"
+        raise ValueError(f"{what}: {name} must be a contiguous int32 tensor{shape}, got {t.dtype} {tuple(t.shape)}"
+                         f"{'' if t.is_contiguous() else ' (not contiguous)'}")
+
+
+def _check_classes(what: str, K: int) -> None:
+    if not isinstance(K, int) or not 1 <= K <= 32:
+        raise ValueError(f"{what}: K={K} outside [1, 32]")
+
+
+_VOTE_TABLES: dict = {}
+_COMPONENT_STATUS: dict = {}
+
+
+def vote_operands(S: int) -> Tuple["np.ndarray", float, float]:
+    """The three fp32 operands of gg_label_vote's entropy, computed in fp64 and rounded once: table[c] = c ln c (c = 0 .. S; table[0] =
+    0), ln S, 1 / S.  Returns (numpy fp32 table, ln_s, inv_s), the two scalars as Python floats that hold fp32 values."""
+    import math
+    import numpy as np
+    table = np.array([0.0] + [c * math.log(c) for c in range(1, S + 1)], dtype=np.float64).astype(np.float32)
+    return table, float(np.float32(math.log(S))), float(np.float32(1.0 / S))
+
+
+def component_status(device) -> torch.Tensor:
+    """The device status word of the component kernels on `device` (int32 [1], zero unless a loop bound was reached)."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"component_status: {device} is not a GPU")
+    key = device.index if device.index is not None else torch.cuda.current_device()
+    if key not in _COMPONENT_STATUS:
+        _COMPONENT_STATUS[key] = torch.zeros(1, dtype=torch.int32, device=torch.device("cuda", key))
+    return _COMPONENT_STATUS[key]
+
+
+def check_component_status(device) -> None:
+    """Reads the status word back (one host sync) and raises if a find or union of gg_label_components reached its bound: the roots it
+    wrote are then not to be trusted.  Called wherever the host layer reads component results back."""
+    st = component_status(device)
+    v = int(st.item())
+    if v != 0:
+        st.zero_()
+        raise RuntimeError(f"label_components: a device loop reached its bound of one volume's voxel count (status {v}: "
+                           "1 find, 2 union, 3 flatten); the component roots of this device are invalid")
+
+
+def label_vote(labels: torch.Tensor, K: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Per-voxel vote of S samples (gg_label_vote): labels int32 [S, M] on the device -> (winner int32 [M], agreement int32 [M], entropy
+    fp32 [M] in nats, skipped int64 [1] on the device: votes outside [0, K), which are not cast).  Ties go to the smallest label."""
+    _labels_i32(labels, "label_vote", "labels", 2)
+    _check_classes("label_vote", K)
+    S, M = int(labels.shape[0]), int(labels.shape[1])
+    if not 1 <= S <= 64:
+        raise ValueError(f"label_vote: S={S} samples outside [1, 64]")
+    if not 1 <= M < 2 ** 31:
+        raise ValueError(f"label_vote: M={M} voxels outside [1, 2^31)")
+    lib = _lib.load()
+    dev = labels.device
+    key = (S, dev.index)
+    if key not in _VOTE_TABLES:
+        table, ln_s, inv_s = vote_operands(S)
+        _VOTE_TABLES[key] = (torch.from_numpy(table).to(dev), ln_s, inv_s)
+    table, ln_s, inv_s = _VOTE_TABLES[key]
+    winner = torch.empty(M, dtype=torch.int32, device=dev)
+    agreement = torch.empty(M, dtype=torch.int32, device=dev)
+    entropy = torch.empty(M, dtype=torch.float32, device=dev)
+    skipped = torch.empty(1, dtype=torch.int64, device=dev)
+    check(lib.gg_label_vote(labels.data_ptr(), S, M, K, table.data_ptr(), ln_s, inv_s, winner.data_ptr(), agreement.data_ptr(),
+                            entropy.data_ptr(), skipped.data_ptr(), _stream()), "gg_label_vote")
+    return winner, agreement, entropy, skipped
+
+
+def _check_volumes(what: str, labels: torch.Tensor) -> Tuple[int, int]:
+    B = int(labels.shape[0])
+    M = 1
+    for v in labels.shape[1:]:
+        M *= int(v)
+    if not 1 <= B <= 65535:
+        raise ValueError(f"{what}: B={B} volumes outside [1, 65535]")
+    if not 1 <= M < 2 ** 31:
+        raise ValueError(f"{what}: {M} voxels per volume outside [1, 2^31)")
+    return B, M
+
+
+def label_components(labels: torch.Tensor, K: int, connectivity: int = 6, background: int = 0) -> torch.Tensor:
+    """Connected components (gg_label_components): labels int32 [B, D, H, W] -> root int32 [B, D*H*W], the smallest linear index of the
+    voxel's component within its volume, -1 for `background` (-1: none) and for labels outside [0, K).  connectivity 6 or 26."""
+    _labels_i32(labels, "label_components", "labels", 4)
+    _check_classes("label_components", K)
+    if connectivity not in (6, 26):
+        raise ValueError(f"label_components: connectivity {connectivity} is neither 6 nor 26")
+    if not isinstance(background, int) or not -1 <= background < K:
+        raise ValueError(f"label_components: background {background} outside [-1, {K})")
+    B, M = _check_volumes("label_components", labels)
+    D, H, W = (int(v) for v in labels.shape[1:])
+    lib = _lib.load()
+    root = torch.empty((B, M), dtype=torch.int32, device=labels.device)
+    nbytes = int(lib.gg_label_components_workspace_bytes(B, M))
+    ws = torch.empty(nbytes // 4, dtype=torch.int32, device=labels.device)
+    status = component_status(labels.device)
+    check(lib.gg_label_components(labels.data_ptr(), B, D, H, W, K, connectivity, background, root.data_ptr(), ws.data_ptr(), nbytes,
+                                  status.data_ptr(), _stream()), "gg_label_components")
+    return root
+
+
+def _check_root(what: str, labels: torch.Tensor, root: torch.Tensor, B: int, M: int) -> None:
+    _labels_i32(root, what, "root", 2)
+    if tuple(root.shape) != (B, M) or root.device != labels.device:
+        raise ValueError(f"{what}: root must be int32 [{B}, {M}] on {labels.device}, got {tuple(root.shape)} on {root.device}")
+
+
+def component_stats(labels: torch.Tensor, root: torch.Tensor, K: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """gg_component_stats: labels int32 [B, ...], root int32 [B, M] -> (size int32 [B, M]: the component's voxel count at its root, 0
+    elsewhere; stats int64 [B, K, 4] = (components, voxels, size of the largest, root of the largest or -1), ties to the smaller root)."""
+    _labels_i32(labels, "component_stats", "labels")
+    if labels.dim() < 2:
+        raise ValueError(f"component_stats: labels must be [B, *spatial], got {tuple(labels.shape)}")
+    _check_classes("component_stats", K)
+    B, M = _check_volumes("component_stats", labels)
+    _check_root("component_stats", labels, root, B, M)
+    lib = _lib.load()
+    size = torch.empty((B, M), dtype=torch.int32, device=labels.device)
+    stats = torch.empty((B, K, 4), dtype=torch.int64, device=labels.device)
+    check(lib.gg_component_stats(labels.data_ptr(), root.data_ptr(), B, M, K, size.data_ptr(), stats.data_ptr(), _stream()),
+          "gg_component_stats")
+    return size, stats
+
+
+def component_filter(labels: torch.Tensor, root: torch.Tensor, size: torch.Tensor, stats: torch.Tensor, K: int, keep_largest: torch.Tensor,
+                     min_size: torch.Tensor, background: int = 0, fill: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """gg_component_filter: a voxel keeps its label iff its class is `background`, or (keep_largest[class] == 0 or its component is the
+    class's largest) and size >= min_size[class]; otherwise it becomes `fill` (default: the background).  keep_largest, min_size: int32
+    [K] on the device.  Returns (cleaned labels, shaped as labels; kept uint8, same shape, 1 where the label was left as it was)."""
+    _labels_i32(labels, "component_filter", "labels")
+    if labels.dim() < 2:
+        raise ValueError(f"component_filter: labels must be [B, *spatial], got {tuple(labels.shape)}")
+    _check_classes("component_filter", K)
+    B, M = _check_volumes("component_filter", labels)
+    _check_root("component_filter", labels, root, B, M)
+    _labels_i32(size, "component_filter", "size", 2)
+    if tuple(size.shape) != (B, M) or size.device != labels.device:
+        raise ValueError(f"component_filter: size must be int32 [{B}, {M}] on {labels.device}, got {tuple(size.shape)}")
+    require_gpu(stats, "component_filter")
+    if stats.dtype != torch.int64 or tuple(stats.shape) != (B, K, 4) or not stats.is_contiguous() or stats.device != labels.device:
+        raise ValueError(f"component_filter: stats must be a contiguous int64 [{B}, {K}, 4] tensor on {labels.device}, "
+                         f"got {stats.dtype} {tuple(stats.shape)}")
+    for name, t in (("keep_largest", keep_largest), ("min_size", min_size)):
+        _labels_i32(t, "component_filter", name, 1)
+        if t.numel() != K or t.device != labels.device:
+            raise ValueError(f"component_filter: {name} must hold K={K} int32 values on {labels.device}, got {tuple(t.shape)}")
+    if not isinstance(background, int) or not -1 <= background < K:
+        raise ValueError(f"component_filter: background {background} outside [-1, {K})")
+    if fill is None:
+        if background < 0:
+            raise ValueError("component_filter: fill must be given when there is no background class")
+        fill = background
+    if not isinstance(fill, int) or not 0 <= fill < K:
+        raise ValueError(f"component_filter: fill {fill} outside [0, {K})")
+    lib = _lib.load()
+    out = torch.empty_like(labels)
+    kept = torch.empty(labels.shape, dtype=torch.uint8, device=labels.device)
+    check(lib.gg_component_filter(labels.data_ptr(), root.data_ptr(), size.data_ptr(), stats.data_ptr(), B, M, K, keep_largest.data_ptr(),
+                                  min_size.data_ptr(), background, fill, out.data_ptr(), kept.data_ptr(), _stream()), "gg_component_filter")
+    return out, kept
+
+
 # ----------------------------------------------------------------------------------------------- LPIPS (gg_lpips.hip)
 def volume_views_cl(x: torch.Tensor, view: int, n0: int, n1: int, shift: torch.Tensor, scale: torch.Tensor, out: torch.Tensor) -> CL:
     """Images [n0, n1) of one axis view of an fp32 volume batch x [B, D, H, W] as channels-last rows (gg_volume_views_cl): view 0 =

@@ -509,12 +509,32 @@ class GuideGenPipeline:
         return ve["samples"].clone().permute(1, 0, 2, 3)
 
     @torch.no_grad()
+    def clean_masks(self, labels: torch.Tensor, largest="all", min_size=0, connectivity: int = 6, background: int = 0,
+                    fill: Optional[int] = None):
+        """postprocess.clean on sampled masks [B, Dm, Hm, Wm] with the CCDM's class count: keep the largest component of the listed
+        classes and drop components below min_size voxels.  Returns (cleaned labels, kept uint8 -- shaped as keep= of mask editing --,
+        scores before, scores after); the scores also go to self.stats["mask_cleanup"]."""
+        from . import postprocess
+        out, kept, before, after = postprocess.clean(labels, self.ccdm.diffusion.num_classes, largest=largest, min_size=min_size,
+                                                     connectivity=connectivity, background=background, fill=fill)
+        self.stats["mask_cleanup"] = dict(before=before, after=after)
+        return out, kept, before, after
+
+    @torch.no_grad()
     def run_volumes(self, seeds: Sequence[int], mask_size=(128, 128, 128), depth: int = 256, hw: int = 512,
-                    ccdm_init_t: Optional[int] = None, max_slices: Optional[int] = None):
+                    ccdm_init_t: Optional[int] = None, max_slices: Optional[int] = None, clean: Optional[dict] = None):
         """B independent volumes in one batch: volume i is run_volume(N=1, seed=seeds[i]) (seed for the CCDM stage, seed + 1 for the
-        LDM stage) up to the bf16 rounding of batch-size-dependent kernel plans.  Returns (labels [B, Dm, Hm, Wm], ct [B, depth, hw, hw])."""
+        LDM stage) up to the bf16 rounding of batch-size-dependent kernel plans.  Returns (labels [B, Dm, Hm, Wm], ct [B, depth, hw, hw]).
+        clean: options of clean_masks (a dict; {} = its defaults), applied to the sampled masks before the slice loop, which is then
+        conditioned on the cleaned masks, the labels returned.  None (the default): the raw samples, and nothing new is launched."""
         t0 = time.time()
         labels = self.sample_masks(seeds, mask_size, ccdm_init_t)
+        if clean is not None:
+            from .postprocess import CLEAN_OPTIONS
+            unknown = sorted(set(clean) - set(CLEAN_OPTIONS))
+            if unknown:
+                raise ValueError(f"run_volumes: clean options {unknown} ({', '.join(CLEAN_OPTIONS)})")
+            labels = self.clean_masks(labels, **clean)[0]
         torch.cuda.synchronize()
         t1 = time.time()
         ct = self.sample_ct_volumes(labels, depth, hw, [int(s) + 1 for s in seeds], max_slices)

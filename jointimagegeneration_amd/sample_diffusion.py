@@ -72,6 +72,10 @@ def get_parser():
                    "where the edited and the original label condition the slice loop alike")
     p.add_argument("--keep-mask", type=str, default=None, help="with --known-ct: directory of explicit uint8 keep volumes (same stems, --slices x --size x "
                    "--size, non-zero = keep), instead of --known-mask")
+    p.add_argument("--largest-component", default=None, help="with --inputs: 'all' or comma-separated classes; keep only the largest connected "
+                   "component of these classes of every stage-1 mask before the slice loop (postprocess.clean; metrics.json gains a mask_cleanup block)")
+    p.add_argument("--min-component", type=int, default=None, help="with --inputs: remove every component of a stage-1 mask below this many voxels")
+    p.add_argument("--connectivity", type=int, default=None, help="with --inputs: 6 (faces, the default) or 26 (faces, edges, corners)")
     p.add_argument("--edit-margin", type=int, default=0, help="with --known-ct: latent cells within R cells of an un-kept pixel are regenerated too")
     return p
 
@@ -225,6 +229,34 @@ def edit_volume(pipe, opt, stem: str, labels: np.ndarray, seed: int):
     return ct, doc
 
 
+def cleanup_from_options(opt):
+    """The postprocess.clean options of --largest-component / --min-component / --connectivity, or None; refusals before any sampling.
+    Stage-1 masks carry their class count in their labels: the options are checked against the 32 classes the kernels take."""
+    from . import postprocess
+    try:
+        opts = postprocess.cleanup_options(opt, 32)
+    except ValueError as e:
+        raise SystemExit(str(e)) from None
+    if opts is not None and not opt.inputs:
+        raise SystemExit("--largest-component / --min-component clean the stage-1 masks of --inputs DIR")
+    return opts
+
+
+def clean_stage1_mask(labels: np.ndarray, opts: dict, stem: str):
+    """One stage-1 label volume through postprocess.clean on the device: (cleaned labels, numpy, dtype kept; its entry of metrics.json's
+    mask_cleanup block)."""
+    from . import postprocess
+    if labels.ndim != 3 or labels.dtype.kind not in "iu" or labels.min() < 0 or labels.max() > 31:
+        raise SystemExit(f"--inputs volume {stem}: cleaning needs an integer [D, H, W] label volume with labels 0..31, got {labels.dtype} "
+                         f"{labels.shape}")
+    K = max(2, int(labels.max()) + 1)
+    largest = opts["largest"] if opts["largest"] in (None, "all") else [c for c in opts["largest"] if c < K]
+    dev_labels = torch.from_numpy(labels.astype(np.int32)).cuda()
+    cleaned, kept, before, after = postprocess.clean(dev_labels, K, largest=largest, min_size=opts["min_size"], connectivity=opts["connectivity"])
+    doc = dict(volume=stem, num_classes=K, removed_voxels=int((kept == 0).sum()), before=before, after=after)
+    return cleaned.cpu().numpy().astype(labels.dtype), doc
+
+
 def render_input(x: torch.Tensor) -> torch.Tensor:
     """One sampled volume [2, D, H, W] = (CT, label / 255) as render.combine_mask_and_im takes it: (CT, label / 11).  The reference
     renders `pred` as it is (sample_diffusion.py:257); label / 255 * 11 truncates to 0 for every label, so nothing would be painted."""
@@ -241,6 +273,8 @@ def main(argv=None):
     if opt.log_every_t is not None and not opt.progress_png:
         raise SystemExit("--log-every-t goes with --progress-png")
     editing = check_edit_options(opt)
+    cleanup = cleanup_from_options(opt)
+    cleanup_docs = []
     scorer = None
     if all(scoring):                         # weights and directory are checked before anything is sampled
         from .lpips import LPIPS
@@ -274,8 +308,14 @@ def main(argv=None):
         files = sorted(f for f in glob.glob(os.path.join(opt.inputs, "*.nii*")) if f.endswith((".nii", ".nii.gz")))
         if not files:
             raise SystemExit(f"--inputs {opt.inputs!r}: no *.nii / *.nii.gz label volumes found")
-        label_volumes = {os.path.basename(f).split(".nii")[0]: read_nifti(f) for f in files} if editing else None
-        jobs = [(os.path.basename(f).split(".nii")[0], stage1_mask_to_wholemask(read_nifti(f), opt.slices, opt.size), opt.seed + i) for i, f in enumerate(files)]
+        stage1 = {os.path.basename(f).split(".nii")[0]: read_nifti(f) for f in files}
+        if cleanup is not None:                  # the slice loop (and an edit) is conditioned on the cleaned masks
+            for stem in list(stage1):
+                stage1[stem], cdoc = clean_stage1_mask(stage1[stem], cleanup, stem)
+                cleanup_docs.append(cdoc)
+        label_volumes = stage1 if editing else None
+        jobs = [(os.path.basename(f).split(".nii")[0], stage1_mask_to_wholemask(stage1[os.path.basename(f).split(".nii")[0]], opt.slices, opt.size),
+                 opt.seed + i) for i, f in enumerate(files)]
     else:
         lab = torch.from_numpy(np.load(opt.mask)).long() if opt.mask else synth_mask_volume(opt.slices, opt.size, opt.size)
         jobs = [("sample", lab.float() / 255.0, opt.seed)]
@@ -313,7 +353,7 @@ def main(argv=None):
             if opt.png:
                 volume_png(render_input(x), os.path.join(out_dir, f"{stem}_{ix:04d}.png"))
         print(f"sampled {tuple(pred.shape)} in {time.time() - t0:.1f}s -> {out_dir}/{stem}_*.nii.gz", file=sys.stderr)
-    if scorer is not None or editing:
+    if scorer is not None or editing or cleanup is not None:
         import json
         doc = {}
         if scorer is not None:
@@ -321,6 +361,9 @@ def main(argv=None):
             doc = score_directory(scorer.cuda(), written, opt.gt, torch.device("cuda"))
         if editing:
             doc["edit"] = dict(edit_margin=opt.edit_margin, known_mask=opt.known_mask, keep_mask=opt.keep_mask, volumes=edit_docs)
+        if cleanup is not None:
+            doc["mask_cleanup"] = dict(largest=cleanup["largest"], min_size=cleanup["min_size"], connectivity=cleanup["connectivity"],
+                                       volumes=cleanup_docs)
         with open(os.path.join(out_dir, "metrics.json"), "w") as f:
             json.dump(doc, f, indent=1)
     if scorer is not None:
