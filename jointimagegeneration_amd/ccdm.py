@@ -169,7 +169,6 @@ class DenoisingModel(nn.Module):
         self.dataset_file, self.step_T_sample = dataset_file, step_T_sample
         self.philox_seed = 1024           # RNG of the throughput path (counter-based, in-kernel)
         self.use_graph = True
-        self._graph_cache: Dict[Any, Any] = {}
 
     @property
     def time_steps(self):
@@ -353,7 +352,8 @@ class DenoisingModel(nn.Module):
                     f"{S} steps (t = {tv[0]} .. {tv[-1]}) x {resample} repetitions{' with a mask' if masked else ''}"
                 raise ValueError(f"sample_labels: {what} need {need} rng tapes, got {len(rng_tapes)}")
         use_graph = self.use_graph and rng_tapes is None and trace is None and S > 3 and not ops.FP32
-        graph, warmed, ti = None, False, 0
+        ladder, ti = dict(warmed=False, graph=None), 0               # lives for this call
+        graphed_step = masked_step if masked else (lambda: step(True))
 
         def tape():
             nonlocal ti
@@ -375,13 +375,7 @@ class DenoisingModel(nn.Module):
                 last, draw = (i == S - 1 and j == resample - 1), (t > 1)
                 x_in = None
                 if use_graph and draw and not last:
-                    if not warmed:
-                        masked_step() if masked else step(True)      # eager warm-up: fills the weight-repack cache
-                        warmed = True
-                    else:
-                        if graph is None:                            # capture the fixed-shape step once (hipGraph)
-                            graph = ops.capture_graph(masked_step if masked else (lambda: step(True)))
-                        graph.replay()
+                    ops.replay_captured(ladder, "graph", graphed_step)   # the fixed-shape step: eager once, captured once (hipGraph)
                 else:
                     if masked:
                         blend(tape())

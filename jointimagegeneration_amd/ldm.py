@@ -2005,13 +2005,7 @@ class DDIMSampler(object):
         S = st["S"]
         if self.chain_graphable(st, ctx_cl, eta, noise_tape):
             # first call: eager (fills the weight-repack caches); afterwards ONE hipGraph replay per chain
-            if not st["warmed"]:
-                self.chain(st, ctx_cl)
-                st["warmed"] = True
-                return
-            if st["graph"] is None:
-                st["graph"] = ops.capture_graph(lambda: self.chain(st, ctx_cl))
-            st["graph"].replay()
+            ops.replay_captured(st, "graph", lambda: self.chain(st, ctx_cl))
             return
         for i in range(S):
             noise = self._noise(st, i, eta, noise_tape, noise_dropout)

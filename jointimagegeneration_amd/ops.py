@@ -98,6 +98,19 @@ def capture_graph(fn) -> "torch.cuda.CUDAGraph":
     return g
 
 
+def replay_captured(holder: dict, slot: str, body) -> None:
+    """The one ladder of a graphable launch sequence `body`, its state in `holder` ("warmed" and `slot`): the first call runs `body`
+    eagerly (that fills the weight-repack caches, which a capture must not do), the second captures it into holder[slot] and
+    replays, every later one replays.  Callers keep their own eager branch for what is not graphable."""
+    if not holder["warmed"]:
+        body()
+        holder["warmed"] = True
+        return
+    if holder[slot] is None:
+        holder[slot] = capture_graph(body)
+    holder[slot].replay()
+
+
 def pad32(c: int) -> int:
     return (c + 31) // 32 * 32
 

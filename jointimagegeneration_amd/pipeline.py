@@ -63,14 +63,14 @@ def build_ldm(seed: int = 1024, device="cuda", use_ema: bool = False) -> LatentD
 
 
 def slice_window(labels: torch.Tensor, depth: int, max_slices: Optional[int] = None) -> List[int]:
-    """The slice loop of ONE volume (labels [Dm, Hm, Wm] or [1, Dm, Hm, Wm]), exactly as GuideGenPipeline.sample_ct visits it: slices whose
-    order-0 upsampled mask is non-empty (sample_diffusion.py:202), from one before the first (python indexing: -1 is the last slice) to
-    the last; an empty mask visits slice 0 only.  Returns the loop values m (slice m % depth, previous slice max(0, m - 1) % depth)."""
+    """The slice loop of labels [Dm, Hm, Wm] or [N, Dm, Hm, Wm], as GuideGenPipeline.sample_ct visits it: slices whose order-0 upsampled
+    mask is non-empty in ANY batch element (sample_diffusion.py:202; the reference's batch is N copies of one mask), from one before the
+    first (python indexing: -1 is the last slice) to the last; an empty mask visits slice 0 only.  Independent volumes pass one volume
+    at a time.  Returns the loop values m (slice m % depth, previous slice max(0, m - 1) % depth)."""
     lab = labels.reshape((-1,) + tuple(labels.shape[-3:]))
-    assert lab.shape[0] == 1, "slice_window: one volume"
     Dm = lab.shape[1]
     nz = (lab != 0).flatten(2).any(-1).any(0).cpu()                                   # [Dm]
-    idx = torch.nonzero(nz[ops.zoom0_index(Dm, depth)]).flatten()
+    idx = torch.nonzero(nz[ops.zoom0_index(Dm, depth)]).flatten()                   # same order-0 rule as the glue kernel
     start, end = (int(idx[0]), int(idx[-1])) if idx.numel() else (1, 0)
     todo = list(range(start - 1, end + 1))
     return todo[:max_slices] if max_slices is not None else todo
@@ -88,6 +88,57 @@ def volume_schedule(windows: Sequence[Sequence[int]], depth: int) -> Tuple[torch
             sched[it, i, 0], sched[it, i, 1], sched[it, i, 2] = m % depth, max(0, m - 1) % depth, 1
     wasted = 1.0 - sum(len(w) for w in windows) / float(B * iters)
     return sched, wasted
+
+
+def plan_ct_edit(labels: torch.Tensor, depth: int, max_slices: Optional[int], known_d: torch.Tensor, keep_d: torch.Tensor,
+                 q_shape: Tuple[int, ...], x_T_tapes=None, q_noise_tapes=None):
+    """What CT editing adds to the loop of independent volumes, on the host: known_d fp32 and keep_d bool are slice-major
+    [depth, B, hw, hw], q_shape is the q-sample noise of one mixed slice, (S, 1, Cz, lat, lat).  Per volume: the slices of its window it
+    visits (one all of whose pixels are kept is skipped) and which of them are mixed (some pixel kept); the four counters of
+    self.stats; the refusals of tapes whose lengths or shapes do not fit the visits; the start volume (known where kept, else 0), which
+    is the result when no volume visits anything.  Returns (windows, mixed, counters, start)."""
+    B = labels.shape[0]
+    kept_all = keep_d.flatten(2).all(-1).cpu()                                         # [depth, B]
+    kept_any = keep_d.flatten(2).any(-1).cpu()
+    unkept_px = (~keep_d).flatten(2).sum(-1).cpu()
+    windows, mixed, skipped, outside = [], [], 0, 0
+    for i in range(B):
+        win = slice_window(labels[i], depth, max_slices)
+        visit = [m for m in win if not bool(kept_all[m % depth, i])]
+        skipped += len(win) - len(visit)
+        inside = {m % depth for m in win}
+        outside += int(sum(int(unkept_px[d, i]) for d in range(depth) if d not in inside))
+        windows.append(visit)
+        mixed.append([bool(kept_any[m % depth, i]) for m in visit])
+    n_mixed = [sum(mx) for mx in mixed]
+    for name, tapes, want in (("x_T_tapes", x_T_tapes, [len(w) for w in windows]), ("q_noise_tapes", q_noise_tapes, n_mixed)):
+        if tapes is not None:
+            for i in range(B):
+                if len(tapes[i]) != want[i]:
+                    raise ValueError(f"sample_ct_volumes: {name}[{i}] holds {len(tapes[i])} tensors, volume {i} "
+                                     f"{'visits' if name == 'x_T_tapes' else 'has'} {want[i]} {'slices' if name == 'x_T_tapes' else 'mixed slices'}")
+    if q_noise_tapes is not None:
+        for i in range(B):
+            for k, t in enumerate(q_noise_tapes[i]):
+                if tuple(t.shape) != tuple(q_shape):
+                    raise ValueError(f"sample_ct_volumes: q_noise_tapes[{i}][{k}] has shape {tuple(t.shape)}, a mixed slice takes {tuple(q_shape)}")
+    counters = dict(slices_visited=sum(len(w) for w in windows), slices_skipped_kept=skipped, slices_mixed=sum(n_mixed),
+                    unkept_outside_window=outside)
+    return windows, mixed, counters, torch.where(keep_d, known_d, torch.zeros_like(known_d))
+
+
+def _tape_or_randn(tape, k: int, shape: Tuple[int, ...], gen: torch.Generator) -> torch.Tensor:
+    """Entry k of a parity tape, or the seeded draw of `shape` from `gen` on its device, in the reference's NCHW element order
+    (ddim.py:124 `torch.randn(shape)`), so that a seeded generator gives sample_diffusion.sample_cond and these loops the same noise."""
+    return tape[k].to(gen.device).float() if tape is not None else torch.randn(shape, generator=gen, device=gen.device)
+
+
+def _load_x_T(st: Dict, x_T: torch.Tensor) -> None:
+    """NCHW x_T [B, Cz, lat, lat] -> the chain state's fp32 x and the bf16 UNet input, both channels-last (plumbing copies)."""
+    Cz = x_T.shape[1]
+    x_T = x_T.permute(0, 2, 3, 1).reshape(st["x"].shape)
+    st["x"].copy_(x_T)
+    st["unet_in"][..., :Cz].copy_(x_T)
 
 
 def _log(msg: str) -> None:
@@ -137,33 +188,52 @@ class GuideGenPipeline:
         labels, _ = self.ccdm.sample_labels(x_T, cond, init_t, philox_seeds=[int(s) for s in seeds], known=known, keep=keep, resample=resample)
         return labels
 
-    def _slice_engine(self, N: int, hw: int, dev, st) -> Dict:
-        """Static buffers + hipGraphs of the two per-slice networks (cond-stage encode, first-stage decode) for one shape."""
+    def _engine(self, cache: Dict, key, N: int, hw: int, dev, st, finish) -> Dict:
+        """What the two slice engines share, cached in `cache` under `key` until the chain state or a network's weights change: the static
+        buffers (cond-stage input, first-stage latent, decoded slices), the ladder's "warmed" flag, and the heads of the two per-slice
+        networks -- cond-stage encode into the chain's c_concat channels (returns the moments), and z = x / scale_factor through the
+        first-stage decode into "ds".  finish(engine, encode_head, decode_head) adds a new engine's own buffers and graph slots and sets
+        its "encode" and "decode"."""
         ldm = self.ldm
         lat, Cz = hw // self.latent_factor, ldm.channels
-        key = (N, hw, str(dev))
         token = (id(st), ops.weights_token(ldm.cond_stage_model), ops.weights_token(ldm.first_stage_model))
-        sg = self._slice_graphs.get(key)
-        if sg is not None and sg["token"] == token:
-            return sg
-        sg = dict(token=token, cond_in=torch.empty((N, 1, hw, hw, 32), dtype=torch.bfloat16, device=dev),
-                  z=torch.zeros((N, 1, lat, lat, 32), dtype=torch.bfloat16, device=dev),
-                  ds=torch.empty((N, hw, hw), dtype=torch.float32, device=dev), enc=None, dec=None, slice=None, mom=None, warmed=False)
-        cond_in, zbuf = sg["cond_in"], sg["z"]
+        eng = cache.get(key)
+        if eng is not None and eng["token"] == token:
+            return eng
+        eng = dict(token=token, cond_in=torch.empty((N, 1, hw, hw, 32), dtype=torch.bfloat16, device=dev),
+                   z=torch.zeros((N, 1, lat, lat, 32), dtype=torch.bfloat16, device=dev),
+                   ds=torch.empty((N, hw, hw), dtype=torch.float32, device=dev), warmed=False)
 
-        def encode():
-            sg["mom"] = ldm.cond_stage_model.encode_moments_cl(CL(cond_in, 2))         # fp32 CL [N,1,lat,lat,32]; mode() = mean
-            st["unet_in"][..., Cz:2 * Cz].copy_(sg["mom"].t[..., :Cz])                # c_concat = posterior mean (plumbing copy)
+        def encode_head():
+            mom = ldm.cond_stage_model.encode_moments_cl(CL(eng["cond_in"], 2))         # fp32 CL [N,1,lat,lat,32]; mode() = mean
+            st["unet_in"][..., Cz:2 * Cz].copy_(mom.t[..., :Cz])                       # c_concat = posterior mean (plumbing copy)
+            return mom
 
-        def decode():
-            zbuf[..., :Cz].copy_(st["x"] * (1.0 / ldm.scale_factor))
-            dec = ldm.first_stage_model.decode_cl(CL(zbuf, Cz))                        # fp32 CL [N,1,hw,hw,32]
-            sg["ds"].copy_(dec.t[..., 0].reshape(N, hw, hw))
-            ops.minmax_normalise(sg["ds"], out=sg["ds"])
+        def decode_head():
+            eng["z"][..., :Cz].copy_(st["x"] * (1.0 / ldm.scale_factor))
+            dec = ldm.first_stage_model.decode_cl(CL(eng["z"], Cz))                     # fp32 CL [N,1,hw,hw,32]
+            eng["ds"].copy_(dec.t[..., 0].reshape(N, hw, hw))
 
-        sg["encode"], sg["decode"] = encode, decode
-        self._slice_graphs[key] = sg
-        return sg
+        finish(eng, encode_head, decode_head)
+        cache[key] = eng
+        return eng
+
+    def _slice_engine(self, N: int, hw: int, dev, st) -> Dict:
+        """Static buffers + hipGraphs of the two per-slice networks (cond-stage encode, first-stage decode) for one shape; the decoded
+        batch is normalised as a whole, in place."""
+        def finish(sg, encode_head, decode_head):
+            sg.update(enc=None, dec=None, slice=None, mom=None)
+
+            def encode():
+                sg["mom"] = encode_head()
+
+            def decode():
+                decode_head()
+                ops.minmax_normalise(sg["ds"], out=sg["ds"])
+
+            sg["encode"], sg["decode"] = encode, decode
+
+        return self._engine(self._slice_graphs, (N, hw, str(dev)), N, hw, dev, st, finish)
 
     @torch.no_grad()
     def time_slice_stages(self, N: int = 1, hw: int = 512) -> Dict[str, float]:
@@ -205,22 +275,15 @@ class GuideGenPipeline:
                   x_T_tape=None) -> torch.Tensor:
         """labels int32 [N,Dm,Hm,Wm] -> CT volume fp32 [N, depth, hw, hw] in [0,1]; slice m conditioned on slice m-1.
         `x_T_tape` (parity runs): one [N, Cz, lat, lat] start latent per generated slice, in loop order, instead of the seeded draw."""
-        ldm, sampler, S = self.ldm, self.sampler, self.ddim_steps
+        ldm, sampler = self.ldm, self.sampler
         dev = labels.device
         N = labels.shape[0]
         lat = hw // self.latent_factor
         Cz = ldm.channels
         g = torch.Generator(device=dev).manual_seed(seed)
         samples = torch.zeros((depth, N, hw, hw), dtype=torch.float32, device=dev)        # slice-major: one slice is contiguous
-        # slices whose upsampled mask is non-empty (sample_diffusion.py:202); python indexing of the reference loop kept
-        Dm = labels.shape[1]
-        nz = (labels != 0).flatten(2).any(-1).any(0)                                       # [Dm]
-        idx = torch.nonzero(nz[ops.zoom0_index(Dm, depth).to(dev)]).flatten()       # same order-0 rule as the glue kernel
-        start, end = (int(idx[0]), int(idx[-1])) if idx.numel() else (1, 0)
+        todo = slice_window(labels, depth, max_slices)                                     # one window for the whole batch
         st = sampler.prepare_state(N, Cz, (lat, lat), dev, Cz)
-        todo = list(range(start - 1, end + 1))
-        if max_slices is not None:
-            todo = todo[:max_slices]
         sg = self._slice_engine(N, hw, dev, st)
         cond_in, encode, decode = sg["cond_in"], sg["encode"], sg["decode"]
 
@@ -232,27 +295,15 @@ class GuideGenPipeline:
             mm = m % depth
             prev = samples[max(0, m - 1) % depth]
             ops.mask_to_cond_slice(labels, mm, depth, hw, hw, prev, cond_in)
-            # drawn in the reference's NCHW element order (ddim.py:124 `torch.randn(shape)`), so that a seeded generator gives
-            # sample_diffusion.sample_cond and this loop the same x_T; stored channels-last (plumbing copies)
-            x_T = x_T_tape[it].to(dev).float() if x_T_tape is not None else torch.randn((N, Cz, lat, lat), generator=g, device=dev)
-            x_T = x_T.permute(0, 2, 3, 1).reshape(N, 1, lat, lat, Cz)
-            st["x"].copy_(x_T)
-            st["unet_in"][..., :Cz].copy_(x_T)                                         # fp32 -> bf16
+            _load_x_T(st, _tape_or_randn(x_T_tape, it, (N, Cz, lat, lat), g))
             if not (self.use_graph and sampler.chain_graphable(st)):
                 encode()
                 sampler.run_steps(st, None, 0.0, None)
                 decode()
-            elif not sg["warmed"]:
-                encode()                                                               # eager once: fills the repack caches
-                sampler.chain(st)
-                decode()
-                sg["warmed"] = True
             else:
                 # ONE hipGraph per slice: cond-encode, the S DDIM steps (each reading its own rows of the bias / scalar tables) and the
                 # decode; the host's share of a slice is the glue kernel, the x_T draw and this replay
-                if sg["slice"] is None:
-                    sg["slice"] = ops.capture_graph(lambda: (encode(), sampler.chain(st), decode()))
-                sg["slice"].replay()
+                ops.replay_captured(sg, "slice", lambda: (encode(), sampler.chain(st), decode()))
             samples[mm].copy_(sg["ds"])
         return samples.permute(1, 0, 2, 3)
 
@@ -262,50 +313,42 @@ class GuideGenPipeline:
         edit_margin (an int): the engine of the editing loop, under its own key -- `st` is then an inpainting state; the
         known / keep volumes, the first-stage input and the edit glue + first-stage encode join the iteration, and the scatter composites."""
         ldm = self.ldm
-        lat, Cz = hw // self.latent_factor, ldm.channels
-        key = (B, hw, depth, tuple(lab_shape), str(dev)) + ((("edit", int(edit_margin)),) if edit_margin is not None else ())
-        token = (id(st), ops.weights_token(ldm.cond_stage_model), ops.weights_token(ldm.first_stage_model))
-        ve = self._volume_graphs.get(key)
-        if ve is not None and ve["token"] == token:
-            return ve
-        ve = dict(token=token, labels=torch.zeros(tuple(lab_shape), dtype=torch.int32, device=dev),
-                  samples=torch.zeros((depth, B, hw, hw), dtype=torch.float32, device=dev),
-                  sched=torch.zeros((depth + 1, B, 3), dtype=torch.int32, device=dev),      # a window has at most depth + 1 iterations
-                  it=torch.zeros(1, dtype=torch.int32, device=dev), ws=torch.empty(2 * B, dtype=torch.float32, device=dev),
-                  cond_in=torch.empty((B, 1, hw, hw, 32), dtype=torch.bfloat16, device=dev),
-                  z=torch.zeros((B, 1, lat, lat, 32), dtype=torch.bfloat16, device=dev),
-                  ds=torch.empty((B, hw, hw), dtype=torch.float32, device=dev), graph=None, warmed=False)
+        Cz = ldm.channels
+        edit = edit_margin is not None
+        key = (B, hw, depth, tuple(lab_shape), str(dev)) + ((("edit", int(edit_margin)),) if edit else ())
 
-        if edit_margin is not None:
-            ve.update(known=torch.zeros((depth, B, hw, hw), dtype=torch.float32, device=dev),
-                      keep=torch.zeros((depth, B, hw, hw), dtype=torch.uint8, device=dev),
-                      fs_in=torch.empty((B, 1, hw, hw, 32), dtype=torch.bfloat16, device=dev))
+        def finish(ve, encode_head, decode_head):
+            ve.update(labels=torch.zeros(tuple(lab_shape), dtype=torch.int32, device=dev),
+                      samples=torch.zeros((depth, B, hw, hw), dtype=torch.float32, device=dev),
+                      sched=torch.zeros((depth + 1, B, 3), dtype=torch.int32, device=dev),  # a window has at most depth + 1 iterations
+                      it=torch.zeros(1, dtype=torch.int32, device=dev), ws=torch.empty(2 * B, dtype=torch.float32, device=dev), graph=None)
+            if edit:
+                ve.update(known=torch.zeros((depth, B, hw, hw), dtype=torch.float32, device=dev),
+                          keep=torch.zeros((depth, B, hw, hw), dtype=torch.uint8, device=dev),
+                          fs_in=torch.empty((B, 1, hw, hw, 32), dtype=torch.bfloat16, device=dev))
 
-        def glue():
-            ops.mask_to_cond_slices(ve["labels"], depth, hw, hw, ve["sched"], ve["it"], ve["samples"], ve["cond_in"])
-            if edit_margin is not None:                # the known slice as first-stage input, the latent keep mask into the chain's state
-                ops.ct_edit_glue(ve["known"], ve["keep"], ve["sched"], ve["it"], int(edit_margin), ve["fs_in"], st["ip_mask"].view(-1, 1))
+            def glue():
+                ops.mask_to_cond_slices(ve["labels"], depth, hw, hw, ve["sched"], ve["it"], ve["samples"], ve["cond_in"])
+                if edit:                               # the known slice as first-stage input, the latent keep mask into the chain's state
+                    ops.ct_edit_glue(ve["known"], ve["keep"], ve["sched"], ve["it"], int(edit_margin), ve["fs_in"], st["ip_mask"].view(-1, 1))
 
-        def encode():
-            mom = ldm.cond_stage_model.encode_moments_cl(CL(ve["cond_in"], 2))
-            st["unet_in"][..., Cz:2 * Cz].copy_(mom.t[..., :Cz])
-            if edit_margin is not None:                # x0 = scale_factor * posterior mean: the mode, no draw
-                mom = ldm.first_stage_model.encode_moments_cl(CL(ve["fs_in"], 1))
-                st["ip_x0"].copy_(mom.t[..., :Cz] * ldm.scale_factor)
+            def encode():
+                encode_head()
+                if edit:                               # x0 = scale_factor * posterior mean: the mode, no draw
+                    mom = ldm.first_stage_model.encode_moments_cl(CL(ve["fs_in"], 1))
+                    st["ip_x0"].copy_(mom.t[..., :Cz] * ldm.scale_factor)
 
-        def decode():
-            ve["z"][..., :Cz].copy_(st["x"] * (1.0 / ldm.scale_factor))
-            dec = ldm.first_stage_model.decode_cl(CL(ve["z"], Cz))
-            ve["ds"].copy_(dec.t[..., 0].reshape(B, hw, hw))
-            if edit_margin is None:
-                ops.minmax_normalise_scatter(ve["ds"], ve["sched"], ve["it"], ve["samples"], advance=True, workspace=ve["ws"])
-            else:
-                ops.minmax_normalise_keep_scatter(ve["ds"], ve["sched"], ve["it"], ve["known"], ve["keep"], ve["samples"], advance=True,
-                                                  workspace=ve["ws"])
+            def decode():
+                decode_head()
+                if not edit:
+                    ops.minmax_normalise_scatter(ve["ds"], ve["sched"], ve["it"], ve["samples"], advance=True, workspace=ve["ws"])
+                else:
+                    ops.minmax_normalise_keep_scatter(ve["ds"], ve["sched"], ve["it"], ve["known"], ve["keep"], ve["samples"], advance=True,
+                                                      workspace=ve["ws"])
 
-        ve["glue"], ve["encode"], ve["decode"] = glue, encode, decode
-        self._volume_graphs[key] = ve
-        return ve
+            ve["glue"], ve["encode"], ve["decode"] = glue, encode, decode
+
+        return self._engine(self._volume_graphs, key, B, hw, dev, st, finish)
 
     def _check_edit(self, B: int, depth: int, hw: int, known_ct, keep, edit_margin, q_noise_tapes) -> None:
         """Host-side refusals of the editing loop, by name, before any launch."""
@@ -345,97 +388,6 @@ class GuideGenPipeline:
             raise ValueError(f"{who}: known_ct holds values {lo:g}..{hi:g} outside [0, 1]")
 
     @torch.no_grad()
-    def _sample_ct_volumes_edit(self, labels, depth, hw, seeds, max_slices, x_T_tapes, known_ct, keep, edit_margin, q_noise_tapes):
-        """The editing loop of sample_ct_volumes."""
-        ldm, sampler, S = self.ldm, self.sampler, self.ddim_steps
-        dev = labels.device
-        B = labels.shape[0]
-        lat, Cz = hw // self.latent_factor, ldm.channels
-        known_d = known_ct.to(dev).permute(1, 0, 2, 3).contiguous()                   # slice-major, as `samples`
-        keep_d = (keep.to(dev) != 0).permute(1, 0, 2, 3).contiguous()
-        kept_all = keep_d.flatten(2).all(-1).cpu()                                     # [depth, B]
-        kept_any = keep_d.flatten(2).any(-1).cpu()
-        unkept_px = (~keep_d).flatten(2).sum(-1).cpu()
-        windows, mixed, skipped, outside = [], [], 0, 0
-        for i in range(B):
-            win = slice_window(labels[i], depth, max_slices)
-            visit = [m for m in win if not bool(kept_all[m % depth, i])]
-            skipped += len(win) - len(visit)
-            inside = {m % depth for m in win}
-            outside += int(sum(int(unkept_px[d, i]) for d in range(depth) if d not in inside))
-            windows.append(visit)
-            mixed.append([bool(kept_any[m % depth, i]) for m in visit])
-        n_mixed = [sum(mx) for mx in mixed]
-        for name, tapes, want in (("x_T_tapes", x_T_tapes, [len(w) for w in windows]), ("q_noise_tapes", q_noise_tapes, n_mixed)):
-            if tapes is not None:
-                for i in range(B):
-                    if len(tapes[i]) != want[i]:
-                        raise ValueError(f"sample_ct_volumes: {name}[{i}] holds {len(tapes[i])} tensors, volume {i} "
-                                         f"{'visits' if name == 'x_T_tapes' else 'has'} {want[i]} {'slices' if name == 'x_T_tapes' else 'mixed slices'}")
-        if q_noise_tapes is not None:
-            for i in range(B):
-                for k, t in enumerate(q_noise_tapes[i]):
-                    if tuple(t.shape) != (S, 1, Cz, lat, lat):
-                        raise ValueError(f"sample_ct_volumes: q_noise_tapes[{i}][{k}] has shape {tuple(t.shape)}, a mixed slice takes {(S, 1, Cz, lat, lat)}")
-        self.stats.update(slices_visited=sum(len(w) for w in windows), slices_skipped_kept=skipped, slices_mixed=sum(n_mixed),
-                          unkept_outside_window=outside)
-        start = torch.where(keep_d, known_d, torch.zeros_like(known_d))
-        iters = max(len(w) for w in windows)
-        if iters == 0:                                                                 # every slice of every window is kept: no iteration
-            self.stats["wasted_slot_fraction"] = 0.0
-            return start.permute(1, 0, 2, 3).contiguous()
-        sched, wasted = volume_schedule(windows, depth)
-        self.stats["wasted_slot_fraction"] = wasted
-        gens = [torch.Generator(device=dev).manual_seed(int(s)) for s in seeds]
-        st = sampler.prepare_state(B, Cz, (lat, lat), dev, Cz, mask_C=1)
-        ve = self._volume_engine(B, hw, depth, tuple(labels.shape), dev, st, edit_margin=edit_margin)
-        ve["labels"].copy_(labels)
-        ve["known"].copy_(known_d)
-        ve["keep"].copy_(keep_d)
-        ve["samples"].copy_(start)
-        ve["sched"].zero_()
-        ve["sched"][:iters].copy_(sched)
-        ve["it"].zero_()
-        glue, encode, decode = ve["glue"], ve["encode"], ve["decode"]
-        q_used = [0] * B
-
-        t_last = time.time()
-        for it in range(iters):
-            if time.time() - t_last > self.progress_every_s:
-                _log(f"LDM edited slice {it}/{iters} (batch of {B})")
-                t_last = time.time()
-            x_T = torch.zeros((B, Cz, lat, lat), dtype=torch.float32, device=dev)
-            q = torch.zeros((S, B, Cz, lat, lat), dtype=torch.float32, device=dev)     # rows of free or inactive volumes stay zero
-            for i in range(B):
-                if it < len(windows[i]):                                               # the x_T draw of the un-edited loop, then the q-sample noise
-                    x_T[i] = (x_T_tapes[i][it].to(dev).float().reshape(Cz, lat, lat) if x_T_tapes is not None
-                              else torch.randn((1, Cz, lat, lat), generator=gens[i], device=dev)[0])
-                    if mixed[i][it]:
-                        q[:, i] = (q_noise_tapes[i][q_used[i]].to(dev).float() if q_noise_tapes is not None
-                                   else torch.randn((S, 1, Cz, lat, lat), generator=gens[i], device=dev))[:, 0]
-                        q_used[i] += 1
-            x_T = x_T.permute(0, 2, 3, 1).reshape(B, 1, lat, lat, Cz)
-            st["x"].copy_(x_T)
-            st["unet_in"][..., :Cz].copy_(x_T)
-            st["ip_noise"].copy_(q.permute(0, 1, 3, 4, 2).reshape(st["ip_noise"].shape))
-            if not (self.use_graph and sampler.chain_graphable(st)):
-                glue()
-                encode()
-                sampler.run_steps(st, None, 0.0, None)
-                decode()
-            elif not ve["warmed"]:
-                glue()
-                encode()                                                               # eager once: fills the repack caches
-                sampler.chain(st)
-                decode()
-                ve["warmed"] = True
-            else:
-                if ve["graph"] is None:
-                    ve["graph"] = ops.capture_graph(lambda: (glue(), encode(), sampler.chain(st), decode()))
-                ve["graph"].replay()
-        return ve["samples"].clone().permute(1, 0, 2, 3)
-
-    @torch.no_grad()
     def sample_ct_volumes(self, labels: torch.Tensor, depth: int, hw: int, seeds: Sequence[int], max_slices: Optional[int] = None,
                           x_T_tapes=None, known_ct: Optional[torch.Tensor] = None, keep: Optional[torch.Tensor] = None, edit_margin: int = 0,
                           q_noise_tapes=None) -> torch.Tensor:
@@ -455,24 +407,40 @@ class GuideGenPipeline:
         loop order); a slice with no kept pixel draws nothing more, so an all-zero keep leaves the volume's stream, and its result, those
         of its un-edited run.  self.stats gains slices_visited / slices_skipped_kept / slices_mixed / unkept_outside_window (un-kept
         pixels on slices outside the window stay 0).  A call without known_ct takes the state, graph and launches it took before."""
-        ldm, sampler = self.ldm, self.sampler
+        ldm, sampler, S = self.ldm, self.sampler, self.ddim_steps
         dev = labels.device
         B = labels.shape[0]
         if len(seeds) != B or (x_T_tapes is not None and len(x_T_tapes) != B):
             raise ValueError(f"sample_ct_volumes: {B} volumes need {B} seeds (and {B} tapes)")
         self._check_edit(B, depth, hw, known_ct, keep, edit_margin, q_noise_tapes)
-        if known_ct is not None:
-            return self._sample_ct_volumes_edit(labels, depth, hw, seeds, max_slices, x_T_tapes, known_ct, keep, edit_margin, q_noise_tapes)
+        edit = known_ct is not None
         lat, Cz = hw // self.latent_factor, ldm.channels
-        windows = [slice_window(labels[i], depth, max_slices) for i in range(B)]
+        if edit:
+            known_d = known_ct.to(dev).permute(1, 0, 2, 3).contiguous()               # slice-major, as `samples`
+            keep_d = (keep.to(dev) != 0).permute(1, 0, 2, 3).contiguous()
+            windows, mixed, counters, start = plan_ct_edit(labels, depth, max_slices, known_d, keep_d, (S, 1, Cz, lat, lat), x_T_tapes,
+                                                           q_noise_tapes)
+            self.stats.update(counters)
+            if not any(windows):                                                       # every slice of every window is kept: no iteration
+                self.stats["wasted_slot_fraction"] = 0.0
+                return start.permute(1, 0, 2, 3).contiguous()
+        else:
+            windows = [slice_window(labels[i], depth, max_slices) for i in range(B)]
         sched, wasted = volume_schedule(windows, depth)
         iters = sched.shape[0]
         self.stats["wasted_slot_fraction"] = wasted
         gens = [torch.Generator(device=dev).manual_seed(int(s)) for s in seeds]
-        st = sampler.prepare_state(B, Cz, (lat, lat), dev, Cz)
-        ve = self._volume_engine(B, hw, depth, tuple(labels.shape), dev, st)
+        x_tapes, q_tapes = ([None] * B if t is None else t for t in (x_T_tapes, q_noise_tapes))
+        st = sampler.prepare_state(B, Cz, (lat, lat), dev, Cz, mask_C=1 if edit else 0)
+        ve = self._volume_engine(B, hw, depth, tuple(labels.shape), dev, st, edit_margin=edit_margin if edit else None)
         ve["labels"].copy_(labels)
-        ve["samples"].zero_()
+        if edit:
+            ve["known"].copy_(known_d)
+            ve["keep"].copy_(keep_d)
+            ve["samples"].copy_(start)
+            q_used = [0] * B
+        else:
+            ve["samples"].zero_()
         ve["sched"].zero_()
         ve["sched"][:iters].copy_(sched)                                               # uploaded once per batch
         ve["it"].zero_()
@@ -481,31 +449,27 @@ class GuideGenPipeline:
         t_last = time.time()
         for it in range(iters):
             if time.time() - t_last > self.progress_every_s:
-                _log(f"LDM slice {it}/{iters} (batch of {B})")
+                _log(f"LDM {'edited ' if edit else ''}slice {it}/{iters} (batch of {B})")
                 t_last = time.time()
             x_T = torch.zeros((B, Cz, lat, lat), dtype=torch.float32, device=dev)
+            if edit:
+                q = torch.zeros((S, B, Cz, lat, lat), dtype=torch.float32, device=dev) # rows of free or inactive volumes stay zero
             for i in range(B):
-                if it < len(windows[i]):                                               # NCHW draw order of sample_ct
-                    x_T[i] = (x_T_tapes[i][it].to(dev).float().reshape(Cz, lat, lat) if x_T_tapes is not None
-                              else torch.randn((1, Cz, lat, lat), generator=gens[i], device=dev)[0])
-            x_T = x_T.permute(0, 2, 3, 1).reshape(B, 1, lat, lat, Cz)
-            st["x"].copy_(x_T)
-            st["unet_in"][..., :Cz].copy_(x_T)
+                if it < len(windows[i]):                                               # the x_T draw of sample_ct, then the q-sample noise
+                    x_T[i] = _tape_or_randn(x_tapes[i], it, (1, Cz, lat, lat), gens[i]).reshape(Cz, lat, lat)
+                    if edit and mixed[i][it]:
+                        q[:, i] = _tape_or_randn(q_tapes[i], q_used[i], (S, 1, Cz, lat, lat), gens[i])[:, 0]
+                        q_used[i] += 1
+            _load_x_T(st, x_T)
+            if edit:
+                st["ip_noise"].copy_(q.permute(0, 1, 3, 4, 2).reshape(st["ip_noise"].shape))
             if not (self.use_graph and sampler.chain_graphable(st)):
                 glue()
                 encode()
                 sampler.run_steps(st, None, 0.0, None)
                 decode()
-            elif not ve["warmed"]:
-                glue()
-                encode()                                                               # eager once: fills the repack caches
-                sampler.chain(st)
-                decode()
-                ve["warmed"] = True
             else:
-                if ve["graph"] is None:
-                    ve["graph"] = ops.capture_graph(lambda: (glue(), encode(), sampler.chain(st), decode()))
-                ve["graph"].replay()
+                ops.replay_captured(ve, "graph", lambda: (glue(), encode(), sampler.chain(st), decode()))
         return ve["samples"].clone().permute(1, 0, 2, 3)
 
     @torch.no_grad()

@@ -71,6 +71,82 @@ def test_schedule_equals_the_solo_slice_loops():
     assert sched[0, 0].tolist() == [15, 0, 1] and sched[1, 0].tolist() == [0, 0, 1]
 
 
+def _batch_window(labels_np, depth, max_slices=None):
+    """The reference's rule for a batch [N, Dm, H, W] (sample_diffusion.py:202 on N masks): slices whose order-0 zoomed mask is non-empty
+    in ANY batch element, from one before the first to the last, python-indexed; an empty batch gives start, end = 1, 0."""
+    Dm = labels_np.shape[1]
+    zf = (Dm - 1) / (depth - 1) if depth > 1 else 1.0
+    src = np.clip(np.floor(np.arange(depth, dtype=np.float64) * zf + 0.5).astype(np.int64), 0, Dm - 1)
+    zoomed = labels_np[:, src]                                                  # [N, depth, H, W]
+    nz = np.array([any((zoomed[n, d] != 0).any() for n in range(zoomed.shape[0])) for d in range(depth)])
+    idx = np.nonzero(nz)[0]
+    start, end = (int(idx[0]), int(idx[-1])) if idx.size else (1, 0)
+    ms = list(range(start - 1, end + 1))
+    return ms[:max_slices] if max_slices is not None else ms
+
+
+def test_slice_window_of_a_batch_is_the_any_over_the_batch_rule():
+    from jointimagegeneration_amd.pipeline import slice_window
+    cases = {                                      # name: (Dm, depth, non-empty mask slices [lo, hi) of the two elements, the window)
+        "empty": (6, 6, [(0, 0), (0, 0)], [0]),
+        "slice 0 (wraps to -1)": (6, 6, [(0, 2), (0, 0)], [-1, 0, 1]),
+        "last slice only": (6, 6, [(0, 0), (5, 6)], [4, 5]),
+        "5 into 7": (5, 7, [(1, 2), (3, 4)], [0, 1, 2, 3, 4, 5]),       # zoom index 0 1 1 2 3 3 4: mask slices 1 and 3 are slices 1, 2, 4, 5
+        "union wider than either": (6, 6, [(1, 3), (3, 5)], [0, 1, 2, 3, 4]),
+    }
+    for name, (Dm, depth, wins, want) in cases.items():
+        labels = torch.stack([_mask(Dm, 4, lo, hi, seed=7 + i) for i, (lo, hi) in enumerate(wins)])
+        assert labels.shape == (2, Dm, 4, 4)
+        for max_slices in (None, 2):
+            ref = _batch_window(labels.numpy(), depth, max_slices)
+            assert ref == (want if max_slices is None else want[:2]), name
+            assert slice_window(labels, depth, max_slices) == ref, name
+    a, b = (slice_window(_mask(6, 4, lo, hi, seed=7 + i), 6) for i, (lo, hi) in enumerate(cases["union wider than either"][2]))
+    assert a == [0, 1, 2] and b == [2, 3, 4]                                    # each element alone is narrower than the union
+
+
+def test_ct_edit_plan_visits_counters_start_volume_and_tape_refusals():
+    """plan_ct_edit on three volumes with the window 0 .. 4 of 6 slices: volume 0's window is kept whole, volume 1 keeps slices 0, 2, 4 and
+    parts of 1 and 3 (two mixed slices), volume 2 keeps nothing."""
+    import pytest
+    from jointimagegeneration_amd.pipeline import plan_ct_edit
+    depth, hw, q_shape = 6, 4, (5, 1, 4, 1, 1)
+    g = torch.Generator().manual_seed(9)
+    labels = torch.stack([_mask(depth, hw, 1, 5, seed=i) for i in range(3)])
+    known = torch.rand((depth, 3, hw, hw), generator=g)                         # slice-major, as the loop holds it
+    keep = torch.ones((depth, 3, hw, hw), dtype=torch.bool)
+    keep[5, 0, 0, 0] = False                                                    # volume 0: one un-kept pixel, outside its window
+    keep[1, 1, :2] = False
+    keep[3, 1, 2, 3] = False
+    keep[5, 1, 0, :3] = False
+    keep[:, 2] = False
+    windows, mixed, counters, start = plan_ct_edit(labels, depth, None, known, keep, q_shape)
+    assert windows == [[], [1, 3], [0, 1, 2, 3, 4]]
+    assert mixed == [[], [True, True], [False] * 5]
+    assert counters == dict(slices_visited=7, slices_skipped_kept=5 + 3, slices_mixed=2, unkept_outside_window=1 + 3 + hw * hw)
+    assert torch.equal(start, torch.where(keep, known, torch.zeros(())))
+    # max_slices truncates the window before the kept slices leave it
+    windows, mixed, counters, _ = plan_ct_edit(labels, depth, 2, known, keep, q_shape)
+    assert windows == [[], [1], [0, 1]] and mixed == [[], [True], [False, False]]
+    assert (counters["slices_visited"], counters["slices_skipped_kept"], counters["slices_mixed"]) == (3, 2 + 1, 1)
+    # nothing to visit: every window kept whole
+    keep_all = torch.ones_like(keep)
+    windows, _, counters, start = plan_ct_edit(labels, depth, None, known, keep_all, q_shape)
+    assert not any(windows) and counters["slices_visited"] == 0 and counters["slices_skipped_kept"] == 15 and torch.equal(start, known)
+    # tapes that fit, then each refusal by its text
+    x_ok = [[], [torch.zeros(1, 4, 1, 1)] * 2, [torch.zeros(1, 4, 1, 1)] * 5]
+    q_ok = [[], [torch.zeros(q_shape)] * 2, []]
+    assert plan_ct_edit(labels, depth, None, known, keep, q_shape, x_ok, q_ok)[0] == [[], [1, 3], [0, 1, 2, 3, 4]]
+    with pytest.raises(ValueError, match=r"sample_ct_volumes: x_T_tapes\[1\] holds 1 tensors, volume 1 visits 2 slices"):
+        plan_ct_edit(labels, depth, None, known, keep, q_shape, [[], x_ok[1][:1], x_ok[2]], q_ok)
+    with pytest.raises(ValueError, match=r"sample_ct_volumes: q_noise_tapes\[1\] holds 0 tensors, volume 1 has 2 mixed slices"):
+        plan_ct_edit(labels, depth, None, known, keep, q_shape, x_ok, [[], [], []])
+    with pytest.raises(ValueError, match=r"sample_ct_volumes: q_noise_tapes\[2\] holds 1 tensors, volume 2 has 0 mixed slices"):
+        plan_ct_edit(labels, depth, None, known, keep, q_shape, None, [[], q_ok[1], [torch.zeros(q_shape)]])
+    with pytest.raises(ValueError, match=r"sample_ct_volumes: q_noise_tapes\[1\]\[1\] has shape \(5, 4, 1, 1\), a mixed slice takes \(5, 1, 4, 1, 1\)"):
+        plan_ct_edit(labels, depth, None, known, keep, q_shape, None, [[], [torch.zeros(q_shape), torch.zeros(5, 4, 1, 1)], []])
+
+
 def _free_port():
     s = socket.socket(); s.bind(("127.0.0.1", 0)); p = s.getsockname()[1]; s.close(); return p
 

@@ -175,6 +175,30 @@ def test_segmented_minmax_normalise_scatter(dev):
     assert int(it[0]) == 2 and bool((vol[~touched.to(dev)] == -1.0).all())
 
 
+# ------------------------------------------------------------------------------------------------ the warm / capture / replay ladder
+def test_replay_captured_runs_eagerly_once_captures_once_then_replays(dev):
+    """ops.replay_captured on its own: the body runs twice in Python (the eager call and the capture), every call computes on the buffers'
+    current contents, and the graph of the second call is the one every later call replays."""
+    from jointimagegeneration_amd import ops
+    a = torch.empty(1024, dtype=torch.float32, device=dev)
+    out = torch.zeros_like(a)
+    calls = [0]
+
+    def body():
+        calls[0] += 1
+        ops.lincomb4([a], [2.0], 1.0, out)
+
+    holder = dict(warmed=False, graph=None)
+    graphs = []
+    for k in range(4):
+        a.copy_(torch.randn(1024, generator=torch.Generator().manual_seed(100 + k)))
+        ops.replay_captured(holder, "graph", body)
+        assert torch.equal(out, 2 * a), f"call {k}"
+        graphs.append(holder["graph"])
+    assert calls[0] == 2 and holder["warmed"] is True
+    assert graphs[0] is None and isinstance(graphs[1], torch.cuda.CUDAGraph) and graphs[3] is graphs[1]
+
+
 # ------------------------------------------------------------------------------------------------ LDM stage at B = 2 (small configs)
 def _small_labels(lo, hi, seed, Dm=5, HW=16):
     lab = torch.zeros((Dm, HW, HW), dtype=torch.int32)
