@@ -1,142 +1,90 @@
-"""ctypes binding of libguidegen_hip.so (the C-ABI in include/guidegen_hip.h).
+"""ctypes binding of libguidegen_hip.so, derived from its public header include/guidegen_hip.h.
 
-There is NO fallback: if the shared library is missing or a symbol is absent this module raises, and every
-product op raises RuntimeError when a call returns a negative gg_status (message from gg_last_error()).
+The header is the one statement of the C-ABI: the constants, the descriptor structs and every prototype below are read from its text
+at import (parse_header), so an entry point or a field is added in the header and nowhere else.  tests/test_capi_cpu.py checks the
+result against the compiler (struct layouts) and against a second reading of the declarations.
+
+There is NO fallback: if the header or the shared library is missing or a symbol is absent this module raises, and every product op
+raises RuntimeError when a call returns a negative gg_status (message from gg_last_error()).
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libguidegen_hip.so")
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "guidegen_hip.h")
 
-GG_BF16, GG_F32 = 0, 1
-
-vp, i32, i64, u64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float
-
-
-class ConvDesc(C.Structure):
-    _fields_ = [
-        ("N", i32), ("D", i32), ("H", i32), ("W", i32),
-        ("C1", i32), ("C2", i32), ("Cout", i32), ("Cout_pad", i32),
-        ("kd", i32), ("kh", i32), ("kw", i32), ("stride", i32), ("pad", i32), ("upsample", i32),
-        ("Do", i32), ("Ho", i32), ("Wo", i32), ("out_dtype", i32), ("prologue_act", i32), ("path_hint", i32),
-        ("src1", vp), ("src2", vp), ("weight", vp), ("bias", vp), ("bias_stride", i64),
-        ("residual", vp), ("out", vp), ("gn_scale", vp), ("gn_shift", vp), ("workspace", vp), ("workspace_bytes", i64), ("reserved_ptr", vp), ("gn_acc", vp),
-        ("ddim_x", vp), ("ddim_scalars", vp), ("ddim_pred_x0", vp), ("ddim_unet_in", vp), ("ddim_unet_in_stride", i64),
-        ("epilogue_geglu", i32), ("pro_c_logical", i32), ("pro_acc1", vp), ("pro_acc2", vp), ("pro_gamma", vp), ("pro_beta", vp),
-        ("pro_eps", f32), ("skip_C1", i32), ("skip_C2", i32), ("reserved_tail", i32), ("skip_src1", vp), ("skip_src2", vp), ("skip_weight", vp),
-        ("post_xt", vp), ("post_labels_out", vp), ("post_scalars", vp), ("post_E", vp), ("post_philox_seed", C.c_uint64),
-        ("post_philox_offset_dev", vp), ("post_onehot_out", vp), ("post_onehot_stride", i64), ("post_draw", i32), ("reserved_tail2", i32),
-        ("post_philox_seeds", vp), ("post_rows_per_sample", i64),
-    ]
+# by-value C types; a name outside this map is an error, never a guess
+_SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "float": C.c_float, "double": C.c_double}
+# one declarator with its type: "const float *bias", "int32_t N", "int32_t plan[4]", "void *stream", and the bare "const char *" of a result
+_DECL = re.compile(r"(?:const\s+)?(\w+)\s*(\*?)\s*(\w*)\s*(\[\w*\])?$")
 
 
-class AttentionDesc(C.Structure):
-    _fields_ = [
-        ("N", i32), ("heads", i32), ("head_dim", i32), ("Tq", i32), ("Tkv", i32),
-        ("ldq", i64), ("hsq", i64), ("ldk", i64), ("hsk", i64), ("ldv", i64), ("hsv", i64), ("ldo", i64), ("hso", i64),
-        ("scale", f32), ("reserved", i32),
-        ("q", vp), ("k", vp), ("v", vp), ("out", vp), ("workspace", vp), ("workspace_bytes", i64),
-    ]
+def _ctype(base: str, pointer: bool, structs: dict, what: str):
+    if pointer:
+        return C.POINTER(structs[base]) if base in structs else C.c_void_p
+    if base not in _SCALARS:
+        raise ValueError(f"{what}: no ctypes type for {base!r}")
+    return _SCALARS[base]
 
 
-# name -> (restype, argtypes); must list every symbol declared in include/guidegen_hip.h
-SIGNATURES = {
-    "gg_last_error": (C.c_char_p, []),
-    "gg_version": (C.c_int, []),
-    "gg_conv_packed_weight_bytes": (i64, [i32, i32, i32]),
-    "gg_conv_pack_weight": (C.c_int, [vp, i32, i32, i32, i32, vp, vp]),
-    "gg_conv_forward": (C.c_int, [C.POINTER(ConvDesc), vp]),
-    "gg_conv_workspace_bytes": (i64, [C.POINTER(ConvDesc)]),
-    "gg_conv_fuses_prologue": (C.c_int, [C.POINTER(ConvDesc)]),
-    "gg_conv_runs_halo_tile": (C.c_int, [C.POINTER(ConvDesc)]),
-    "gg_conv_emits_stats": (C.c_int, [C.POINTER(ConvDesc)]),
-    "gg_conv_runs_tile": (C.c_int, [C.POINTER(ConvDesc)]),
-    "gg_conv_runs_halo_split": (C.c_int, [C.POINTER(ConvDesc)]),
-    "gg_conv_runs_tile_s2": (C.c_int, [C.POINTER(ConvDesc)]),
-    "gg_conv_prologue_from_acc": (C.c_int, [C.POINTER(ConvDesc)]),
-    "gg_conv_fuses_skip": (C.c_int, [C.POINTER(ConvDesc)]),
-    "gg_conv_fuses_ddim": (C.c_int, [C.POINTER(ConvDesc)]),
-    "gg_conv_fuses_posterior": (C.c_int, [C.POINTER(ConvDesc)]),
-    "gg_groupnorm_workspace_bytes": (i64, [i32, i64, i32]),
-    "gg_groupnorm_stats": (C.c_int, [vp, i32, vp, i32, i32, i64, i32, vp, vp, f32, vp, vp, vp, i64, vp]),
-    "gg_groupnorm_apply": (C.c_int, [vp, i32, vp, i32, i32, i64, vp, vp, i32, vp, vp]),
-    "gg_groupnorm_apply_acc": (C.c_int, [vp, i32, vp, vp, i32, vp, i32, i64, i32, vp, vp, f32, i32, vp, vp]),
-    "gg_groupnorm_fused_supported": (C.c_int, [i64, i32, i32, i32]),
-    "gg_groupnorm_fused": (C.c_int, [vp, i32, vp, i32, i32, i64, i32, vp, vp, f32, i32, vp, vp]),
-    "gg_groupnorm_scale_shift_acc": (C.c_int, [vp, i32, i32, vp, i32, i32, i32, i64, i32, vp, vp, f32, vp, vp, vp]),
-    "gg_attention_forward": (C.c_int, [C.POINTER(AttentionDesc), vp]),
-    "gg_attention_workspace_bytes": (i64, [C.POINTER(AttentionDesc)]),
-    "gg_attention_plan": (C.c_int, [C.POINTER(AttentionDesc), C.POINTER(i32)]),
-    "gg_attention_forward_kvlen": (C.c_int, [C.POINTER(AttentionDesc), vp, vp]),
-    "gg_layernorm": (C.c_int, [vp, i64, i32, vp, vp, f32, vp, vp]),
-    "gg_geglu": (C.c_int, [vp, i64, i32, vp, vp]),
-    "gg_add": (C.c_int, [vp, vp, i64, vp, vp]),
-    "gg_linear_f32": (C.c_int, [vp, i32, i32, vp, vp, i32, i32, vp, i64, vp]),
-    "gg_timestep_embedding": (C.c_int, [vp, i32, i32, f32, vp, vp]),
-    "gg_nchw_f32_to_cl_bf16": (C.c_int, [vp, i32, i32, i64, vp, i32, i32, i32, vp]),
-    "gg_cl_to_nchw_f32": (C.c_int, [vp, i32, i32, i32, i64, i32, vp, vp]),
-    "gg_ccdm_posterior_sample": (C.c_int, [vp, i32, i32, vp, vp, u64, vp, i32, vp, i32, i64, vp, vp, vp, i32, vp]),
-    "gg_ccdm_posterior_sample_seeds": (C.c_int, [vp, i32, i32, vp, vp, vp, i64, vp, i32, vp, i32, i64, vp, vp, vp, i32, vp]),
-    "gg_ccdm_draw_tape": (C.c_int, [u64, vp, i64, vp, i32, i64, vp, vp, vp, vp]),
-    "gg_labels_to_onehot": (C.c_int, [vp, i64, i32, vp, i32, vp]),
-    "gg_ddim_step": (C.c_int, [vp, vp, i32, vp, vp, i64, i32, vp, vp, i32, vp]),
-    "gg_minmax_normalise": (C.c_int, [vp, i64, vp, vp, vp]),
-    "gg_ddpm_step": (C.c_int, [vp, vp, i32, vp, vp, i64, i32, vp, i32, vp]),
-    "gg_inpaint_blend": (C.c_int, [vp, vp, vp, i32, vp, vp, i64, i32, vp, i32, vp]),
-    "gg_ddpm_step_x0": (C.c_int, [vp, vp, i32, vp, vp, i32, i64, i32, vp, vp, i32, vp]),
-    "gg_log_rows": (C.c_int, [vp, i32, i32, i64, vp, vp]),
-    "gg_vq_nearest": (C.c_int, [vp, i32, vp, i32, i32, i64, vp, vp, i32, vp]),
-    "gg_ddim_step_vq": (C.c_int, [vp, vp, i32, vp, vp, i32, vp, i32, i64, i32, vp, vp, vp, i32, vp]),
-    "gg_label_confusion": (C.c_int, [vp, i32, vp, i32, i64, i32, vp, vp, vp]),
-    "gg_label_vote": (C.c_int, [vp, i32, i64, i32, vp, f32, f32, vp, vp, vp, vp, vp]),
-    "gg_label_components_workspace_bytes": (i64, [i32, i64]),
-    "gg_label_components": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, i64, vp, vp]),
-    "gg_component_stats": (C.c_int, [vp, vp, i32, i64, i32, vp, vp, vp]),
-    "gg_component_filter": (C.c_int, [vp, vp, vp, vp, i32, i64, i32, vp, vp, i32, i32, vp, vp, vp]),
-    "gg_volume_views_cl": (C.c_int, [vp, i32, i32, i32, i32, i32, i64, i64, vp, vp, vp, i32, vp]),
-    "gg_relu_cl": (C.c_int, [vp, i32, i64, vp]),
-    "gg_lpips_tap_workspace_bytes": (i64, [i32, i32, i32, i32, i32]),
-    "gg_lpips_tap": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, i64, vp]),
-    "gg_unfold_cl": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
-    "gg_fold_weighted_cl": (C.c_int, [vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
-    "gg_lincomb4": (C.c_int, [vp, vp, vp, vp, f32, f32, f32, f32, f32, i64, vp, vp]),
-    "gg_conv_forward_f32": (C.c_int, [C.POINTER(ConvDesc), vp]),
-    "gg_groupnorm_f32": (C.c_int, [vp, i32, vp, i32, i32, i64, i32, vp, vp, f32, i32, vp, vp, vp]),
-    "gg_attention_forward_f32": (C.c_int, [C.POINTER(AttentionDesc), vp]),
-    "gg_attention_forward_kvlen_f32": (C.c_int, [C.POINTER(AttentionDesc), vp, vp]),
-    "gg_groupnorm_f32_film": (C.c_int, [vp, i32, i32, i64, i32, vp, vp, f32, vp, i64, i32, vp, vp, vp]),
-    "gg_resample2x": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp]),
-    "gg_film_fold": (C.c_int, [vp, vp, i32, i32, i32, vp, i64, vp]),
-    "gg_mask_to_cond_slice": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp]),
-    "gg_mask_to_cond_slices": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp, i32, vp]),
-    "gg_minmax_normalise_scatter": (C.c_int, [vp, i32, i64, vp, vp, i32, vp, i32, i32, vp, vp]),
-    "gg_ct_edit_glue": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp, i32, vp, vp]),
-    "gg_minmax_normalise_keep_scatter": (C.c_int, [vp, i32, i64, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp]),
-    "gg_label_keep_volume": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
-    "gg_embed_rows": (C.c_int, [vp, i64, i32, vp, i32, i32, vp, i32, vp, i32, i32, vp]),
-    "gg_bert_embed": (C.c_int, [vp, vp, i64, i32, vp, i32, vp, i32, vp, i32, i32, vp, vp, f32, vp, i32, vp, vp, vp]),
-    "gg_gelu": (C.c_int, [vp, i64, vp, vp]),
-    "gg_layernorm_rows": (C.c_int, [vp, i64, i32, i32, vp, vp, f32, vp, vp]),
-    "gg_interpolate2d_f32": (C.c_int, [vp, i64, i32, i32, i32, i32, f32, f32, i32, vp, vp]),
-    "gg_mask_overlay": (C.c_int, [vp, i32, i32, i32, i32, C.c_double, C.POINTER(i32), vp, vp]),
-    "gg_make_grid_u8": (C.c_int, [vp, i32, i32, i32, i32, i32, i32, f32, vp, vp]),
-    "gg_loss_workspace_bytes": (i64, [i32, i64]),
-    "gg_q_sample_rows": (C.c_int, [vp, vp, vp, i32, i32, i64, vp, vp, i32, i32, vp]),
-    "gg_loss_rows": (C.c_int, [vp, i32, vp, vp, vp, i32, i32, i32, i64, vp, vp, i64, vp]),
-    "gg_ccdm_q_sample": (C.c_int, [vp, vp, i64, i32, vp, vp, vp, i64, vp, vp, i32, vp]),
-    "gg_ccdm_inpaint_blend": (C.c_int, [vp, vp, vp, vp, i64, i32, vp, u64, vp, vp, i64, vp, i32, vp]),
-    "gg_ccdm_step_loss": (C.c_int, [vp, i32, vp, vp, vp, i64, vp, i32, i64, vp, vp, i64, vp]),
-    "gg_patch_conv_forward": (C.c_int, [vp, vp, vp, vp, f32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp]),
-    "gg_patch_conv_forward_f32": (C.c_int, [vp, vp, vp, vp, f32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
-    "gg_gauss_kl_rows": (C.c_int, [vp, i32, i32, i32, i64, vp, vp, i64, vp]),
-    "gg_gauss_sample_rows": (C.c_int, [vp, i32, vp, i32, i32, i64, vp, vp, i32, i32, vp]),
-    "gg_logit_stats": (C.c_int, [vp, i32, i64, vp, vp, i64, vp]),
-    "gg_ubench_mfma_bf16": (C.c_int, [i32, i32, i32, vp, C.POINTER(C.c_double), vp]),
-    "gg_ubench_stream_copy": (C.c_int, [vp, vp, i64, vp]),
-}
+def parse_header(text: str):
+    """(constants, structs, signatures) of a header in the C subset guidegen_hip.h is written in: `#define GG_X <int>`, `typedef enum`,
+    `typedef struct` of scalars and pointers, and prototypes.  Anything else raises ValueError naming the declaration."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", "", text, flags=re.S)
+    constants = {m[1]: int(m[2], 0) for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(GG_\w+)[ \t]+(-?\w+)[ \t]*$", text, flags=re.M)}
+    text = re.sub(r"^[ \t]*#[ \t]*ifdef[ \t]+__cplusplus.*?^[ \t]*#[ \t]*endif[^\n]*$", "", text, flags=re.S | re.M)   # extern "C" { ... }
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    for m in re.finditer(r"typedef\s+enum\s*\{(.*?)\}\s*\w+\s*;", text, flags=re.S):
+        value = 0
+        for item in filter(None, (s.strip() for s in m[1].split(","))):
+            name, _, given = (s.strip() for s in item.partition("="))
+            value = int(given, 0) if given else value
+            constants[name] = value
+            value += 1
+    structs = {}
+    for m in re.finditer(r"typedef\s+struct\s*\{(.*?)\}\s*(\w+)\s*;", text, flags=re.S):
+        fields = []
+        for stmt in filter(None, (s.strip() for s in m[1].split(";"))):
+            first, *more = (s.strip() for s in stmt.split(","))                 # "int32_t N, D" / "const void *q, *k": one type, several names
+            d = _DECL.match(first)
+            if not d or not d[3] or d[4]:
+                raise ValueError(f"{m[2]}: cannot read the field declaration {stmt!r}")
+            for star, name in [(d[2], d[3])] + [re.fullmatch(r"(\*?)\s*(\w+)", s).groups() for s in more]:
+                fields.append((name, _ctype(d[1], bool(star), {}, f"{m[2]}.{name}")))
+        structs[m[2]] = type(m[2], (C.Structure,), {"_fields_": fields})
+    signatures = {}
+    for stmt in filter(None, (s.strip() for s in re.sub(r"typedef\s+(?:struct|enum)\s*\{.*?\}\s*\w+\s*;", "", text, flags=re.S).split(";"))):
+        m = re.fullmatch(r"(.*?)\b(\w+)\s*\((.*)\)", stmt, flags=re.S)
+        res = m and _DECL.match(m[1].strip())
+        if not res or res[3] or res[4]:
+            raise ValueError(f"cannot read the declaration {stmt!r}")
+        restype = C.c_char_p if (res[1], res[2]) == ("char", "*") else _ctype(res[1], bool(res[2]), structs, m[2])
+        argtypes = []
+        for arg in ([] if m[3].strip() == "void" else (a.strip() for a in m[3].split(","))):
+            d = _DECL.match(arg)
+            if not d or not d[3]:
+                raise ValueError(f"{m[2]}: cannot read the parameter {arg!r}")
+            argtypes.append(_ctype(d[1], bool(d[2] or d[4]), structs, f"{m[2]}({arg})"))        # an array parameter is a pointer
+        signatures[m[2]] = (restype, argtypes)
+    return constants, structs, signatures
+
+
+def _header_text(path: str) -> str:
+    if not os.path.exists(path):
+        raise RuntimeError(f"{path} not found: the ctypes binding is derived from the C header, which ships with the package's source tree")
+    with open(path) as fh:
+        return fh.read()
+
+
+# GG_OK, GG_ERR_*, GG_BF16, GG_F32, GG_LOSS_*, GG_DDPM_* become module attributes; SIGNATURES: name -> (restype, argtypes)
+CONSTANTS, STRUCTS, SIGNATURES = parse_header(_header_text(HEADER_PATH))
+globals().update(CONSTANTS)
+GG_BF16, GG_F32 = CONSTANTS["GG_BF16"], CONSTANTS["GG_F32"]
+ConvDesc, AttentionDesc = STRUCTS["gg_conv_desc"], STRUCTS["gg_attention_desc"]
 
 _lib = None
 
@@ -169,3 +117,8 @@ def check(rc: int, what: str) -> None:
     if rc != 0:
         msg = load().gg_last_error()
         raise RuntimeError(f"{what} failed with gg_status {rc}: {msg.decode() if msg else ''}")
+
+
+def call(name: str, *args) -> None:
+    """Call a status-returning entry point of the loaded library; a failure raises with the library's message."""
+    check(getattr(load(), name)(*args), name)

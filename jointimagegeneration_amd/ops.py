@@ -13,7 +13,7 @@ from typing import Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from ._lib import GG_BF16, GG_F32, AttentionDesc, ConvDesc, check
+from ._lib import GG_BF16, GG_F32, AttentionDesc, ConvDesc, call, check
 
 
 def _stream() -> int:
@@ -139,7 +139,6 @@ def to_cl(x: torch.Tensor, c_pad: Optional[int] = None, out: Optional[torch.Tens
           zero_fill: bool = True) -> CL:
     """NC[D]HW fp32 -> CL bf16 (optionally into channels [c_offset, c_offset+C) of an existing buffer)."""
     require_gpu(x, "to_cl")
-    lib = _lib.load()
     x = x.contiguous().float()
     N, Cc = x.shape[:2]
     sp = tuple(x.shape[2:])
@@ -156,20 +155,18 @@ def to_cl(x: torch.Tensor, c_pad: Optional[int] = None, out: Optional[torch.Tens
         cp = c_pad or pad32(Cc + c_offset)
         out = torch.empty((N,) + sp3 + (cp,), dtype=torch.bfloat16, device=x.device)
     cp = out.shape[-1]
-    check(lib.gg_nchw_f32_to_cl_bf16(x.data_ptr(), N, Cc, S, out.data_ptr(), cp, c_offset, 1 if zero_fill else 0, _stream()),
-          "gg_nchw_f32_to_cl_bf16")
+    call("gg_nchw_f32_to_cl_bf16", x.data_ptr(), N, Cc, S, out.data_ptr(), cp, c_offset, 1 if zero_fill else 0, _stream())
     return CL(out, Cc + c_offset)
 
 
 def from_cl(cl: CL, ndim_spatial: int) -> torch.Tensor:
     """CL (bf16 or fp32) -> NC[D]HW fp32."""
-    lib = _lib.load()
     t = cl.t
     N, D, H, W, cp = t.shape
     sp = (D, H, W)[3 - ndim_spatial:]
     out = torch.empty((N, cl.C) + sp, dtype=torch.float32, device=t.device)
     dt = GG_BF16 if t.dtype == torch.bfloat16 else GG_F32
-    check(lib.gg_cl_to_nchw_f32(t.data_ptr(), dt, N, cl.C, D * H * W, cp, out.data_ptr(), _stream()), "gg_cl_to_nchw_f32")
+    call("gg_cl_to_nchw_f32", t.data_ptr(), dt, N, cl.C, D * H * W, cp, out.data_ptr(), _stream())
     return out
 
 
@@ -190,7 +187,7 @@ def pack_conv_weight(w: torch.Tensor, cin_pad: int) -> torch.Tensor:
         ntaps *= s
     nbytes = lib.gg_conv_packed_weight_bytes(Cout, cin_pad, ntaps)
     out = torch.empty(nbytes // 2, dtype=torch.bfloat16, device=w.device)
-    check(lib.gg_conv_pack_weight(w.data_ptr(), Cout, Cin, cin_pad, ntaps, out.data_ptr(), _stream()), "gg_conv_pack_weight")
+    call("gg_conv_pack_weight", w.data_ptr(), Cout, Cin, cin_pad, ntaps, out.data_ptr(), _stream())
     return out
 
 
@@ -360,7 +357,7 @@ def conv(src1: CL, weight: torch.Tensor, bias: Optional[torch.Tensor], cout: int
         d.weight, d.bias, d.bias_stride = weight.data_ptr(), _ptr(bias), (cp if bias_per_sample else 0)
         d.residual = _ptr(residual.t) if residual is not None else None
         d.out = out.data_ptr()
-        check(lib.gg_conv_forward_f32(C.byref(d), _stream()), "gg_conv_forward_f32")
+        call("gg_conv_forward_f32", C.byref(d), _stream())
         return CL(out, cout)
     if geglu:      # fused GEGLU epilogue (gg_conv_desc.epilogue_geglu): cout = 2 * inner value | gate rows in, inner channels out
         if cout % 32 or out is not None or out_f32 or residual is not None:
@@ -424,7 +421,7 @@ def conv(src1: CL, weight: torch.Tensor, bias: Optional[torch.Tensor], cout: int
         if seeds is not None:                   # one Philox key per sample (gg_conv_desc.post_philox_seeds)
             d.post_philox_seeds, d.post_rows_per_sample = _seeds_ptr(seeds, N), Do * Ho * Wo
         fused_post = True
-    check(lib.gg_conv_forward(C.byref(d), _stream()), "gg_conv_forward")
+    call("gg_conv_forward", C.byref(d), _stream())
     return CL(out, cout // 2 if geglu else cout, acc=acc, fused_ddim=fused, fused_post=fused_post)
 
 
@@ -457,17 +454,15 @@ def groupnorm_stats(src1: CL, gamma: torch.Tensor, beta: torch.Tensor, eps: floa
     ws_bytes = lib.gg_groupnorm_workspace_bytes(N, S, C1 + C2)
     ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=src1.t.device)
     scale, shift = _gn_tables(src1, N, C1 + C2)
-    check(lib.gg_groupnorm_stats(src1.t.data_ptr(), C1, p2, C2, N, S, c_log,
-                                 gamma.data_ptr(), beta.data_ptr(), eps, scale.data_ptr(), shift.data_ptr(), ws.data_ptr(),
-                                 ws_bytes, _stream()), "gg_groupnorm_stats")
+    call("gg_groupnorm_stats", src1.t.data_ptr(), C1, p2, C2, N, S, c_log, gamma.data_ptr(), beta.data_ptr(), eps, scale.data_ptr(),
+         shift.data_ptr(), ws.data_ptr(), ws_bytes, _stream())
     return scale, shift
 
 
 def groupnorm_apply(src1: CL, scale: torch.Tensor, shift: torch.Tensor, act: bool, src2: Optional[CL] = None) -> CL:
     N, S, C1, C2, c_log, p2 = _gn_sources(src1, src2, "ignore")       # per-(n, c) tables: padding lanes of the first source have their own rows
     out = _gn_out(src1, C1 + C2)
-    check(_lib.load().gg_groupnorm_apply(src1.t.data_ptr(), C1, p2, C2, N, S, scale.data_ptr(),
-                                         shift.data_ptr(), 1 if act else 0, out.data_ptr(), _stream()), "gg_groupnorm_apply")
+    call("gg_groupnorm_apply", src1.t.data_ptr(), C1, p2, C2, N, S, scale.data_ptr(), shift.data_ptr(), 1 if act else 0, out.data_ptr(), _stream())
     return CL(out, c_log)
 
 
@@ -480,8 +475,8 @@ def groupnorm_fused(src1: CL, gamma: torch.Tensor, beta: torch.Tensor, eps: floa
     """act(GroupNorm(32)(cat[src1, src2])) in one launch (small tensors: see groupnorm_fused_ok)."""
     N, S, C1, C2, c_log, p2 = _gn_sources(src1, src2, "ignore")       # the caller asked groupnorm_fused_ok
     out = _gn_out(src1, C1 + C2)
-    check(_lib.load().gg_groupnorm_fused(src1.t.data_ptr(), C1, p2, C2, N, S, c_log, gamma.data_ptr(),
-                                         beta.data_ptr(), eps, 1 if act else 0, out.data_ptr(), _stream()), "gg_groupnorm_fused")
+    call("gg_groupnorm_fused", src1.t.data_ptr(), C1, p2, C2, N, S, c_log, gamma.data_ptr(), beta.data_ptr(), eps, 1 if act else 0, out.data_ptr(),
+         _stream())
     return CL(out, c_log)
 
 
@@ -490,8 +485,8 @@ def groupnorm_f32(src1: CL, gamma: torch.Tensor, beta: torch.Tensor, eps: float,
     N, S, C1, C2, c_log, p2 = _gn_sources(src1, src2)
     out = _gn_out(src1, C1 + C2, torch.float32)
     ws = torch.empty(64 * N, dtype=torch.float32, device=src1.t.device)
-    check(_lib.load().gg_groupnorm_f32(src1.t.data_ptr(), C1, p2, C2, N, S, c_log, gamma.data_ptr(), beta.data_ptr(),
-                                       eps, 1 if act else 0, out.data_ptr(), ws.data_ptr(), _stream()), "gg_groupnorm_f32")
+    call("gg_groupnorm_f32", src1.t.data_ptr(), C1, p2, C2, N, S, c_log, gamma.data_ptr(), beta.data_ptr(), eps, 1 if act else 0, out.data_ptr(),
+         ws.data_ptr(), _stream())
     return CL(out, c_log)
 
 
@@ -502,8 +497,8 @@ def groupnorm_f32_film(src: CL, gamma: torch.Tensor, beta: torch.Tensor, eps: fl
     _check_film(film, N, src.C)
     out = _gn_out(src, src.Cpad, torch.float32)
     ws = torch.empty(64 * N, dtype=torch.float32, device=src.t.device)
-    check(_lib.load().gg_groupnorm_f32_film(src.t.data_ptr(), src.Cpad, N, S, src.C, gamma.data_ptr(), beta.data_ptr(), eps, film.data_ptr(),
-                                            film.stride(0), 1 if act else 0, out.data_ptr(), ws.data_ptr(), _stream()), "gg_groupnorm_f32_film")
+    call("gg_groupnorm_f32_film", src.t.data_ptr(), src.Cpad, N, S, src.C, gamma.data_ptr(), beta.data_ptr(), eps, film.data_ptr(), film.stride(0),
+         1 if act else 0, out.data_ptr(), ws.data_ptr(), _stream())
     return CL(out, src.C)
 
 
@@ -511,8 +506,7 @@ def film_fold(scale: torch.Tensor, shift: torch.Tensor, film: torch.Tensor, C: i
     """In place: per-(n, c) GroupNorm coefficients [N, Ct] of a FiLM out-norm take the per-sample term *(1 + s) + t, s = film[n, :C],
     t = film[n, C:2C] (gg_film_fold); channels >= C are left as they are."""
     _check_film(film, scale.shape[0], C)
-    check(_lib.load().gg_film_fold(scale.data_ptr(), shift.data_ptr(), scale.stride(0), scale.shape[0], C, film.data_ptr(), film.stride(0),
-                                   _stream()), "gg_film_fold")
+    call("gg_film_fold", scale.data_ptr(), shift.data_ptr(), scale.stride(0), scale.shape[0], C, film.data_ptr(), film.stride(0), _stream())
 
 
 def _check_film(film: torch.Tensor, N: int, C: int) -> None:
@@ -524,16 +518,14 @@ def resample2x(src: CL, up: bool, resample_d: bool, prologue: Optional[Tuple[tor
     """Nearest x2 upsample (up) or 2x average pool of a channels-last tensor (bf16, or fp32 in validation mode): H and W, and D too if
     resample_d.  prologue = per-(n, c) fp32 (scale, shift) [N, Cpad]: every input element becomes act(x * scale + shift) first (the h path
     of a down ResBlock in one launch).  The output carries no GroupNorm accumulators."""
-    lib = _lib.load()
     N, D, H, W, cp = src.t.shape
     Do = (D * 2 if up else D // 2) if resample_d else D
     out = torch.empty((N, Do, H * 2 if up else H // 2, W * 2 if up else W // 2, cp), dtype=src.t.dtype, device=src.t.device)
     if prologue is not None and tuple(prologue[0].shape) != (N, cp):
         raise ValueError(f"resample2x: prologue coefficients must be [{N}, {cp}]")
-    check(lib.gg_resample2x(src.t.data_ptr(), GG_F32 if is_f32(src.t) else GG_BF16, N, D, H, W, cp, src.C, 1 if resample_d else 0,
-                            0 if up else 1, _ptr(prologue[0]) if prologue is not None else None,
-                            _ptr(prologue[1]) if prologue is not None else None, 1 if (act and prologue is not None) else 0,
-                            out.data_ptr(), _stream()), "gg_resample2x")
+    call("gg_resample2x", src.t.data_ptr(), GG_F32 if is_f32(src.t) else GG_BF16, N, D, H, W, cp, src.C, 1 if resample_d else 0, 0 if up else 1,
+         _ptr(prologue[0]) if prologue is not None else None, _ptr(prologue[1]) if prologue is not None else None,
+         1 if (act and prologue is not None) else 0, out.data_ptr(), _stream())
     return CL(out, src.C)
 
 
@@ -541,9 +533,8 @@ def groupnorm_apply_acc(src1: CL, gamma: torch.Tensor, beta: torch.Tensor, eps: 
     """act(GroupNorm(32)(cat[src1, src2])) with the statistics taken from the accumulators the producing convs left in CL.acc."""
     N, S, C1, C2, c_log, p2 = _gn_sources(src1, src2)
     out = _gn_out(src1, C1 + C2)
-    check(_lib.load().gg_groupnorm_apply_acc(src1.t.data_ptr(), C1, src1.acc.data_ptr(), p2, C2,
-                                             src2.acc.data_ptr() if src2 is not None else None, N, S, c_log, gamma.data_ptr(),
-                                             beta.data_ptr(), eps, 1 if act else 0, out.data_ptr(), _stream()), "gg_groupnorm_apply_acc")
+    call("gg_groupnorm_apply_acc", src1.t.data_ptr(), C1, src1.acc.data_ptr(), p2, C2, src2.acc.data_ptr() if src2 is not None else None, N, S,
+         c_log, gamma.data_ptr(), beta.data_ptr(), eps, 1 if act else 0, out.data_ptr(), _stream())
     return CL(out, c_log)
 
 
@@ -562,33 +553,30 @@ def groupnorm_scale_shift_acc(src1: CL, gamma: torch.Tensor, beta: torch.Tensor,
     """Per-(n, c) fp32 (scale, shift) of GroupNorm(32)(cat[src1, src2]) from the accumulators in CL.acc (no pass over the tensors)."""
     N, S, C1, C2, c_log, p2 = _gn_sources(src1, src2)
     scale, shift = _gn_tables(src1, N, C1 + C2)
-    check(_lib.load().gg_groupnorm_scale_shift_acc(src1.acc.data_ptr(), src1.acc.shape[1], C1, src2.acc.data_ptr() if src2 is not None else None,
-                                                   src2.acc.shape[1] if src2 is not None else 0, C2, N, S, c_log, gamma.data_ptr(), beta.data_ptr(),
-                                                   eps, scale.data_ptr(), shift.data_ptr(), _stream()), "gg_groupnorm_scale_shift_acc")
+    call("gg_groupnorm_scale_shift_acc", src1.acc.data_ptr(), src1.acc.shape[1], C1, src2.acc.data_ptr() if src2 is not None else None,
+         src2.acc.shape[1] if src2 is not None else 0, C2, N, S, c_log, gamma.data_ptr(), beta.data_ptr(), eps, scale.data_ptr(), shift.data_ptr(),
+         _stream())
     return scale, shift
 
 
 def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-5) -> torch.Tensor:
-    lib = _lib.load()
     Cc = x.shape[-1]
     rows = x.numel() // Cc
     out = torch.empty_like(x)
-    check(lib.gg_layernorm(x.data_ptr(), rows, Cc, gamma.data_ptr(), beta.data_ptr(), eps, out.data_ptr(), _stream()), "gg_layernorm")
+    call("gg_layernorm", x.data_ptr(), rows, Cc, gamma.data_ptr(), beta.data_ptr(), eps, out.data_ptr(), _stream())
     return out
 
 
 def geglu(h: torch.Tensor, inner: int) -> torch.Tensor:
-    lib = _lib.load()
     rows = h.numel() // (2 * inner)
     out = torch.empty(tuple(h.shape[:-1]) + (inner,), dtype=torch.bfloat16, device=h.device)
-    check(lib.gg_geglu(h.data_ptr(), rows, inner, out.data_ptr(), _stream()), "gg_geglu")
+    call("gg_geglu", h.data_ptr(), rows, inner, out.data_ptr(), _stream())
     return out
 
 
 def add(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
-    lib = _lib.load()
     out = torch.empty_like(a)
-    check(lib.gg_add(a.data_ptr(), b.data_ptr(), a.numel(), out.data_ptr(), _stream()), "gg_add")
+    call("gg_add", a.data_ptr(), b.data_ptr(), a.numel(), out.data_ptr(), _stream())
     return out
 
 
@@ -622,8 +610,8 @@ def embed_rows(ids: torch.Tensor, tok: torch.Tensor, pos: Optional[torch.Tensor]
         out = torch.empty((B, 1, 1, T, pad32(D)), dtype=torch.bfloat16, device=ids.device)
     else:
         out = torch.empty((B, T, D), dtype=torch.float32, device=ids.device)
-    check(_lib.load().gg_embed_rows(ids32.data_ptr(), B * T, T, tok.data_ptr(), V, D, _ptr(pos), P, out.data_ptr(),
-                                    GG_BF16 if bf16 else GG_F32, out.shape[-1], _stream()), "gg_embed_rows")
+    call("gg_embed_rows", ids32.data_ptr(), B * T, T, tok.data_ptr(), V, D, _ptr(pos), P, out.data_ptr(), GG_BF16 if bf16 else GG_F32, out.shape[-1],
+         _stream())
     return out
 
 
@@ -647,10 +635,9 @@ def bert_embed(ids: torch.Tensor, type_ids: Optional[torch.Tensor], word: torch.
             raise ValueError(f"bert_embed: {name} must be a contiguous fp32 table of width {D} on {ids.device}")
     B, T = (int(v) for v in ids.shape)
     out = torch.empty((B, 1, 1, T, pad32(D)), dtype=torch.bfloat16, device=ids.device)
-    check(_lib.load().gg_bert_embed(ids.data_ptr(), _ptr(type_ids), B * T, T, word.data_ptr(), int(word.shape[0]), pos.data_ptr(),
-                                    int(pos.shape[0]), type_tab.data_ptr(), int(type_tab.shape[0]), D, gamma.data_ptr(), beta.data_ptr(),
-                                    float(eps), out.data_ptr(), out.shape[-1], _ptr(ids_host), _ptr(type_ids_host), _stream()),
-          "gg_bert_embed")
+    call("gg_bert_embed", ids.data_ptr(), _ptr(type_ids), B * T, T, word.data_ptr(), int(word.shape[0]), pos.data_ptr(), int(pos.shape[0]),
+         type_tab.data_ptr(), int(type_tab.shape[0]), D, gamma.data_ptr(), beta.data_ptr(), float(eps), out.data_ptr(), out.shape[-1],
+         _ptr(ids_host), _ptr(type_ids_host), _stream())
     return out
 
 
@@ -660,7 +647,7 @@ def gelu(x: torch.Tensor) -> torch.Tensor:
     if x.dtype != torch.bfloat16 or not x.is_contiguous() or x.numel() == 0:
         raise ValueError(f"gelu: a non-empty contiguous bf16 tensor, got {x.dtype} {tuple(x.shape)}")
     out = torch.empty_like(x)
-    check(_lib.load().gg_gelu(x.data_ptr(), x.numel(), out.data_ptr(), _stream()), "gg_gelu")
+    call("gg_gelu", x.data_ptr(), x.numel(), out.data_ptr(), _stream())
     return out
 
 
@@ -670,8 +657,7 @@ def layernorm_rows(x: CL, gamma: torch.Tensor, beta: torch.Tensor, eps: float = 
     if x.t.dtype != torch.bfloat16 or not x.t.is_contiguous() or gamma.numel() != x.C or beta.numel() != x.C:
         raise ValueError(f"layernorm_rows: contiguous bf16 rows and {x.C} fp32 coefficients, got {x.t.dtype} {tuple(x.t.shape)}")
     out = torch.empty_like(x.t)
-    check(_lib.load().gg_layernorm_rows(x.t.data_ptr(), x.t.numel() // x.Cpad, x.C, x.Cpad, gamma.data_ptr(), beta.data_ptr(), eps,
-                                        out.data_ptr(), _stream()), "gg_layernorm_rows")
+    call("gg_layernorm_rows", x.t.data_ptr(), x.t.numel() // x.Cpad, x.C, x.Cpad, gamma.data_ptr(), beta.data_ptr(), eps, out.data_ptr(), _stream())
     return CL(out, x.C)
 
 
@@ -702,8 +688,7 @@ def interpolate2d(x: torch.Tensor, scale_factor: float, mode: str) -> torch.Tens
     x = x.contiguous()
     out = torch.empty((N, Cc, Ho, Wo), dtype=torch.float32, device=x.device)
     scale = 1.0 / s                                         # ctypes rounds the double to fp32: float(1.0 / s)
-    check(_lib.load().gg_interpolate2d_f32(x.data_ptr(), N * Cc, H, W, Ho, Wo, scale, scale, INTERPOLATE_MODES[mode], out.data_ptr(),
-                                           _stream()), "gg_interpolate2d_f32")
+    call("gg_interpolate2d_f32", x.data_ptr(), N * Cc, H, W, Ho, Wo, scale, scale, INTERPOLATE_MODES[mode], out.data_ptr(), _stream())
     return out
 
 
@@ -714,7 +699,6 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tens
     """q/k/v/out are bf16 tensors; element (n,t,h,d) at base + off + (n*T+t)*ld + h*hs + d.
     kv_len: int32 device tensor [N]; sample n then attends to keys [0, kv_len[n]) only (gg_attention_forward_kvlen).  It is not read
     back: the caller checks 1 <= kv_len[n] <= Tkv on the host values it built the tensor from."""
-    lib = _lib.load()
     if kv_len is not None and (not isinstance(kv_len, torch.Tensor) or kv_len.dtype != torch.int32 or tuple(kv_len.shape) != (N,)
                                or not kv_len.is_contiguous() or kv_len.device != q.device):
         what = f"{kv_len.dtype} {tuple(kv_len.shape)} on {kv_len.device}" if isinstance(kv_len, torch.Tensor) else type(kv_len).__name__
@@ -732,38 +716,34 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tens
     d.v = v.data_ptr() + esz * v_off
     d.out = out.data_ptr()
     if kv_len is not None:                          # key lengths: the plain kernel, no workspace
-        fn = "gg_attention_forward_kvlen_f32" if is_f32(q) else "gg_attention_forward_kvlen"
-        check(getattr(lib, fn)(C.byref(d), kv_len.data_ptr(), _stream()), fn)
+        call("gg_attention_forward_kvlen_f32" if is_f32(q) else "gg_attention_forward_kvlen", C.byref(d), kv_len.data_ptr(), _stream())
         return
     if is_f32(q):                                   # fp32 validation path
-        check(lib.gg_attention_forward_f32(C.byref(d), _stream()), "gg_attention_forward_f32")
+        call("gg_attention_forward_f32", C.byref(d), _stream())
         return
-    wsb = lib.gg_attention_workspace_bytes(C.byref(d))
+    wsb = _lib.load().gg_attention_workspace_bytes(C.byref(d))
     if wsb > 0:                                     # under-filled single-head grid (AE mid attention): keys split over workgroups
         ws = torch.empty(wsb // 4, dtype=torch.float32, device=q.device)
         d.workspace, d.workspace_bytes = ws.data_ptr(), wsb
-    check(lib.gg_attention_forward(C.byref(d), _stream()), "gg_attention_forward")
+    call("gg_attention_forward", C.byref(d), _stream())
 
 
 # ----------------------------------------------------------------------------------------------- small fp32 ops
 def linear_f32(x: torch.Tensor, W: torch.Tensor, b: Optional[torch.Tensor], act_in: bool = False,
                out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    lib = _lib.load()
     x = x.contiguous()
     M, I = x.shape
     O = W.shape[0]
     if out is None:
         out = torch.empty((M, O), dtype=torch.float32, device=x.device)
-    check(lib.gg_linear_f32(x.data_ptr(), M, I, W.data_ptr(), _ptr(b), O, 1 if act_in else 0, out.data_ptr(), out.stride(0), _stream()),
-          "gg_linear_f32")
+    call("gg_linear_f32", x.data_ptr(), M, I, W.data_ptr(), _ptr(b), O, 1 if act_in else 0, out.data_ptr(), out.stride(0), _stream())
     return out
 
 
 def timestep_embedding(t: torch.Tensor, dim: int, max_period: float = 10000.0) -> torch.Tensor:
-    lib = _lib.load()
     t = t.float().contiguous()
     out = torch.empty((t.shape[0], dim), dtype=torch.float32, device=t.device)
-    check(lib.gg_timestep_embedding(t.data_ptr(), t.shape[0], dim, max_period, out.data_ptr(), _stream()), "gg_timestep_embedding")
+    call("gg_timestep_embedding", t.data_ptr(), t.shape[0], dim, max_period, out.data_ptr(), _stream())
     return out
 
 
@@ -775,7 +755,6 @@ def ccdm_posterior_sample(head: torch.Tensor, head_is_logits: bool, xt: torch.Te
     """head: fp32 [..., stride] (probs or logits, channels-last); xt int32 [M]; scalars fp32[2] on device.
     philox_seeds: device int64 [N] (bit patterns of the uint64 keys) with M a multiple of N: one Philox key per sample of M / N rows
     (gg_ccdm_posterior_sample_seeds) instead of `philox_seed` for all."""
-    lib = _lib.load()
     stride = head.shape[-1]
     M = head.numel() // stride
     if labels_out is None:
@@ -784,14 +763,12 @@ def ccdm_posterior_sample(head: torch.Tensor, head_is_logits: bool, xt: torch.Te
     if philox_seeds is not None:
         Ns = philox_seeds.numel()
         rps = _rows_per_sample(M, Ns, "ccdm_posterior_sample")
-        check(lib.gg_ccdm_posterior_sample_seeds(head.data_ptr(), stride, 1 if head_is_logits else 0, xt.data_ptr(), _ptr(E),
-                                                 _seeds_ptr(philox_seeds, Ns), rps, _ptr(philox_offset), 1 if draw else 0,
-                                                 scalars.data_ptr(), K, M, labels_out.data_ptr(), _ptr(probs_out), _ptr(onehot_out),
-                                                 oh_stride, _stream()), "gg_ccdm_posterior_sample_seeds")
+        call("gg_ccdm_posterior_sample_seeds", head.data_ptr(), stride, 1 if head_is_logits else 0, xt.data_ptr(), _ptr(E),
+             _seeds_ptr(philox_seeds, Ns), rps, _ptr(philox_offset), 1 if draw else 0, scalars.data_ptr(), K, M, labels_out.data_ptr(),
+             _ptr(probs_out), _ptr(onehot_out), oh_stride, _stream())
         return labels_out
-    check(lib.gg_ccdm_posterior_sample(head.data_ptr(), stride, 1 if head_is_logits else 0, xt.data_ptr(), _ptr(E), philox_seed,
-                                       _ptr(philox_offset), 1 if draw else 0, scalars.data_ptr(), K, M, labels_out.data_ptr(),
-                                       _ptr(probs_out), _ptr(onehot_out), oh_stride, _stream()), "gg_ccdm_posterior_sample")
+    call("gg_ccdm_posterior_sample", head.data_ptr(), stride, 1 if head_is_logits else 0, xt.data_ptr(), _ptr(E), philox_seed, _ptr(philox_offset),
+         1 if draw else 0, scalars.data_ptr(), K, M, labels_out.data_ptr(), _ptr(probs_out), _ptr(onehot_out), oh_stride, _stream())
     return labels_out
 
 
@@ -829,7 +806,6 @@ def ccdm_draw_tape(M: int, kmax: int, *, philox_seed: int = 0, philox_seeds: Opt
     ccdm_posterior_sample / ccdm_q_sample / the fused head conv draw them for the same philox_seed (or philox_seeds: device int64 [N], M a
     multiple of N) and philox_offset; kmax is 16 for K <= 16 and 32 above.  E[:, :K].contiguous() is the tape `E` of those calls.
     bits_in: device int32 [M, kmax] words to map instead of drawing."""
-    lib = _lib.load()
     if bits_in is not None:
         if bits_in.dtype != torch.int32 or not bits_in.is_cuda or not bits_in.is_contiguous() or bits_in.numel() != M * kmax:
             raise ValueError(f"ccdm_draw_tape: bits_in must be a contiguous device int32 [{M}, {kmax}] tensor")
@@ -848,41 +824,38 @@ def ccdm_draw_tape(M: int, kmax: int, *, philox_seed: int = 0, philox_seeds: Opt
         rps = _rows_per_sample(M, Ns, "ccdm_draw_tape")
     bits = torch.empty((M, kmax), dtype=torch.int32, device=device) if want_bits else None
     E = torch.empty((M, kmax), dtype=torch.float32, device=device) if want_E else None
-    check(lib.gg_ccdm_draw_tape(int(philox_seed) & ((1 << 64) - 1), _seeds_ptr(philox_seeds, Ns) if Ns else None, rps, _ptr(philox_offset),
-                                kmax, M, _ptr(bits_in), _ptr(bits), _ptr(E), _stream()), "gg_ccdm_draw_tape")
+    call("gg_ccdm_draw_tape", int(philox_seed) & ((1 << 64) - 1), _seeds_ptr(philox_seeds, Ns) if Ns else None, rps, _ptr(philox_offset), kmax, M,
+         _ptr(bits_in), _ptr(bits), _ptr(E), _stream())
     return bits, E
 
 
 def labels_to_onehot(labels: torch.Tensor, K: int, out: torch.Tensor) -> None:
-    lib = _lib.load()
     if is_f32(out):                                 # fp32 validation path: index scatter (plumbing)
         out[:, :K] = torch.nn.functional.one_hot(labels.long(), K).to(torch.float32)
         return
-    check(lib.gg_labels_to_onehot(labels.data_ptr(), labels.numel(), K, out.data_ptr(), out.shape[-1], _stream()), "gg_labels_to_onehot")
+    call("gg_labels_to_onehot", labels.data_ptr(), labels.numel(), K, out.data_ptr(), out.shape[-1], _stream())
 
 
 def ddim_step(x: torch.Tensor, eps: torch.Tensor, scalars: torch.Tensor, noise: Optional[torch.Tensor] = None,
               pred_x0_out: Optional[torch.Tensor] = None, unet_in: Optional[torch.Tensor] = None) -> None:
     """x fp32 CL [M, C] (updated in place); eps fp32 CL [M, stride]; scalars fp32[4] on device."""
-    lib = _lib.load()
     Cc = x.shape[-1]
     M = x.numel() // Cc
-    check(lib.gg_ddim_step(x.data_ptr(), eps.data_ptr(), eps.shape[-1], _ptr(noise), scalars.data_ptr(), M, Cc, _ptr(pred_x0_out),
-                           _ptr(unet_in), unet_in.shape[-1] if unet_in is not None else 0, _stream()), "gg_ddim_step")
+    call("gg_ddim_step", x.data_ptr(), eps.data_ptr(), eps.shape[-1], _ptr(noise), scalars.data_ptr(), M, Cc, _ptr(pred_x0_out), _ptr(unet_in),
+         unet_in.shape[-1] if unet_in is not None else 0, _stream())
 
 
 def inpaint_blend(x: torch.Tensor, x0: torch.Tensor, mask: torch.Tensor, noise: torch.Tensor, scalars: torch.Tensor,
                   unet_in: Optional[torch.Tensor] = None) -> None:
     """x <- q_sample(x0, t, noise) * mask + (1 - mask) * x in place; x, x0, noise fp32 CL [M, C], mask fp32 CL [M, 1 or C],
     scalars fp32[2] = (sqrt_alphas_cumprod[t], sqrt_one_minus_alphas_cumprod[t]) on device; unet_in channels [0, C) <- bf16(x)."""
-    lib = _lib.load()
     Cc = x.shape[-1]
     M = x.numel() // Cc
     for name, t, c in (("x", x, Cc), ("x0", x0, Cc), ("noise", noise, Cc), ("mask", mask, mask.shape[-1])):
         if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != M * c:
             raise ValueError(f"inpaint_blend: {name} must be contiguous fp32 [{M}, {c}], got {t.dtype} {tuple(t.shape)}")
-    check(lib.gg_inpaint_blend(x.data_ptr(), x0.data_ptr(), mask.data_ptr(), mask.shape[-1], noise.data_ptr(), scalars.data_ptr(), M, Cc,
-                               _ptr(unet_in), unet_in.shape[-1] if unet_in is not None else 0, _stream()), "gg_inpaint_blend")
+    call("gg_inpaint_blend", x.data_ptr(), x0.data_ptr(), mask.data_ptr(), mask.shape[-1], noise.data_ptr(), scalars.data_ptr(), M, Cc,
+         _ptr(unet_in), unet_in.shape[-1] if unet_in is not None else 0, _stream())
 
 
 def _codebook(codebook: torch.Tensor, what: str) -> Tuple[int, int]:
@@ -896,7 +869,6 @@ def vq_nearest(rows: torch.Tensor, codebook: torch.Tensor, C: Optional[int] = No
     """Nearest codebook entry of every channels-last row (gg_vq_nearest).  rows fp32 [..., stride] with the channels in [0, C) (C defaults
     to the codebook's width, stride >= C); codebook fp32 [n_embed, C].  Returns (indices int32 [M], straight-through rows fp32 [M, C] =
     z + (E[idx] - z), or None with want_st=False).  st_out may be given (fp32 [M, st_stride >= C], or `rows` itself for in place)."""
-    lib = _lib.load()
     require_gpu(rows, "vq_nearest")
     n_embed, Ce = _codebook(codebook, "vq_nearest")
     C = Ce if C is None else C
@@ -916,8 +888,7 @@ def vq_nearest(rows: torch.Tensor, codebook: torch.Tensor, C: Optional[int] = No
         st_stride = st_out.shape[-1]
         if st_out.dtype != torch.float32 or not st_out.is_contiguous() or st_stride < C or st_out.numel() != M * st_stride:
             raise ValueError(f"vq_nearest: st_out must be contiguous fp32 [{M}, stride >= {C}]")
-    check(lib.gg_vq_nearest(rows.data_ptr(), stride, codebook.data_ptr(), n_embed, C, M, idx_out.data_ptr(), _ptr(st_out), st_stride,
-                            _stream()), "gg_vq_nearest")
+    call("gg_vq_nearest", rows.data_ptr(), stride, codebook.data_ptr(), n_embed, C, M, idx_out.data_ptr(), _ptr(st_out), st_stride, _stream())
     return idx_out, st_out
 
 
@@ -927,7 +898,6 @@ def ddim_step_vq(x: torch.Tensor, eps: torch.Tensor, scalars: torch.Tensor, code
     """One reverse step with the prediction of x_0 quantised (gg_ddim_step_vq).  x fp32 CL [M, C] (updated in place); eps fp32 CL
     [M, stride]; scalars fp32[5] on device: (a_t, a_prev, sigma_t, sqrt(1 - a_t), noise coefficient), or with ancestral=True gg_ddpm_step's
     five; codebook fp32 [n_embed, C], or None for the step without a quantiser; pred_x0_out receives the quantised prediction."""
-    lib = _lib.load()
     Cc = x.shape[-1]
     M = x.numel() // Cc
     n_embed = 0
@@ -942,9 +912,8 @@ def ddim_step_vq(x: torch.Tensor, eps: torch.Tensor, scalars: torch.Tensor, code
             raise ValueError(f"ddim_step_vq: {name} must be contiguous fp32 [{M}, {Cc}], got {t.dtype} {tuple(t.shape)}")
     if idx_out is not None and (idx_out.dtype != torch.int32 or idx_out.numel() != M or not idx_out.is_contiguous()):
         raise ValueError(f"ddim_step_vq: idx_out must be a contiguous int32 tensor of {M} indices")
-    check(lib.gg_ddim_step_vq(x.data_ptr(), eps.data_ptr(), eps.shape[-1], _ptr(noise), scalars.data_ptr(), 1 if ancestral else 0,
-                              _ptr(codebook), n_embed, M, Cc, _ptr(idx_out), _ptr(pred_x0_out), _ptr(unet_in),
-                              unet_in.shape[-1] if unet_in is not None else 0, _stream()), "gg_ddim_step_vq")
+    call("gg_ddim_step_vq", x.data_ptr(), eps.data_ptr(), eps.shape[-1], _ptr(noise), scalars.data_ptr(), 1 if ancestral else 0, _ptr(codebook),
+         n_embed, M, Cc, _ptr(idx_out), _ptr(pred_x0_out), _ptr(unet_in), unet_in.shape[-1] if unet_in is not None else 0, _stream())
 
 
 def unfold_extent(H: int, W: int, kh: int, kw: int, sy: int, sx: int) -> Tuple[int, int]:
@@ -971,7 +940,6 @@ def unfold_cl(src: torch.Tensor, C: int, kh: int, kw: int, sy: int, sx: int, out
     `stride` elements apart) -> out [L * N, kh, kw, stride_out], channels [c_offset, c_offset + C), crop l of sample n at row l * N + n.
     out defaults to a fresh tensor of src's dtype and C channels; a bf16 out of an fp32 src converts on the way.  Other lanes of out
     are left as they are."""
-    lib = _lib.load()
     require_gpu(src, "unfold_cl")
     if not _rows_dense(src):
         raise ValueError(f"unfold_cl: src must be channels-last [N, H, W, C] with densely packed rows, got {tuple(src.shape)} strides {src.stride()}")
@@ -984,8 +952,8 @@ def unfold_cl(src: torch.Tensor, C: int, kh: int, kw: int, sy: int, sx: int, out
         out = torch.empty((Ly * Lx * N, kh, kw, C), dtype=src.dtype, device=src.device)
     if out.dim() != 4 or tuple(out.shape[:3]) != (Ly * Lx * N, kh, kw) or not out.is_contiguous():
         raise ValueError(f"unfold_cl: out must be a contiguous [{Ly * Lx * N}, {kh}, {kw}, stride] tensor, got {tuple(out.shape)}")
-    check(lib.gg_unfold_cl(src.data_ptr(), _cl_dtype(src, "unfold_cl"), N, H, W, s_stride, C, out.data_ptr(), _cl_dtype(out, "unfold_cl"),
-                           out.shape[-1], c_offset, kh, kw, sy, sx, _stream()), "gg_unfold_cl")
+    call("gg_unfold_cl", src.data_ptr(), _cl_dtype(src, "unfold_cl"), N, H, W, s_stride, C, out.data_ptr(), _cl_dtype(out, "unfold_cl"),
+         out.shape[-1], c_offset, kh, kw, sy, sx, _stream())
     return out
 
 
@@ -995,7 +963,6 @@ def fold_weighted_cl(crops: torch.Tensor, C: int, weight: torch.Tensor, tie: Opt
     channels [0, C): sum_l(o[l] * w[l]) / sum_l(w[l]) with w[l][ky, kx] = weight[ky, kx] * tie[l], crops visited in descending l (the
     order of torch's CPU Fold; include/guidegen_hip.h).  weight fp32 [kh, kw], tie fp32 [L] or None.  crops / out may be views whose
     rows are `stride` elements apart."""
-    lib = _lib.load()
     require_gpu(crops, "fold_weighted_cl")
     if out.dtype != torch.float32 or not _rows_dense(out):
         raise ValueError(f"fold_weighted_cl: out must be fp32 channels-last [N, H, W, C] with densely packed rows, got {out.dtype} {tuple(out.shape)}")
@@ -1009,8 +976,8 @@ def fold_weighted_cl(crops: torch.Tensor, C: int, weight: torch.Tensor, tie: Opt
         raise ValueError(f"fold_weighted_cl: weight must be a contiguous device fp32 [{kh}, {kw}] table")
     if tie is not None and (tie.dtype != torch.float32 or not tie.is_contiguous() or tie.numel() != Ly * Lx or tie.device != crops.device):
         raise ValueError(f"fold_weighted_cl: tie must be a contiguous device fp32 [{Ly * Lx}] table")
-    check(lib.gg_fold_weighted_cl(crops.data_ptr(), int(crops.stride(2)), weight.data_ptr(), _ptr(tie), out.data_ptr(), int(out.stride(2)),
-                                  N, H, W, C, kh, kw, sy, sx, _stream()), "gg_fold_weighted_cl")
+    call("gg_fold_weighted_cl", crops.data_ptr(), int(crops.stride(2)), weight.data_ptr(), _ptr(tie), out.data_ptr(), int(out.stride(2)), N, H, W, C,
+         kh, kw, sy, sx, _stream())
     return out
 
 
@@ -1036,11 +1003,10 @@ def label_confusion(a: torch.Tensor, b: torch.Tensor, K: int) -> torch.Tensor:
         raise ValueError(f"label_confusion: volumes of {tuple(a.shape[1:])} and {tuple(b.shape[1:])} voxels (or on two devices)")
     if not 1 <= K <= 32:
         raise ValueError(f"label_confusion: K={K} outside [1, 32]")
-    lib = _lib.load()
     Sa, Sb, M = ra.shape[0], rb.shape[0], ra.shape[1]
     cm = torch.empty((Sa, Sb, K, K), dtype=torch.int64, device=ra.device)
     skipped = torch.empty((Sa, Sb), dtype=torch.int64, device=ra.device)
-    check(lib.gg_label_confusion(ra.data_ptr(), Sa, rb.data_ptr(), Sb, M, K, cm.data_ptr(), skipped.data_ptr(), _stream()), "gg_label_confusion")
+    call("gg_label_confusion", ra.data_ptr(), Sa, rb.data_ptr(), Sb, M, K, cm.data_ptr(), skipped.data_ptr(), _stream())
     sk = skipped.cpu()
     if int(sk.sum()) != 0:
         i, j = (int(v) for v in torch.nonzero(sk)[0])
@@ -1108,7 +1074,6 @@ def label_vote(labels: torch.Tensor, K: int) -> Tuple[torch.Tensor, torch.Tensor
         raise ValueError(f"label_vote: S={S} samples outside [1, 64]")
     if not 1 <= M < 2 ** 31:
         raise ValueError(f"label_vote: M={M} voxels outside [1, 2^31)")
-    lib = _lib.load()
     dev = labels.device
     key = (S, dev.index)
     if key not in _VOTE_TABLES:
@@ -1119,8 +1084,8 @@ def label_vote(labels: torch.Tensor, K: int) -> Tuple[torch.Tensor, torch.Tensor
     agreement = torch.empty(M, dtype=torch.int32, device=dev)
     entropy = torch.empty(M, dtype=torch.float32, device=dev)
     skipped = torch.empty(1, dtype=torch.int64, device=dev)
-    check(lib.gg_label_vote(labels.data_ptr(), S, M, K, table.data_ptr(), ln_s, inv_s, winner.data_ptr(), agreement.data_ptr(),
-                            entropy.data_ptr(), skipped.data_ptr(), _stream()), "gg_label_vote")
+    call("gg_label_vote", labels.data_ptr(), S, M, K, table.data_ptr(), ln_s, inv_s, winner.data_ptr(), agreement.data_ptr(), entropy.data_ptr(),
+         skipped.data_ptr(), _stream())
     return winner, agreement, entropy, skipped
 
 
@@ -1152,8 +1117,8 @@ def label_components(labels: torch.Tensor, K: int, connectivity: int = 6, backgr
     nbytes = int(lib.gg_label_components_workspace_bytes(B, M))
     ws = torch.empty(nbytes // 4, dtype=torch.int32, device=labels.device)
     status = component_status(labels.device)
-    check(lib.gg_label_components(labels.data_ptr(), B, D, H, W, K, connectivity, background, root.data_ptr(), ws.data_ptr(), nbytes,
-                                  status.data_ptr(), _stream()), "gg_label_components")
+    call("gg_label_components", labels.data_ptr(), B, D, H, W, K, connectivity, background, root.data_ptr(), ws.data_ptr(), nbytes,
+         status.data_ptr(), _stream())
     return root
 
 
@@ -1172,11 +1137,9 @@ def component_stats(labels: torch.Tensor, root: torch.Tensor, K: int) -> Tuple[t
     _check_classes("component_stats", K)
     B, M = _check_volumes("component_stats", labels)
     _check_root("component_stats", labels, root, B, M)
-    lib = _lib.load()
     size = torch.empty((B, M), dtype=torch.int32, device=labels.device)
     stats = torch.empty((B, K, 4), dtype=torch.int64, device=labels.device)
-    check(lib.gg_component_stats(labels.data_ptr(), root.data_ptr(), B, M, K, size.data_ptr(), stats.data_ptr(), _stream()),
-          "gg_component_stats")
+    call("gg_component_stats", labels.data_ptr(), root.data_ptr(), B, M, K, size.data_ptr(), stats.data_ptr(), _stream())
     return size, stats
 
 
@@ -1210,11 +1173,10 @@ def component_filter(labels: torch.Tensor, root: torch.Tensor, size: torch.Tenso
         fill = background
     if not isinstance(fill, int) or not 0 <= fill < K:
         raise ValueError(f"component_filter: fill {fill} outside [0, {K})")
-    lib = _lib.load()
     out = torch.empty_like(labels)
     kept = torch.empty(labels.shape, dtype=torch.uint8, device=labels.device)
-    check(lib.gg_component_filter(labels.data_ptr(), root.data_ptr(), size.data_ptr(), stats.data_ptr(), B, M, K, keep_largest.data_ptr(),
-                                  min_size.data_ptr(), background, fill, out.data_ptr(), kept.data_ptr(), _stream()), "gg_component_filter")
+    call("gg_component_filter", labels.data_ptr(), root.data_ptr(), size.data_ptr(), stats.data_ptr(), B, M, K, keep_largest.data_ptr(),
+         min_size.data_ptr(), background, fill, out.data_ptr(), kept.data_ptr(), _stream())
     return out, kept
 
 
@@ -1235,8 +1197,8 @@ def volume_views_cl(x: torch.Tensor, view: int, n0: int, n1: int, shift: torch.T
             raise ValueError(f"volume_views_cl: {name} must be 3 contiguous fp32 values on {x.device}")
     if tuple(out.shape) != (n1 - n0, 1, hh, ww, 32) or not out.is_contiguous() or out.device != x.device:
         raise ValueError(f"volume_views_cl: out must be a contiguous {(n1 - n0, 1, hh, ww, 32)} tensor on {x.device}, got {tuple(out.shape)}")
-    check(_lib.load().gg_volume_views_cl(x.data_ptr(), B, D, H, W, view, n0, n1, shift.data_ptr(), scale.data_ptr(), out.data_ptr(),
-                                         _cl_dtype(out, "volume_views_cl"), _stream()), "gg_volume_views_cl")
+    call("gg_volume_views_cl", x.data_ptr(), B, D, H, W, view, n0, n1, shift.data_ptr(), scale.data_ptr(), out.data_ptr(),
+         _cl_dtype(out, "volume_views_cl"), _stream())
     return CL(out, 3)
 
 
@@ -1245,7 +1207,7 @@ def relu_cl(x: CL) -> CL:
     require_gpu(x.t, "relu_cl")
     if not x.t.is_contiguous():
         raise ValueError("relu_cl: a contiguous channels-last tensor")
-    check(_lib.load().gg_relu_cl(x.t.data_ptr(), _cl_dtype(x.t, "relu_cl"), x.t.numel(), _stream()), "gg_relu_cl")
+    call("gg_relu_cl", x.t.data_ptr(), _cl_dtype(x.t, "relu_cl"), x.t.numel(), _stream())
     return x
 
 
@@ -1273,9 +1235,8 @@ def lpips_tap(a: torch.Tensor, b: torch.Tensor, lin_w: torch.Tensor, pool: bool 
         if t is not None and (t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous() or t.device != a.device):
             raise ValueError(f"lpips_tap: {name} must be {n} contiguous fp32 values on {a.device}")
     pooled = torch.empty((2 * n, 1, h // 2, w // 2, Cc), dtype=a.dtype, device=a.device) if pool else None
-    check(lib.gg_lpips_tap(a.data_ptr(), b.data_ptr(), dt, n, h, w, Cc, lin_w.data_ptr(), _ptr(pooled[:n]) if pool else None,
-                           _ptr(pooled[n:]) if pool else None, tap_out.data_ptr(), _ptr(total), 1 if accumulate else 0, ws.data_ptr(), wsb,
-                           _stream()), "gg_lpips_tap")
+    call("gg_lpips_tap", a.data_ptr(), b.data_ptr(), dt, n, h, w, Cc, lin_w.data_ptr(), _ptr(pooled[:n]) if pool else None,
+         _ptr(pooled[n:]) if pool else None, tap_out.data_ptr(), _ptr(total), 1 if accumulate else 0, ws.data_ptr(), wsb, _stream())
     return tap_out, pooled
 
 
@@ -1304,8 +1265,7 @@ def mask_overlay(x: torch.Tensor, colors: Sequence[Sequence[int]], overlay_coef:
         out = torch.empty((N, D, 3, H, W), dtype=torch.float32, device=x.device)
     elif tuple(out.shape) != (N, D, 3, H, W) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
         raise ValueError(f"mask_overlay: out must be a contiguous fp32 {(N, D, 3, H, W)} tensor on {x.device}, got {out.dtype} {tuple(out.shape)}")
-    check(_lib.load().gg_mask_overlay(x.data_ptr(), N, D, H, W, float(overlay_coef), (C.c_int32 * 36)(*table), out.data_ptr(), _stream()),
-          "gg_mask_overlay")
+    call("gg_mask_overlay", x.data_ptr(), N, D, H, W, float(overlay_coef), (C.c_int32 * 36)(*table), out.data_ptr(), _stream())
     return out
 
 
@@ -1323,47 +1283,42 @@ def make_grid_u8(imgs: torch.Tensor, nrow: int = 8, padding: int = 2, pad_value:
         out = torch.empty((Hg, Wg, 3), dtype=torch.uint8, device=imgs.device)
     elif tuple(out.shape) != (Hg, Wg, 3) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != imgs.device:
         raise ValueError(f"make_grid_u8: out must be a contiguous uint8 {(Hg, Wg, 3)} tensor on {imgs.device}, got {out.dtype} {tuple(out.shape)}")
-    check(_lib.load().gg_make_grid_u8(imgs.data_ptr(), B, Cc, H, W, int(nrow), int(padding), float(pad_value), out.data_ptr(), _stream()),
-          "gg_make_grid_u8")
+    call("gg_make_grid_u8", imgs.data_ptr(), B, Cc, H, W, int(nrow), int(padding), float(pad_value), out.data_ptr(), _stream())
     return out
 
 
 def minmax_normalise(src: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    lib = _lib.load()
     if out is None:
         out = torch.empty_like(src)
     ws = torch.empty(2, dtype=torch.float32, device=src.device)
-    check(lib.gg_minmax_normalise(src.data_ptr(), src.numel(), out.data_ptr(), ws.data_ptr(), _stream()), "gg_minmax_normalise")
+    call("gg_minmax_normalise", src.data_ptr(), src.numel(), out.data_ptr(), ws.data_ptr(), _stream())
     return out
 
 
 def mask_to_cond_slice(labels: torch.Tensor, slice_idx: int, D: int, H: int, W: int, prev: Optional[torch.Tensor],
                        cond: torch.Tensor, mask_out: Optional[torch.Tensor] = None) -> None:
     """labels int32 [N,Dm,Hm,Wm] -> cond bf16 CL [N,1,H,W,stride] (ch0 prev slice, ch1 mask/255)."""
-    lib = _lib.load()
     N, Dm, Hm, Wm = labels.shape
-    check(lib.gg_mask_to_cond_slice(labels.data_ptr(), N, Dm, Hm, Wm, slice_idx, D, H, W, _ptr(prev), cond.data_ptr(), cond.shape[-1],
-                                    _ptr(mask_out), _stream()), "gg_mask_to_cond_slice")
+    call("gg_mask_to_cond_slice", labels.data_ptr(), N, Dm, Hm, Wm, slice_idx, D, H, W, _ptr(prev), cond.data_ptr(), cond.shape[-1], _ptr(mask_out),
+         _stream())
 
 
 def mask_to_cond_slices(labels: torch.Tensor, D: int, H: int, W: int, schedule: torch.Tensor, it: torch.Tensor, volume: torch.Tensor,
                         cond: torch.Tensor) -> None:
     """Batched glue of independent volumes: sample n's conditioning row from its own schedule row schedule[it[0], n] = (slice, prev,
     active) (device int32 [iterations, N, 3]; `it` device int32[1]); prev read from volume fp32 [D, N, H, W].  cond bf16 CL [N,1,H,W,stride]."""
-    lib = _lib.load()
     N, Dm, Hm, Wm = labels.shape
     _check_schedule(schedule, N, it)
     if tuple(volume.shape) != (D, N, H, W) or volume.dtype != torch.float32 or not volume.is_contiguous():
         raise ValueError(f"mask_to_cond_slices: volume must be contiguous fp32 {(D, N, H, W)}")
-    check(lib.gg_mask_to_cond_slices(labels.data_ptr(), N, Dm, Hm, Wm, D, H, W, schedule.data_ptr(), schedule.shape[0], it.data_ptr(),
-                                     volume.data_ptr(), cond.data_ptr(), cond.shape[-1], _stream()), "gg_mask_to_cond_slices")
+    call("gg_mask_to_cond_slices", labels.data_ptr(), N, Dm, Hm, Wm, D, H, W, schedule.data_ptr(), schedule.shape[0], it.data_ptr(),
+         volume.data_ptr(), cond.data_ptr(), cond.shape[-1], _stream())
 
 
 def minmax_normalise_scatter(src: torch.Tensor, schedule: torch.Tensor, it: torch.Tensor, volume: torch.Tensor, advance: bool = True,
                              workspace: Optional[torch.Tensor] = None) -> None:
     """src fp32 [N, ...]: each sample min-max normalised over its own values (bit-equal to minmax_normalise on that sample) and written
     to volume[slice_n, n] (volume fp32 [depth, N, ...]) where its row schedule[it[0], n] is active; advance: then it[0] += 1."""
-    lib = _lib.load()
     N = src.shape[0]
     _check_schedule(schedule, N, it)
     n_per = src.numel() // N
@@ -1371,9 +1326,8 @@ def minmax_normalise_scatter(src: torch.Tensor, schedule: torch.Tensor, it: torc
         raise ValueError(f"minmax_normalise_scatter: volume must be contiguous fp32 [depth, {N}, ...] of {n_per} values per slice")
     if workspace is None:
         workspace = torch.empty(2 * N, dtype=torch.float32, device=src.device)
-    check(lib.gg_minmax_normalise_scatter(src.data_ptr(), N, n_per, workspace.data_ptr(), schedule.data_ptr(), schedule.shape[0],
-                                          it.data_ptr(), 1 if advance else 0, volume.shape[0], volume.data_ptr(), _stream()),
-          "gg_minmax_normalise_scatter")
+    call("gg_minmax_normalise_scatter", src.data_ptr(), N, n_per, workspace.data_ptr(), schedule.data_ptr(), schedule.shape[0], it.data_ptr(),
+         1 if advance else 0, volume.shape[0], volume.data_ptr(), _stream())
 
 
 def _check_edit_volumes(who: str, known: torch.Tensor, keep: torch.Tensor, shape: Tuple[int, ...], device) -> None:
@@ -1388,7 +1342,6 @@ def ct_edit_glue(known: torch.Tensor, keep: torch.Tensor, schedule: torch.Tensor
     """CT editing glue of independent volumes: known fp32 / keep uint8 [D, N, H, W]; sample n at its own slice schedule[it[0], n, 0] ->
     image bf16 CL [N,1,H,W,stride] (channel 0 the known slice, other lanes 0) and latent_keep fp32 [N*lat*lat, 1]: 1 iff every in-image
     pixel of the cell's window, grown by `margin` cells on each side, is kept.  Inactive rows: zero image, mask 0."""
-    lib = _lib.load()
     if known.dim() != 4:
         raise ValueError(f"ct_edit_glue: known must be [D, N, H, W], got {tuple(known.shape)}")
     D, N, H, W = (int(v) for v in known.shape)
@@ -1405,15 +1358,14 @@ def ct_edit_glue(known: torch.Tensor, keep: torch.Tensor, schedule: torch.Tensor
                          f"got {latent_keep.dtype} {tuple(latent_keep.shape)}")
     if int(margin) < 0 or (H // lat) * (2 * int(margin) + 1) > H:
         raise ValueError(f"ct_edit_glue: margin = {margin}: the window of {(H // lat) * (2 * int(margin) + 1)} pixels must fit the {H} x {W} slice")
-    check(lib.gg_ct_edit_glue(known.data_ptr(), keep.data_ptr(), N, D, H, W, lat, int(margin), schedule.data_ptr(), schedule.shape[0],
-                              it.data_ptr(), image.data_ptr(), image.shape[-1], latent_keep.data_ptr(), _stream()), "gg_ct_edit_glue")
+    call("gg_ct_edit_glue", known.data_ptr(), keep.data_ptr(), N, D, H, W, lat, int(margin), schedule.data_ptr(), schedule.shape[0], it.data_ptr(),
+         image.data_ptr(), image.shape[-1], latent_keep.data_ptr(), _stream())
 
 
 def minmax_normalise_keep_scatter(src: torch.Tensor, schedule: torch.Tensor, it: torch.Tensor, known: torch.Tensor, keep: torch.Tensor,
                                   volume: torch.Tensor, advance: bool = True, workspace: Optional[torch.Tensor] = None) -> None:
     """minmax_normalise_scatter with the pixel composite: known fp32 / keep uint8 of volume's shape [depth, N, ...]; of the active row's
     slice, kept pixels receive known bit for bit, the others the normalised value (bit-equal to minmax_normalise on that sample)."""
-    lib = _lib.load()
     N = src.shape[0]
     require_gpu(src, "minmax_normalise_keep_scatter")
     _check_schedule(schedule, N, it)
@@ -1425,15 +1377,13 @@ def minmax_normalise_keep_scatter(src: torch.Tensor, schedule: torch.Tensor, it:
     _check_edit_volumes("minmax_normalise_keep_scatter", known, keep, tuple(volume.shape), volume.device)
     if workspace is None:
         workspace = torch.empty(2 * N, dtype=torch.float32, device=src.device)
-    check(lib.gg_minmax_normalise_keep_scatter(src.data_ptr(), N, n_per, workspace.data_ptr(), schedule.data_ptr(), schedule.shape[0],
-                                               it.data_ptr(), 1 if advance else 0, volume.shape[0], known.data_ptr(), keep.data_ptr(),
-                                               volume.data_ptr(), _stream()), "gg_minmax_normalise_keep_scatter")
+    call("gg_minmax_normalise_keep_scatter", src.data_ptr(), N, n_per, workspace.data_ptr(), schedule.data_ptr(), schedule.shape[0], it.data_ptr(),
+         1 if advance else 0, volume.shape[0], known.data_ptr(), keep.data_ptr(), volume.data_ptr(), _stream())
 
 
 def label_keep_volume(old_labels: torch.Tensor, new_labels: torch.Tensor, D: int, H: int, W: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """int32 label volumes [N, Dm, Hm, Wm] -> keep uint8 [D, N, H, W]: 1 where the stage glue's zoomed, rotated label of new_labels equals
     that of old_labels (the index rule and rot90(k=3) of mask_to_cond_slice)."""
-    lib = _lib.load()
     require_gpu(old_labels, "label_keep_volume")
     for name, t in (("old_labels", old_labels), ("new_labels", new_labels)):
         if t.dim() != 4 or t.dtype != torch.int32 or not t.is_contiguous() or t.shape != old_labels.shape or t.device != old_labels.device:
@@ -1444,8 +1394,7 @@ def label_keep_volume(old_labels: torch.Tensor, new_labels: torch.Tensor, D: int
         out = torch.empty((D, N, H, W), dtype=torch.uint8, device=old_labels.device)
     elif tuple(out.shape) != (D, N, H, W) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != old_labels.device:
         raise ValueError(f"label_keep_volume: out must be a contiguous uint8 {(D, N, H, W)} tensor on {old_labels.device}")
-    check(lib.gg_label_keep_volume(old_labels.data_ptr(), new_labels.data_ptr(), N, Dm, Hm, Wm, D, H, W, out.data_ptr(), _stream()),
-          "gg_label_keep_volume")
+    call("gg_label_keep_volume", old_labels.data_ptr(), new_labels.data_ptr(), N, Dm, Hm, Wm, D, H, W, out.data_ptr(), _stream())
     return out
 
 
@@ -1466,25 +1415,23 @@ def zoom0_index(n_in: int, n_out: int) -> torch.Tensor:
 
 def lincomb4(es, coefs, denom: float, out: torch.Tensor) -> torch.Tensor:
     """out = (sum_i coefs[i] * es[i]) / denom, fp32, left-to-right (PLMS multistep combination)."""
-    lib = _lib.load()
     es = list(es) + [None] * (4 - len(es))
     cs = list(coefs) + [0.0] * (4 - len(coefs))
-    check(lib.gg_lincomb4(es[0].data_ptr(), _ptr(es[1]), _ptr(es[2]), _ptr(es[3]), cs[0], cs[1], cs[2], cs[3], denom, out.numel(),
-                          out.data_ptr(), _stream()), "gg_lincomb4")
+    call("gg_lincomb4", es[0].data_ptr(), _ptr(es[1]), _ptr(es[2]), _ptr(es[3]), cs[0], cs[1], cs[2], cs[3], denom, out.numel(), out.data_ptr(),
+         _stream())
     return out
 
 
 def ddpm_step(x: torch.Tensor, eps: torch.Tensor, scalars: torch.Tensor, noise: Optional[torch.Tensor] = None,
               unet_in: Optional[torch.Tensor] = None) -> None:
     """Ancestral DDPM update in place; x fp32 CL [M, C], eps fp32 CL [M, stride], scalars fp32[5] on device."""
-    lib = _lib.load()
     Cc = x.shape[-1]
     M = x.numel() // Cc
-    check(lib.gg_ddpm_step(x.data_ptr(), eps.data_ptr(), eps.shape[-1], _ptr(noise), scalars.data_ptr(), M, Cc, _ptr(unet_in),
-                           unet_in.shape[-1] if unet_in is not None else 0, _stream()), "gg_ddpm_step")
+    call("gg_ddpm_step", x.data_ptr(), eps.data_ptr(), eps.shape[-1], _ptr(noise), scalars.data_ptr(), M, Cc, _ptr(unet_in),
+         unet_in.shape[-1] if unet_in is not None else 0, _stream())
 
 
-DDPM_PREDICTS_X0, DDPM_CLIP = 1, 2        # gg_ddpm_step_x0 flag bits (include/guidegen_hip.h)
+DDPM_PREDICTS_X0, DDPM_CLIP = _lib.GG_DDPM_PREDICTS_X0, _lib.GG_DDPM_CLIP        # gg_ddpm_step_x0 flag bits
 
 
 def ddpm_step_x0(x: torch.Tensor, out: torch.Tensor, scalars: torch.Tensor, noise: Optional[torch.Tensor] = None, *, predicts_x0: bool = False,
@@ -1492,29 +1439,27 @@ def ddpm_step_x0(x: torch.Tensor, out: torch.Tensor, scalars: torch.Tensor, nois
     """Ancestral update with the reference's options, in place (gg_ddpm_step_x0): x fp32 CL [M, C], out fp32 CL [M, stride] (the UNet's
     output: eps, or x_0 with predicts_x0), scalars fp32[5] on device as for ddpm_step; clip clamps the prediction of x_0 to [-1, 1];
     pred_x0_out fp32 [M, C] receives it."""
-    lib = _lib.load()
     Cc = x.shape[-1]
     M = x.numel() // Cc
     flags = (DDPM_PREDICTS_X0 if predicts_x0 else 0) | (DDPM_CLIP if clip else 0)
-    check(lib.gg_ddpm_step_x0(x.data_ptr(), out.data_ptr(), out.shape[-1], _ptr(noise), scalars.data_ptr(), flags, M, Cc, _ptr(pred_x0_out),
-                              _ptr(unet_in), unet_in.shape[-1] if unet_in is not None else 0, _stream()), "gg_ddpm_step_x0")
+    call("gg_ddpm_step_x0", x.data_ptr(), out.data_ptr(), out.shape[-1], _ptr(noise), scalars.data_ptr(), flags, M, Cc, _ptr(pred_x0_out),
+         _ptr(unet_in), unet_in.shape[-1] if unet_in is not None else 0, _stream())
 
 
 def log_rows(state: torch.Tensor, N: int, slot: torch.Tensor) -> None:
     """The fp32 channels-last state [N * S, C] -> slot fp32 [N, C, *sp] (prod(sp) = S), one entry of a pre-allocated log buffer
     (gg_log_rows: from_cl's kernel at a given destination; no allocation, capturable)."""
-    lib = _lib.load()
     Cc = state.shape[-1]
     S = state.numel() // (Cc * N) if N else 0
     if state.dtype != torch.float32 or slot.dtype != torch.float32 or not state.is_contiguous() or not slot.is_contiguous() \
             or slot.numel() != state.numel() or state.numel() != N * S * Cc or (slot.ndim >= 2 and tuple(slot.shape[:2]) != (N, Cc)):
         raise ValueError(f"log_rows: state {tuple(state.shape)} {state.dtype} does not fill a slot {tuple(slot.shape)} {slot.dtype} as "
                          f"[{N}, {Cc}, S]")
-    check(lib.gg_log_rows(state.data_ptr(), N, Cc, S, slot.data_ptr(), _stream()), "gg_log_rows")
+    call("gg_log_rows", state.data_ptr(), N, Cc, S, slot.data_ptr(), _stream())
 
 
 # ----------------------------------------------------------------------------------------------- held-out objectives (gg_loss.hip)
-LOSS_MODES = {"l2": 0, "l1": 1, "prior_kl": 2}        # gg_loss_mode (include/guidegen_hip.h)
+LOSS_MODES = {"l2": _lib.GG_LOSS_L2, "l1": _lib.GG_LOSS_L1, "prior_kl": _lib.GG_LOSS_PRIOR_KL}        # gg_loss_mode
 
 
 def _f32_dev(t: torch.Tensor, numel: int, what: str) -> torch.Tensor:
@@ -1539,7 +1484,6 @@ def q_sample_rows(x: torch.Tensor, noise: torch.Tensor, scalars: torch.Tensor, o
                   unet_in: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
     """x_noisy[n] = s0[n] * x[n] + s1[n] * noise[n] (gg_q_sample_rows): x, noise fp32 NC(D)HW on the device, scalars fp32 [N, 2].
     out: fp32 NC(D)HW; unet_in: channels-last [N, ..., Cpad] bf16 (or fp32 in validation mode), channels [0, C) written."""
-    lib = _lib.load()
     require_gpu(x, "q_sample_rows")
     N, Cc = int(x.shape[0]), int(x.shape[1])
     S = x.numel() // (N * Cc)
@@ -1554,8 +1498,7 @@ def q_sample_rows(x: torch.Tensor, noise: torch.Tensor, scalars: torch.Tensor, o
         if unet_in.dtype not in (torch.bfloat16, torch.float32) or not unet_in.is_contiguous() or unet_in.numel() != N * S * stride or stride < Cc:
             raise ValueError(f"q_sample_rows: unet_in {unet_in.dtype} {tuple(unet_in.shape)} is not a channels-last buffer of {N * S} rows, >= {Cc} lanes")
         dt = GG_F32 if is_f32(unet_in) else GG_BF16
-    check(lib.gg_q_sample_rows(x.data_ptr(), noise.data_ptr(), scalars.data_ptr(), N, Cc, S, _ptr(out), _ptr(unet_in), dt, stride, _stream()),
-          "gg_q_sample_rows")
+    call("gg_q_sample_rows", x.data_ptr(), noise.data_ptr(), scalars.data_ptr(), N, Cc, S, _ptr(out), _ptr(unet_in), dt, stride, _stream())
     return out
 
 
@@ -1564,7 +1507,6 @@ def loss_rows(mode: str, N: int, C: int, S: int, *, pred: Optional[torch.Tensor]
               workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Per-sample means, fp64 [N] (gg_loss_rows).  "l2" / "l1": pred fp32 channels-last [N * S, stride] (the UNet head's output) against
     target fp32 NC(D)HW; "prior_kl": x_start fp32 NC(D)HW and scalars fp32 [N, 2] = (sqrt_alphas_cumprod[T-1], log_one_minus_alphas_cumprod[T-1])."""
-    lib = _lib.load()
     if mode not in LOSS_MODES:
         raise ValueError(f"loss_rows: unknown mode '{mode}' (one of {sorted(LOSS_MODES)})")
     stride = 0
@@ -1579,8 +1521,8 @@ def loss_rows(mode: str, N: int, C: int, S: int, *, pred: Optional[torch.Tensor]
         out = torch.empty(N, dtype=torch.float64, device=dev)
     if workspace is None:
         workspace = loss_workspace(N, S, dev)
-    check(lib.gg_loss_rows(_ptr(pred), stride, _ptr(target), _ptr(x_start), _ptr(scalars), LOSS_MODES[mode], N, C, S, out.data_ptr(),
-                           workspace.data_ptr(), workspace.numel() * 8, _stream()), "gg_loss_rows")
+    call("gg_loss_rows", _ptr(pred), stride, _ptr(target), _ptr(x_start), _ptr(scalars), LOSS_MODES[mode], N, C, S, out.data_ptr(),
+         workspace.data_ptr(), workspace.numel() * 8, _stream())
     return out
 
 
@@ -1590,7 +1532,6 @@ def ccdm_q_sample(x0: torch.Tensor, mix: torch.Tensor, K: int, *, E: Optional[to
     """q_xt_given_x0(x0, t).sample() on labels (gg_ccdm_q_sample): x0 int32 [M] of N equal samples, mix fp32 [N, 2] = (keep, unif), the
     weights of the one-hot and of the uniform part: (cumalphas[t - 1], 1 - cumalphas[t - 1]), or (1 - betas[t - 1], betas[t - 1]).
     E: fp32 [M, K] exponential tape, or philox_seeds: device int64 [N] keys.  Returns int32 [M]."""
-    lib = _lib.load()
     require_gpu(x0, "ccdm_q_sample")
     M, N = x0.numel(), mix.numel() // 2
     rps = _rows_per_sample(M, N, "ccdm_q_sample")
@@ -1603,9 +1544,8 @@ def ccdm_q_sample(x0: torch.Tensor, mix: torch.Tensor, K: int, *, E: Optional[to
         labels_out = torch.empty(M, dtype=torch.int32, device=x0.device)
     _i32_dev(labels_out, M, "ccdm_q_sample: labels_out")
     oh_stride = _onehot_stride(onehot_out, M, "ccdm_q_sample")
-    check(lib.gg_ccdm_q_sample(x0.data_ptr(), mix.data_ptr(), rps, K, _ptr(E),
-                               _seeds_ptr(philox_seeds, N) if philox_seeds is not None else None, _ptr(philox_offset), M,
-                               labels_out.data_ptr(), _ptr(onehot_out), oh_stride, _stream()), "gg_ccdm_q_sample")
+    call("gg_ccdm_q_sample", x0.data_ptr(), mix.data_ptr(), rps, K, _ptr(E), _seeds_ptr(philox_seeds, N) if philox_seeds is not None else None,
+         _ptr(philox_offset), M, labels_out.data_ptr(), _ptr(onehot_out), oh_stride, _stream())
     return labels_out
 
 
@@ -1633,7 +1573,6 @@ def ccdm_inpaint_blend(labels: torch.Tensor, known: torch.Tensor, keep: torch.Te
     left as it is.  known int32 [M] may be `labels` itself.  E: fp32 [M, K] exponential tape; otherwise Philox with philox_seeds (device
     int64 [N], one key per sample) or the single key philox_seed, at philox_offset (device int64 [1]).  onehot_out: bf16 rows
     [M, stride], channels [0, K) of the kept rows written.  Returns labels."""
-    lib = _lib.load()
     require_gpu(labels, "ccdm_inpaint_blend")
     M, N = labels.numel(), mix.numel() // 2
     rps = _rows_per_sample(M, N, "ccdm_inpaint_blend")
@@ -1643,9 +1582,9 @@ def ccdm_inpaint_blend(labels: torch.Tensor, known: torch.Tensor, keep: torch.Te
     if E is not None:
         _f32_dev(E, M * K, "ccdm_inpaint_blend: E")
     oh_stride = _onehot_stride(onehot_out, M, "ccdm_inpaint_blend")
-    check(lib.gg_ccdm_inpaint_blend(labels.data_ptr(), known.data_ptr(), keep.data_ptr(), mix.data_ptr(), rps, K, _ptr(E),
-                                    int(philox_seed) & ((1 << 64) - 1), _seeds_ptr(philox_seeds, N) if philox_seeds is not None else None,
-                                    _ptr(philox_offset), M, _ptr(onehot_out), oh_stride, _stream()), "gg_ccdm_inpaint_blend")
+    call("gg_ccdm_inpaint_blend", labels.data_ptr(), known.data_ptr(), keep.data_ptr(), mix.data_ptr(), rps, K, _ptr(E),
+         int(philox_seed) & ((1 << 64) - 1), _seeds_ptr(philox_seeds, N) if philox_seeds is not None else None, _ptr(philox_offset), M,
+         _ptr(onehot_out), oh_stride, _stream())
     return labels
 
 
@@ -1653,7 +1592,6 @@ def ccdm_step_loss(logits: torch.Tensor, xt: torch.Tensor, x0: torch.Tensor, sca
                    out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
     """fp64 [N, 2] per-sample sums of (class-weighted KL, CE) of trainer.py:305-320 (gg_ccdm_step_loss): logits fp32 channels-last
     [M, stride], xt / x0 int32 [M], scalars fp32 [N, 2] per sample, class_weights fp32 [K]."""
-    lib = _lib.load()
     require_gpu(logits, "ccdm_step_loss")
     stride = int(logits.shape[-1])
     M = logits.numel() // stride
@@ -1665,8 +1603,8 @@ def ccdm_step_loss(logits: torch.Tensor, xt: torch.Tensor, x0: torch.Tensor, sca
         out = torch.empty((N, 2), dtype=torch.float64, device=logits.device)
     if workspace is None:
         workspace = loss_workspace(N, rps, logits.device)
-    check(lib.gg_ccdm_step_loss(logits.data_ptr(), stride, xt.data_ptr(), x0.data_ptr(), scalars.data_ptr(), rps, class_weights.data_ptr(),
-                                K, M, out.data_ptr(), workspace.data_ptr(), workspace.numel() * 8, _stream()), "gg_ccdm_step_loss")
+    call("gg_ccdm_step_loss", logits.data_ptr(), stride, xt.data_ptr(), x0.data_ptr(), scalars.data_ptr(), rps, class_weights.data_ptr(), K, M,
+         out.data_ptr(), workspace.data_ptr(), workspace.numel() * 8, _stream())
     return out
 
 
@@ -1682,7 +1620,6 @@ def patch_conv(src: CL, weight: torch.Tensor, alpha: Optional[torch.Tensor], bet
     """One PatchGAN convolution (gg_patch_conv_forward, or the fp32 kernel for fp32 inputs): kernel 4, padding 2, then
     y = acc * alpha + beta and LeakyReLU(slope) (slope 1: none).  weight: pack_conv_weight of the OI[D]HW weight; alpha (or None) and
     beta: fp32 [pad32(cout)], the folded conv bias and eval-mode BatchNorm."""
-    lib = _lib.load()
     require_gpu(src.t, "patch_conv")
     N, D, H, W, cin = src.t.shape
     Do, Ho, Wo = patch_conv_out_extent((D, H, W), kd, stride)
@@ -1694,15 +1631,15 @@ def patch_conv(src: CL, weight: torch.Tensor, alpha: Optional[torch.Tensor], bet
         if weight.dtype != torch.float32 or tuple(weight.shape) != (16 * kd, cin, cp):
             raise ValueError(f"patch_conv: fp32 input needs an fp32 weight [{16 * kd}, {cin}, {cp}], got {weight.dtype} {tuple(weight.shape)}")
         out = torch.empty((N, Do, Ho, Wo, cp), dtype=torch.float32, device=src.t.device)
-        check(lib.gg_patch_conv_forward_f32(src.t.data_ptr(), weight.data_ptr(), _ptr(alpha), beta.data_ptr(), slope, N, D, H, W, cin, cout, kd,
-                                            stride, Do, Ho, Wo, out.data_ptr(), _stream()), "gg_patch_conv_forward_f32")
+        call("gg_patch_conv_forward_f32", src.t.data_ptr(), weight.data_ptr(), _ptr(alpha), beta.data_ptr(), slope, N, D, H, W, cin, cout, kd,
+             stride, Do, Ho, Wo, out.data_ptr(), _stream())
         return CL(out, cout)
     if src.t.dtype != torch.bfloat16 or weight.dtype != torch.bfloat16 or weight.numel() != cp * 16 * kd * cin:
         raise ValueError(f"patch_conv: bf16 input needs a packed bf16 weight of {cp * 16 * kd * cin} elements, got {src.t.dtype} input, "
                          f"{weight.dtype} weight of {weight.numel()}")
     out = torch.empty((N, Do, Ho, Wo, cp), dtype=torch.float32 if out_f32 else torch.bfloat16, device=src.t.device)
-    check(lib.gg_patch_conv_forward(src.t.data_ptr(), weight.data_ptr(), _ptr(alpha), beta.data_ptr(), slope, N, D, H, W, cin, cout, kd, stride,
-                                    Do, Ho, Wo, out.data_ptr(), GG_F32 if out_f32 else GG_BF16, _stream()), "gg_patch_conv_forward")
+    call("gg_patch_conv_forward", src.t.data_ptr(), weight.data_ptr(), _ptr(alpha), beta.data_ptr(), slope, N, D, H, W, cin, cout, kd, stride, Do,
+         Ho, Wo, out.data_ptr(), GG_F32 if out_f32 else GG_BF16, _stream())
     return CL(out, cout)
 
 
@@ -1718,14 +1655,13 @@ def _moment_rows(moments: torch.Tensor, C: int, what: str) -> Tuple[int, int]:
 def gauss_kl_rows(moments: torch.Tensor, C: int, out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
     """fp64 [N] = DiagonalGaussianDistribution.kl() (gg_gauss_kl_rows) of fp32 channels-last moments [N, ..., stride]: mean lanes [0, C),
     logvar lanes [C, 2C)."""
-    lib = _lib.load()
     N, S = _moment_rows(moments, C, "gauss_kl_rows")
     if out is None:
         out = torch.empty(N, dtype=torch.float64, device=moments.device)
     if workspace is None:
         workspace = loss_workspace(N, S, moments.device)
-    check(lib.gg_gauss_kl_rows(moments.data_ptr(), int(moments.shape[-1]), N, C, S, out.data_ptr(), workspace.data_ptr(), workspace.numel() * 8,
-                               _stream()), "gg_gauss_kl_rows")
+    call("gg_gauss_kl_rows", moments.data_ptr(), int(moments.shape[-1]), N, C, S, out.data_ptr(), workspace.data_ptr(), workspace.numel() * 8,
+         _stream())
     return out
 
 
@@ -1733,7 +1669,6 @@ def gauss_sample_rows(moments: torch.Tensor, C: int, noise: torch.Tensor, out: O
                       z_in: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
     """z = mean + exp(0.5 * logvar) * noise (gg_gauss_sample_rows): moments as in gauss_kl_rows, noise fp32 [N, C, *spatial].
     out: fp32 like noise; z_in: channels-last [N, ..., Cpad] bf16 (or fp32 in validation mode), channels [0, C) written."""
-    lib = _lib.load()
     N, S = _moment_rows(moments, C, "gauss_sample_rows")
     _f32_dev(noise, N * C * S, "gauss_sample_rows: noise")
     if out is None and z_in is None:
@@ -1746,15 +1681,13 @@ def gauss_sample_rows(moments: torch.Tensor, C: int, noise: torch.Tensor, out: O
         if z_in.dtype not in (torch.bfloat16, torch.float32) or not z_in.is_cuda or not z_in.is_contiguous() or z_in.numel() != N * S * stride or stride < C:
             raise ValueError(f"gauss_sample_rows: z_in {z_in.dtype} {tuple(z_in.shape)} is not a channels-last device buffer of {N * S} rows, >= {C} lanes")
         dt = GG_F32 if is_f32(z_in) else GG_BF16
-    check(lib.gg_gauss_sample_rows(moments.data_ptr(), int(moments.shape[-1]), noise.data_ptr(), N, C, S, _ptr(out), _ptr(z_in), dt, stride,
-                                   _stream()), "gg_gauss_sample_rows")
+    call("gg_gauss_sample_rows", moments.data_ptr(), int(moments.shape[-1]), noise.data_ptr(), N, C, S, _ptr(out), _ptr(z_in), dt, stride, _stream())
     return out
 
 
 def logit_stats(logits: torch.Tensor, out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
     """fp64 [5] = means over all logits l of (l, relu(1 - l), relu(1 + l), softplus(-l), softplus(l)) (gg_logit_stats); logits: lane 0
     of fp32 channels-last rows [..., stride] (a discriminator's last convolution with out_f32)."""
-    lib = _lib.load()
     require_gpu(logits, "logit_stats")
     stride = int(logits.shape[-1])
     M = logits.numel() // stride
@@ -1763,5 +1696,5 @@ def logit_stats(logits: torch.Tensor, out: Optional[torch.Tensor] = None, worksp
         out = torch.empty(5, dtype=torch.float64, device=logits.device)
     if workspace is None:
         workspace = loss_workspace(3, M, logits.device)
-    check(lib.gg_logit_stats(logits.data_ptr(), stride, M, out.data_ptr(), workspace.data_ptr(), workspace.numel() * 8, _stream()), "gg_logit_stats")
+    call("gg_logit_stats", logits.data_ptr(), stride, M, out.data_ptr(), workspace.data_ptr(), workspace.numel() * 8, _stream())
     return out

@@ -9,11 +9,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_every_dispatch_answer_equals_the_recorded_one():
-    import __graft_entry__ as ge
     from jointimagegeneration_amd import _lib, ops
-    if not os.path.exists(_lib.LIB_PATH):
-        ge.build()
-    lib = _lib.load()
+    from util import load_lib
+    lib = load_lib()
     with open(os.path.join(ROOT, "tests", "golden", "conv_dispatch.json")) as fh:
         gold = json.load(fh)
     fields, preds, cases = gold["fields"], gold["predicates"], gold["cases"]

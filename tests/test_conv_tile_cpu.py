@@ -3,18 +3,14 @@ no HIP call.  The seven 1x1 skip projections of the CCDM UNet @128^3 and @64^3 a
 stride-2 convs (which stay on the gather kernel), every descriptor under path_hint 12 and everything with a prologue, a residual, fp32
 output or a fused epilogue answer "not taken".  The other dispatch predicates keep their answers for these shapes."""
 import ctypes as C
-import os
 
 import pytest
 
 
 @pytest.fixture(scope="module")
 def lib():
-    import __graft_entry__ as ge
-    from jointimagegeneration_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        ge.build()
-    return _lib.load()
+    from util import load_lib
+    return load_lib()
 
 
 def desc(N, sp, C1, C2, cout, k=1, stride=1, hint=0, **extra):

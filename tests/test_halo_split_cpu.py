@@ -8,7 +8,6 @@ that kernel first, and it also leaves GroupNorm statistics there, which a split 
 depth, (8, 16, 16), which has the batch-1 16^3 level's position count.
 """
 import ctypes as C
-import os
 
 import pytest
 
@@ -21,11 +20,8 @@ HINT_OFF = 13
 
 @pytest.fixture(scope="module")
 def lib():
-    import __graft_entry__ as ge
-    from jointimagegeneration_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        ge.build()
-    return _lib.load()
+    from util import load_lib
+    return load_lib()
 
 
 def slabs_of_workspace(lib, d):

@@ -4,15 +4,12 @@ batched_hungarian_matching returned for those labels (make_golden_metrics.py); D
 gg_label_confusion; the host-side refusals of ops.label_confusion, metrics.load_gt and ddpm_eval."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 from util import GOLD
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
@@ -95,20 +92,6 @@ def test_dice_is_the_formula_and_ignore_index_removes_exactly_that_entry(gold):
 
 
 # ------------------------------------------------------------------------------------------------ C-ABI
-_CT = {"float": C.c_void_p, "void": C.c_void_p, "int32_t": C.c_int32, "int64_t": C.c_int64}
-
-
-def test_declaration_matches_the_ctypes_signature():
-    from jointimagegeneration_amd import _lib
-    txt = open(os.path.join(ROOT, "include", "guidegen_hip.h")).read()
-    m = re.search(r"\bint\s+gg_label_confusion\s*\(([^)]*)\)\s*;", txt)
-    assert m, "gg_label_confusion is not declared in guidegen_hip.h"
-    want = [C.c_void_p if "*" in arg else _CT[arg.replace("const", "").split()[0]] for arg in m.group(1).split(",")]
-    res, args = _lib.SIGNATURES["gg_label_confusion"]
-    assert res is C.c_int and args == want and len(want) == 9
-    assert "gg_metrics" in open(os.path.join(ROOT, "jointimagegeneration_amd", "csrc", "build.sh")).read()
-
-
 def test_entry_rejects_bad_arguments_on_the_host():
     """No device here: every refusal comes from host code, before any launch."""
     from jointimagegeneration_amd import _lib
@@ -116,7 +99,7 @@ def test_entry_rejects_bad_arguments_on_the_host():
     buf = (C.c_int64 * 64)()
     p = C.cast(buf, C.c_void_p)
     bad = -1
-    assert re.search(r"GG_ERR_BAD_SHAPE\s*=\s*-1\b", open(os.path.join(ROOT, "include", "guidegen_hip.h")).read())
+    assert _lib.GG_ERR_BAD_SHAPE == -1
     f = lib.gg_label_confusion
     assert f(None, 1, p, 1, 8, 4, p, p, None) == bad and b"null" in lib.gg_last_error()
     assert f(p, 1, None, 1, 8, 4, p, p, None) == bad

@@ -45,11 +45,8 @@ def test_draw_tape_argument_checks_run_before_any_launch():
     """Host-side checks of gg_ccdm_draw_tape, callable without a GPU; the draw loop stands once in csrc/."""
     import os
     import re
-    import __graft_entry__ as ge
-    from jointimagegeneration_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        ge.build()
-    lib = _lib.load()
+    from util import load_lib
+    lib = load_lib()
     one = 1                                                  # any non-NULL address: no check dereferences it
     assert lib.gg_ccdm_draw_tape(0, None, 0, None, 16, 8, None, None, None, None) != 0 and b"no output" in lib.gg_last_error()
     assert lib.gg_ccdm_draw_tape(0, None, 0, None, 24, 8, None, one, None, None) != 0 and b"kmax=24" in lib.gg_last_error()

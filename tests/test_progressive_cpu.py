@@ -1,11 +1,9 @@
 """CPU suite for progressive sampling: the cosine / sqrt_linear / sqrt / given_betas schedules bit for bit against the reference's
 buffers (tests/golden/progressive.npz, make_golden_progressive.py), the DDPM class and its state_dict surface, the logging rule of the
-three loops against what the reference logged, the options refused by name before any launch, and the C-ABI of gg_ddpm_step_x0 and
-gg_log_rows (declaration, ctypes signature, host-side argument checks)."""
-import ctypes as C
+three loops against what the reference logged, the options refused by name before any launch, and the host-side argument checks of
+gg_ddpm_step_x0 and gg_log_rows (their declarations are checked with every other in test_capi_cpu.py)."""
 import json
 import os
-import re
 
 import numpy as np
 import pytest
@@ -14,7 +12,6 @@ import torch
 from progressive_ref import BUFFERS, ddpm_config, ddpm_small, ldm_small, logged, recorded_list
 from util import GOLD, gold, surface
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPE = (2, 4, 8, 8)
 
 
@@ -175,31 +172,10 @@ def test_cpu_models_and_score_corrector_are_refused(m20):
 
 
 # ------------------------------------------------------------------------------------------------ C-ABI
-_CT = {"float": C.c_void_p, "void": C.c_void_p, "int32_t": C.c_int32, "int64_t": C.c_int64}
-_NAMES = {"gg_ddpm_step_x0": ["x", "out", "out_stride", "noise", "scalars_dev", "flags", "M", "C", "pred_x0_out", "unet_in", "unet_in_stride", "stream"],
-          "gg_log_rows": ["state", "N", "C", "S", "slot", "stream"]}
-
-
-@pytest.mark.parametrize("fn", sorted(_NAMES))
-def test_declarations_match_the_ctypes_signatures(fn):
-    from jointimagegeneration_amd import _lib
-    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "guidegen_hip.h")).read(), flags=re.S)
-    m = re.search(r"\bint\s+" + fn + r"\s*\(([^)]*)\)\s*;", txt)
-    assert m, f"{fn} is not declared in guidegen_hip.h"
-    params = [p.strip() for p in m.group(1).split(",")]
-    assert [re.findall(r"\w+", p)[-1] for p in params] == _NAMES[fn]
-    want = [_CT[re.sub(r"\bconst\b", "", p).split()[0]] if "*" not in p else C.c_void_p for p in params]
-    res, args = _lib.SIGNATURES[fn]
-    assert res is C.c_int and args == want
-
-
 @pytest.fixture(scope="module")
 def lib():
-    import __graft_entry__ as ge
-    from jointimagegeneration_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        ge.build()
-    return _lib.load()
+    from util import load_lib
+    return load_lib()
 
 
 def test_gg_ddpm_step_x0_rejects_bad_arguments_on_the_host(lib):
@@ -232,12 +208,6 @@ def test_gg_log_rows_rejects_bad_arguments_on_the_host(lib):
     assert lib.gg_log_rows(p, 2, 4, -5, p, None) == bad_shape
     assert lib.gg_log_rows(p, 0, 4, 64, p, None) == 0                                          # empty: no launch
     assert lib.gg_log_rows(p, 2, 4, 0, p, None) == 0
-
-
-def test_error_codes_are_the_header_ones():
-    txt = open(os.path.join(ROOT, "include", "guidegen_hip.h")).read()
-    assert re.search(r"GG_ERR_BAD_SHAPE\s*=\s*-1\b", txt) and re.search(r"GG_ERR_UNSUPPORTED\s*=\s*-3\b", txt)
-    assert re.search(r"#define\s+GG_DDPM_PREDICTS_X0\s+1\b", txt) and re.search(r"#define\s+GG_DDPM_CLIP\s+2\b", txt)
 
 
 # ------------------------------------------------------------------------------------------------ entry point

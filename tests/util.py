@@ -24,6 +24,15 @@ AE_FULL = dict(double_z=True, z_channels=4, resolution=512, in_channels=1, out_c
                num_res_blocks=2, dropout=0.0, dims=2, attn_resolutions=[16, 8])
 
 
+def load_lib():
+    """The loaded C-ABI library (ctypes), built first where this checkout has not been built yet."""
+    import __graft_entry__ as ge
+    from jointimagegeneration_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        ge.build()
+    return _lib.load()
+
+
 def gold(name):
     return np.load(os.path.join(GOLD, name + ".npz"), allow_pickle=False)
 
