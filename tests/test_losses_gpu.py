@@ -157,7 +157,9 @@ def test_loss_rows_against_the_fp64_restatement(dev, g, tag):
 
 
 def test_loss_rows_over_several_workgroups_with_a_partial_last_one(dev):
-    """N = 3, C = 3, S = 5 * 6 * 19 = 570 positions: three workgroups per sample, the last one partial; a stride that is no multiple of 4."""
+    """N = 3, C = 3, S = 5 * 6 * 19 = 570 positions: three workgroups per sample, the last one partial; a stride that is no multiple of 4.
+    Every thread still takes one trip of its loop (the grid is capped at 1024 workgroups per sample): the later trips run in
+    tests/test_grid_caps_gpu.py::test_loss_rows_exact_integers and ::test_loss_rows_prior_kl."""
     from jointimagegeneration_amd import ops
     gen = torch.Generator().manual_seed(31)
     pred, target = (torch.randn(3, 3, 5, 6, 19, generator=gen).half().float() for _ in range(2))
@@ -204,7 +206,8 @@ def test_ccdm_step_loss_against_the_fp64_restatement(dev, g, tag, K):
 
 
 def test_ccdm_step_loss_over_several_workgroups(dev):
-    """K = 14, N = 2, 5 * 6 * 19 = 570 voxels per sample (three workgroups, the last partial), t = 1 and t = 27, against the restatement."""
+    """K = 14, N = 2, 5 * 6 * 19 = 570 voxels per sample (three workgroups, the last partial), t = 1 and t = 27, against the restatement.
+    Every thread still takes one trip of its loop: the later trips run in tests/test_grid_caps_gpu.py::test_ccdm_step_loss."""
     from jointimagegeneration_amd import ops
     from jointimagegeneration_amd.ccdm import DiffusionModel
     K, gen = 14, torch.Generator().manual_seed(57)
