@@ -1,6 +1,10 @@
 """CPU suite: the shadow harness (tests/shadow.py) itself.  Its fp64 references equal torch's CPU operators (F.conv2d / conv3d,
 F.group_norm, scaled-dot-product attention, in fp64) to 1e-12 on small shapes with every conv feature production uses, and its
-comparator passes a clean kernel-like output (the reference rounded to the kernel's output type) but fails on each injected defect."""
+comparator passes a clean kernel-like output (the reference rounded to the kernel's output type) but fails on each injected defect.
+The same for the families of the text, 3-D, GAN and LPIPS networks (F.gelu, F.layer_norm, F.embedding, F.interpolate, F.conv2d /
+conv3d(k=4, padding=2) + leaky_relu, F.max_pool2d(F.relu(.)), attention under a key mask, torch.cdist(...).argmin), one planted
+violation per rule of the operand contract, and the completeness check: every `ops.X(` call of the network modules is wrapped by the
+shadow or listed, with a reason, in its EXEMPT table."""
 import math
 
 import pytest
@@ -376,3 +380,390 @@ def test_other_families_pass_clean_and_fail_defects():
     gg = (h.double()[:, :32] * SH.gelu(h.double()[:, 32:])).to(torch.bfloat16)
     assert SH.geglu_ratio(h, 32, gg) <= 1.0
     assert SH.geglu_ratio(h, 32, (h.double()[:, 32:] * SH.gelu(h.double()[:, :32])).to(torch.bfloat16)) > 1.0
+    _text_families(g)
+    _patch_conv_family(g)
+    _lpips_families(g)
+    _interpolate_and_vq_families(g)
+
+
+# ------------------------------------------------------------------------------------------------ text, 3-D, GAN and LPIPS families
+def rnd(g, *shape):
+    return torch.randn(*shape, generator=g)
+
+
+def masked_sdpa(q, k, v, lens, scale):
+    """[N, T, heads, hd] views -> scaled_dot_product_attention in fp64 under the key mask j < lens[n]."""
+    T = k.shape[1]
+    mask = (torch.arange(T)[None, :] < torch.tensor(lens)[:, None])[:, None, None, :]
+    return F.scaled_dot_product_attention(q.double().transpose(1, 2), k.double().transpose(1, 2), v.double().transpose(1, 2),
+                                          attn_mask=mask, scale=scale).transpose(1, 2)
+
+
+def test_attention_reference_with_key_lengths_equals_masked_sdpa():
+    N, T, heads, hd = 3, 23, 2, 32
+    g = gen(51)
+    q, k, v = (rnd(g, N, T, heads, hd).to(torch.bfloat16) for _ in range(3))
+    lens, scale = [5, 23, 1], hd ** -0.5
+    want = masked_sdpa(q, k, v, lens, scale)
+    for n in range(N):
+        for h in range(heads):
+            ref, _ = SH.attention_reference(q[n, :, h], k[n, :lens[n], h], v[n, :lens[n], h], scale)
+            assert float((ref - want[n, :, h]).abs().max()) <= REF_TOL * float(want.abs().max())
+    clean = want.to(torch.bfloat16)
+    assert SH.attention_ratio(q, k, v, clean, scale, 0, lens) <= 1.0
+    assert SH.attention_ratio(q, k, v, clean, scale, 0, [5, 99, 0]) <= 1.0           # the clamp: [1, Tkv]
+    assert SH.attention_ratio(q, k, v, clean, scale, 0, None) > 1.0                 # judged against all Tkv keys: the old reference
+    # planted: one sample's length off by one; two samples' lengths swapped
+    assert SH.attention_ratio(q, k, v, masked_sdpa(q, k, v, [5, 22, 1], scale).to(torch.bfloat16), scale, 0, lens) > 1.0
+    assert SH.attention_ratio(q, k, v, masked_sdpa(q, k, v, [6, 23, 1], scale).to(torch.bfloat16), scale, 0, lens) > 1.0
+    assert SH.attention_ratio(q, k, v, masked_sdpa(q, k, v, [23, 5, 1], scale).to(torch.bfloat16), scale, 0, lens) > 1.0
+
+
+def padded(t, cp):
+    out = torch.zeros(tuple(t.shape[:-1]) + (cp,), dtype=t.dtype)
+    out[..., :t.shape[-1]] = t
+    return out
+
+
+def _text_families(g):
+    # gelu
+    x = (3.0 * rnd(g, 7, 64)).to(torch.bfloat16)
+    assert float((SH.gelu(x.double()) - F.gelu(x.double())).abs().max()) <= REF_TOL
+    assert SH.gelu_ratio(x, F.gelu(x.double()).to(torch.bfloat16)) <= 1.0
+    assert SH.gelu_ratio(x, F.gelu(x.double(), approximate="tanh").to(torch.bfloat16).roll(1, 1)) > 1.0
+    assert SH.add_ratio(x, x.roll(1, 0), (x.double() + x.roll(1, 0).double()).to(torch.bfloat16)) <= 1.0
+    assert SH.add_ratio(x, x.roll(1, 0), (x.double() + x.double()).to(torch.bfloat16)) > 1.0
+    # layernorm_rows: C = 48 in rows of 64
+    C, cp = 48, 64
+    xr = padded((2.0 * rnd(g, 5, 1, 1, 3, C) + 0.5).to(torch.bfloat16), cp)
+    gm, bt = 1 + 0.1 * rnd(g, C), 0.1 * rnd(g, C)
+    ln = lambda t, width, w, b: F.layer_norm(t[..., :width].double(), (width,), w, b, 1e-5)
+    ref, _ = SH.layernorm_reference(xr[..., :C].reshape(-1, C).double(), gm, bt, 1e-5)
+    assert float((ref - ln(xr, C, gm.double(), bt.double()).reshape(-1, C)).abs().max()) <= REF_TOL * 10
+    clean = padded(ln(xr, C, gm.double(), bt.double()).to(torch.bfloat16), cp)
+    assert SH.layernorm_rows_ratio(xr, C, gm, bt, 1e-5, clean) <= 1.0
+    over_cpad = padded((ln(xr, cp, None, None)[..., :C] * gm.double() + bt.double()).to(torch.bfloat16), cp)      # statistics over Cpad
+    assert SH.layernorm_rows_ratio(xr, C, gm, bt, 1e-5, over_cpad) > 1.0
+    dirty = clean.clone()
+    dirty[2, 0, 0, 1, C + 3] = 2.0 ** -20                           # a non-zero pad lane
+    assert SH.layernorm_rows_ratio(xr, C, gm, bt, 1e-5, dirty) == math.inf
+    # embed_rows
+    V, P, D, B, T = 97, 20, 48, 3, 7
+    tok, pos = rnd(g, V, D), rnd(g, P, D)
+    ids = torch.randint(0, V, (B, T), generator=g)
+    want = F.embedding(ids, tok) + pos[:T][None]
+    assert SH.embed_rows_ratio(ids, tok, pos, want) == 0.0 and SH.embed_rows_ratio(ids, tok, None, F.embedding(ids, tok)) == 0.0
+    rows = lambda t: padded(t.to(torch.bfloat16), 64).reshape(B, 1, 1, T, 64)
+    assert SH.embed_rows_ratio(ids, tok, pos, rows(want)) == 0.0
+    shifted = F.embedding(ids, tok) + pos[1:T + 1][None]            # a position row shifted by one
+    assert SH.embed_rows_ratio(ids, tok, pos, shifted) == math.inf and SH.embed_rows_ratio(ids, tok, pos, rows(shifted)) == math.inf
+    dirty = rows(want).clone()
+    dirty[1, 0, 0, 2, D] = 1.0
+    assert SH.embed_rows_ratio(ids, tok, pos, dirty) == math.inf
+    assert SH.embed_rows_ratio(ids, tok, pos, (want.double() * (1 + 2.0 ** -22)).float()) == math.inf       # bit-equal, not close
+    # bert_embed
+    typ = rnd(g, 2, D)
+    tts = torch.randint(0, 2, (B, T), generator=g)
+    tts[0, 0], tts[0, 1] = 1, 0
+    emb = lambda tt: F.layer_norm((F.embedding(ids, tok) + F.embedding(tt, typ) + pos[:T][None]).double(), (D,), gm.double(), bt.double(), 1e-12)
+    assert SH.bert_embed_ratio(ids, tts, tok, pos, typ, gm, bt, 1e-12, rows(emb(tts))) <= 1.0
+    assert SH.bert_embed_ratio(ids, None, tok, pos, typ, gm, bt, 1e-12, rows(emb(torch.zeros_like(tts)))) <= 1.0
+    assert SH.bert_embed_ratio(ids, tts, tok, pos, typ, gm, bt, 1e-12, rows(emb(torch.zeros_like(tts)))) > 1.0      # the token-type row ignored
+    x32 = (F.embedding(ids, tok) + F.embedding(tts, typ)) + pos[:T][None]                                        # the kernel's fp32 sums
+    assert SH.bert_embed_ratio(ids, tts, tok, pos, typ, gm, bt, 1e-12, rows(F.layer_norm(x32.double(), (D,), gm.double(), bt.double(), 1e-12))) <= 1.0
+
+
+def torch_patch_conv(src, w, alpha, beta, kd, stride, slope, pad=2):
+    """F.conv2d / conv3d(kernel 4) + affine + leaky_relu in fp64, channels-last [N, Do, Ho, Wo, Cout]; pad = 2 is the operation, pad = 1
+    the planted defect at the same output extent (taps start at o * stride - 1)."""
+    x = ncdhw(src)
+    cout, cin = w.shape[0], src.shape[-1]
+    Wf = torch.zeros((cout, cin, w.shape[2]), dtype=torch.float64)
+    Wf[:, :w.shape[1]] = w.to(torch.bfloat16).double()
+    lo, hi = pad, 4 - pad
+    if kd == 1:
+        y = F.conv2d(F.pad(x[:, :, 0], (lo, hi, lo, hi)), Wf.reshape(cout, cin, 4, 4), stride=stride)[:, :, None]
+    else:
+        y = F.conv3d(F.pad(x, (lo, hi, lo, hi, lo, hi)), Wf.reshape(cout, cin, 4, 4, 4), stride=stride)
+    y = y.permute(0, 2, 3, 4, 1)
+    y = y * (alpha[:cout].double() if alpha is not None else 1.0) + beta[:cout].double()
+    return F.leaky_relu(y, slope)
+
+
+@pytest.mark.parametrize("kd, stride", [(1, 1), (1, 2), (4, 1), (4, 2)])
+def test_patch_conv_reference_equals_torch_conv(kd, stride):
+    g = gen(60 + kd + stride)
+    sp = (1, 9, 10) if kd == 1 else (3, 5, 6)
+    src = cl(2, sp, 24, 61, cpad=32)
+    cout = 40
+    w = rnd(g, cout, 24, 16 * kd) * 0.1
+    alpha, beta = padded(1 + 0.3 * rnd(g, cout), 64), padded(0.5 * rnd(g, cout), 64)
+    want = torch_patch_conv(src, w, alpha, beta, kd, stride, 0.2)
+    same = F.conv2d(ncdhw(src)[:, :, 0], torch.zeros(1, 32, 4, 4, dtype=torch.float64), stride=stride, padding=2) if kd == 1 else \
+        F.conv3d(ncdhw(src), torch.zeros(1, 32, 4, 4, 4, dtype=torch.float64), stride=stride, padding=2)
+    assert tuple(want.shape[1:4]) == SH.patch_conv_extent(sp, kd, stride) == ((1,) if kd == 1 else ()) + tuple(same.shape[2:])
+    pos = SH._all_positions(want.shape[1:4])
+    for n in range(2):
+        ref, bound = SH.patch_conv_reference(src, w, alpha, beta, kd, stride, 0.2, n, pos)
+        assert float((ref - want[n][pos[:, 0], pos[:, 1], pos[:, 2]]).abs().max()) <= REF_TOL * float(want.abs().max())
+        assert bool((bound > 0).all())
+
+
+def _patch_conv_family(g):
+    for kd, stride, dtype, with_alpha in ((1, 2, torch.bfloat16, True), (4, 1, torch.bfloat16, True), (1, 1, torch.float32, False)):
+        sp = (1, 9, 10) if kd == 1 else (3, 5, 6)
+        src = cl(2, sp, 24, 62, cpad=32)
+        cout = 40
+        w = rnd(g, cout, 24, 16 * kd) * 0.1
+        alpha = padded(1 + 0.3 * rnd(g, cout), 64) if with_alpha else None
+        beta = padded(0.5 * rnd(g, cout), 64)
+        out = lambda y: padded(y.to(dtype), 64)
+        ratio = lambda got: SH.patch_conv_ratio(src, w, alpha, beta, cout, kd, stride, 0.2, got)
+        clean = out(torch_patch_conv(src, w, alpha, beta, kd, stride, 0.2))
+        assert ratio(clean)[1] == 2 and ratio(clean)[0] <= 1.0
+        assert ratio(out(torch_patch_conv(src, w, alpha, beta, kd, stride, 0.2, pad=1)))[0] > 1.0               # padding 1
+        if with_alpha:
+            sw = list(range(64))
+            sw[3], sw[4] = 4, 3
+            assert ratio(out(torch_patch_conv(src, w, alpha[sw], beta[sw], kd, stride, 0.2)))[0] > 1.0           # alpha / beta of two channels swapped
+        short = clean.clone()
+        short[:, :, -1] = 0                                                                                    # the last output row missing
+        assert ratio(short)[0] > 1.0
+        dirty = clean.clone()
+        dirty[1, 0, 0, 0, cout] = 2.0 ** -20
+        assert ratio(dirty)[0] == math.inf
+        assert ratio(clean[:, :, :-1])[0] == math.inf                                                          # a wrong extent
+
+
+def _lpips_families(g):
+    import lpips_ref
+    # relu, pooled halves, tap value
+    a = rnd(g, 3, 1, 5, 7, 64).to(torch.bfloat16)
+    b = (a.float() + 0.5 * rnd(g, 3, 1, 5, 7, 64)).to(torch.bfloat16)
+    lw = torch.rand(64, generator=g) + 0.05
+    assert SH.relu_ratio(a, F.relu(a)) == 0.0 and SH.relu_ratio(a, a.abs()) == math.inf
+    pool = lambda t: F.max_pool2d(F.relu(t[:, 0].permute(0, 3, 1, 2).float()), 2).permute(0, 2, 3, 1).to(t.dtype)[:, None]
+    pooled = torch.cat([pool(a), pool(b)])
+    assert torch.equal(SH.lpips_pool_reference(a, b), pooled)
+    nchw = lambda t: F.relu(t.double())[:, 0].permute(0, 3, 1, 2)
+    want = lpips_ref.tap_distance(nchw(a), nchw(b), lw.double())
+    assert float((SH.lpips_tap_reference(a, b, lw) - want).abs().max()) <= REF_TOL
+    got = want.float()
+    assert SH.lpips_tap_ratio(a, b, lw, got, pooled, got.clone(), None) <= 1.0
+    before = torch.full((3,), 2.0)
+    assert SH.lpips_tap_ratio(a, b, lw, got, pooled, before + got, before) <= 1.0
+    assert SH.lpips_tap_ratio(a, b, lw, got, pooled, before, before) == math.inf                               # total not updated
+    assert SH.lpips_tap_ratio(a, b, lw, got, torch.cat([pool(b), pool(a)])) == math.inf                        # a's and b's halves swapped
+    assert SH.lpips_tap_ratio(a, b, lw, (want * (1 + 4 * SH.LPIPS_TAP_RTOL)).float()) > 1.0
+    assert SH.lpips_tap_ratio(a, b, lw, got.flip(0)) > 1.0
+    # volume views: the reference's rearrange and ScalingLayer
+    x = torch.rand(2, 4, 5, 6, generator=g) * 1.5 - 0.25
+    shift, scale = torch.tensor(lpips_ref.SHIFT), torch.tensor(lpips_ref.SCALE)
+    for view in range(3):
+        imgs = lpips_ref.views(x[:, None].double())[view]
+        want = lpips_ref.scaling(imgs).permute(0, 2, 3, 1)
+        n0, n1 = 1, imgs.shape[0] - 2
+        ref, _ = SH.volume_views_reference(x, view, n0, n1, shift, scale)
+        assert float((ref - want[n0:n1]).abs().max()) <= 1e-6                                  # scaling() holds shift / scale in fp32
+        for dtype in (torch.float32, torch.bfloat16):
+            clean = padded(ref.to(dtype), 32)[:, None]
+            assert SH.volume_views_ratio(x, view, n0, n1, shift, scale, clean) <= 1.0
+            assert SH.volume_views_ratio(x, (view + 1) % 3, n0, n1, shift, scale, clean) > 1.0          # another axis (another extent: inf)
+            assert SH.volume_views_ratio(x, view, n0 - 1, n1 - 1, shift, scale, clean) > 1.0            # the image range off by one
+            dirty = clean.clone()
+            dirty[0, 0, 0, 0, 3] = 1.0
+            assert SH.volume_views_ratio(x, view, n0, n1, shift, scale, dirty) == math.inf
+    x3 = torch.rand(3, 3, 5, 7, generator=g)
+    ref, _ = SH.volume_views_reference(x3, 3, 1, 3, shift, scale)
+    assert float((ref - lpips_ref.scaling(x3.double()).permute(0, 2, 3, 1)[1:3]).abs().max()) <= 1e-6
+
+
+MODES = ("nearest", "bilinear", "bicubic", "area")
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_interpolate_reference_equals_f_interpolate(mode):
+    g = gen(70)
+    for shape in ((2, 3, 17, 20), (1, 2, 13, 10), (1, 1, 2, 3)):
+        x = rnd(g, *shape)
+        for s in (0.5, 2):
+            ref, mag = SH.interpolate2d_reference(x, s, mode)
+            want = F.interpolate(x.double(), scale_factor=s, mode=mode)
+            assert ref.shape == want.shape and float((ref - want).abs().max()) <= REF_TOL * 100, (shape, s)
+            assert bool((mag >= ref.abs() - 1e-12).all())
+            assert SH.interpolate2d_ratio(x, s, mode, want.float()) <= 1.0
+            assert want.shape[3] == 1 or SH.interpolate2d_ratio(x, s, mode, want.float().roll(1, 3)) > 1.0
+
+
+def _interpolate_and_vq_families(g):
+    # bilinear at scale 0.5 without the half-pixel offset: source 2 d instead of 2 d + 0.5
+    x = rnd(g, 2, 3, 16, 20)
+    assert SH.interpolate2d_ratio(x, 0.5, "bilinear", F.interpolate(x, scale_factor=0.5, mode="bilinear")) <= 1.0
+    assert SH.interpolate2d_ratio(x, 0.5, "bilinear", x[:, :, ::2, ::2].contiguous()) > 1.0
+    assert SH.interpolate2d_ratio(x, 0.5, "bilinear", F.interpolate(x, scale_factor=0.5, mode="bilinear")[:, :, :-1]) == math.inf
+    # vq_nearest
+    E = rnd(g, 16, 4)
+    z = padded(rnd(g, 200, 4), 8)
+    idx, second, tie = SH.vq_reference(z[:, :4], E)
+    assert torch.equal(idx, torch.cdist(z[:, :4].double(), E.double()).argmin(1)) and float(tie.double().mean()) <= SH.VQ_TIE_CAP
+    st = lambda i: z[:, :4] + (E[i] - z[:, :4])
+    assert SH.vq_ratio(z, E, idx.int(), st(idx)) == (0.0, float(tie.double().mean()))
+    m = int((~tie).nonzero()[0])
+    bad = idx.clone()
+    bad[m] = second[m]                                              # one row given the second-nearest code, outside the margin
+    assert SH.vq_ratio(z, E, bad.int(), st(bad))[0] == math.inf
+    assert SH.vq_ratio(z, E, idx.int(), E[idx])[0] == math.inf       # the codebook row itself is not the straight-through expression
+    dE = torch.cdist(E.double(), E.double()) + 1e9 * torch.eye(16, dtype=torch.float64)
+    ci, cj = divmod(int(dE.argmin()), 16)                           # the closest pair of codes: their midpoint is nearest to exactly these two
+    zt = z.clone()
+    zt[0, :4] = (E[ci] + E[cj]) / 2                                   # a row on the bisector of two codes: either may win, nothing else
+    i2, s2, t2 = SH.vq_reference(zt[:, :4], E)
+    assert bool(t2[0]) and {int(i2[0]), int(s2[0])} == {ci, cj}
+    if True:
+        for pick, ok in ((int(i2[0]), True), (int(s2[0]), True), ((int(i2[0]) + 1) % 16 if (int(i2[0]) + 1) % 16 != int(s2[0]) else (int(i2[0]) + 2) % 16, False)):
+            alt = i2.clone()
+            alt[0] = pick
+            assert (SH.vq_ratio(zt, E, alt.int())[0] == 0.0) == ok
+    many = z.clone()
+    many[:10, :4] = ((E[ci] + E[cj]) / 2)[None]
+    r, share = SH.vq_ratio(many, E, SH.vq_reference(many[:, :4], E)[0].int())                 # 10 of 200 rows on a bisector: over the cap
+    assert share >= 0.05 > SH.VQ_TIE_CAP and r == math.inf
+
+
+def test_vq_fixture_rows_stay_under_the_near_tie_cap():
+    """The rows the 3-D VQ first stage quantises in tests/test_shadow_nets_gpu.py: the reference's recorded pre-quantisation rows of the
+    fixture volume against the seeded codebook.  Their own fp64 near-tie share stays under VQ_TIE_CAP."""
+    import json
+    import os
+    from util import GOLD, T, gold
+    from jointimagegeneration_amd.synth import synth_tensor
+    from test_ae3d_cpu import vq3d
+    from util import seeded
+    with open(os.path.join(GOLD, "ae3d_surface.json")) as f:
+        meta = json.load(f)
+    E = seeded(vq3d(meta), "ae3d_vq.").quantize.embedding.weight.detach() * meta["code_scale"]
+    z = T(gold("ae3d")["vq_prequant"])
+    rows = z.permute(0, 2, 3, 4, 1).reshape(-1, z.shape[1])
+    idx, _, tie = SH.vq_reference(rows, E)
+    assert torch.equal(idx, T(gold("ae3d")["vq_idx"]).long().reshape(-1))
+    assert float(tie.double().mean()) <= SH.VQ_TIE_CAP, float(tie.double().mean())
+
+
+# ------------------------------------------------------------------------------------------------ operand contract
+def _cl(t, C):
+    from jointimagegeneration_amd.ops import CL
+    return CL(t, C)
+
+
+def _conv_args(**over):
+    a = dict(src1=_cl(cl(2, (1, 5, 6), 40, 80), 40), src2=None, weight=torch.zeros(8, dtype=torch.bfloat16), bias=torch.zeros(64), cout=48,
+             k=(1, 3, 3), stride=1, pad=1, upsample=False, residual=None, bias_per_sample=False, prologue=None, prologue_acc=None, skip=None,
+             out=None, ddim=None, geglu=False)
+    a.update(over)
+    return a
+
+
+def _gn_args(**over):
+    a = dict(src1=_cl(cl(2, (1, 5, 6), 64, 81), 64), src2=None, gamma=torch.ones(64), beta=torch.zeros(64), eps=1e-5)
+    a.update(over)
+    return a
+
+
+def _attn_args(**over):
+    qkv = torch.zeros(2, 1, 1, 7, 3 * 64, dtype=torch.bfloat16)
+    a = dict(q=qkv, k=qkv, v=qkv, out=torch.zeros(2, 1, 1, 7, 64, dtype=torch.bfloat16), N=2, heads=2, head_dim=32, Tq=7, Tkv=7, ld_hs_q=(192, 32),
+             ld_hs_k=(192, 32), ld_hs_v=(192, 32), ld_hs_o=(64, 32), q_off=0, k_off=64, v_off=128, kv_len=None)
+    a.update(over)
+    return a
+
+
+def _contract_cases():
+    bf, f32 = torch.bfloat16, torch.float32
+    x = torch.zeros(4, 64, dtype=bf)
+    lin = dict(x=torch.zeros(3, 16), W=torch.zeros(8, 16), b=torch.zeros(8), out=None)
+    res_ok = _cl(cl(2, (1, 5, 6), 48, 82), 48)
+    return [
+        # (rule, op, clean arguments, violating arguments, operand named, word in what was found)
+        ("dtype", "layernorm", dict(x=x, gamma=torch.ones(64), beta=torch.zeros(64)), dict(x=x, gamma=torch.ones(64, dtype=bf), beta=torch.zeros(64)), "gamma", "dtype"),
+        ("contiguous", "conv", _conv_args(), _conv_args(src1=_cl(cl(2, (1, 5, 12), 40, 80)[:, :, :, ::2], 40)), "src1", "stride"),
+        ("forwarded stride", "film_fold", dict(scale=torch.zeros(2, 128)[:, :96], shift=torch.zeros(2, 128)[:, :96], C=64),
+         dict(scale=torch.zeros(2, 128)[:, :96], shift=torch.zeros(2, 96), C=64), "shift", "stride"),
+        ("gamma / beta >= c_log", "groupnorm_stats", _gn_args(), _gn_args(gamma=torch.ones(32)), "gamma", "extent"),
+        ("gamma / beta >= c_log", "groupnorm_fused", _gn_args(), _gn_args(beta=torch.zeros(63)), "beta", "extent"),
+        ("scale / shift [N, C1 + C2]", "groupnorm_apply", dict(_gn_args(src2=_cl(cl(2, (1, 5, 6), 32, 83), 32)), scale=torch.zeros(2, 96), shift=torch.zeros(2, 96)),
+         dict(_gn_args(src2=_cl(cl(2, (1, 5, 6), 32, 83), 32)), scale=torch.zeros(2, 96), shift=torch.zeros(2, 64)), "shift", "extent"),
+        ("bias pad32(cout)", "conv", _conv_args(), _conv_args(bias=torch.zeros(48)), "bias", "extent"),
+        ("bias per sample", "conv", _conv_args(bias=torch.zeros(128), bias_per_sample=True), _conv_args(bias=torch.zeros(64), bias_per_sample=True), "bias", "extent"),
+        ("residual = output shape", "conv", _conv_args(residual=res_ok), _conv_args(residual=_cl(cl(2, (1, 5, 5), 48, 82), 48)), "residual", "extent"),
+        ("prologue[1] matches prologue[0]", "resample2x", dict(src=_cl(cl(2, (2, 4, 6), 40, 84), 40), prologue=(torch.zeros(2, 64), torch.zeros(2, 64))),
+         dict(src=_cl(cl(2, (2, 4, 6), 40, 84), 40), prologue=(torch.zeros(2, 64), torch.zeros(2, 40))), "prologue[1]", "extent"),
+        ("add: equal numel", "add", dict(a=x, b=x.clone()), dict(a=x, b=x[:3].clone()), "b", "extent"),
+        ("layernorm: contiguous bf16", "layernorm", dict(x=x, gamma=torch.ones(64), beta=torch.zeros(64)),
+         dict(x=torch.zeros(4, 128, dtype=bf)[:, :64], gamma=torch.ones(64), beta=torch.zeros(64)), "x", "stride"),
+        ("geglu: contiguous bf16", "geglu", dict(h=x, inner=32), dict(h=x.float(), inner=32), "h", "dtype"),
+        ("linear_f32: W [O, I]", "linear_f32", lin, dict(lin, W=torch.zeros(8, 32)[:, :16]), "W", "stride"),
+        ("linear_f32: W [O, I]", "linear_f32", lin, dict(lin, W=torch.zeros(8, 12)), "W", "extent"),
+        ("linear_f32: b [O]", "linear_f32", lin, dict(lin, b=torch.zeros(4)), "b", "extent"),
+        ("attention views inside their tensors", "attention", _attn_args(), _attn_args(v_off=129), "v", "extent"),
+        ("attention views inside their tensors", "attention", _attn_args(kv_len=torch.ones(2, dtype=torch.int32)), _attn_args(kv_len=torch.ones(2, dtype=torch.int64)), "kv_len", "dtype"),
+        ("ddim_step rows", "ddim_step", dict(x=torch.zeros(6, 4), eps=torch.zeros(6, 32), scalars=torch.zeros(4), noise=None, pred_x0_out=None, unet_in=None),
+         dict(x=torch.zeros(6, 4), eps=torch.zeros(5, 32), scalars=torch.zeros(4), noise=None, pred_x0_out=None, unet_in=None), "eps", "extent"),
+    ]
+
+
+@pytest.mark.parametrize("case", _contract_cases(), ids=lambda c: f"{c[1]}-{c[0]}".replace(" ", "_"))
+def test_contract_violations_are_named(case):
+    rule, op, clean, bad, operand, word = case
+    assert SH.contract_violations(op, clean, None) == [], rule
+    found = SH.contract_violations(op, bad, None)
+    assert [o for o, _ in found] == [operand] and word in found[0][1], (rule, found)
+    # the device rule: host tensors handed to a kernel that reads device memory, every tensor operand named
+    on_host = SH.contract_violations(op, clean, "cuda")
+    assert on_host and all("device" in what for _, what in on_host), on_host
+
+
+def test_contract_record_fails_assert_within_bounds():
+    """What the harness does with a violation: a `contract` record with ratio inf that assert_within_bounds reports by op and operand."""
+    sh = SH.Shadow.__new__(SH.Shadow)
+    sh.records, sh.calls = [], 0
+    import inspect
+    sh.sig = {"add": inspect.signature(lambda a, b: None)}
+    x = torch.zeros(4, 64, dtype=torch.bfloat16)
+    sh._args("add", (x, x[:3].clone()), {})
+    assert [r.family for r in sh.records] == ["contract", "contract", "contract"]          # two host tensors and the short operand
+    assert all(r.ratio == math.inf for r in sh.records) and dict(sh.records[-1].plan)["operand"] == "b"
+    with pytest.raises(AssertionError, match=r"contract.*'op': 'add'.*'operand': 'b'"):
+        sh.assert_within_bounds(1)
+
+
+# ------------------------------------------------------------------------------------------------ completeness
+NETWORK_MODULES = ("cond", "lpips", "aeloss", "blocks", "unet", "ldm")
+
+
+def ops_calls(source: str):
+    """every X of an `ops.X(...)` call in `source`"""
+    import ast
+    return {n.func.attr for n in ast.walk(ast.parse(source))
+            if isinstance(n, ast.Call) and isinstance(n.func, ast.Attribute) and isinstance(n.func.value, ast.Name) and n.func.value.id == "ops"}
+
+
+def undecided(names):
+    return sorted(n for n in names if n not in SH.WRAPPED and n not in SH.EXEMPT)
+
+
+def test_every_ops_call_of_the_network_modules_is_wrapped_or_exempt():
+    import os
+    import jointimagegeneration_amd as pkg
+    from jointimagegeneration_amd import ops
+    called = set()
+    for mod in NETWORK_MODULES:
+        with open(os.path.join(os.path.dirname(pkg.__file__), mod + ".py")) as f:
+            names = ops_calls(f.read())
+        assert names, mod
+        called |= names
+    assert {"conv", "attention", "patch_conv", "lpips_tap", "vq_nearest", "bert_embed", "to_cl"} <= called       # the walk does find calls
+    assert undecided(called) == [], f"ops calls of the network modules that tests/shadow.py neither wraps nor exempts: {undecided(called)}"
+    assert not set(SH.WRAPPED) & set(SH.EXEMPT)
+    assert all(hasattr(ops, n) for n in list(SH.WRAPPED) + list(SH.EXEMPT)) and all(len(r) > 8 and "\n" not in r for r in SH.EXEMPT.values())
+    assert undecided(ops_calls("y = ops.conv(x)\nz = ops.brand_new_kernel(y, 1)\n")) == ["brand_new_kernel"]     # a new op fails by name
+    assert "to_cl" in SH.EXEMPT and undecided(called | {"to_cl_v2"}) == ["to_cl_v2"]
