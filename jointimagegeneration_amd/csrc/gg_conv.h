@@ -122,12 +122,25 @@ __device__ __forceinline__ bf16x4 gg_conv_epi_bf16(f32x4 v)
     return ob;
 }
 
-// streaming 1x1 tile kernel (gg_conv_tile.hip); same contract as gg_conv_halo_try.  gg_conv_tile_family: 0 = declines, 1 = streaming 1x1
-int gg_conv_tile_try(const ConvParams &p, hipStream_t stream);
-int gg_conv_tile_family(const ConvParams &p);
-// stride-2 3x3x3 tile kernel (gg_conv_tile.hip): the shape envelope, and the launch for a shape that plan_tile_s2 (gg_conv.hip) has vetted
+// ---- host entry points of the conv units, each declared here once; conv_walk (gg_conv.hip) asks them in gg_conv_forward's one order.
+// *_try: GG_OK where the kernel takes the conv, GG_ERR_UNSUPPORTED (silently, no error text) where it declines; launch == false plans and returns
+int gg_conv_halo_try(const ConvParams &p, hipStream_t stream, bool launch);        // halo-tile kernel (gg_conv_halo.hip)
+int gg_conv_halo3_try(const ConvParams &p, hipStream_t stream, bool launch);       // team kernel for filled 3-D grids (gg_conv_halo3.hip), asked by gg_conv_halo_try
+int gg_conv_box_try(const ConvParams &p, hipStream_t stream, bool launch);         // box-resident 2-D kernel for under-filled grids (gg_conv_box.hip)
+int gg_conv_tile_try(const ConvParams &p, hipStream_t stream, bool launch);        // streaming 1x1 tile kernel (gg_conv_tile.hip)
+bool gg_conv_halo_prefers_separate_norm(const ConvParams &p);                       // kernel-specific rules, for a conv that the kernel takes
+bool gg_conv_halo_fuses_posterior(const ConvParams &p);
+bool gg_conv_box_fuses_prologue(const ConvParams &p);
+bool gg_conv_box_emits_stats(const ConvParams &p);
+bool gg_conv_box_prologue_from_acc(const ConvParams &p);
+int gg_conv_tile_family(const ConvParams &p);                                       // 0 = declines, 1 = streaming 1x1
+// stride-2 3x3x3 tile kernel (gg_conv_tile.hip): the shape envelope, and the launch for a shape that conv_walk has vetted
 bool gg_conv_tile_s2_family(const ConvParams &p);
 int gg_conv_tile_s2_launch(const ConvParams &p, hipStream_t stream);
 // one K slab per blockIdx.z on the 256-position 3-D halo box (gg_conv_halo.hip): p.splitk slabs of whole chunks into p.ws, no epilogue
 bool gg_conv_halo_split_box_fits(const ConvParams &p);
 int gg_conv_halo_split_launch(const ConvParams &p, hipStream_t stream);
+// tiny-M weight-streaming kernel (gg_conv_tiny.hip): plan returns 0 (not applicable) or the K split
+int gg_conv_tiny_plan(long long M, int Cout_pad, int KS, int prologue_act);
+int gg_conv_tiny_launch(const ConvParams &p, hipStream_t stream);
+int gg_conv_box_spec_launch(const ConvParams &p, const struct BoxPlan &pl, hipStream_t stream);       // gg_conv_box_spec.hip, asked by gg_conv_box_try

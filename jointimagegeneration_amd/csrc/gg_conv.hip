@@ -615,19 +615,6 @@ extern "C" int gg_conv_pack_weight(const float *w, int32_t Cout, int32_t Cin, in
     return GG_OK;
 }
 
-// halo fast path (gg_conv_halo.hip); returns GG_ERR_UNSUPPORTED when the shape is outside its envelope
-int gg_conv_halo_try(const ConvParams &p, hipStream_t stream);
-bool gg_conv_halo_prefers_separate_norm(const ConvParams &p);
-#ifndef GG_HALO_SEPARATE_NORM
-#define GG_HALO_SEPARATE_NORM 1      /* A/B switch: 0 = halo-tile convs always fuse the GroupNorm prologue */
-#endif
-// box-resident 2-D path for under-filled grids (gg_conv_box.hip); same contract as gg_conv_halo_try
-int gg_conv_box_try(const ConvParams &p, hipStream_t stream);
-bool gg_conv_box_fuses_prologue(const ConvParams &p);
-// tiny-M weight-streaming path (gg_conv_tiny.hip): plan returns 0 (not applicable) or the K split
-int gg_conv_tiny_plan(long long M, int Cout_pad, int KS, int prologue_act);
-int gg_conv_tiny_launch(const ConvParams &p, hipStream_t stream);
-
 // combine + epilogue of a split-K conv.  cap_blocks: at most 2048 blocks (grid-stride loop); the tiny path launches one thread per
 // 4 couts uncapped
 static int launch_splitk_reduce(const ConvParams &p, hipStream_t stream, bool cap_blocks)
@@ -702,15 +689,21 @@ static int plan_gather5(long long M, int C1, int C2, int Cout_pad, int ntaps)
     return (int)sk;
 }
 
-extern "C" int64_t gg_conv_workspace_bytes(const gg_conv_desc *d)
+// The kernels of gg_conv_forward's ladder in conv_walk's order, and what a walk reports: the kernel, its K split (1: none), the gather kernel's cout tile
+enum ConvPath { CP_HALO, CP_BOX, CP_TILE_1X1, CP_TILE_S2, CP_HALO_SPLIT, CP_TINY, CP_GATHER5, CP_GATHER };
+struct ConvRoute { ConvPath path; int splitk, NT; };
+
+// The foot of the ladder: the tiny-M kernel, else the 160-step gather, else the gather kernel, which takes everything.  The fused GEGLU
+// epilogue is implemented in the gather kernel's single-pass (no split-K) epilogue only.
+static ConvRoute gather_family(const ConvParams &p)
 {
-    if (!d || d->epilogue_geglu) return 0;           // (the GEGLU epilogue runs on the single-pass gather kernel)
-    long long M = (long long)d->N * d->Do * d->Ho * d->Wo;
-    int KS = d->kd * d->kh * d->kw * ((d->C1 + d->C2) / 32);
-    if (int tsk = gg_conv_tiny_plan(M, d->Cout_pad, KS, d->prologue_act)) return tsk > 1 ? (int64_t)tsk * M * d->Cout_pad * 4 : 0;
-    if (int s5 = plan_gather5(M, d->C1, d->C2, d->Cout_pad, d->kd * d->kh * d->kw)) return s5 > 1 ? (int64_t)s5 * M * d->Cout_pad * 4 : 0;
-    GatherPlan pl = plan_gather(M, d->Cout_pad, KS);
-    return pl.splitk > 1 ? (int64_t)pl.splitk * M * d->Cout_pad * 4 : 0;
+    const int KS = p.ntaps * p.nchunk;
+    if (!p.epi_geglu) {
+        if (int tsk = gg_conv_tiny_plan(p.M, p.Cout_pad, KS, p.prologue_act)) return {CP_TINY, tsk, 0};
+        if (int s5 = plan_gather5(p.M, p.C1, p.C2, p.Cout_pad, p.ntaps)) return {CP_GATHER5, s5, 0};
+    }
+    const GatherPlan pl = plan_gather(p.M, p.Cout_pad, KS);
+    return {CP_GATHER, p.epi_geglu ? 1 : pl.splitk, pl.NT};
 }
 
 static void fill_params(const gg_conv_desc *d, ConvParams &p)
@@ -742,9 +735,16 @@ static void fill_params(const gg_conv_desc *d, ConvParams &p)
     p.mg_osp = gg_magic_u32(p.M, d->Do * d->Ho * d->Wo); p.mg_ohw = gg_magic_u32(p.M, d->Ho * d->Wo); p.mg_wo = gg_magic_u32(p.M, d->Wo);
 }
 
-// dry runs (stream -1): would the halo-tile / box kernel take this conv?  No HIP call is made.
-static bool halo_try_dry(const ConvParams &p) { return gg_conv_halo_try(p, (hipStream_t)-1) == GG_OK; }
-static bool box_try_dry(const ConvParams &p) { return gg_conv_box_try(p, (hipStream_t)-1) == GG_OK; }
+extern "C" int64_t gg_conv_workspace_bytes(const gg_conv_desc *d)
+{
+    if (!d) return 0;
+    ConvParams p;
+    fill_params(d, p);
+    // the gather family's K split, whichever kernel above it runs the conv: the split halo path takes that very split, the others need none
+    const int splitk = gather_family(p).splitk;
+    return splitk > 1 ? (int64_t)splitk * p.M * p.Cout_pad * 4 : 0;
+}
+
 // what every dispatch predicate asks of a descriptor before it reads anything else
 static bool desc_channels_ok(const gg_conv_desc *d) { return d && d->C1 > 0 && d->C1 % 32 == 0 && d->C2 % 32 == 0 && d->Cout_pad % 32 == 0; }
 
@@ -761,30 +761,139 @@ static int take_splitk_workspace(const gg_conv_desc *d, ConvParams &p, int split
     return GG_OK;
 }
 
-extern "C" int gg_conv_runs_halo_tile(const gg_conv_desc *d)
+// The stride-2 3x3x3 convs that the gather kernel runs in ONE pass (gf, the gather family's plan: no K split -- with a split it is no bit
+// reference for a one-pass kernel) on the tile kernel of gg_conv_tile.hip, 128 couts only.  32^3 -> 16^3 and deeper split K and stay where they are.
+// (GG_CONV_HINT_TILE_S2: tests, small shapes that are compared with fp64 only.)
+static bool plan_tile_s2(const ConvParams &p, const ConvRoute &gf)
 {
-    if (!desc_channels_ok(d) || d->epilogue_geglu) return 0;
-    ConvParams p;
-    fill_params(d, p);
-    return halo_try_dry(p) ? 1 : 0;
+    return gg_conv_tile_s2_family(p) && (p.path_hint == GG_CONV_HINT_TILE_S2 || (gf.path == CP_GATHER && gf.splitk == 1));
 }
 
+// The 3x3x3 stride-1 convs of 3-D grids too small for the halo-tile gate (CCDM 16^3 level at batch 1) ran on the split gather kernel, where every
+// workgroup gathers its activation rows again for each of the 27 taps.  The halo kernel's 256-position box stages a chunk once for all taps;
+// with the gather plan's own K split as a grid axis (whole chunks per slab: splitk | nchunk) it fills the chip as well, and because both kernels
+// walk chunk-outer / tap-inner with the same MFMA, the slabs hold the same fp32 partials and the fixed-order reduce gives the same bytes.
+// Returns the K split (that of the gather family's plan gf, so gg_conv_workspace_bytes stays what it was), 0 where the path declines.
+#ifndef GG_HALO_SPLIT
+#define GG_HALO_SPLIT 1        /* A/B switch: 0 = these shapes stay on the split gather kernel */
+#endif
+static int plan_halo_split(const ConvParams &p, const ConvRoute &gf)
+{
+    if (!GG_HALO_SPLIT || !gg_hint_is_production(p.path_hint) || p.path_hint == GG_CONV_HINT_NO_HALO_SPLIT) return 0;
+    if (p.kd != 3 || p.kh != 3 || p.kw != 3 || p.stride != 1 || p.pad != 1 || p.upsample || p.prologue_act) return 0;
+    if (p.post_xt || p.ddim_x || p.skip_C1 || !gg_conv_halo_split_box_fits(p)) return 0;
+    return (gf.path == CP_GATHER && gf.NT == 1 && gf.splitk >= 2 && p.nchunk % gf.splitk == 0) ? gf.splitk : 0;
+}
+
+#ifdef GG_EXP_WPREFETCH
+__global__ __launch_bounds__(256) void exp_wprefetch_kernel(const u32x4 *w, long long n16, unsigned *sink)
+{
+    unsigned a = 0;
+    if (n16 <= (3 << 20) / 16 * 1) {        // <= 3 MB: EVERY XCD (blockIdx & 7) reads all of it into its own L2
+        for (long long i = (long long)(blockIdx.x >> 3) * 256 + threadIdx.x; i < n16; i += 32 * 256) { const u32x4 v = w[i]; a ^= v[0] ^ v[1] ^ v[2] ^ v[3]; }
+    } else
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n16; i += 256 * 256) { const u32x4 v = w[i]; a ^= v[0] ^ v[1] ^ v[2] ^ v[3]; }
+    if (a == 0x12345679u) sink[0] = a;      // practically never
+}
+#endif
+// THE statement of which kernel runs a convolution: the rungs in their order, each asked once; the first that takes the conv is reported in
+// *route and, with launch, launched (split-K workspace and reduce included).  Without launch GG_OK comes back and no HIP call is made (but for the
+// team kernel's CU count under GG_HALO_HINT_TEAM): so the dispatch predicates below ask, and a rung's place here is all that says which rungs it yields to.
+static int conv_walk(const gg_conv_desc *d, ConvParams &p, hipStream_t stream, bool launch, ConvRoute *route)
+{
+    int rc = GG_OK;
+    const ConvRoute gf = gather_family(p);
+    // a *_try rung ends the walk where its kernel takes the conv or, launching, fails
+    auto ends = [&](ConvPath path) { *route = {path, 1, 0}; return rc == GG_OK || (launch && rc != GG_ERR_UNSUPPORTED); };
+    if (!p.epi_geglu) {
+#ifdef GG_EXP_WPREFETCH
+        // experiment (tools/experiments/README.md, "warm weights"): every conv preceded by a launch that reads its packed weights with the whole
+        // chip, so that the conv finds them in L2 / the memory-side cache -- bounds what a CONCURRENT weight prefetcher could buy
+        if (launch) {
+            const long long wbytes = (long long)(p.Cout_pad / 32) * p.ntaps * p.nchunk * 2048;
+            hipLaunchKernelGGL(exp_wprefetch_kernel, dim3(256), dim3(256), 0, stream, (const u32x4 *)p.weight, wbytes >> 4, (unsigned *)d->out);
+        }
+#endif
+#ifdef GG_H3_STAMPS
+        if (d->path_hint == GG_HALO_HINT_TEAM && d->workspace) p.ws = (float *)d->workspace;      // diagnostic build: phase stamps of the team halo kernel
+#endif
+        rc = gg_conv_halo_try(p, stream, launch);
+#ifdef GG_H3_STAMPS
+        p.ws = nullptr;
+#endif
+        if (ends(CP_HALO)) return rc;
+        // the fused CCDM reverse step exists on the halo-tile kernel only: the kernels below would ignore post_xt and leave the labels stale
+        if (launch && d->post_xt) GG_FAIL(GG_ERR_UNSUPPORTED, "conv: the halo-tile kernel did not take this shape, and no other kernel runs the fused CCDM reverse step");
+#ifdef GG_BOX_STAMPS
+        if (d->path_hint == 98) p.ws = (float *)d->workspace;      // diagnostic build: phase stamps of the box kernel
+#endif
+        rc = gg_conv_box_try(p, stream, launch);
+#ifdef GG_BOX_STAMPS
+        p.ws = nullptr;
+#endif
+        if (ends(CP_BOX)) return rc;
+        // streaming 1x1 on big grids (gg_conv_tile.hip): byte-identical to the gather kernel, which takes whatever it declines
+        rc = gg_conv_tile_try(p, stream, launch);
+        if (ends(CP_TILE_1X1)) return rc;
+        // stride-2 3x3x3 on big grids: byte-identical to the one-pass gather kernel
+        *route = {CP_TILE_S2, 1, 0};
+        if (plan_tile_s2(p, gf)) return launch ? gg_conv_tile_s2_launch(p, stream) : GG_OK;
+        // K split as a grid axis of the halo-tile kernel: byte-identical to the split gather kernel, which takes whatever this declines
+        if (const int hs = plan_halo_split(p, gf)) {
+            *route = {CP_HALO_SPLIT, hs, 1};
+            if (!launch) return GG_OK;
+            if ((rc = take_splitk_workspace(d, p, hs)) != GG_OK) return rc;
+            if ((rc = gg_conv_halo_split_launch(p, stream)) != GG_OK) return rc;
+            return launch_splitk_reduce(p, stream, true);
+        }
+    }
+    *route = gf;
+    if (!launch) return GG_OK;
+    if ((rc = take_splitk_workspace(d, p, gf.splitk)) != GG_OK) return rc;
+    if (gf.path == CP_TINY)
+        return ((rc = gg_conv_tiny_launch(p, stream)) != GG_OK || gf.splitk == 1) ? rc : launch_splitk_reduce(p, stream, false);
+    if (gf.path == CP_GATHER5) {
+        dim3 grid((unsigned)((p.M + 63) / 64), (unsigned)(p.Cout_pad / 32), (unsigned)gf.splitk);
+        if (p.prologue_act && (((long long)p.Do * p.Ho * p.Wo) % 64 || p.C1 + p.C2 > 2560))
+            GG_FAIL(GG_ERR_UNSUPPORTED, "conv: fused prologue on the 160-step kernel needs Do*Ho*Wo %% 64 == 0 and C <= 2560");
+        if (p.prologue_act) hipLaunchKernelGGL(conv_gather5_kernel<1>, grid, dim3(256), 0, stream, p);
+        else hipLaunchKernelGGL(conv_gather5_kernel<0>, grid, dim3(256), 0, stream, p);
+        GG_CHECK_LAUNCH();
+        return gf.splitk > 1 ? launch_splitk_reduce(p, stream, true) : GG_OK;
+    }
+    return launch_gather_nt(gf.NT, p, stream);
+}
+
+// the route of a descriptor (p: its parameters, filled in here): a walk that launches nothing
+static ConvRoute route_of(const gg_conv_desc *d, ConvParams &p)
+{
+    ConvRoute r;
+    fill_params(d, p);
+    conv_walk(d, p, nullptr, false, &r);
+    return r;
+}
+static ConvRoute route_of(const gg_conv_desc *d) { ConvParams p; return route_of(d, p); }
+
+extern "C" int gg_conv_runs_halo_tile(const gg_conv_desc *d)
+{
+    return desc_channels_ok(d) && !d->epilogue_geglu && route_of(d).path == CP_HALO;
+}
+
+#ifndef GG_HALO_SEPARATE_NORM
+#define GG_HALO_SEPARATE_NORM 1      /* A/B switch: 0 = halo-tile convs always fuse the GroupNorm prologue */
+#endif
 extern "C" int gg_conv_fuses_prologue(const gg_conv_desc *d)
 {
     if (!desc_channels_ok(d) || d->epilogue_geglu) return 0;
     ConvParams p;
-    fill_params(d, p);
+    const ConvPath path = route_of(d, p).path;
     // halo-tile convs CAN always fuse it; the answer is whether they should (measured rule in gg_conv_halo.hip)
-    if (halo_try_dry(p)) return (GG_HALO_SEPARATE_NORM && gg_hint_is_production(d->path_hint) && gg_conv_halo_prefers_separate_norm(p)) ? 0 : 1;
-    if (box_try_dry(p)) return gg_conv_box_fuses_prologue(p) ? 1 : 0;
+    if (path == CP_HALO) return (GG_HALO_SEPARATE_NORM && gg_hint_is_production(d->path_hint) && gg_conv_halo_prefers_separate_norm(p)) ? 0 : 1;
+    if (path == CP_BOX) return gg_conv_box_fuses_prologue(p) ? 1 : 0;
     // GroupNorm*SiLU inside the 160-step gather loop was measured slower (26 vs 16.6 us per conv: SiLU on the load -> LDS critical
     // path once per tap), so the gather kernels never fuse the prologue
     return 0;
 }
-
-bool gg_conv_box_emits_stats(const ConvParams &p);
-bool gg_conv_box_prologue_from_acc(const ConvParams &p);
-bool gg_conv_halo_fuses_posterior(const ConvParams &p);
 
 extern "C" int gg_conv_fuses_posterior(const gg_conv_desc *d)
 {
@@ -802,9 +911,7 @@ extern "C" int gg_conv_prologue_from_acc(const gg_conv_desc *d)
     // logical one (pro_c_logical >= C1 says exactly that: padding lanes may only sit at the end of the second source)
     if (d->pro_c_logical <= 0 || d->pro_c_logical % 32 || d->pro_c_logical > d->C1 + d->C2 || (d->C2 && d->pro_c_logical < d->C1)) return 0;
     ConvParams p;
-    fill_params(d, p);
-    if (halo_try_dry(p)) return 0;
-    return box_try_dry(p) && gg_conv_box_prologue_from_acc(p) ? 1 : 0;
+    return route_of(d, p).path == CP_BOX && gg_conv_box_prologue_from_acc(p) ? 1 : 0;
 }
 
 // K-concatenated 1x1 skip projection: box kernel only (3x3, stride 1, no upsample: plan_box checks).
@@ -813,104 +920,52 @@ extern "C" int gg_conv_fuses_skip(const gg_conv_desc *d)
     if (!desc_channels_ok(d) || d->epilogue_geglu || d->skip_C1 <= 0 || d->skip_C1 % 32 || d->skip_C2 % 32 ||
         d->skip_C2 < 0 || d->residual || d->ddim_x)
         return 0;
-    ConvParams p;
-    fill_params(d, p);
-    if (halo_try_dry(p)) return 0;
-    return box_try_dry(p) ? 1 : 0;
+    return route_of(d).path == CP_BOX;
 }
 
 // The fused DDIM epilogue lives in the box kernel's epilogue (the latent UNet's head conv at batch 1..4 runs there).
 extern "C" int gg_conv_fuses_ddim(const gg_conv_desc *d)
 {
     if (!desc_channels_ok(d) || d->out_dtype != GG_F32 || d->Cout != 4 || d->residual) return 0;
-    ConvParams p;
-    fill_params(d, p);
-    if (halo_try_dry(p)) return 0;
-    return box_try_dry(p) ? 1 : 0;
+    gg_conv_desc shape = *d;
+    shape.epilogue_geglu = 0;          // (this answer never read it; gg_conv_forward refuses GEGLU with ddim_x itself)
+    return route_of(&shape).path == CP_BOX;
 }
 
-
-// Which path a desc takes is decided by the same plan functions gg_conv_forward uses.
 extern "C" int gg_conv_emits_stats(const gg_conv_desc *d)
 {
     if (!desc_channels_ok(d) || d->out_dtype != GG_BF16 || d->epilogue_geglu) return 0;
     ConvParams p;
-    fill_params(d, p);
-    if (halo_try_dry(p)) return GG_ACC_STRIPES_HALO;
-    if (box_try_dry(p)) return gg_conv_box_emits_stats(p) ? GG_ACC_STRIPES : 0;
-    if (gg_conv_tiny_plan(p.M, p.Cout_pad, p.ntaps * p.nchunk, p.prologue_act)) return 0;
-    const long long osp = (long long)d->Do * d->Ho * d->Wo;
-    return (plan_gather5(p.M, p.C1, p.C2, p.Cout_pad, p.ntaps) == 1 && osp % 64 == 0) ? GG_ACC_STRIPES : 0;
+    const ConvPath path = route_of(d, p).path;
+    if (path == CP_HALO) return GG_ACC_STRIPES_HALO;
+    if (path == CP_BOX) return gg_conv_box_emits_stats(p) ? GG_ACC_STRIPES : 0;
+    // below the box kernel only the one-pass 160-step gather emits them.  The gather family is asked, not the route: the rungs between take
+    // nothing of 160-channel steps, except the stride-2 tile kernel under its tests-only hint, where this keeps the answer it had
+    const ConvRoute gf = gather_family(p);
+    return (gf.path == CP_GATHER5 && gf.splitk == 1 && ((long long)d->Do * d->Ho * d->Wo) % 64 == 0) ? GG_ACC_STRIPES : 0;
 }
 
 // 0: gg_conv_forward does not run this descriptor on a tile kernel (gg_conv_tile.hip); 1: the streaming 1x1 kernel.
 extern "C" int gg_conv_runs_tile(const gg_conv_desc *d)
 {
     if (!desc_channels_ok(d) || d->epilogue_geglu || d->skip_C1 || d->ddim_x || d->post_xt) return 0;
-    ConvParams p;
-    fill_params(d, p);
-    if (halo_try_dry(p) || box_try_dry(p)) return 0;
-    return gg_conv_tile_family(p);
-}
-
-// The 3x3x3 stride-1 convs of 3-D grids too small for the halo-tile gate (CCDM 16^3 level at batch 1) ran on the split gather kernel, where every
-// workgroup gathers its activation rows again for each of the 27 taps.  The halo kernel's 256-position box stages a chunk once for all taps;
-// with the gather plan's own K split as a grid axis (whole chunks per slab: splitk | nchunk) it fills the chip as well, and because both kernels
-// walk chunk-outer / tap-inner with the same MFMA, the slabs hold the same fp32 partials and the fixed-order reduce gives the same bytes.
-// Returns the K split (that of plan_gather, so gg_conv_workspace_bytes stays what it was), 0 where the path declines.
-#ifndef GG_HALO_SPLIT
-#define GG_HALO_SPLIT 1        /* A/B switch: 0 = these shapes stay on the split gather kernel */
-#endif
-static int plan_halo_split(const gg_conv_desc *d, const ConvParams &p)
-{
-    if (!GG_HALO_SPLIT || !gg_hint_is_production(p.path_hint) || p.path_hint == GG_CONV_HINT_NO_HALO_SPLIT) return 0;
-    if (p.kd != 3 || p.kh != 3 || p.kw != 3 || p.stride != 1 || p.pad != 1 || p.upsample || p.prologue_act) return 0;
-    if (d->epilogue_geglu || d->post_xt || d->ddim_x || d->skip_C1) return 0;
-    if (halo_try_dry(p) || box_try_dry(p) || !gg_conv_halo_split_box_fits(p)) return 0;
-    if (gg_conv_tiny_plan(p.M, p.Cout_pad, p.ntaps * p.nchunk, p.prologue_act) || plan_gather5(p.M, p.C1, p.C2, p.Cout_pad, p.ntaps)) return 0;
-    const GatherPlan pl = plan_gather(p.M, p.Cout_pad, p.ntaps * p.nchunk);
-    return (pl.NT == 1 && pl.splitk >= 2 && p.nchunk % pl.splitk == 0) ? pl.splitk : 0;
+    return route_of(d).path == CP_TILE_1X1;
 }
 
 // 0: gg_conv_forward does not run this descriptor on the split halo path; else its number of K slabs (= workspace bytes / (M * Cout_pad * 4)).
 extern "C" int gg_conv_runs_halo_split(const gg_conv_desc *d)
 {
     if (!desc_channels_ok(d)) return 0;
-    ConvParams p;
-    fill_params(d, p);
-    return plan_halo_split(d, p);
-}
-
-// The stride-2 3x3x3 convs that the gather kernel runs in ONE pass (plan_gather: no K split -- with a split it is no bit reference for a
-// one-pass kernel) on the tile kernel of gg_conv_tile.hip, 128 couts only.  32^3 -> 16^3 and deeper split K and stay where they are.
-static bool plan_tile_s2(const gg_conv_desc *d, const ConvParams &p)
-{
-    if (!gg_conv_tile_s2_family(p) || halo_try_dry(p) || box_try_dry(p)) return false;
-    if (p.path_hint == GG_CONV_HINT_TILE_S2) return true;          // tests: small shapes, compared with fp64 only
-    if (gg_conv_tiny_plan(p.M, p.Cout_pad, p.ntaps * p.nchunk, p.prologue_act) || plan_gather5(p.M, p.C1, p.C2, p.Cout_pad, p.ntaps)) return false;
-    return plan_gather(p.M, p.Cout_pad, p.ntaps * p.nchunk).splitk == 1;
+    const ConvRoute r = route_of(d);
+    return r.path == CP_HALO_SPLIT ? r.splitk : 0;
 }
 
 // 1 if gg_conv_forward runs this descriptor on the stride-2 tile kernel, else 0.
 extern "C" int gg_conv_runs_tile_s2(const gg_conv_desc *d)
 {
-    if (!desc_channels_ok(d)) return 0;
-    ConvParams p;
-    fill_params(d, p);
-    return plan_tile_s2(d, p) ? 1 : 0;
+    return desc_channels_ok(d) && route_of(d).path == CP_TILE_S2;
 }
 
-#ifdef GG_EXP_WPREFETCH
-__global__ __launch_bounds__(256) void exp_wprefetch_kernel(const u32x4 *w, long long n16, unsigned *sink)
-{
-    unsigned a = 0;
-    if (n16 <= (3 << 20) / 16 * 1) {        // <= 3 MB: EVERY XCD (blockIdx & 7) reads all of it into its own L2
-        for (long long i = (long long)(blockIdx.x >> 3) * 256 + threadIdx.x; i < n16; i += 32 * 256) { const u32x4 v = w[i]; a ^= v[0] ^ v[1] ^ v[2] ^ v[3]; }
-    } else
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n16; i += 256 * 256) { const u32x4 v = w[i]; a ^= v[0] ^ v[1] ^ v[2] ^ v[3]; }
-    if (a == 0x12345679u) sink[0] = a;      // practically never
-}
-#endif
 extern "C" int gg_conv_forward(const gg_conv_desc *d, void *stream_)
 {
     hipStream_t stream = (hipStream_t)stream_;
@@ -961,73 +1016,10 @@ extern "C" int gg_conv_forward(const gg_conv_desc *d, void *stream_)
     if (p.M >= (1LL << 31) || (long long)d->D * d->H * d->W * (d->C1 > d->C2 ? d->C1 : d->C2) >= (1LL << 31))
         GG_FAIL(GG_ERR_UNSUPPORTED, "conv: tensor too large for 32-bit in-sample offsets");
 
-    if (d->epilogue_geglu) {
-        // fused GEGLU epilogue: implemented in the generic gather kernel's single-pass (no split-K) epilogue only
-        if (d->kd != 1 || d->kh != 1 || d->kw != 1 || d->stride != 1 || d->upsample || d->residual || d->out_dtype != GG_BF16 || d->gn_acc ||
-            d->ddim_x || d->Cout % 32 || d->bias_stride)
-            GG_FAIL(GG_ERR_UNSUPPORTED, "conv: the GEGLU epilogue needs a 1x1 conv, bf16 output, Cout = 2*inner with inner %% 16 == 0, a shared bias, no residual / gn_acc / ddim");
-        return launch_gather_nt(plan_gather(p.M, p.Cout_pad, p.ntaps * p.nchunk).NT, p, stream);
-    }
-#ifdef GG_EXP_WPREFETCH
-    // experiment (tools/experiments/README.md, "warm weights"): every conv preceded by a launch that reads its packed weights with the whole
-    // chip, so that the conv finds them in L2 / the memory-side cache -- bounds what a CONCURRENT weight prefetcher could buy
-    {
-        const long long wbytes = (long long)(p.Cout_pad / 32) * p.ntaps * p.nchunk * 2048;
-        hipLaunchKernelGGL(exp_wprefetch_kernel, dim3(256), dim3(256), 0, stream, (const u32x4 *)p.weight, wbytes >> 4, (unsigned *)d->out);
-    }
-#endif
-#ifdef GG_H3_STAMPS
-    if (d->path_hint == GG_HALO_HINT_TEAM && d->workspace) p.ws = (float *)d->workspace;      // diagnostic build: phase stamps of the team halo kernel
-#endif
-    int rc = gg_conv_halo_try(p, stream);
-#ifdef GG_H3_STAMPS
-    p.ws = nullptr;
-#endif
-    if (rc != GG_ERR_UNSUPPORTED) return rc;
-    // the fused CCDM reverse step exists on the halo-tile kernel only: the kernels below would ignore post_xt and leave the labels stale
-    if (d->post_xt) GG_FAIL(GG_ERR_UNSUPPORTED, "conv: the halo-tile kernel did not take this shape, and no other kernel runs the fused CCDM reverse step");
-#ifdef GG_BOX_STAMPS
-    if (d->path_hint == 98) p.ws = (float *)d->workspace;      // diagnostic build: phase stamps of the box kernel
-#endif
-    rc = gg_conv_box_try(p, stream);
-#ifdef GG_BOX_STAMPS
-    p.ws = nullptr;
-#endif
-    if (rc != GG_ERR_UNSUPPORTED) return rc;
-
-    // streaming 1x1 on big grids (gg_conv_tile.hip): byte-identical to the gather kernel, which takes whatever it declines
-    rc = gg_conv_tile_try(p, stream);
-    if (rc != GG_ERR_UNSUPPORTED) return rc;
-
-    // stride-2 3x3x3 on big grids: byte-identical to the one-pass gather kernel
-    if (plan_tile_s2(d, p)) return gg_conv_tile_s2_launch(p, stream);
-
-    // K split as a grid axis of the halo-tile kernel: byte-identical to the split gather kernel, which takes whatever this declines
-    if (int hs = plan_halo_split(d, p)) {
-        if ((rc = take_splitk_workspace(d, p, hs)) != GG_OK) return rc;
-        if ((rc = gg_conv_halo_split_launch(p, stream)) != GG_OK) return rc;
-        return launch_splitk_reduce(p, stream, true);
-    }
-
-    if (int tsk = gg_conv_tiny_plan(p.M, p.Cout_pad, p.ntaps * p.nchunk, p.prologue_act)) {
-        if ((rc = take_splitk_workspace(d, p, tsk)) != GG_OK) return rc;
-        rc = gg_conv_tiny_launch(p, stream);
-        if (rc != GG_OK || tsk == 1) return rc;
-        return launch_splitk_reduce(p, stream, false);
-    }
-
-    if (int s5 = plan_gather5(p.M, p.C1, p.C2, p.Cout_pad, p.ntaps)) {
-        if ((rc = take_splitk_workspace(d, p, s5)) != GG_OK) return rc;
-        dim3 grid((unsigned)((p.M + 63) / 64), (unsigned)(p.Cout_pad / 32), (unsigned)s5);
-        if (p.prologue_act && (((long long)p.Do * p.Ho * p.Wo) % 64 || p.C1 + p.C2 > 2560))
-            GG_FAIL(GG_ERR_UNSUPPORTED, "conv: fused prologue on the 160-step kernel needs Do*Ho*Wo %% 64 == 0 and C <= 2560");
-        if (p.prologue_act) hipLaunchKernelGGL(conv_gather5_kernel<1>, grid, dim3(256), 0, stream, p);
-        else hipLaunchKernelGGL(conv_gather5_kernel<0>, grid, dim3(256), 0, stream, p);
-        GG_CHECK_LAUNCH();
-        return s5 > 1 ? launch_splitk_reduce(p, stream, true) : GG_OK;
-    }
-
-    GatherPlan pl = plan_gather(p.M, p.Cout_pad, p.ntaps * p.nchunk);
-    if ((rc = take_splitk_workspace(d, p, pl.splitk)) != GG_OK) return rc;
-    return launch_gather_nt(pl.NT, p, stream);
+    // fused GEGLU epilogue: implemented in the generic gather kernel's single-pass (no split-K) epilogue only
+    if (d->epilogue_geglu && (d->kd != 1 || d->kh != 1 || d->kw != 1 || d->stride != 1 || d->upsample || d->residual || d->out_dtype != GG_BF16 || d->gn_acc ||
+                              d->ddim_x || d->Cout % 32 || d->bias_stride))
+        GG_FAIL(GG_ERR_UNSUPPORTED, "conv: the GEGLU epilogue needs a 1x1 conv, bf16 output, Cout = 2*inner with inner %% 16 == 0, a shared bias, no residual / gn_acc / ddim");
+    ConvRoute route;
+    return conv_walk(d, p, stream, true, &route);
 }

@@ -165,14 +165,12 @@ bool gg_conv_box_prologue_from_acc(const ConvParams &p)
     return p.Cout_pad / (16 * pl.CT) <= 2 || rows * (p.C1 + p.C2) <= silu_max_elems;
 }
 
-int gg_conv_box_spec_launch(const ConvParams &p, const BoxPlan &pl, hipStream_t stream);
-
-// Returns GG_ERR_UNSUPPORTED (silently) when the shape is outside the envelope.  stream == (hipStream_t)-1: dry run.
-int gg_conv_box_try(const ConvParams &p, hipStream_t stream)
+// the box rung of conv_walk (contract: gg_conv.h)
+int gg_conv_box_try(const ConvParams &p, hipStream_t stream, bool launch)
 {
     BoxPlan pl;
     if (!plan_box(p, pl)) return GG_ERR_UNSUPPORTED;
-    if (stream == (hipStream_t)-1) return GG_OK;
+    if (!launch) return GG_OK;
     const int rs = gg_conv_box_spec_launch(p, pl, stream);     // a batch-1 latent-UNet layer listed in gg_conv_box_specs.inc
     if (rs != GG_ERR_UNSUPPORTED) return rs;
     if (p.skip_C1 > 0) return pl.CT == 2 ? dispatch_box<2, 0, 1, 1>(p, pl, stream) : dispatch_box<1, 0, 1, 1>(p, pl, stream);     // (plan_box: 3x3, no upsample)

@@ -576,9 +576,6 @@ static int halo_dispatch(const ConvParams &p, const HaloPlan &pl, hipStream_t st
 #undef GG_HALO_CASE
 }
 
-// team kernel for filled 3-D grids (gg_conv_halo3.hip); same contract
-int gg_conv_halo3_try(const ConvParams &p, hipStream_t stream);
-
 // widest cout tile (fewest re-stagings of the box) that still gives >= 256 workgroups; else the widest with >= 128.
 // 3-D: 27 taps per staged box, so filling the chip comes first (>= 256 workgroups, else >= 128).  2-D: only 9 taps per staged
 // box, staging dominates, so the widest cout tile that still gives 128 workgroups wins (AE 512->512 @128x128: NT 4 x 128
@@ -674,9 +671,8 @@ int gg_conv_halo_split_launch(const ConvParams &p, hipStream_t stream)
     return launch_halo<1, 1, 0, 1, 2>(p, pl, stream);
 }
 
-// Returns GG_ERR_UNSUPPORTED (silently, no error text) when the shape is outside the envelope: the caller then uses the
-// generic gather kernel.  stream == (hipStream_t)-1: dry run (only answers whether the halo kernel would be used).
-int gg_conv_halo_try(const ConvParams &p, hipStream_t stream)
+// The halo-tile rung of conv_walk (contract: gg_conv.h); the team kernel is asked from here.
+int gg_conv_halo_try(const ConvParams &p, hipStream_t stream, bool launch)
 {
     const HaloPlan pl = halo_plan(p);
     if (!pl.family) return GG_ERR_UNSUPPORTED;
@@ -685,10 +681,10 @@ int gg_conv_halo_try(const ConvParams &p, hipStream_t stream)
 #define GG_HALO3_DEFAULT 0
 #endif
     if (pl.d3 && !p.post_xt && ((GG_HALO3_DEFAULT && p.path_hint == 0) || p.path_hint == GG_HALO_HINT_TEAM)) {
-        const int rc3 = gg_conv_halo3_try(p, stream);
+        const int rc3 = gg_conv_halo3_try(p, stream, launch);
         if (rc3 != GG_ERR_UNSUPPORTED) return rc3;
     }
     if (!pl.ok) return GG_ERR_UNSUPPORTED;
-    if (stream == (hipStream_t)-1) return GG_OK;
+    if (!launch) return GG_OK;
     return halo_dispatch(p, pl, stream);
 }

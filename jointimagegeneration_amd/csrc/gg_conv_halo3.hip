@@ -486,8 +486,7 @@ __global__ __launch_bounds__(512, 2) void conv_halo3_team_kernel(const ConvParam
     if (team == 0) { dummy_phase(); pphase(1, 0, 0, false); }
 }
 
-// Returns GG_ERR_UNSUPPORTED (silently) outside the envelope; stream == (hipStream_t)-1: dry run.
-int gg_conv_halo3_try(const ConvParams &p, hipStream_t stream)
+int gg_conv_halo3_try(const ConvParams &p, hipStream_t stream, bool launch)
 {
     if (!(p.kd == 3 && p.kh == 3 && p.kw == 3) || p.stride != 1 || p.pad != 1 || p.upsample) return GG_ERR_UNSUPPORTED;
     if (p.out_dtype != GG_BF16 || (p.Cout_pad % 64) || (p.Do % 8) || (p.Ho % 8) || (p.Wo % 16)) return GG_ERR_UNSUPPORTED;
@@ -499,7 +498,7 @@ int gg_conv_halo3_try(const ConvParams &p, hipStream_t stream)
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return GG_ERR_HIP;
     // persistent: one workgroup per CU; under-filled grids (fewer items than ~3/4 of the CUs) stay on the 256-position boxes of conv_halo_kernel
     if (p.path_hint != GG_HALO_HINT_TEAM && items < (long long)cus * 3 / 4) return GG_ERR_UNSUPPORTED;
-    if (stream == (hipStream_t)-1) return GG_OK;
+    if (!launch) return GG_OK;
     static std::atomic<unsigned long long> attr_mask{0};
     const unsigned long long dev_bit = 1ull << (dev & 63);
     if (!(attr_mask.load(std::memory_order_acquire) & dev_bit)) {

@@ -226,10 +226,10 @@ static int launch_tile1x1(const ConvParams &p, hipStream_t stream)
     return GG_OK;
 }
 
-int gg_conv_tile_try(const ConvParams &p, hipStream_t stream)
+int gg_conv_tile_try(const ConvParams &p, hipStream_t stream, bool launch)
 {
     if (gg_conv_tile_family(p) != 1) return GG_ERR_UNSUPPORTED;
-    if (stream == (hipStream_t)-1) return GG_OK;
+    if (!launch) return GG_OK;
     const int CT = p.Cout_pad / 16;
     if (CT == 4 && p.nchunk == 4) return launch_tile1x1<4, 4>(p, stream);
     if (CT == 4 && p.nchunk == 6) return launch_tile1x1<4, 6>(p, stream);
