@@ -166,6 +166,50 @@ def norm_conv(h: CL, norm: nn.GroupNorm, act: bool, weight, bias, cout, src2: Op
     return ops.conv(a, weight, bias, cout, **conv_kw)
 
 
+def conv_of(mod, h: CL, *, src2: Optional[CL] = None, bias: Optional[torch.Tensor] = None, tag: str = "", norm=None, **conv_kw) -> CL:
+    """conv(cat[h, src2]) with the weights of the conv / linear container `mod`, the one statement of "run this container as a conv":
+    packed for the inputs' padded width (packed_conv's cache keys; a list of containers is fused along Cout under `tag` as packed_cat
+    does, geglu=True packs as packed_geglu does), cout and the kernel extent read from the weight, pad = k // 2 unless given; every
+    other keyword goes to ops.conv.  bias= replaces the packed bias (a per-sample time bias, conv2's bias + the skip's).
+    norm=(GroupNorm container, act): conv(act(GroupNorm(cat[h, src2]))) through norm_conv, which also takes film=."""
+    cin_pad = h.Cpad + (src2.Cpad if src2 is not None else 0)
+    if isinstance(mod, (list, tuple)):
+        (pw, pb), weights = packed_cat(list(mod), cin_pad, tag), [m.weight for m in mod]
+    else:
+        (pw, pb), weights = (packed_geglu(mod, cin_pad) if conv_kw.get("geglu") else packed_conv(mod, cin_pad, tag)), [mod.weight]
+    k = _k3(weights[0])
+    conv_kw.setdefault("pad", k[-1] // 2)
+    args = (pw, pb if bias is None else bias, sum(w.shape[0] for w in weights))
+    if norm is not None:
+        return norm_conv(h, *norm, *args, src2=src2, k=k, **conv_kw)
+    return ops.conv(h, *args, src2=src2, k=k, **conv_kw)
+
+
+def qkv_attention(qkv: CL, heads: int, head_dim: int, scale: float, *, legacy: bool = False, kv_len: Optional[torch.Tensor] = None,
+                  dtype=torch.bfloat16) -> CL:
+    """Self-attention over fused q|k|v rows (the output of one 1x1 projection): softmax(scale q k^T) v per head, as an unpadded CL of
+    heads * head_dim channels at qkv's positions.  Blocked order: q | k | v blocks of all heads' channels, heads of head_dim inside each
+    block; legacy order: head-major, q | k | v per head.  kv_len: per-sample key lengths (ops.attention).  dtype: the output buffer's."""
+    inner = heads * head_dim
+    att = torch.empty(tuple(qkv.t.shape[:4]) + (inner,), dtype=dtype, device=qkv.t.device)
+    ld_hs, step = ((qkv.Cpad, 3 * head_dim), head_dim) if legacy else ((qkv.Cpad, head_dim), inner)
+    ops.attention(qkv.t, qkv.t, qkv.t, att, qkv.N, heads, head_dim, qkv.S, qkv.S, ld_hs, ld_hs, ld_hs, (inner, head_dim), scale,
+                  q_off=0, k_off=step, v_off=2 * step, **({} if kv_len is None else {"kv_len": kv_len}))
+    return CL(att, inner)
+
+
+def layernorm_cl(x: CL, ln: nn.LayerNorm) -> CL:
+    """LayerNorm over the logical channels of token rows: whole rows on gg_layernorm, padded rows on gg_layernorm_rows."""
+    if x.C == x.Cpad:
+        return CL(ops.layernorm(x.t, f32(ln.weight), f32(ln.bias), ln.eps), x.C)
+    return ops.layernorm_rows(x, f32(ln.weight), f32(ln.bias), ln.eps)
+
+
+def token_rows_f32(x: CL) -> torch.Tensor:
+    """Plumbing: the logical lanes of bf16 token rows CL [B, 1, 1, T, Cpad] as fp32 [B, T, C]."""
+    return x.t[:, 0, 0, :, :x.C].float()
+
+
 class TimestepBlock(nn.Module):
     pass
 
@@ -189,8 +233,7 @@ class Upsample(nn.Module):
     def run(self, h: CL) -> CL:
         if not self.use_conv:                # nearest x2 (D too for dims == 3, unet.py:104-110): the resample kernel
             return ops.resample2x(h, True, self.dims == 3)
-        pw, pb = packed_conv(self.conv, h.Cpad)
-        return ops.conv(h, pw, pb, self.out_channels, k=_k3(self.conv.weight), stride=1, pad=1, upsample=True)
+        return conv_of(self.conv, h, upsample=True)
 
 
 class Downsample(nn.Module):
@@ -206,12 +249,11 @@ class Downsample(nn.Module):
     def run(self, h: CL) -> CL:
         if not self.use_conv:                # 2x average pool (stride (2, 2, 2) for dims == 3): the resample kernel, no GroupNorm sums
             return ops.resample2x(h, False, self.dims == 3)
-        pw, pb = packed_conv(self.op, h.Cpad)
         # the output is a skip tensor: a decoder GroupNorm over cat[h, skip] takes its statistics from accumulators only if BOTH sources
         # carry them, so leave the sums behind also below ops.GN_ACC_MIN_ELEMS (the 16x16 x 320 tensor of the latent UNet: otherwise
         # that norm falls back to a statistics launch + an apply launch)
         small = (h.S // (4 if self.dims == 2 else 8)) * pad32(self.out_channels) >= (1 << 16)
-        return ops.conv(h, pw, pb, self.out_channels, k=_k3(self.op.weight), stride=2, pad=1, want_stats=small)
+        return conv_of(self.op, h, stride=2, want_stats=small)
 
 
 class ResBlock(TimestepBlock):
@@ -265,40 +307,29 @@ class ResBlock(TimestepBlock):
         qkv conv, or a tiny-image ResBlock): conv2 leaves them even for tensors below ops.GN_ACC_MIN_ELEMS."""
         if self.use_scale_shift_norm or self.updown:
             return self._run_options(h, tbias, src2, want_stats)
-        c1, c2 = self.in_layers[2], self.out_layers[3]
-        k = _k3(c1.weight)
-        cin_pad = h.Cpad + (src2.Cpad if src2 is not None else 0)
+        c1, c2, sk = self.in_layers[2], self.out_layers[3], self.skip_connection
         # (running the 1x1 skip projection on a side stream beside the GN -> conv1 -> GN chain was measured slower: the fork / join
         # edges in the hipGraph cost more than the overlap saves, 3.03 vs 2.69 ms per latent-UNet forward)
-        res, skip_kw = h, {}
-        pw1, _ = packed_conv(c1, cin_pad)
-        pw2, pb2 = packed_conv(c2, pad32(self.out_channels))
-        sk = self.skip_connection
+        res, kw2 = h, {}
         if not isinstance(sk, nn.Identity):
-            pws, pbs = packed_conv(sk, cin_pad)
-            ks = _k3(sk.weight)
             h1_shape = CL(h.t[..., :1].expand(*h.t.shape[:4], pad32(self.out_channels)), self.out_channels)     # shape carrier for the query (no data read)
-            if ks == (1, 1, 1) and ops.conv_fuses_skip(h1_shape, self.out_channels, h, src2, k=k):
+            if _k3(sk.weight) == (1, 1, 1) and ops.conv_fuses_skip(h1_shape, self.out_channels, h, src2, k=_k3(c1.weight)):
                 # 1x1 skip projection K-concatenated into conv2 (gg_conv_desc.skip_src1): no skip launch, no residual round trip
-                pb_c2 = pb2
-                pb2 = PACKED.get((id(self), "b2s"), [c2.bias, sk.bias], lambda: pb_c2 + pbs)          # conv2 bias + skip bias
-                res, skip_kw = None, {"skip": (h, src2, pws)}
+                pws, pbs = packed_conv(sk, h.Cpad + (src2.Cpad if src2 is not None else 0))
+                pb2 = packed_conv(c2, pad32(self.out_channels))[1]
+                b2s = PACKED.get((id(self), "b2s"), [c2.bias, sk.bias], lambda: pb2 + pbs)            # conv2 bias + skip bias
+                res, kw2 = None, {"skip": (h, src2, pws), "bias": b2s}
             else:
-                res = ops.conv(h, pws, pbs, self.out_channels, k=ks, pad=ks[-1] // 2, src2=src2)
-        h1 = norm_conv(h, self.in_layers[0], True, pw1, tbias, self.out_channels, src2=src2, k=k, bias_per_sample=True)
+                res = conv_of(sk, h, src2=src2)
+        h1 = conv_of(c1, h, src2=src2, norm=(self.in_layers[0], True), bias=tbias, bias_per_sample=True)
         assert h1.Cpad == pad32(self.out_channels)
-        return norm_conv(h1, self.out_layers[0], True, pw2, pb2, self.out_channels, k=k, residual=res, want_stats=want_stats, **skip_kw)
+        return conv_of(c2, h1, norm=(self.out_layers[0], True), residual=res, want_stats=want_stats, **kw2)
 
     def _run_options(self, h: CL, tbias: torch.Tensor, src2: Optional[CL], want_stats: bool) -> CL:
         """The same block with use_scale_shift_norm and / or up / down (unet.py:238-259)."""
-        c1, c2, n1 = self.in_layers[2], self.out_layers[3], self.in_layers[0]
-        k = _k3(c1.weight)
-        cout = self.out_channels
-        cin_pad = h.Cpad + (src2.Cpad if src2 is not None else 0)
+        c1, c2, n1, sk = self.in_layers[2], self.out_layers[3], self.in_layers[0], self.skip_connection
         film = tbias.view(h.N, -1) if self.use_scale_shift_norm else None     # per-sample rows [s | t]
-        pw1, pb1 = packed_conv(c1, cin_pad)
-        b1, b1_ps = (pb1, False) if film is not None else (tbias, True)       # FiLM: conv1 keeps its own bias
-        pw2, pb2 = packed_conv(c2, pad32(cout))
+        b1 = {} if film is not None else {"bias": tbias, "bias_per_sample": True}       # FiLM: conv1 keeps its own bias
         x = h
         if self.updown:
             if src2 is not None:
@@ -306,24 +337,18 @@ class ResBlock(TimestepBlock):
             x = self.x_upd.run(h)                                             # residual source: x_upd(x)
             if self.up:
                 # nearest x2 commutes with the pointwise GN+SiLU: normalise at low resolution, conv1 upsamples while it gathers
-                h1 = norm_conv(h, n1, True, pw1, b1, cout, k=k, upsample=True, bias_per_sample=b1_ps)
+                h1 = conv_of(c1, h, norm=(n1, True), upsample=True, **b1)
             else:
                 # avgpool(SiLU(GN(h))) in one resample launch from the per-(n, c) coefficients, then conv1
                 if ops.is_f32(h.t):
                     a = ops.resample2x(_gn_f32(h, n1, True), False, self.dims == 3)
                 else:
                     a = ops.resample2x(h, False, self.dims == 3, prologue=_gn_coeffs(h, n1), act=True)
-                h1 = ops.conv(a, pw1, b1, cout, k=k, pad=1, bias_per_sample=b1_ps)
+                h1 = conv_of(c1, a, **b1)
         else:
-            h1 = norm_conv(h, n1, True, pw1, b1, cout, src2=src2, k=k, bias_per_sample=b1_ps)
-        sk = self.skip_connection
-        if isinstance(sk, nn.Identity):
-            res = x
-        else:
-            pws, pbs = packed_conv(sk, cin_pad)
-            ks = _k3(sk.weight)
-            res = ops.conv(x, pws, pbs, cout, k=ks, pad=ks[-1] // 2, src2=src2 if not self.updown else None)
-        return norm_conv(h1, self.out_layers[0], True, pw2, pb2, cout, k=k, residual=res, want_stats=want_stats, film=film)
+            h1 = conv_of(c1, h, src2=src2, norm=(n1, True), **b1)
+        res = x if isinstance(sk, nn.Identity) else conv_of(sk, x, src2=src2)
+        return conv_of(c2, h1, norm=(self.out_layers[0], True), residual=res, want_stats=want_stats, film=film)
 
 
 class AttentionBlock(nn.Module):
@@ -344,22 +369,12 @@ class AttentionBlock(nn.Module):
         self.proj_out = zero_module(conv_nd(1, channels, channels, 1))
 
     def run(self, h: CL) -> CL:
-        Cc, nh = self.channels, self.num_heads
-        ch = Cc // nh
-        N, T = h.N, h.S
-        pw, pb = packed_conv(self.qkv, h.Cpad)
-        qkv = norm_conv(h, self.norm, False, pw, pb, 3 * Cc, k=(1, 1, 1), pad=0)
-        att = torch.empty(tuple(h.t.shape[:4]) + (Cc,), dtype=h.t.dtype, device=h.t.device)
-        ld = qkv.Cpad
-        # (q ch^-1/4)(k ch^-1/4) == scale 1/sqrt(ch) on q k^T in both orders (unet.py:352-354,379-385)
-        if self.new_order:          # QKVAttention: q | k | v blocks of C channels first, then heads of ch inside each block
-            ops.attention(qkv.t, qkv.t, qkv.t, att, N, nh, ch, T, T, (ld, ch), (ld, ch), (ld, ch), (Cc, ch),
-                          1.0 / math.sqrt(ch), q_off=0, k_off=Cc, v_off=2 * Cc)
-        else:                       # legacy order: head-major, q|k|v per head
-            ops.attention(qkv.t, qkv.t, qkv.t, att, N, nh, ch, T, T, (ld, 3 * ch), (ld, 3 * ch), (ld, 3 * ch), (Cc, ch),
-                          1.0 / math.sqrt(ch), q_off=0, k_off=ch, v_off=2 * ch)
-        pw2, pb2 = packed_conv(self.proj_out, Cc)
-        return ops.conv(CL(att, Cc), pw2, pb2, Cc, k=(1, 1, 1), pad=0, residual=h)
+        ch = self.channels // self.num_heads
+        qkv = conv_of(self.qkv, h, norm=(self.norm, False))
+        # (q ch^-1/4)(k ch^-1/4) == scale 1/sqrt(ch) on q k^T in both orders (unet.py:352-354,379-385); QKVAttention (new order) is the
+        # blocked layout, QKVAttentionLegacy the head-major one
+        att = qkv_attention(qkv, self.num_heads, ch, 1.0 / math.sqrt(ch), legacy=not self.new_order, dtype=h.t.dtype)
+        return conv_of(self.proj_out, att, residual=h)
 
 
 # ------------------------------------------------------------------------------------------------ SpatialTransformer
@@ -393,27 +408,15 @@ class CrossAttention(nn.Module):
 
     def run(self, xn: CL, context: Optional[CL], residual: CL) -> CL:
         """to_out(attn(to_q(xn), to_k(ctx), to_v(ctx))) + residual; xn/context are token rows as CL [N,1,1,T,C]."""
-        N, T = xn.N, xn.S
         inner, hd = self.inner, self.dim_head
         if context is None:
-            pw, pb = packed_cat([self.to_q, self.to_k, self.to_v], xn.Cpad, "qkv")
-            qkv = ops.conv(xn, pw, pb, 3 * inner, k=(1, 1, 1), pad=0)
-            q = k = v = qkv.t
-            ldq = ldk = qkv.Cpad
-            qo, ko, vo, Tkv = 0, inner, 2 * inner, T
+            att = qkv_attention(conv_of([self.to_q, self.to_k, self.to_v], xn, tag="qkv"), self.heads, hd, self.scale)
         else:
-            pwq, pbq = packed_conv(self.to_q, xn.Cpad)
-            qc = ops.conv(xn, pwq, pbq, inner, k=(1, 1, 1), pad=0)
-            pwk, pbk = packed_cat([self.to_k, self.to_v], context.Cpad, "kv")
-            kvc = ops.conv(context, pwk, pbk, 2 * inner, k=(1, 1, 1), pad=0)
-            q, k, v = qc.t, kvc.t, kvc.t
-            ldq, ldk = qc.Cpad, kvc.Cpad
-            qo, ko, vo, Tkv = 0, 0, inner, context.S
-        att = torch.empty(tuple(xn.t.shape[:4]) + (inner,), dtype=torch.bfloat16, device=xn.t.device)
-        ops.attention(q, k, v, att, N, self.heads, hd, T, Tkv, (ldq, hd), (ldk, hd), (ldk, hd), (inner, hd), self.scale,
-                      q_off=qo, k_off=ko, v_off=vo)
-        pwo, pbo = packed_conv(self.to_out[0], inner)
-        return ops.conv(CL(att, inner), pwo, pbo, self.to_out[0].weight.shape[0], k=(1, 1, 1), pad=0, residual=residual)
+            qc, kvc = conv_of(self.to_q, xn), conv_of([self.to_k, self.to_v], context, tag="kv")
+            att = CL(torch.empty(tuple(xn.t.shape[:4]) + (inner,), dtype=torch.bfloat16, device=xn.t.device), inner)
+            ops.attention(qc.t, kvc.t, kvc.t, att.t, xn.N, self.heads, hd, xn.S, context.S, (qc.Cpad, hd), (kvc.Cpad, hd), (kvc.Cpad, hd),
+                          (inner, hd), self.scale, q_off=0, k_off=0, v_off=inner)
+        return conv_of(self.to_out[0], att, residual=residual)
 
 
 class BasicTransformerBlock(nn.Module):
@@ -424,23 +427,16 @@ class BasicTransformerBlock(nn.Module):
         self.attn2 = CrossAttention(query_dim=dim, context_dim=context_dim, heads=n_heads, dim_head=d_head, dropout=dropout)
         self.norm1, self.norm2, self.norm3 = nn.LayerNorm(dim), nn.LayerNorm(dim), nn.LayerNorm(dim)
 
-    def _ln(self, x: CL, ln: nn.LayerNorm) -> CL:
-        return CL(ops.layernorm(x.t, f32(ln.weight), f32(ln.bias), ln.eps), x.C)
-
     def run(self, x: CL, context: Optional[CL]) -> CL:
-        x = self.attn1.run(self._ln(x, self.norm1), None, x)
-        x = self.attn2.run(self._ln(x, self.norm2), context, x)
-        y = self._ln(x, self.norm3)
+        x = self.attn1.run(layernorm_cl(x, self.norm1), None, x)
+        x = self.attn2.run(layernorm_cl(x, self.norm2), context, x)
+        y = layernorm_cl(x, self.norm3)
         proj, lin2 = self.ff.net[0].proj, self.ff.net[2]
         if FUSE_GEGLU and self.ff.inner % 16 == 0:
-            pw, pb = packed_geglu(proj, y.Cpad)
-            ggcl = ops.conv(y, pw, pb, proj.weight.shape[0], k=(1, 1, 1), pad=0, geglu=True)      # value * gelu(gate) from the fp32 accumulators
+            ggcl = conv_of(proj, y, geglu=True)                                    # value * gelu(gate) from the fp32 accumulators
         else:
-            pw, pb = packed_conv(proj, y.Cpad)
-            hcl = ops.conv(y, pw, pb, proj.weight.shape[0], k=(1, 1, 1), pad=0)
-            ggcl = CL(ops.geglu(hcl.t, self.ff.inner), self.ff.inner)
-        pw2, pb2 = packed_conv(lin2, self.ff.inner)
-        return ops.conv(ggcl, pw2, pb2, lin2.weight.shape[0], k=(1, 1, 1), pad=0, residual=x)
+            ggcl = CL(ops.geglu(conv_of(proj, y).t, self.ff.inner), self.ff.inner)
+        return conv_of(lin2, ggcl, residual=x)
 
 
 class SpatialTransformer(nn.Module):
@@ -456,12 +452,10 @@ class SpatialTransformer(nn.Module):
         self.proj_out = zero_module(nn.Conv2d(inner, in_channels, kernel_size=1, stride=1, padding=0))
 
     def run(self, h: CL, context: Optional[CL]) -> CL:
-        pw, pb = packed_conv(self.proj_in, h.Cpad)
-        x = norm_conv(h, self.norm, False, pw, pb, self.inner, k=(1, 1, 1), pad=0)   # 'b c h w -> b (h w) c' is free in CL
+        x = conv_of(self.proj_in, h, norm=(self.norm, False))                        # 'b c h w -> b (h w) c' is free in CL
         for blk in self.transformer_blocks:
             x = blk.run(x, context)
-        pw2, pb2 = packed_conv(self.proj_out, x.Cpad)
-        return ops.conv(x, pw2, pb2, self.in_channels, k=(1, 1, 1), pad=0, residual=h)
+        return conv_of(self.proj_out, x, residual=h)
 
 
 class TimestepEmbedSequential(nn.Sequential, TimestepBlock):
@@ -480,8 +474,7 @@ class TimestepEmbedSequential(nn.Sequential, TimestepBlock):
             elif isinstance(layer, (AttentionBlock, Upsample, Downsample)):
                 h = layer.run(h)
             elif isinstance(layer, (nn.Conv1d, nn.Conv2d, nn.Conv3d)):
-                pw, pb = packed_conv(layer, h.Cpad)
-                h = ops.conv(h, pw, pb, layer.weight.shape[0], k=_k3(layer.weight), pad=1)
+                h = conv_of(layer, h)
             else:
                 raise TypeError(f"no HIP execution rule for {type(layer).__name__}")
         if skip is not None:
@@ -505,8 +498,7 @@ class AEUpsample(nn.Module):
         self.conv = conv_nd(dims, in_channels, in_channels, kernel_size=3, stride=1, padding=1)
 
     def run(self, h: CL) -> CL:
-        pw, pb = packed_conv(self.conv, h.Cpad)
-        return ops.conv(h, pw, pb, self.conv.weight.shape[0], k=_k3(self.conv.weight), upsample=True)
+        return conv_of(self.conv, h, upsample=True)
 
 
 class AEDownsample(nn.Module):
@@ -520,8 +512,7 @@ class AEDownsample(nn.Module):
         self.conv = conv_nd(dims, in_channels, in_channels, kernel_size=3, stride=2, padding=0)
 
     def run(self, h: CL) -> CL:
-        pw, pb = packed_conv(self.conv, h.Cpad)
-        return ops.conv(h, pw, pb, self.conv.weight.shape[0], k=_k3(self.conv.weight), stride=2, pad=0)
+        return conv_of(self.conv, h, stride=2, pad=0)
 
 
 class ResnetBlock(nn.Module):
@@ -539,15 +530,9 @@ class ResnetBlock(nn.Module):
             self.nin_shortcut = conv_nd(dims, in_channels, out_channels, 1, 1, 0)
 
     def run(self, h: CL) -> CL:
-        k = _k3(self.conv1.weight)
-        pw1, pb1 = packed_conv(self.conv1, h.Cpad)
-        h1 = norm_conv(h, self.norm1, True, pw1, pb1, self.out_channels, k=k)
-        res = h
-        if self.in_channels != self.out_channels:
-            pws, pbs = packed_conv(self.nin_shortcut, h.Cpad)
-            res = ops.conv(h, pws, pbs, self.out_channels, k=(1, 1, 1), pad=0)
-        pw2, pb2 = packed_conv(self.conv2, h1.Cpad)
-        return norm_conv(h1, self.norm2, True, pw2, pb2, self.out_channels, k=k, residual=res)
+        h1 = conv_of(self.conv1, h, norm=(self.norm1, True))
+        res = conv_of(self.nin_shortcut, h) if self.in_channels != self.out_channels else h
+        return conv_of(self.conv2, h1, norm=(self.norm2, True), residual=res)
 
 
 ATTN_HEAD_DIMS = (32, 64, 128, 256, 384, 512)          # head dims gg_attention_forward has kernels for
@@ -568,15 +553,8 @@ class AttnBlock2d(nn.Module):
 
     def run(self, h: CL) -> CL:
         Cc = self.in_channels
-        N, T = h.N, h.S
-        pw, pb = packed_cat([self.q, self.k, self.v], h.Cpad, "qkv")
-        qkv = norm_conv(h, self.norm, False, pw, pb, 3 * Cc, k=(1, 1, 1), pad=0)
-        att = torch.empty(tuple(h.t.shape[:4]) + (Cc,), dtype=h.t.dtype, device=h.t.device)
-        ld = qkv.Cpad
-        ops.attention(qkv.t, qkv.t, qkv.t, att, N, 1, Cc, T, T, (ld, Cc), (ld, Cc), (ld, Cc), (Cc, Cc), int(Cc) ** -0.5,
-                      q_off=0, k_off=Cc, v_off=2 * Cc)
-        pw2, pb2 = packed_conv(self.proj_out, Cc)
-        return ops.conv(CL(att, Cc), pw2, pb2, Cc, k=(1, 1, 1), pad=0, residual=h)
+        qkv = conv_of([self.q, self.k, self.v], h, tag="qkv", norm=(self.norm, False))
+        return conv_of(self.proj_out, qkv_attention(qkv, 1, Cc, int(Cc) ** -0.5, dtype=h.t.dtype), residual=h)
 
 
 class AttnBlock3d(AttnBlock2d):

@@ -25,7 +25,7 @@ import torch.nn as nn
 
 from . import io as gio
 from . import ops
-from .blocks import f32, packed_cat, packed_conv
+from .blocks import conv_of, f32, layernorm_cl, qkv_attention, token_rows_f32  # noqa: F401  (layernorm_cl: also imported from here)
 from .ops import CL
 from .tokenizer import BertWordPieceTokenizer
 
@@ -87,16 +87,8 @@ class Attention(nn.Module):
 
     def run(self, xn: CL, residual: CL) -> CL:
         """to_out(softmax(q k^T / 8) v) + residual on token rows CL [B, 1, 1, T, C] (blocks.CrossAttention.run without a context)."""
-        N, T = xn.N, xn.S
-        inner, hd = self.inner, self.dim_head
-        pw, pb = packed_cat([self.to_q, self.to_k, self.to_v], xn.Cpad, "qkv")
-        qkv = ops.conv(xn, pw, pb, 3 * inner, k=(1, 1, 1), pad=0)
-        att = torch.empty(tuple(xn.t.shape[:4]) + (inner,), dtype=torch.bfloat16, device=xn.t.device)
-        ld = qkv.Cpad
-        ops.attention(qkv.t, qkv.t, qkv.t, att, N, self.heads, hd, T, T, (ld, hd), (ld, hd), (ld, hd), (inner, hd), self.scale,
-                      q_off=0, k_off=inner, v_off=2 * inner)
-        pwo, pbo = packed_conv(self.to_out, inner)
-        return ops.conv(CL(att, inner), pwo, pbo, self.to_out.weight.shape[0], k=(1, 1, 1), pad=0, residual=residual)
+        qkv = conv_of([self.to_q, self.to_k, self.to_v], xn, tag="qkv")
+        return conv_of(self.to_out, qkv_attention(qkv, self.heads, self.dim_head, self.scale), residual=residual)
 
 
 class FeedForward(nn.Module):
@@ -110,11 +102,8 @@ class FeedForward(nn.Module):
 
     def run(self, xn: CL, residual: CL) -> CL:
         lin1, lin2 = self.net[0][0], self.net[2]
-        pw, pb = packed_conv(lin1, xn.Cpad)
-        h = ops.conv(xn, pw, pb, self.inner, k=(1, 1, 1), pad=0)
-        h = CL(ops.gelu(h.t), self.inner)                    # GELU(0) = 0: the pad lanes stay zero
-        pw2, pb2 = packed_conv(lin2, h.Cpad)
-        return ops.conv(h, pw2, pb2, lin2.weight.shape[0], k=(1, 1, 1), pad=0, residual=residual)
+        h = CL(ops.gelu(conv_of(lin1, xn).t), self.inner)    # GELU(0) = 0: the pad lanes stay zero
+        return conv_of(lin2, h, residual=residual)
 
 
 class Residual(nn.Module):
@@ -133,13 +122,6 @@ class Encoder(nn.Module):
         for _ in range(depth):
             self.layers.append(nn.ModuleList([nn.LayerNorm(dim), Attention(dim, heads=heads), Residual()]))
             self.layers.append(nn.ModuleList([nn.LayerNorm(dim), FeedForward(dim), Residual()]))
-
-
-def layernorm_cl(x: CL, ln: nn.LayerNorm) -> CL:
-    """LayerNorm over the logical channels of token rows: whole rows on gg_layernorm, padded rows on gg_layernorm_rows."""
-    if x.C == x.Cpad:
-        return CL(ops.layernorm(x.t, f32(ln.weight), f32(ln.bias), ln.eps), x.C)
-    return ops.layernorm_rows(x, f32(ln.weight), f32(ln.bias), ln.eps)
 
 
 class TransformerWrapper(nn.Module):
@@ -165,8 +147,7 @@ class TransformerWrapper(nn.Module):
         x = CL(ops.embed_rows(tokens, f32(self.token_emb.weight), f32(self.pos_emb.emb.weight), bf16=True), dim)
         for norm, block, _ in self.attn_layers.layers:
             x = block.run(layernorm_cl(x, norm), x)
-        x = layernorm_cl(x, self.norm)
-        return x.t[:, 0, 0, :, :dim].float()                 # plumbing: the logical lanes of the bf16 rows as fp32 [B, T, dim]
+        return token_rows_f32(layernorm_cl(x, self.norm))
 
 
 class _Embedder(nn.Module):
@@ -236,10 +217,7 @@ class SpatialRescaler(nn.Module):
         for _ in range(self.n_stages):
             x = ops.interpolate2d(x, self.multiplier, self.method)
         if self.remap_output:
-            cm = self.channel_mapper
-            src = ops.to_cl(x)
-            pw, pb = packed_conv(cm, src.Cpad)
-            x = ops.from_cl(ops.conv(src, pw, pb, cm.weight.shape[0], k=(1, 1, 1), pad=0, out_f32=True), 2)
+            x = ops.from_cl(conv_of(self.channel_mapper, ops.to_cl(x), out_f32=True), 2)
         return x
 
     def encode(self, x):
@@ -279,8 +257,7 @@ class BertSelfOutput(nn.Module):
         self.LayerNorm = nn.LayerNorm(hidden, eps=eps)
 
     def run(self, h: CL, x: CL) -> CL:
-        pw, pb = packed_conv(self.dense, h.Cpad)
-        return layernorm_cl(ops.conv(h, pw, pb, self.dense.weight.shape[0], k=(1, 1, 1), pad=0, residual=x), self.LayerNorm)
+        return layernorm_cl(conv_of(self.dense, h, residual=x), self.LayerNorm)
 
 
 class BertAttention(nn.Module):
@@ -291,15 +268,9 @@ class BertAttention(nn.Module):
         self.output = BertSelfOutput(hidden, hidden, eps)
 
     def run(self, x: CL, kv_len: torch.Tensor) -> CL:
-        N, T, hidden, hd = x.N, x.S, self.heads * self.head_dim, self.head_dim
         sa = getattr(self, "self")
-        pw, pb = packed_cat([sa.query, sa.key, sa.value], x.Cpad, "qkv")
-        qkv = ops.conv(x, pw, pb, 3 * hidden, k=(1, 1, 1), pad=0)
-        att = torch.empty(tuple(x.t.shape[:4]) + (hidden,), dtype=torch.bfloat16, device=x.t.device)
-        ld = qkv.Cpad
-        ops.attention(qkv.t, qkv.t, qkv.t, att, N, self.heads, hd, T, T, (ld, hd), (ld, hd), (ld, hd), (hidden, hd), hd ** -0.5,
-                      q_off=0, k_off=hidden, v_off=2 * hidden, kv_len=kv_len)
-        return self.output.run(CL(att, hidden), x)
+        qkv = conv_of([sa.query, sa.key, sa.value], x, tag="qkv")
+        return self.output.run(qkv_attention(qkv, self.heads, self.head_dim, self.head_dim ** -0.5, kv_len=kv_len), x)
 
 
 class BertIntermediate(nn.Module):
@@ -318,9 +289,7 @@ class BertLayer(nn.Module):
 
     def run(self, x: CL, kv_len: torch.Tensor) -> CL:
         x = self.attention.run(x, kv_len)
-        lin = self.intermediate.dense
-        pw, pb = packed_conv(lin, x.Cpad)
-        h = ops.conv(x, pw, pb, lin.weight.shape[0], k=(1, 1, 1), pad=0)
+        h = conv_of(self.intermediate.dense, x)
         h = CL(ops.gelu(h.t), h.C)                           # GELU(0) = 0: the pad lanes stay zero
         return self.output.run(h, x)
 
@@ -386,7 +355,7 @@ class BertModel(nn.Module):
                               f32(e.LayerNorm.weight), f32(e.LayerNorm.bias), e.LayerNorm.eps, ids_host=ids_host), hidden)
         for layer in self.encoder.layer:
             x = layer.run(x, kv_len)
-        return x.t[:, 0, 0, :, :hidden].float()              # plumbing: the logical lanes of the bf16 rows as fp32 [B, T, hidden]
+        return token_rows_f32(x)
 
 
 def hf_bert_state_dict(sd: dict) -> dict:

@@ -24,7 +24,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .blocks import AEDownsample, AEUpsample, AttnBlock2d, AttnBlock3d, Normalize, ResnetBlock, _k3, conv_nd, norm_conv, packed_conv
+from .blocks import AEDownsample, AEUpsample, AttnBlock2d, AttnBlock3d, Normalize, ResnetBlock, conv_nd, conv_of
 from .config import instantiate_from_config
 from .ops import CL, pad32
 
@@ -166,9 +166,7 @@ class Encoder(nn.Module):
         self.conv_out = conv_nd(dims, block_in, 2 * z_channels if double_z else z_channels, 3, 1, 1)
 
     def run(self, x: CL) -> CL:
-        k = _k3(self.conv_in.weight)
-        pw, pb = packed_conv(self.conv_in, x.Cpad)
-        h = ops.conv(x, pw, pb, self.ch, k=k)
+        h = conv_of(self.conv_in, x)
         for i_level in range(self.num_resolutions):
             lvl = self.down[i_level]
             for i_block in range(self.num_res_blocks):
@@ -178,8 +176,7 @@ class Encoder(nn.Module):
             if i_level != self.num_resolutions - 1:
                 h = lvl.downsample.run(h)
         h = self.mid.block_2.run(self.mid.attn_1.run(self.mid.block_1.run(h)))
-        pw, pb = packed_conv(self.conv_out, h.Cpad)
-        return norm_conv(h, self.norm_out, True, pw, pb, self.conv_out.weight.shape[0], k=k)
+        return conv_of(self.conv_out, h, norm=(self.norm_out, True))
 
 
 class Decoder(nn.Module):
@@ -218,9 +215,7 @@ class Decoder(nn.Module):
         self.conv_out = conv_nd(dims, block_in, out_ch, 3, 1, 1)
 
     def run(self, z: CL, out_f32: bool = True) -> CL:
-        k = _k3(self.conv_in.weight)
-        pw, pb = packed_conv(self.conv_in, z.Cpad)
-        h = ops.conv(z, pw, pb, self.conv_in.weight.shape[0], k=k)
+        h = conv_of(self.conv_in, z)
         h = self.mid.block_2.run(self.mid.attn_1.run(self.mid.block_1.run(h)))
         for i_level in reversed(range(self.num_resolutions)):
             lvl = self.up[i_level]
@@ -230,8 +225,7 @@ class Decoder(nn.Module):
                     h = lvl.attn[i_block].run(h)
             if i_level != 0:
                 h = lvl.upsample.run(h)
-        pw, pb = packed_conv(self.conv_out, h.Cpad)
-        return norm_conv(h, self.norm_out, True, pw, pb, self.conv_out.weight.shape[0], k=k, out_f32=out_f32)
+        return conv_of(self.conv_out, h, norm=(self.norm_out, True), out_f32=out_f32)
 
 
 def first_stage_dims(who, ddconfig, dims) -> int:
@@ -298,18 +292,14 @@ class AutoencoderKL(nn.Module):
     def encode_moments_cl(self, x: CL) -> CL:
         ops.stats_begin(x.t.device)        # conv epilogues leave the GroupNorm sums of the next norm in the (zeroed) arena
         try:
-            h = self.encoder.run(x)
-            pw, pb = packed_conv(self.quant_conv, h.Cpad)
-            return ops.conv(h, pw, pb, self.quant_conv.weight.shape[0], k=(1, 1, 1), pad=0, out_f32=True)
+            return conv_of(self.quant_conv, self.encoder.run(x), out_f32=True)
         finally:
             ops.stats_end(x.t.device)
 
     def decode_cl(self, z: CL) -> CL:
         ops.stats_begin(z.t.device)
         try:
-            pw, pb = packed_conv(self.post_quant_conv, z.Cpad)
-            h = ops.conv(z, pw, pb, self.post_quant_conv.weight.shape[0], k=(1, 1, 1), pad=0)
-            return self.decoder.run(h)
+            return self.decoder.run(conv_of(self.post_quant_conv, z))
         finally:
             ops.stats_end(z.t.device)
 
@@ -453,9 +443,7 @@ class VQModel(nn.Module):
         """encoder -> quant_conv, fp32 channels-last output (what the quantiser reads)."""
         ops.stats_begin(x.t.device)
         try:
-            h = self.encoder.run(x)
-            pw, pb = packed_conv(self.quant_conv, h.Cpad)
-            return ops.conv(h, pw, pb, self.quant_conv.weight.shape[0], k=(1, 1, 1), pad=0, out_f32=True)
+            return conv_of(self.quant_conv, self.encoder.run(x), out_f32=True)
         finally:
             ops.stats_end(x.t.device)
 

@@ -13,8 +13,8 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .blocks import (AttentionBlock, Downsample, ResBlock, SpatialTransformer, TimestepEmbedSequential, Upsample, conv_nd,
-                     f32, gn_silu, norm_conv, normalization, packed_conv, zero_module, _k3)
+from .blocks import (AttentionBlock, Downsample, ResBlock, SpatialTransformer, TimestepEmbedSequential, Upsample, conv_nd, conv_of,
+                     f32, normalization, zero_module)
 from .ops import CL, pad32
 
 
@@ -133,12 +133,10 @@ class _UNetBase(nn.Module):
             h = self.middle_block.run(h, tb, context)
             for module in self.output_blocks:
                 h = module.run(h, tb, context, skip=hs.pop())
-            conv = self.out[2]
-            pw, pb = packed_conv(conv, h.Cpad)
             extra = {"ddim": head_ddim} if head_ddim is not None else {}     # DDIM update as the head conv's epilogue (ddim.py:190-204)
             if head_post is not None:
                 extra["post"] = head_post                                    # CCDM reverse step as the head conv's epilogue
-            return norm_conv(h, self.out[0], True, pw, pb, conv.weight.shape[0], k=_k3(conv.weight), out_f32=True, out=head_out, **extra)
+            return conv_of(self.out[2], h, norm=(self.out[0], True), out_f32=True, out=head_out, **extra)
         finally:
             ops.stats_end(x.t.device)
 
