@@ -380,6 +380,26 @@ int gg_ddpm_step(float *x, const float *eps, int32_t eps_stride, const float *no
 int gg_ddpm_step_x0(float *x, const float *out, int32_t out_stride, const float *noise, const float *scalars_dev, int32_t flags,
                     int64_t M, int32_t C, float *pred_x0_out, void *unet_in, int32_t unet_in_stride, void *stream);
 
+/* One reverse step of DPM-Solver++ in its multistep second-order data-prediction form ("2M": Lu et al. 2022, Algorithm 2), fp32
+ * elementwise on CL rows, from the current point s of the schedule to the next point t.  scalars device fp32[6] =
+ * {alpha_s, sigma_s, k_x, k_d, c0, c1} with alpha = sqrt(a), sigma = sqrt(1 - a), lambda = log(alpha / sigma), h = lambda_t - lambda_s,
+ * k_x = sigma_t / sigma_s, k_d = -alpha_t * expm1(-h); a first-order step has c0 = 1, c1 = 0, a second-order step c0 = 1 + 1/(2r),
+ * c1 = -1/(2r) with r = h_prev / h (the host computes the row in fp64 and rounds it once).
+ *   p = (x - s[1]*out) / s[0];  flags & GG_DDPM_PREDICTS_X0: p = out (parameterization "x0");  flags & GG_DDPM_CLIP: p clamped to [-1, 1];
+ *   D = p when s[5] == 0, else s[4]*p + s[5]*hist (hist is then the previous step's p; when s[5] == 0 it does not enter the result,
+ *   whatever it holds, NaN included);  xn = s[2]*x + s[3]*D;  hist <- p;  pred_x0_out <- p;  x <- xn;  unet_in channels [0, C) <- bf16(xn).
+ *   Evaluated in that order without contraction, every product and sum rounded on its own, IEEE division, the fp32 -> bf16 cast of
+ *   gg_ddim_step; with s[5] == 0 and {k_x, k_d} of a DDIM pair the step is DDIM's at eta 0 up to rounding.
+ *   x fp32 [M, C] (in/out), out fp32 [M, out_stride] (the UNet's output), hist fp32 [M, C] (in/out, the caller keeps it between the
+ *   steps of one chain), pred_x0_out fp32 [M, C] or NULL, unet_in bf16 CL [M, unet_in_stride] or NULL (pad lanes are not touched).
+ *   GG_ERR_BAD_SHAPE: NULL x / out / scalars / hist, out_stride < C, unet_in_stride < C, M < 0; GG_ERR_UNSUPPORTED: flag bits other than
+ *   the two, or more units than one grid of 2^31 - 1 workgroups of 256 lanes holds (the kernels run one unit per lane, without a loop).
+ *   M == 0 returns GG_OK without a launch.  C == 4 with 16-byte aligned rows (out_stride and unet_in_stride multiples of 4, 8-byte
+ *   unet_in rows) runs one row per lane; any other case one element per lane.  A NaN through the clamp is unspecified.
+ *   No allocation, no synchronisation: capturable. */
+int gg_dpm_solver_step(float *x, const float *out, int32_t out_stride, const float *scalars_dev, int32_t flags, int64_t M, int32_t C,
+                       float *hist, float *pred_x0_out, void *unet_in, int32_t unet_in_stride, void *stream);
+
 /* Sampler log entry: the fp32 channels-last state [N * S, C] (dense rows; S voxels per sample) -> slot fp32 [N, C, S], one entry of a
  * caller-allocated log buffer.  It runs gg_cl_to_nchw_f32's kernel with C_pad == C, at a fixed destination: no allocation, no
  * synchronisation, so it can sit inside a captured chain.  GG_ERR_BAD_SHAPE: NULL pointers, C <= 0, negative N or S; an empty extent

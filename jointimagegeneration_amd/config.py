@@ -34,6 +34,7 @@ TARGET_ALIASES = {
     "ddpm.models.encoder.FrozenBERTEmbedder": "jointimagegeneration_amd.encoder.FrozenBERTEmbedder",
     "ldm.models.diffusion.ddim.DDIMSampler": "jointimagegeneration_amd.ldm.DDIMSampler",
     "ldm.models.diffusion.plms.PLMSSampler": "jointimagegeneration_amd.ldm.PLMSSampler",
+    "ldm.models.diffusion.dpm_solver.DPMSolverSampler": "jointimagegeneration_amd.dpm_solver.DPMSolverSampler",
     "ldm.modules.losses.LPIPSWithDiscriminator": "jointimagegeneration_amd.aeloss.LPIPSWithDiscriminator",
     "ldm.modules.losses.contperceptual.LPIPSWithDiscriminator": "jointimagegeneration_amd.aeloss.LPIPSWithDiscriminator",
     "torch.nn.Identity": "torch.nn.Identity",

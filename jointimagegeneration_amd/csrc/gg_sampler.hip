@@ -310,6 +310,87 @@ extern "C" int gg_ddpm_step_x0(float *x, const float *out, int32_t out_stride, c
 }
 
 // ------------------------------------------------------------------------------------------------------------
+// DPM-Solver++ (2M) reverse step, fp32 (dpm_pred_x0 / dpm_combine / dpm_x_next of gg_step.h).  One unit per lane over an exact grid (the
+// entry refuses more workgroups than a grid holds): a row at C == 4 with 16-byte rows, an element otherwise, as gg_ddpm_step_x0 splits.
+// scalars device fp32[6] = {alpha_s, sigma_s, k_x, k_d, c0, c1}; hist is read on a second-order step (c1 != 0) only.
+// ------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void dpm_step_c4_kernel(float *__restrict__ x, const float *__restrict__ out, int out_stride,
+                                                          const float *__restrict__ sc, int flags, long long M, float *__restrict__ hist,
+                                                          float *__restrict__ pred_x0_out, bf16_t *__restrict__ unet_in, int unet_in_stride)
+{
+    const long long m = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (m >= M) return;
+    const float alpha_s = sc[0], sigma_s = sc[1], k_x = sc[2], k_d = sc[3], c0 = sc[4], c1 = sc[5];
+    const f32x4 xv = *reinterpret_cast<const f32x4 *>(x + m * 4);
+    const f32x4 ov = *reinterpret_cast<const f32x4 *>(out + m * out_stride);
+    f32x4 hv = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (c1 != 0.0f) hv = *reinterpret_cast<const f32x4 *>(hist + m * 4);
+    f32x4 r, p;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        p[c] = dpm_pred_x0(xv[c], ov[c], sigma_s, alpha_s, flags);
+        const float D = c1 != 0.0f ? dpm_combine(p[c], hv[c], c0, c1) : p[c];
+        r[c] = dpm_x_next(xv[c], D, k_x, k_d);
+    }
+    *reinterpret_cast<f32x4 *>(hist + m * 4) = p;
+    if (pred_x0_out) *reinterpret_cast<f32x4 *>(pred_x0_out + m * 4) = p;
+    *reinterpret_cast<f32x4 *>(x + m * 4) = r;
+    if (unet_in) {
+        bf16x4 o;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) o[c] = (bf16_t)r[c];
+        *reinterpret_cast<bf16x4 *>(unet_in + m * unet_in_stride) = o;
+    }
+}
+
+__global__ __launch_bounds__(256) void dpm_step_kernel(float *__restrict__ x, const float *__restrict__ out, int out_stride,
+                                                       const float *__restrict__ sc, int flags, long long total, int C,
+                                                       float *__restrict__ hist, float *__restrict__ pred_x0_out,
+                                                       bf16_t *__restrict__ unet_in, int unet_in_stride)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const float alpha_s = sc[0], sigma_s = sc[1], k_x = sc[2], k_d = sc[3], c0 = sc[4], c1 = sc[5];
+    const long long m = i / C;
+    const int c = (int)(i - m * C);
+    const float xv = x[i];
+    const float p = dpm_pred_x0(xv, out[m * out_stride + c], sigma_s, alpha_s, flags);
+    const float D = c1 != 0.0f ? dpm_combine(p, hist[i], c0, c1) : p;
+    const float xn = dpm_x_next(xv, D, k_x, k_d);
+    hist[i] = p;
+    if (pred_x0_out) pred_x0_out[i] = p;
+    x[i] = xn;
+    if (unet_in) unet_in[m * unet_in_stride + c] = (bf16_t)xn;
+}
+
+extern "C" int gg_dpm_solver_step(float *x, const float *out, int32_t out_stride, const float *scalars_dev, int32_t flags, int64_t M,
+                                  int32_t C, float *hist, float *pred_x0_out, void *unet_in, int32_t unet_in_stride, void *stream_)
+{
+    if (!x || !out || !scalars_dev || !hist) GG_FAIL(GG_ERR_BAD_SHAPE, "dpm_solver_step: null pointer");
+    if (C <= 0 || out_stride < C) GG_FAIL(GG_ERR_BAD_SHAPE, "dpm_solver_step: out_stride %d < C=%d", out_stride, C);
+    if (unet_in && unet_in_stride < C) GG_FAIL(GG_ERR_BAD_SHAPE, "dpm_solver_step: unet_in_stride %d < C=%d", unet_in_stride, C);
+    if (M < 0) GG_FAIL(GG_ERR_BAD_SHAPE, "dpm_solver_step: M=%lld", (long long)M);
+    if (flags & ~(GG_DDPM_PREDICTS_X0 | GG_DDPM_CLIP)) GG_FAIL(GG_ERR_UNSUPPORTED, "dpm_solver_step: unknown flag bits 0x%x", flags);
+    if (M == 0) return GG_OK;
+    const auto al = [](const void *p, uintptr_t n) { return ((uintptr_t)p & (n - 1)) == 0; };
+    const bool vec = C == 4 && al(x, 16) && al(out, 16) && out_stride % 4 == 0 && al(hist, 16) && (!pred_x0_out || al(pred_x0_out, 16)) &&
+                     (!unet_in || (al(unet_in, 8) && unet_in_stride % 4 == 0));
+    const long long max_units = 0x7fffffffLL * 256;          // one unit per lane: the grid is exact, there is no loop to fall back on
+    if ((long long)M > max_units / (vec ? 1 : C))
+        GG_FAIL(GG_ERR_UNSUPPORTED, "dpm_solver_step: M=%lld rows of %d channels exceed the grid", (long long)M, C);
+    if (vec) {
+        hipLaunchKernelGGL(dpm_step_c4_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, (hipStream_t)stream_, x, out, out_stride,
+                           scalars_dev, flags, (long long)M, hist, pred_x0_out, (bf16_t *)unet_in, unet_in_stride);
+    } else {
+        const long long total = (long long)M * C;
+        hipLaunchKernelGGL(dpm_step_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream_, x, out, out_stride,
+                           scalars_dev, flags, total, C, hist, pred_x0_out, (bf16_t *)unet_in, unet_in_stride);
+    }
+    GG_CHECK_LAUNCH();
+    return GG_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------
 // Inpainting blend x <- q_sample(x0, t, noise) * mask + (1 - mask) * x, fp32 (inpaint_blend_one of gg_step.h).
 // scalars device fp32[2] = {sqrt_alphas_cumprod[t], sqrt_one_minus_alphas_cumprod[t]}; mask has 1 or C channels.
 // ------------------------------------------------------------------------------------------------------------

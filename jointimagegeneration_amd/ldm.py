@@ -1619,6 +1619,11 @@ class DDIMSampler(object):
     LatentDiffusion models it runs entirely channels-last on the GPU: per step one UNet forward + one fused update
     kernel, captured in a hipGraph; any other `model` object only needs `apply_model` etc. (eager path)."""
 
+    # hooks of the subclasses (dpm_solver.py): the parameterizations whose output the update can read, and what a sampler adds to the
+    # key of its chain states
+    parameterizations = ("eps",)
+    state_tag = ()
+
     def __init__(self, model, schedule="linear", **kwargs):
         self.model = model
         self.ddpm_num_timesteps = model.num_timesteps
@@ -1698,7 +1703,7 @@ class DDIMSampler(object):
         host call sits between its steps, so it cannot be one captured graph.
         A model with parameterization "x0" is refused: the reference's DDIM / PLMS would read its output as eps."""
         who = f"{type(self).__name__}.sample"
-        if getattr(self.model, "parameterization", "eps") != "eps":
+        if getattr(self.model, "parameterization", "eps") not in self.parameterizations:
             raise NotImplementedError(f"{who}: parameterization '{self.model.parameterization}' is not supported (the DDIM / PLMS update "
                                       "reads the model's output as eps, ddim.py:173-180; use p_sample_loop / progressive_denoising)")
         if log_every_t is not None:
@@ -1784,7 +1789,7 @@ class DDIMSampler(object):
         unet = self.model.model.diffusion_model
         sp3 = (1,) * (3 - len(sp)) + tuple(sp)
         S = self.ddim_timesteps.shape[0]
-        key = (N, Cx, sp3, Cc, str(dev), ctx_shape) + ((("inpaint", mask_C),) if mask_C else ())
+        key = (N, Cx, sp3, Cc, str(dev), ctx_shape) + tuple(self.state_tag) + ((("inpaint", mask_C),) if mask_C else ())
         if vq is not None:
             key = key + (("vq", vq[0] is not None),)
         if logged is not None:

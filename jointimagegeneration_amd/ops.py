@@ -1446,6 +1446,24 @@ def ddpm_step_x0(x: torch.Tensor, out: torch.Tensor, scalars: torch.Tensor, nois
          _ptr(unet_in), unet_in.shape[-1] if unet_in is not None else 0, _stream())
 
 
+def dpm_solver_step(x: torch.Tensor, out: torch.Tensor, scalars: torch.Tensor, hist: torch.Tensor, *, predicts_x0: bool = False,
+                    clip: bool = False, pred_x0_out: Optional[torch.Tensor] = None, unet_in: Optional[torch.Tensor] = None) -> None:
+    """One DPM-Solver++ (2M) reverse step in place (gg_dpm_solver_step): x fp32 CL [M, C], out fp32 CL [M, stride] (the UNet's output:
+    eps, or x_0 with predicts_x0), scalars fp32[6] on device = (alpha_s, sigma_s, k_x, k_d, c0, c1), hist fp32 [M, C] the previous step's
+    prediction of x_0 (read when c1 != 0 only; this step's is written to it); clip clamps the prediction to [-1, 1]; pred_x0_out fp32
+    [M, C] receives it; unet_in channels [0, C) <- bf16(x)."""
+    Cc = x.shape[-1]
+    M = x.numel() // Cc
+    for name, t in (("x", x), ("hist", hist), ("pred_x0_out", pred_x0_out)):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != M * Cc):
+            raise ValueError(f"dpm_solver_step: {name} must be contiguous fp32 [{M}, {Cc}], got {t.dtype} {tuple(t.shape)}")
+    if scalars.dtype != torch.float32 or scalars.numel() < 6:
+        raise ValueError(f"dpm_solver_step: scalars must hold six fp32 values, got {scalars.dtype} {tuple(scalars.shape)}")
+    flags = (DDPM_PREDICTS_X0 if predicts_x0 else 0) | (DDPM_CLIP if clip else 0)
+    call("gg_dpm_solver_step", x.data_ptr(), out.data_ptr(), out.shape[-1], scalars.data_ptr(), flags, M, Cc, hist.data_ptr(),
+         _ptr(pred_x0_out), _ptr(unet_in), unet_in.shape[-1] if unet_in is not None else 0, _stream())
+
+
 def log_rows(state: torch.Tensor, N: int, slot: torch.Tensor) -> None:
     """The fp32 channels-last state [N * S, C] -> slot fp32 [N, C, *sp] (prod(sp) = S), one entry of a pre-allocated log buffer
     (gg_log_rows: from_cl's kernel at a given destination; no allocation, capturable)."""

@@ -7,7 +7,7 @@ Volumes are independent units: multi-GPU runs shard volumes over ranks with no c
 
 CLI (one process per GPU, under torch.distributed.run or alone):
     python -m jointimagegeneration_amd.pipeline --volumes V --out DIR [--mask-size D H W] [--depth 256] [--hw 512] [--ccdm-steps 250] [--ddim-steps 50]
-                                                [--volumes-per-gpu B]
+                                                [--volumes-per-gpu B] [--sampler ddim|dpmpp_2m] [--discretize uniform|quad|logsnr]
 samples volumes `volume_id mod world_size == rank` and writes `mask_<id>.nii.gz` (uint8 labels) and `ct_<id>.nii.gz` (fp32 in [0, 1])
 per volume; volume id v uses seed `--seed + 1000 v` for the mask chain and `+ 1` for the slice loop, whatever the world size.
 With B > 1 a rank samples its volumes in groups of B independent volumes per batch (GuideGenPipeline.run_volumes; the last group may
@@ -145,13 +145,41 @@ def _log(msg: str) -> None:
     print(f"[guidegen {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
+SAMPLERS = ("ddim", "dpmpp_2m")                       # GuideGenPipeline(sampler=); the command lines add "plms" where they take it
+DISCRETIZATIONS = {"ddim": ("uniform", "quad"), "plms": ("uniform", "quad"), "dpmpp_2m": ("uniform", "quad", "logsnr")}
+
+
+def check_sampler_options(sampler: str, discretize: Optional[str], samplers: Sequence[str] = SAMPLERS) -> None:
+    """Host-side refusal, by name, of a sampler / grid pair that does not exist."""
+    if sampler not in samplers:
+        raise ValueError(f"sampler = {sampler!r} is not one of {', '.join(samplers)}")
+    if discretize is not None and discretize not in DISCRETIZATIONS[sampler]:
+        raise ValueError(f"discretize = {discretize!r} is not a grid of the {sampler} sampler ({', '.join(DISCRETIZATIONS[sampler])})")
+
+
 class GuideGenPipeline:
     progress_every_s = 30.0
 
-    def __init__(self, ccdm: DenoisingModel, ldm: LatentDiffusion, ddim_steps: int = 50):
+    @property
+    def steps(self) -> int:
+        """The chain's own step count: the grid's, which may differ from the ddim_steps asked for."""
+        return int(self.sampler.ddim_timesteps.shape[0])
+
+    def __init__(self, ccdm: DenoisingModel, ldm: LatentDiffusion, ddim_steps: int = 50, sampler: str = "ddim", discretize: Optional[str] = None):
+        """sampler: "ddim" (the default: DDIM at eta 0 on its uniform grid, or on `discretize` "quad") or "dpmpp_2m" (DPM-Solver++ 2M,
+        dpm_solver.py, on its log-SNR grid unless `discretize` names "uniform" / "quad"); ddim_steps is the step count asked of the grid."""
         self.ccdm, self.ldm, self.ddim_steps = ccdm, ldm, ddim_steps
-        self.sampler = DDIMSampler(ldm)
-        self.sampler.make_schedule(ddim_steps, ddim_eta=0.0, verbose=False)
+        check_sampler_options(sampler, discretize)
+        self.sampler_name = sampler
+        if sampler == "dpmpp_2m":
+            from .dpm_solver import DPMSolverSampler
+            self.discretize = discretize or "logsnr"
+            self.sampler = DPMSolverSampler(ldm)
+            self.sampler.make_schedule(ddim_steps, ddim_discretize=self.discretize, ddim_eta=0.0, verbose=False)
+        else:
+            self.discretize = discretize or "uniform"
+            self.sampler = DDIMSampler(ldm)
+            self.sampler.make_schedule(ddim_steps, ddim_discretize=self.discretize, ddim_eta=0.0, verbose=False)
         self.stats: Dict[str, float] = {}
         self.use_graph = True
         self._slice_graphs: Dict = {}
@@ -238,7 +266,8 @@ class GuideGenPipeline:
     @torch.no_grad()
     def time_slice_stages(self, N: int = 1, hw: int = 512) -> Dict[str, float]:
         """HIP-event times (ms) of the three per-slice stages on the engine's own buffers, as the slice loop runs them
-        (captured graphs when enabled): cond-encode, one DDIM step (average over the S steps of a slice), decode."""
+        (captured graphs when enabled): cond-encode, one sampler step (average over the steps of a slice: DDIM divides by the
+        ddim_steps asked for, as it always has; any other sampler by its chain's own count, `steps`), decode."""
         dev = self.ldm.device
         lat, Cz = hw // self.latent_factor, self.ldm.channels
         st = self.sampler.prepare_state(N, Cz, (lat, lat), dev, Cz)
@@ -266,7 +295,7 @@ class GuideGenPipeline:
             run(sg["dec"], sg["decode"])
             ev[3].record()
         torch.cuda.synchronize()
-        return {"encode_ms": ev[0].elapsed_time(ev[1]), "ddim_step_ms": ev[1].elapsed_time(ev[2]) / self.ddim_steps,
+        return {"encode_ms": ev[0].elapsed_time(ev[1]), "ddim_step_ms": ev[1].elapsed_time(ev[2]) / (self.ddim_steps if self.sampler_name == "ddim" else st["S"]),
                 "decode_ms": ev[2].elapsed_time(ev[3])}
 
     # ---- stage 2 ------------------------------------------------------------------------------------------------
@@ -579,9 +608,16 @@ def main(argv=None) -> None:
     ap.add_argument("--seed", type=int, default=1024)
     ap.add_argument("--max-slices", type=int, default=None, help="DEV ONLY: truncate the slice loop")
     ap.add_argument("--volumes-per-gpu", type=int, default=1, help="independent volumes per batch (groups of a rank's shard)")
+    ap.add_argument("--sampler", choices=SAMPLERS, default="ddim", help="latent sampler: DDIM at eta 0, or DPM-Solver++ 2M (about 20 steps)")
+    ap.add_argument("--discretize", choices=("uniform", "quad", "logsnr"), default=None,
+                    help="step grid (default: uniform for ddim, logsnr for dpmpp_2m; logsnr is the solver's own)")
     args = ap.parse_args(argv)
     if args.volumes_per_gpu < 1:
         ap.error("--volumes-per-gpu must be >= 1")
+    try:
+        check_sampler_options(args.sampler, args.discretize)
+    except ValueError as e:
+        ap.error(str(e))
     rank, local, world = ggd.env_rank_world()
     dry = os.environ.get("GG_PIPELINE_DRY") == "1"          # CPU rehearsal of the sharding (tests): no model, no GPU
     os.makedirs(args.out, exist_ok=True)
@@ -594,7 +630,9 @@ def main(argv=None) -> None:
         dev = torch.device("cuda", local)
         torch.cuda.set_device(dev)
         ggd.init("nccl", dev)
-        pipe = GuideGenPipeline(build_ccdm(args.classes, args.ccdm_steps, 1024, dev), build_ldm(1024, dev), ddim_steps=args.ddim_steps)
+        pipe = GuideGenPipeline(build_ccdm(args.classes, args.ccdm_steps, 1024, dev), build_ldm(1024, dev), ddim_steps=args.ddim_steps,
+                                sampler=args.sampler, discretize=args.discretize)
+        _log(f"latent sampler {pipe.sampler_name} on the {pipe.discretize} grid: {pipe.steps} steps per slice")
     t0 = time.time()
     B = args.volumes_per_gpu
     if B == 1:

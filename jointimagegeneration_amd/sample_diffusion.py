@@ -35,8 +35,12 @@ from .config import apply_dotlist, instantiate_from_config, load_yaml, merge
 from . import ops
 from .io import load_checkpoint, read_nifti, write_nifti, write_png
 from .ldm import DDIMSampler, PLMSSampler
+from .pipeline import DISCRETIZATIONS, check_sampler_options
 from .render import volume_png
 from .synth import randomize_parameters, synth_mask_volume
+
+
+SAMPLERS = tuple(DISCRETIZATIONS)                     # ddim, plms, dpmpp_2m
 
 
 def get_parser():
@@ -46,6 +50,10 @@ def get_parser():
     p.add_argument("-e", "--eta", type=float, nargs="?", default=0.0, help="eta for ddim sampling (0.0 yields deterministic sampling)")
     p.add_argument("-v", "--vanilla_sample", default=False, action="store_true", help="vanilla ancestral sampling (default: DDIM)")
     p.add_argument("--plms", default=False, action="store_true", help="PLMS sampler instead of DDIM")
+    p.add_argument("--sampler", choices=SAMPLERS, default=None, help="latent sampler (default ddim; --plms is --sampler plms): dpmpp_2m is "
+                   "DPM-Solver++ 2M, a second-order multistep solver meant for about 20 steps (-c 20), eta 0 only")
+    p.add_argument("--discretize", choices=("uniform", "quad", "logsnr"), default=None, help="step grid: uniform (the default of ddim / plms), "
+                   "quad, or logsnr (dpmpp_2m only, and its default: steps uniform in the log-SNR)")
     p.add_argument("-l", "--logdir", type=str, nargs="?", default="none", help="extra logdir")
     p.add_argument("-c", "--custom_steps", type=int, nargs="?", default=50, help="number of steps for ddim sampling")
     p.add_argument("--batch_size", type=int, nargs="?", default=1)
@@ -78,6 +86,29 @@ def get_parser():
     p.add_argument("--connectivity", type=int, default=None, help="with --inputs: 6 (faces, the default) or 26 (faces, edges, corners)")
     p.add_argument("--edit-margin", type=int, default=0, help="with --known-ct: latent cells within R cells of an un-kept pixel are regenerated too")
     return p
+
+
+def sampler_from_options(opt):
+    """(sampler name, grid or None) of --sampler / --plms / --discretize / -e, refused by name before a model is loaded."""
+    name = opt.sampler or ("plms" if opt.plms else "ddim")
+    if opt.plms and name != "plms":
+        raise SystemExit(f"--plms contradicts --sampler {name}")
+    try:
+        check_sampler_options(name, opt.discretize, SAMPLERS)
+    except ValueError as e:
+        raise SystemExit(f"--sampler / --discretize: {e}") from None
+    if name == "dpmpp_2m" and opt.eta != 0:
+        raise SystemExit(f"--sampler dpmpp_2m: eta = {opt.eta} is not supported (the solver is deterministic; -e must be 0)")
+    if name == "dpmpp_2m" and opt.vanilla_sample:
+        raise SystemExit("--sampler dpmpp_2m contradicts -v / --vanilla_sample (ancestral sampling)")
+    return name, opt.discretize
+
+
+def make_sampler(model, name: str):
+    if name == "dpmpp_2m":
+        from .dpm_solver import DPMSolverSampler
+        return DPMSolverSampler(model)
+    return PLMSSampler(model) if name == "plms" else DDIMSampler(model)
 
 
 def load_model_from_config(config, sd):
@@ -127,13 +158,16 @@ def stage1_mask_to_wholemask(labels, depth: int, hw: int) -> torch.Tensor:
 
 @torch.no_grad()
 def sample_cond(model, instance, n_samples=1, ddim_steps=50, ddim_eta=0.0, noise_seed=None, vanilla=False, plms=False, x_T_tape=None,
-                progress=None):
+                progress=None, sampler_name=None, discretize=None, record=None):
     """The reference slice loop (sample_diffusion.py:196-224) on the reference-shaped API. instance["wholemask"] is
     [1, D, H, W, 1] (label/255); returns pred [n, 2, D, H, W] = cat([samples, gen_mask]).  `x_T_tape` (parity runs): one
     [n, C, h, w] start latent per generated slice, in loop order, instead of the generator draw of ddim.py:124.  `progress` (a dict, with
     vanilla): the last slice is sampled by progressive_denoising(log_every_t=progress.get("log_every_t")) and its list of x_0 predictions
-    is left in progress["intermediates"]; the other slices, and every call without it, run as before."""
-    sampler = PLMSSampler(model) if plms else DDIMSampler(model)
+    is left in progress["intermediates"]; the other slices, and every call without it, run as before.  `sampler_name` ("ddim" | "plms" |
+    "dpmpp_2m"; None: `plms` decides) and `discretize` (None: the sampler's default grid) choose the sampler; `record` (a dict) receives
+    the sampler, the grid and the chain's own step count."""
+    sampler = make_sampler(model, sampler_name or ("plms" if plms else "ddim"))
+    grid = {} if discretize is None else {"ddim_discretize": discretize}
     with model.ema_scope():
         wholemask = instance["wholemask"].permute(0, 4, 1, 2, 3).cuda()
         nz = torch.where(wholemask.sum((0, 1, 3, 4)))[0]
@@ -158,9 +192,13 @@ def sample_cond(model, instance, n_samples=1, ddim_steps=50, ddim_eta=0.0, noise
                 s = model.p_sample_loop(c, (n_samples,) + shape, x_T=x_T, verbose=False)
             else:
                 s, _ = sampler.sample(S=ddim_steps, dims=len(shape) - 1, conditioning=c, batch_size=n_samples, shape=shape,
-                                      verbose=False, eta=ddim_eta, x_T=x_T)
+                                      verbose=False, eta=ddim_eta, x_T=x_T, **grid)
             ds = model.decode_first_stage(s)
             samples[:, :, m_] = (ds - ds.min()) / (ds.max() - ds.min())
+        if record is not None and not vanilla:
+            record.update(sampler=sampler_name or ("plms" if plms else "ddim"),
+                          discretize=discretize or ("logsnr" if sampler_name == "dpmpp_2m" else "uniform"), steps_asked=int(ddim_steps),
+                          steps=int(sampler.ddim_timesteps.shape[0]) if hasattr(sampler, "ddim_timesteps") else None)
         return torch.cat([samples, gen_mask], dim=1)
 
 
@@ -272,7 +310,11 @@ def main(argv=None):
         raise SystemExit("--progress-png goes with -v / --vanilla_sample (the denoise row comes from progressive_denoising)")
     if opt.log_every_t is not None and not opt.progress_png:
         raise SystemExit("--log-every-t goes with --progress-png")
+    sampler_name, discretize = sampler_from_options(opt)
     editing = check_edit_options(opt)
+    if editing and (sampler_name != "ddim" or discretize is not None):
+        raise SystemExit(f"--known-ct: --sampler {sampler_name} / --discretize is not supported (CT editing runs the DDIM sampler at eta 0 on its "
+                         "uniform grid)")
     cleanup = cleanup_from_options(opt)
     cleanup_docs = []
     scorer = None
@@ -321,6 +363,7 @@ def main(argv=None):
         jobs = [("sample", lab.float() / 255.0, opt.seed)]
     written = []
     edit_docs = []
+    sampler_doc = {}
     if editing:
         if getattr(model, "no_first_stage", False):
             raise SystemExit("--known-ct: a model without a first stage is not supported (the known slice is encoded by the first stage)")
@@ -343,7 +386,8 @@ def main(argv=None):
             continue
         progress = dict(log_every_t=opt.log_every_t) if opt.progress_png else None
         pred = sample_cond(model, instance, n_samples=opt.n_samples, ddim_steps=opt.custom_steps, ddim_eta=opt.eta, noise_seed=seed,
-                           vanilla=opt.vanilla_sample, plms=opt.plms, progress=progress)
+                           vanilla=opt.vanilla_sample, plms=opt.plms, progress=progress, sampler_name=sampler_name, discretize=discretize,
+                           record=sampler_doc)
         torch.cuda.synchronize()
         if progress is not None:
             write_png(os.path.join(out_dir, f"{stem}_progress.png"), model.denoise_row(progress["intermediates"], value_range=(-1.0, 1.0)).cpu().numpy())
@@ -353,12 +397,18 @@ def main(argv=None):
             if opt.png:
                 volume_png(render_input(x), os.path.join(out_dir, f"{stem}_{ix:04d}.png"))
         print(f"sampled {tuple(pred.shape)} in {time.time() - t0:.1f}s -> {out_dir}/{stem}_*.nii.gz", file=sys.stderr)
-    if scorer is not None or editing or cleanup is not None:
+        if sampler_doc:
+            print(f"sampler {sampler_doc['sampler']} on the {sampler_doc['discretize']} grid: {sampler_doc['steps']} steps per slice "
+                  f"({sampler_doc['steps_asked']} asked)", file=sys.stderr)
+    chosen = opt.sampler is not None or opt.discretize is not None          # an explicit choice is recorded even when nothing is scored
+    if scorer is not None or editing or cleanup is not None or (chosen and sampler_doc):
         import json
         doc = {}
         if scorer is not None:
             from .lpips import score_directory
             doc = score_directory(scorer.cuda(), written, opt.gt, torch.device("cuda"))
+        if sampler_doc:
+            doc["sampler"] = dict(sampler_doc)
         if editing:
             doc["edit"] = dict(edit_margin=opt.edit_margin, known_mask=opt.known_mask, keep_mask=opt.keep_mask, volumes=edit_docs)
         if cleanup is not None:
