@@ -112,6 +112,7 @@ class DPMSolverSampler(DDIMSampler):
         """DDIMSampler.make_schedule's tables on the solver's grid (`dpm_timesteps`); the chain's step count is the grid's own."""
         if ddim_eta != 0:
             raise ValueError(f"{type(self).__name__}: eta = {ddim_eta} is not supported (the solver is deterministic; eta must be 0)")
+        self._note_schedule(ddim_num_steps, ddim_discretize, ddim_eta)
         ac = self.model.alphas_cumprod.detach().cpu().float()
         assert ac.shape[0] == self.ddpm_num_timesteps, "alphas have to be defined for each timestep"
         ts = dpm_timesteps(ddim_discretize, int(ddim_num_steps), ac.numpy())

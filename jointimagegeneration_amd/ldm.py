@@ -15,6 +15,7 @@ Training and logging are out of scope.
 """
 from __future__ import annotations
 
+import weakref
 from contextlib import contextmanager
 from dataclasses import dataclass
 from typing import Any, Dict, List, Optional, Sequence
@@ -1632,14 +1633,33 @@ class DDIMSampler(object):
         self.fuse_ddim = True            # DDIM update as the UNet head conv's epilogue (deterministic steps)
         self.last_step_fused = False
         self._graphs: Dict[Any, Any] = {}
+        self._schedule_made = None       # (make_schedule's arguments, the alphas_cumprod buffer they were read from): refresh_schedule
 
     def register_buffer(self, name, attr):
         setattr(self, name, attr)
+
+    def _note_schedule(self, *args):
+        """make_schedule's arguments and the identity of the model's alphas_cumprod at that moment (the tensor object, weakly, with its
+        storage address and version counter: a freed buffer's address and version can come back, the object cannot)."""
+        ac = self.model.alphas_cumprod
+        self._schedule_made = (args, weakref.ref(ac), ac.data_ptr(), ac._version)
+
+    def refresh_schedule(self) -> None:
+        """Rebuild the schedule tables with make_schedule's last arguments if the model's alphas_cumprod is no longer the buffer they were
+        read from (register_schedule, a load_state_dict that carries another schedule): a sampler that lives on, as the pipeline's does,
+        otherwise keeps the alphas of the schedule it was built on.  Host-side identity checks only; no device work on a hit."""
+        if self._schedule_made is None:
+            return
+        args, ref, ptr, version = self._schedule_made
+        ac = self.model.alphas_cumprod
+        if ref() is not ac or ac.data_ptr() != ptr or ac._version != version:
+            self.make_schedule(*args, verbose=False)
 
     def make_schedule(self, ddim_num_steps, ddim_discretize="uniform", ddim_eta=0.0, verbose=True):
         """fp32 tables with the reference's numerics: a_t = acp[ts] (fp32), a_prev from fp32 values,
         sqrt(1-a_t) in fp32, sigmas in fp64 -> fp32 (ddim.py:24-53, util.py:46-74)."""
         ts = make_ddim_timesteps(ddim_discretize, ddim_num_steps, self.ddpm_num_timesteps, verbose=False)
+        self._note_schedule(ddim_num_steps, ddim_discretize, ddim_eta)
         ac = self.model.alphas_cumprod.detach().cpu().float()
         assert ac.shape[0] == self.ddpm_num_timesteps, "alphas have to be defined for each timestep"
         alphas = ac[ts]
@@ -1776,6 +1796,21 @@ class DDIMSampler(object):
             logs = (list(st["log_x"].clone().unbind(0)), list(st["log_p0"].clone().unbind(0)))
         return z, p0, logs
 
+    def state_token(self, vq=None, inpaint=False):
+        """What everything cached in a chain state is a function of: the schedule -- the steps, eta -> sigmas, and the VALUES of the step
+        scalar table (and of the q_sample table of an inpainting state): at eta = 0 another schedule under the same step count has the
+        same timesteps and sigmas, and its alphas are buffers, which `ops.weights_token` does not count --, the UNet's weights (time-bias
+        table, packed weights baked into the captured graph), whether the head conv takes the DDIM update (read while the chain is
+        captured), and the codebook's identity on a quantising state."""
+        unet = self.model.model.diffusion_model
+        token = (self.ddim_timesteps.shape[0], tuple(int(v) for v in self.ddim_timesteps), tuple(float(v) for v in self.ddim_sigmas),
+                 ops.weights_token(unet), bool(self.fuse_ddim), self.step_scalar_table().numpy().tobytes())
+        if inpaint:
+            token = token + (self.q_sample_scalar_table().numpy().tobytes(),)
+        if vq is not None and vq[0] is not None:
+            token = token + ((vq[0].data_ptr(), vq[0]._version, tuple(vq[0].shape)),)
+        return token
+
     def prepare_state(self, N, Cx, sp, dev, Cc, ctx_shape=None, *, mask_C=0, vq=None, logged=None):
         """Static buffers (and the captured graph) of one chain shape.  mask_C > 0: the inpainting state of a mask with mask_C channels --
         static fp32 CL buffers for x0 [M, Cx], the mask [M, mask_C] and the per-step q_sample noise [S, M, Cx], plus the [S, 2] q_sample
@@ -1788,6 +1823,7 @@ class DDIMSampler(object):
         key, so an unlogged call never sees this state or its graph."""
         unet = self.model.model.diffusion_model
         sp3 = (1,) * (3 - len(sp)) + tuple(sp)
+        self.refresh_schedule()
         S = self.ddim_timesteps.shape[0]
         key = (N, Cx, sp3, Cc, str(dev), ctx_shape) + tuple(self.state_tag) + ((("inpaint", mask_C),) if mask_C else ())
         if vq is not None:
@@ -1798,11 +1834,8 @@ class DDIMSampler(object):
         if par is not None:            # patch-wise eps: a state of its own (crop buffers, time-bias rows for L * N), keyed by the geometry
             key = key + (("split",) + tuple((k, str(par.get(k))) for k in ("ks", "stride", "tie_braker", "clip_min_weight", "clip_max_weight",
                                                                           "clip_min_tie_weight", "clip_max_tie_weight")),)
-        # everything cached below is a function of the schedule (steps, eta -> sigmas) and of the UNet's weights (time-bias
-        # table, packed weights baked into the captured graph): a changed schedule or weight version rebuilds the state
-        token = (S, tuple(int(v) for v in self.ddim_timesteps), tuple(float(v) for v in self.ddim_sigmas), ops.weights_token(unet))
-        if vq is not None and vq[0] is not None:
-            token = token + ((vq[0].data_ptr(), vq[0]._version, tuple(vq[0].shape)),)
+        # everything cached below is a function of what the token holds: a changed schedule or weight version rebuilds the state
+        token = self.state_token(vq, bool(mask_C))
         st = self._graphs.get(key)
         if st is not None and st["token"] == token:
             if vq is not None:
@@ -1993,12 +2026,14 @@ class DDIMSampler(object):
             self._blend(st, i)
             self._step(st, ctx_cl, st["table"][i], st["scal"][i], None)
             self._after_step(st, i)
+        st["fused"] = self.last_step_fused
 
     def run_steps(self, st, ctx_cl, eta, noise_tape, noise_dropout=0.0):
         S = st["S"]
         if self.chain_graphable(st, ctx_cl, eta, noise_tape):
             # first call: eager (fills the weight-repack caches); afterwards ONE hipGraph replay per chain
             ops.replay_captured(st, "graph", lambda: self.chain(st, ctx_cl))
+            self.last_step_fused = st["fused"]          # a replay runs no host code: what the captured steps did
             return
         for i in range(S):
             noise = self._noise(st, i, eta, noise_tape, noise_dropout)

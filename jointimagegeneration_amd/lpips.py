@@ -136,9 +136,16 @@ class LPIPS(nn.Module):
     def _convs(self) -> List[List[_Conv]]:
         return [[getattr(getattr(self.net, f"slice{k}"), str(i)) for i in idxs] for k, idxs in enumerate(VGG_SLICES, 1)]
 
+    def _pack_key(self):
+        """The precision mode, the weights' token and the identity of the scaling layer's shift / scale: those two are buffers, which
+        `ops.weights_token` does not count, and the pack holds copies of them."""
+        sc = self.scaling_layer
+        return (ops.FP32, ops.weights_token(self)) + tuple((b.data_ptr(), b._version) for b in (sc.shift, sc.scale))
+
     def _packed(self):
-        """Per precision mode: ([[(packed weight, padded bias, cout)]], [lin weights fp32 [C]], shift[3], scale[3]); rebuilt when the weights change."""
-        key = (ops.FP32, ops.weights_token(self))
+        """Per precision mode: ([[(packed weight, padded bias, cout)]], [lin weights fp32 [C]], shift[3], scale[3]); rebuilt when the
+        weights or the scaling buffers change."""
+        key = self._pack_key()
         hit = self._packs.get(ops.FP32)
         if hit is None or hit[0] != key:
             convs = [[(ops.pack_conv_weight(c.weight, ops.pad32(c.weight.shape[1])), ops.pad_bias(c.bias, c.weight.shape[0], c.weight.device),

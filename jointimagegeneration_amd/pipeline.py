@@ -224,7 +224,11 @@ class GuideGenPipeline:
         its "encode" and "decode"."""
         ldm = self.ldm
         lat, Cz = hw // self.latent_factor, ldm.channels
-        token = (id(st), ops.weights_token(ldm.cond_stage_model), ops.weights_token(ldm.first_stage_model))
+        # decode_head divides by scale_factor: a Python float is folded into the captured launch, the scale_by_std buffer is read by it
+        # in place -- so the float's value, or the buffer's identity (address and version), joins the token
+        sf = ldm.scale_factor
+        sf = (sf.data_ptr(), sf._version) if isinstance(sf, torch.Tensor) else float(sf)
+        token = (id(st), ops.weights_token(ldm.cond_stage_model), ops.weights_token(ldm.first_stage_model), sf)
         eng = cache.get(key)
         if eng is not None and eng["token"] == token:
             return eng
