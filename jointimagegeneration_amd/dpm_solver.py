@@ -28,6 +28,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .chain import rows
 from .ldm import DDIMSampler, make_ddim_timesteps
 
 DISCRETIZATIONS = ("uniform", "quad", "logsnr")
@@ -92,6 +93,7 @@ class DPMSolverSampler(DDIMSampler):
     the prediction of x_0), and `sample(clip_denoised=True)` clamps that prediction to [-1, 1]."""
 
     parameterizations = ("eps", "x0")
+    head_update_is_ddim = False           # the head conv's epilogue is DDIM's update: never asked for here, whatever fuse_ddim says
 
     def __init__(self, model, order=2, lower_order_final=True, **kwargs):
         if isinstance(order, bool) or order not in (1, 2):
@@ -99,7 +101,7 @@ class DPMSolverSampler(DDIMSampler):
         super().__init__(model, **kwargs)
         self.order = int(order)
         self.lower_order_final = bool(lower_order_final)
-        self.fuse_ddim = False                # the head conv's epilogue is DDIM's update: never asked for here
+        self.fuse_ddim = False
         self.clip_denoised = False
         self.ddim_discretize = None
 
@@ -169,29 +171,22 @@ class DPMSolverSampler(DDIMSampler):
             self.clip_denoised = keep
 
     def prepare_state(self, N, Cx, sp, dev, Cc, ctx_shape=None, *, mask_C=0, vq=None, logged=None):
-        """DDIMSampler.prepare_state under this sampler's `state_tag`, with the six-column scalar table and "hist", the fp32 CL buffer of
-        the previous step's prediction of x_0.  A captured chain needs no reset of it: its first step is first order and does not read it."""
+        """DDIMSampler.prepare_state, with sample()'s refusals of what the solver cannot run for a caller that asks for such a state directly."""
         if vq is not None:
             raise NotImplementedError(f"{type(self).__name__}: quantize_x0 / temperature are not supported")
         if getattr(self.model, "split_input_params", None) is not None:
             raise NotImplementedError(f"{type(self).__name__}: split_input_params (patch-wise evaluation) is not supported")
-        st = super().prepare_state(N, Cx, sp, dev, Cc, ctx_shape, mask_C=mask_C, logged=logged)
-        if "hist" not in st:
-            st["hist"] = torch.empty_like(st["pred_x0"])
-        return st
+        return super().prepare_state(N, Cx, sp, dev, Cc, ctx_shape, mask_C=mask_C, logged=logged)
 
-    def _step(self, st, ctx_cl, bias, scal, noise):
-        """One reverse step on the state's buffers: the UNet's output as it is (the head conv never fuses an update), then the solver."""
-        self._eps(st, st["unet_in"], bias, ctx_cl, st["eps"])
-        self.last_step_fused = False
-        self._update(st, st["eps"], scal, noise)
+    def extend_state(self, st):
+        """"hist": the fp32 CL buffer of the previous step's prediction of x_0.  A captured chain needs no reset of it: its first step is
+        first order and does not read it."""
+        st["hist"] = torch.empty_like(st["pred_x0"])
 
     def _update(self, st, eps, scal, noise=None):
         """The solver's update as one launch on the state's buffers (gg_dpm_solver_step); `scal` is a row of the six-column table."""
         if noise is not None:
             raise NotImplementedError(f"{type(self).__name__}: a step with noise (eta != 0 or a noise_tape) is not supported")
-        Cx = st["Cx"]
-        M = st["x"].numel() // Cx
-        ops.dpm_solver_step(st["x"].view(M, Cx), eps.view(M, -1), scal, st["hist"].view(M, Cx),
-                            predicts_x0=getattr(self.model, "parameterization", "eps") == "x0", clip=bool(self.clip_denoised),
-                            pred_x0_out=st["pred_x0"].view(M, Cx), unet_in=st["unet_in"].view(M, -1))
+        x, out, hist, p0, uin = rows(st, "x", eps, "hist", "pred_x0", "unet_in")
+        ops.dpm_solver_step(x, out, scal, hist, predicts_x0=getattr(self.model, "parameterization", "eps") == "x0", clip=bool(self.clip_denoised),
+                            pred_x0_out=p0, unet_in=uin)

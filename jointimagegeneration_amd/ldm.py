@@ -10,7 +10,7 @@ Volumetric first stages (dims = 3; model.py:42-83,154-206, autoencoder.py:36-52,
 AttnBlock3d, a trailing pad of one on D, H and W in front of the stride-2 conv and an x2 upsample of D, H and W; the samplers carry
 [N, C, D, H, W] latents through the same row kernels.
 VQ first stage: ldm/models/autoencoder.py:18-131,283-301,464-481 (VQModel, VQModelInterface, IdentityFirstStage) with taming's
-VectorQuantizer.  Patch-wise evaluation (`split_input_params`, ddpm.py:573-660,718-776,839-876,915-997): SplitPlan / SplitUNet below.
+VectorQuantizer.  Patch-wise evaluation (`split_input_params`, ddpm.py:573-660,718-776,839-876,915-997): SplitPlan below, SplitUNet and the samplers' chain state in chain.py.
 Training and logging are out of scope.
 """
 from __future__ import annotations
@@ -24,20 +24,12 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from . import chain as cs
 from . import ops
 from .blocks import AEDownsample, AEUpsample, AttnBlock2d, AttnBlock3d, Normalize, ResnetBlock, conv_nd, conv_of
+from .chain import SplitUNet, inpaint_operands, logged_steps, nc_to_rows, rows_to_nc, split_cond
 from .config import instantiate_from_config
 from .ops import CL, pad32
-
-
-def nc_to_rows(t: torch.Tensor) -> torch.Tensor:
-    """[N, C, *sp] -> [N, *sp, C], the channels-last view (a permutation, no copy)."""
-    return t.permute((0,) + tuple(range(2, t.ndim)) + (1,))
-
-
-def rows_to_nc(t: torch.Tensor) -> torch.Tensor:
-    """[N, *sp, C] -> [N, C, *sp], the inverse view."""
-    return t.permute((0, t.ndim - 1) + tuple(range(1, t.ndim - 1)))
 
 
 def cut_cond(cond, batch_size: int):
@@ -47,22 +39,6 @@ def cut_cond(cond, batch_size: int):
     if isinstance(cond, dict):
         return {key: cond[key][:batch_size] if not isinstance(cond[key], list) else [c[:batch_size] for c in cond[key]] for key in cond}
     return [c[:batch_size] for c in cond] if isinstance(cond, list) else cond[:batch_size]
-
-
-def split_cond(conditioning, conditioning_key):
-    """-> (c_concat, context) of a conditioning: a dict as the reference's apply_model takes it (c_concat's first entry, c_crossattn
-    concatenated), or a bare tensor read by the model's conditioning key."""
-    c_concat, context = None, None
-    if conditioning is not None:
-        if isinstance(conditioning, dict):
-            c_concat = conditioning.get("c_concat", [None])[0]
-            cc = conditioning.get("c_crossattn")
-            context = torch.cat(cc, 1) if cc else None
-        elif conditioning_key == "concat":
-            c_concat = conditioning
-        elif conditioning_key == "crossattn":
-            context = conditioning
-    return c_concat, context
 
 
 # ================================================================================================ autoencoder
@@ -567,15 +543,6 @@ def make_beta_schedule(schedule, n_timestep, linear_start=1e-4, linear_end=2e-2,
     raise ValueError(f"schedule '{schedule}' unknown.")
 
 
-def logged_steps(n: int, log_every_t: int) -> List[int]:
-    """The loop values at which the reference's samplers append to their intermediates, in loop order (n - 1 down to 0): the timestep i
-    of p_sample_loop / progressive_denoising (ddpm.py:1172,1220), the index of DDIM / PLMS (ddim.py:160, plms.py:166)."""
-    k = int(log_every_t)
-    if k < 1:
-        raise ValueError(f"log_every_t = {log_every_t} must be a positive integer")
-    return [i for i in range(n - 1, -1, -1) if i % k == 0 or i == n - 1]
-
-
 class LitEma(nn.Module):
     """EMA shadow buffers with the reference's name mangling ('.' removed, ema.py:15-22) so that checkpoints load."""
 
@@ -682,70 +649,6 @@ class SplitPlan:
         if key not in cache:
             cache[key] = (self.weight.to(device).contiguous(), self.tie.to(device).contiguous() if self.tie is not None else None)
         return cache[key]
-
-
-class SplitUNet:
-    """The UNet evaluated on overlapping crops (apply_model with split_input_params, ddpm.py:915-997): per call one gg_unfold_cl of the
-    fp32 state into the crop batch's UNet input (fp32 -> bf16, channels [0, Cx)), ONE UNet forward at batch L * N (crop l of sample n at
-    row l * N + n; every layer is per sample, so this is the reference's loop over crops), one gg_fold_weighted_cl of the head conv's
-    fp32 output into the full-size eps.  Concat conditioning is cut into crops once per `bind`, cross-attention context is repeated per
-    crop.  All buffers are static, so a chain of calls is capturable."""
-
-    def __init__(self, model, N: int, Cx: int, Cc: int, sp: Sequence[int], device):
-        if len(sp) != 2:
-            raise NotImplementedError(f"split_input_params: the patch-wise path is 2-D, the latent has spatial shape {tuple(sp)}")
-        par = model.split_input_params
-        self.plan = model.get_fold_unfold((N, Cx) + tuple(sp), par["ks"], par["stride"])
-        self.N, self.Cx, self.Cc, self.device = N, Cx, Cc, device
-        self.B = self.plan.L * N
-        unet = model.model.diffusion_model
-        p = self.plan
-        self.eps = torch.empty((self.B, 1, p.kh, p.kw, pad32(unet.out_channels)), dtype=torch.float32, device=device)
-        self.inputs: Dict[int, Any] = {}
-        self.contexts: Dict[int, Any] = {}
-
-    def time_bias_table(self, unet, steps: torch.Tensor) -> torch.Tensor:
-        return unet.time_bias_table(steps, self.B)          # the rows of a step are equal for all samples: repeated per crop
-
-    def bind(self, uin: torch.Tensor, ctx: Optional[CL] = None):
-        """(Re)cut the concat conditioning held in channels [Cx, Cx + Cc) of the full-size UNet input `uin` into the crop batch's input
-        buffer, and repeat the context per crop.  Outside any graph; the buffers keep their addresses.  One crop buffer is kept per
-        distinct `uin` (and one repeated context per distinct `ctx`) for as long as this object lives, so a caller that keeps the
-        SplitUNet binds static buffers of its own, never per-call temporaries."""
-        p = self.plan
-        ent = self.inputs.get(id(uin))
-        if ent is None or ent[0] is not uin:
-            ent = (uin, torch.zeros((self.B, 1, p.kh, p.kw, uin.shape[-1]), dtype=uin.dtype, device=uin.device))
-            self.inputs[id(uin)] = ent
-        if self.Cc:
-            src = uin.view(self.N, p.H, p.W, uin.shape[-1])[..., self.Cx:self.Cx + self.Cc]
-            ops.unfold_cl(src, self.Cc, p.kh, p.kw, p.sy, p.sx, out=ent[1].view(self.B, p.kh, p.kw, -1), c_offset=self.Cx)
-        if ctx is not None:
-            c = self.contexts.get(id(ctx.t))
-            if c is None or c[0] is not ctx.t:
-                c = (ctx.t, CL(ctx.t.repeat((p.L,) + (1,) * (ctx.t.dim() - 1)), ctx.C))
-                self.contexts[id(ctx.t)] = c
-            else:
-                c[1].t.copy_(ctx.t.repeat((p.L,) + (1,) * (ctx.t.dim() - 1)))
-
-    def __call__(self, unet, x: torch.Tensor, uin: torch.Tensor, bias_row: torch.Tensor, ctx: Optional[CL], out: torch.Tensor) -> None:
-        p = self.plan
-        buf = self.inputs[id(uin)][1]
-        ops.unfold_cl(x.view(self.N, p.H, p.W, self.Cx), self.Cx, p.kh, p.kw, p.sy, p.sx, out=buf.view(self.B, p.kh, p.kw, -1), c_offset=0)
-        unet.forward_cl(CL(buf, self.Cx + self.Cc), bias_row, self.contexts[id(ctx.t)][1] if ctx is not None else None, head_out=self.eps)
-        w, t = p.on(self.eps.device)
-        ops.fold_weighted_cl(self.eps.view(self.B, p.kh, p.kw, -1), unet.out_channels, w, t, out.view(self.N, p.H, p.W, -1),
-                             p.kh, p.kw, p.sy, p.sx)
-
-
-def unet_eps(unet, split: Optional[SplitUNet], x: torch.Tensor, uin: torch.Tensor, C: int, bias_row: torch.Tensor, ctx: Optional[CL],
-             out: torch.Tensor, head_ddim: Optional[tuple] = None) -> Optional[CL]:
-    """The one place where the samplers obtain eps: the UNet on the full-size input `uin` (returns the head conv's CL, whose epilogue may
-    have applied the DDIM update), or with `split` on crops of the fp32 state `x`, folded into `out` (returns None: no fused update)."""
-    if split is None:
-        return unet.forward_cl(CL(uin, C), bias_row, ctx, head_out=out, head_ddim=head_ddim)
-    split(unet, x, uin, bias_row, ctx, out)
-    return None
 
 
 class DiffusionWrapper(nn.Module):
@@ -970,7 +873,6 @@ class GaussianDiffusion(nn.Module):
         unet = self.model.diffusion_model
         N, Cx = shape[0], shape[1]
         sp = tuple(shape[2:])
-        sp3 = (1,) * (3 - len(sp)) + sp
         if mask is not None and x0 is not None and tuple(x0.shape[2:3]) != tuple(mask.shape[2:3]):
             raise ValueError(f"{who}: x0 {tuple(x0.shape)} and mask {tuple(mask.shape)} differ in spatial size "
                              "(ddpm.py:1200 asserts x0.shape[2:3] == mask.shape[2:3])")
@@ -984,70 +886,50 @@ class GaussianDiffusion(nn.Module):
         elif float(temperature) != 1.0:
             per_step_temp = [float(temperature)] * T
         c_concat, context = split_cond(cond, self.model.conditioning_key)
-        Cc = c_concat.shape[1] if c_concat is not None else 0
         img = torch.randn(tuple(shape), device=dev) if x_T is None else x_T.to(dev).float()
-        x = nc_to_rows(img).contiguous().view((N,) + sp3 + (Cx,))
-        unet_in = torch.zeros((N,) + sp3 + (pad32(Cx + Cc),), dtype=torch.bfloat16, device=dev)
-        ops.to_cl(img, out=unet_in, c_offset=0, zero_fill=False)
-        if c_concat is not None:
-            ops.to_cl(c_concat.float(), out=unet_in, c_offset=Cx, zero_fill=False)
-        ctx_cl = unet.context_cl(context) if context is not None else None
         ts = torch.arange(T - 1, -1, -1, device=dev)
-        split = None
-        if hasattr(self, "split_input_params"):                      # patch-wise eps (ddpm.py:915-997): crops of x, one UNet forward, fold
-            split = SplitUNet(self, N, Cx, Cc, sp, dev)
-            split.bind(unet_in, ctx_cl)
-        table = unet.time_bias_table(ts.float(), N) if split is None else split.time_bias_table(unet, ts.float())
         sig = torch.exp(0.5 * self.posterior_log_variance_clipped[ts]) * (ts > 0).float()
         scal = torch.stack([self.sqrt_recip_alphas_cumprod[ts], self.sqrt_recipm1_alphas_cumprod[ts], self.posterior_mean_coef1[ts],
                             self.posterior_mean_coef2[ts], sig], 1).float().contiguous()
-        eps = torch.empty((N,) + sp3 + (pad32(unet.out_channels),), dtype=torch.float32, device=dev)
-        M = x.numel() // Cx
+        qscal = torch.stack([self.sqrt_alphas_cumprod[ts], self.sqrt_one_minus_alphas_cumprod[ts]], 1).contiguous() if ip is not None else None
+        # an uncached chain state (chain.py): no q_sample noise ahead of the chain (each step draws its own), one log buffer
+        st = cs.new_state(self, N, Cx, c_concat.shape[1] if c_concat is not None else 0, sp, dev, scal,
+                          ctx_shape=tuple(context.shape[1:]) if context is not None else None, inpaint=(ip[2], qscal, 0) if ip is not None else None,
+                          logged=logged or None, log_of=("pred_x0",) if log_x0 else ("x",))
+        cs.load(st, img, c_concat, context)
+        if ip is not None:
+            cs.load_inpaint(st, ip[0], ip[1])
+        cs.set_bias_table(st, unet, ts.float())
         want_x0 = bool(log_x0 and logged)
         vq_split = codebook is not None and (px0 or clip)        # gg_ddim_step_vq quantises the unclipped eps prediction: three launches instead
-        p0 = torch.empty_like(x) if (want_x0 or vq_split) else None
+        x, eps, p0, uin = cs.rows(st, "x", "eps", "pred_x0", "unet_in")
         x_keep = torch.empty_like(x) if vq_split else None
-        log = torch.empty((len(logged), N, Cx) + sp, dtype=torch.float32, device=dev) if logged else None      # the pre-allocated log buffer
-        slot = {t: j for j, t in enumerate(logged)}
-        if ip is not None:
-            x0_cl = nc_to_rows(ip[0].to(dev)).contiguous()
-            mask_cl = nc_to_rows(ip[1].to(dev)).contiguous()
-            qscal = torch.stack([self.sqrt_alphas_cumprod[ts], self.sqrt_one_minus_alphas_cumprod[ts]], 1).contiguous()
         for i in range(T):
             t = T - 1 - i
-            unet_eps(unet, split, x, unet_in, Cx + Cc, table[i], ctx_cl, eps)
-            nz = noise_tape[i].to(dev).float() if noise_tape is not None else torch.randn_like(x)
-            if per_step_temp is not None:                # host-side ops on the noise as given (the tape's [N, C, *sp] tensor, or the draw)
-                nz = nz * per_step_temp[t]
-            if noise_dropout > 0.0:
-                nz = torch.nn.functional.dropout(nz, p=float(noise_dropout))
-            if noise_tape is not None:
-                nz = nc_to_rows(nz).contiguous()
+            cs.unet_eps(st, unet, st["unet_in"], st["table"][i], st["ctx"], st["eps"])
+            # host-side ops on the noise as given (the tape's [N, C, *sp] tensor, or the draw): temperature, then dropout
+            nz = cs.rows(st, cs.step_noise(st, i, noise_tape, True, float(noise_dropout), per_step_temp[t] if per_step_temp is not None else None))
             if vq_split:
                 # x_recon (x0 / clip) on a scratch copy of x -> quantised in place -> the posterior mean and noise with x_recon given
                 x_keep.copy_(x)
-                ops.ddpm_step_x0(x_keep.view(M, Cx), eps.view(M, -1), scal[i], predicts_x0=px0, clip=clip, pred_x0_out=p0.view(M, Cx))
-                ops.vq_nearest(p0.view(M, Cx), codebook, Cx, st_out=p0.view(M, Cx))
-                ops.ddpm_step_x0(x.view(M, Cx), p0.view(M, Cx), scal[i], noise=nz.view(M, Cx), predicts_x0=True, unet_in=unet_in.view(M, -1))
+                ops.ddpm_step_x0(x_keep, eps, scal[i], predicts_x0=px0, clip=clip, pred_x0_out=p0)
+                ops.vq_nearest(p0, codebook, Cx, st_out=p0)
+                ops.ddpm_step_x0(x, p0, scal[i], noise=nz, predicts_x0=True, unet_in=uin)
             elif codebook is not None:
-                ops.ddim_step_vq(x.view(M, Cx), eps.view(M, -1), scal[i], codebook, noise=nz.view(M, Cx),
-                                 pred_x0_out=p0.view(M, Cx) if want_x0 else None, unet_in=unet_in.view(M, -1), ancestral=True)
+                ops.ddim_step_vq(x, eps, scal[i], codebook, noise=nz, pred_x0_out=p0 if want_x0 else None, unet_in=uin, ancestral=True)
             elif px0 or clip or want_x0:
-                ops.ddpm_step_x0(x.view(M, Cx), eps.view(M, -1), scal[i], noise=nz.view(M, Cx), predicts_x0=px0, clip=clip,
-                                 pred_x0_out=p0.view(M, Cx) if want_x0 else None, unet_in=unet_in.view(M, -1))
+                ops.ddpm_step_x0(x, eps, scal[i], noise=nz, predicts_x0=px0, clip=clip, pred_x0_out=p0 if want_x0 else None, unet_in=uin)
             else:
-                ops.ddpm_step(x.view(M, Cx), eps.view(M, -1), scal[i], noise=nz.view(M, Cx), unet_in=unet_in.view(M, -1))
-            if ip is not None:
-                nm = nc_to_rows(mask_noise_tape[i].to(dev).float()).contiguous() if mask_noise_tape is not None else torch.randn_like(x)
-                ops.inpaint_blend(x.view(M, Cx), x0_cl.view(M, Cx), mask_cl.view(M, -1), nm.view(M, Cx), qscal[i], unet_in=unet_in.view(M, -1))
-            if t in slot:
-                ops.log_rows((p0 if log_x0 else x).view(M, Cx), N, log[slot[t]])
+                ops.ddpm_step(x, eps, scal[i], noise=nz, unet_in=uin)
+            if ip is not None:                            # the blend follows the step (ddpm.py:1201-1218), on a fresh q_sample noise
+                cs.blend(st, i, cs.step_noise(st, i, mask_noise_tape, True))
+            cs.after_step(st, i)
             if callback:
                 callback(t)
             if img_callback:
-                img_callback(rows_to_nc(x.view((N,) + sp + (Cx,))).contiguous(), t)
-        out = rows_to_nc(x.view((N,) + sp + (Cx,))).contiguous()
-        return out, img, (list(log.unbind(0)) if logged else [])
+                img_callback(cs.to_nc(st, "x"), t)
+        log = st.get("log_p0" if log_x0 else "log_x")
+        return cs.to_nc(st, "x"), img, (list(log.unbind(0)) if log is not None else [])
 
 
 class LatentDiffusion(GaussianDiffusion):
@@ -1567,41 +1449,6 @@ class DDPM(GaussianDiffusion):
         return self.p_sample_loop((batch_size, self.channels) + tuple(size), return_intermediates=return_intermediates, **kwargs)
 
 
-def inpaint_operands(mask, x0, shape, tape=None, steps=0):
-    """Host-side validation of the inpainting operands of the samplers (ddim.py:144-148, plms.py:147-150, ddpm.py:1201-1218), run
-    before any launch.  Returns None without a mask (x0 alone is ignored, as in the reference); else (x0 fp32 [N, C, *sp],
-    mask fp32 [N, Cm, *sp], Cm) as broadcast views, Cm = the mask's channel extent (1 or C).  Bool / integer masks are cast to fp32.
-    `tape` (optional): at least `steps` q_sample noises of shape [N, C, *sp].  Anything else raises ValueError naming the shapes."""
-    if mask is None:
-        return None
-    if x0 is None:
-        raise ValueError("inpainting: mask= was given without x0= (the latent whose mask = 1 region is kept)")
-    if not isinstance(mask, torch.Tensor) or not isinstance(x0, torch.Tensor):
-        raise ValueError(f"inpainting: mask and x0 must be tensors, got {type(mask).__name__} and {type(x0).__name__}")
-    full = tuple(int(s) for s in shape)
-    N, C = full[:2]
-
-    def fits(t):
-        try:
-            return tuple(torch.broadcast_shapes(tuple(t.shape), full)) == full
-        except RuntimeError:
-            return False
-    if x0.is_complex() or not fits(x0):
-        raise ValueError(f"inpainting: x0 of shape {tuple(x0.shape)} ({x0.dtype}) does not broadcast to the latent shape {full}")
-    if mask.is_complex() or not fits(mask):
-        raise ValueError(f"inpainting: mask of shape {tuple(mask.shape)} ({mask.dtype}) does not broadcast to the latent shape {full}")
-    ch = mask.ndim - (len(full) - 1)                  # the mask's channel axis once right-aligned against [N, C, *sp]
-    Cm = int(mask.shape[ch]) if ch >= 0 else 1
-    m = mask.float().reshape((1,) * (len(full) - mask.ndim) + tuple(mask.shape)).expand((N, Cm) + full[2:])
-    if tape is not None:
-        if len(tape) < steps:
-            raise ValueError(f"inpainting: mask_noise_tape holds {len(tape)} tensors, the schedule has {steps} steps")
-        for i in range(steps):
-            if tuple(tape[i].shape) != full:
-                raise ValueError(f"inpainting: mask_noise_tape[{i}] has shape {tuple(tape[i].shape)}, the latent is {full}")
-    return x0.float().expand(full), m, Cm
-
-
 # ================================================================================================ DDIM
 def make_ddim_timesteps(ddim_discr_method, num_ddim_timesteps, num_ddpm_timesteps, verbose=True):
     """ldm/modules/diffusionmodules/util.py:46-59 (both discretisations; + 1 "to get the final alpha values right")."""
@@ -1620,10 +1467,14 @@ class DDIMSampler(object):
     LatentDiffusion models it runs entirely channels-last on the GPU: per step one UNet forward + one fused update
     kernel, captured in a hipGraph; any other `model` object only needs `apply_model` etc. (eager path)."""
 
-    # hooks of the subclasses (dpm_solver.py): the parameterizations whose output the update can read, and what a sampler adds to the
-    # key of its chain states
+    # hooks of the subclasses (dpm_solver.py): the parameterizations whose output the update can read, what a sampler adds to the key
+    # of its chain states, a method (st) that adds its own buffers to a freshly built state, and whether `_update` is the DDIM update,
+    # which the head conv's epilogue can apply in its place (a property of the class: `fuse_ddim` only switches it off)
     parameterizations = ("eps",)
     state_tag = ()
+    extend_state = None
+    head_update_is_ddim = True
+    load_state = staticmethod(cs.load)           # for callers that drive a state by hand
 
     def __init__(self, model, schedule="linear", **kwargs):
         self.model = model
@@ -1768,33 +1619,26 @@ class DDIMSampler(object):
     # ---- channels-last fast path -------------------------------------------------------------------------
     def _sample_cl(self, x_T: torch.Tensor, conditioning, eta: float, noise_tape, cfg=None, inpaint=None, mask_noise_tape=None, *, vq=None,
                    noise_dropout=0.0, logged=None, callbacks=None):
-        model = self.model
-        unet = model.model.diffusion_model
-        ck = model.model.conditioning_key
-        dev = x_T.device
         N, Cx = x_T.shape[:2]
-        sp = tuple(x_T.shape[2:])
-        c_concat, context = split_cond(conditioning, ck)
-        st = self.prepare_state(N, Cx, sp, dev, c_concat.shape[1] if c_concat is not None else 0,
+        c_concat, context = split_cond(conditioning, self.model.model.conditioning_key)
+        st = self.prepare_state(N, Cx, tuple(x_T.shape[2:]), x_T.device, c_concat.shape[1] if c_concat is not None else 0,
                                 ctx_shape=tuple(context.shape[1:]) if context is not None else None, mask_C=inpaint[2] if inpaint else 0, vq=vq,
                                 logged=logged)
-        self.load_state(st, x_T, c_concat, context)
+        cs.load(st, x_T, c_concat, context)
         if inpaint is not None:
-            self.load_inpaint(st, inpaint[0], inpaint[1], mask_noise_tape)
+            cs.load_inpaint(st, inpaint[0], inpaint[1], mask_noise_tape)
         st["callbacks"] = callbacks                      # host calls between the steps: such a chain runs eagerly (chain_graphable)
         try:
             if cfg is not None:
-                self._run_steps_cfg(st, x_T, cfg, eta, noise_tape, noise_dropout)
+                self._run_steps_cfg(st, cfg, eta, noise_tape, noise_dropout)
             else:
                 self.run_steps(st, st["ctx"], eta, noise_tape, noise_dropout)
         finally:
             st["callbacks"] = None
-        z = rows_to_nc(st["x"].view((N,) + sp + (Cx,))).contiguous()
-        p0 = rows_to_nc(st["pred_x0"].view((N,) + sp + (Cx,))).contiguous()
         logs = None
         if logged is not None:                           # copies: the state's log buffers are rewritten by the next logged call
             logs = (list(st["log_x"].clone().unbind(0)), list(st["log_p0"].clone().unbind(0)))
-        return z, p0, logs
+        return cs.to_nc(st, "x"), cs.to_nc(st, "pred_x0"), logs
 
     def state_token(self, vq=None, inpaint=False):
         """What everything cached in a chain state is a function of: the schedule -- the steps, eta -> sigmas, and the VALUES of the step
@@ -1811,235 +1655,120 @@ class DDIMSampler(object):
             token = token + ((vq[0].data_ptr(), vq[0]._version, tuple(vq[0].shape)),)
         return token
 
+    def state_key(self, N, Cx, sp3, Cc, dev, ctx_shape, mask_C, vq, logged):
+        """The key of a chain state in `_graphs`: the chain's shape, the sampler's `state_tag`, and one entry per option that gives the
+        state other buffers or another launch sequence, so that a call without the option never sees that state or its graph."""
+        key = (N, Cx, sp3, Cc, str(dev), ctx_shape) + tuple(self.state_tag)
+        key += (("inpaint", mask_C),) if mask_C else ()
+        key += (("vq", vq[0] is not None),) if vq is not None else ()                  # quantised or not; the temperature is not part of it
+        key += (("log", tuple(logged)),) if logged is not None else ()
+        par = getattr(self.model, "split_input_params", None)                        # patch-wise eps: keyed by the geometry
+        names = ("ks", "stride", "tie_braker", "clip_min_weight", "clip_max_weight", "clip_min_tie_weight", "clip_max_tie_weight")
+        return key + ((("split",) + tuple((k, str(par.get(k))) for k in names),) if par is not None else ())
+
     def prepare_state(self, N, Cx, sp, dev, Cc, ctx_shape=None, *, mask_C=0, vq=None, logged=None):
-        """Static buffers (and the captured graph) of one chain shape.  mask_C > 0: the inpainting state of a mask with mask_C channels --
-        static fp32 CL buffers for x0 [M, Cx], the mask [M, mask_C] and the per-step q_sample noise [S, M, Cx], plus the [S, 2] q_sample
-        scalar table; it lives under its own key, so a mask-free call never sees it.  vq = (codebook or None, temperature): the state of
-        a chain whose update is `gg_ddim_step_vq` -- its scalar table has a fifth column sigma_t * temperature, refreshed here on every
-        call (outside any graph: the steps read their rows in place), and "vq" holds the codebook the steps read in place; also under
-        its own key (quantised or not; the temperature is not part of it), with the codebook's identity in the token.
-        logged (a tuple of step indices, `logged_steps`): the state of a chain that records its intermediates -- "log" maps a sampling step
-        i to its slot, "log_x" / "log_p0" are the fp32 log buffers [L, N, Cx, *sp] that `gg_log_rows` fills in place; the tuple joins the
-        key, so an unlogged call never sees this state or its graph."""
-        unet = self.model.model.diffusion_model
-        sp3 = (1,) * (3 - len(sp)) + tuple(sp)
+        """The chain state (chain.new_state: static buffers, and here the captured graph) of one chain shape, cached in `_graphs` under
+        `state_key` and rebuilt when `state_token` changes.  mask_C > 0: the inpainting state of a mask with mask_C channels, with the S
+        q_sample noises as a static buffer and the [S, 2] q_sample scalar table.  vq = (codebook or None, temperature): the state of a
+        chain whose update is `gg_ddim_step_vq` -- its scalar table has a fifth column sigma_t * temperature, refreshed here on every
+        call (outside any graph: the steps read their rows in place), and "vq" holds the codebook the steps read in place.  logged (a
+        tuple of step indices, `logged_steps`): the state of a chain that records its intermediates in "log_x" / "log_p0"."""
         self.refresh_schedule()
-        S = self.ddim_timesteps.shape[0]
-        key = (N, Cx, sp3, Cc, str(dev), ctx_shape) + tuple(self.state_tag) + ((("inpaint", mask_C),) if mask_C else ())
-        if vq is not None:
-            key = key + (("vq", vq[0] is not None),)
-        if logged is not None:
-            key = key + (("log", tuple(logged)),)
-        par = getattr(self.model, "split_input_params", None)
-        if par is not None:            # patch-wise eps: a state of its own (crop buffers, time-bias rows for L * N), keyed by the geometry
-            key = key + (("split",) + tuple((k, str(par.get(k))) for k in ("ks", "stride", "tie_braker", "clip_min_weight", "clip_max_weight",
-                                                                          "clip_min_tie_weight", "clip_max_tie_weight")),)
+        key = self.state_key(N, Cx, (1,) * (3 - len(sp)) + tuple(sp), Cc, dev, ctx_shape, mask_C, vq, logged)
         # everything cached below is a function of what the token holds: a changed schedule or weight version rebuilds the state
         token = self.state_token(vq, bool(mask_C))
         st = self._graphs.get(key)
-        if st is not None and st["token"] == token:
+        if st is None or st["token"] != token:
+            st = cs.new_state(self.model, N, Cx, Cc, sp, dev, self.step_scalar_table().to(dev), ctx_shape=ctx_shape, logged=logged,
+                              inpaint=(mask_C, self.q_sample_scalar_table().to(dev), self.ddim_timesteps.shape[0]) if mask_C else None)
+            cs.set_bias_table(st, self.model.model.diffusion_model, torch.tensor(np.flip(self.ddim_timesteps).copy(), dtype=torch.float32, device=dev))
+            st.update(token=token, graph=None, warmed=False, callbacks=None)
             if vq is not None:
-                st["scal"][:, 4].copy_(st["scal"][:, 2] * vq[1])
-            return st
-        steps = torch.tensor(np.flip(self.ddim_timesteps).copy(), dtype=torch.float32, device=dev)
-        split = SplitUNet(self.model, N, Cx, Cc, sp, dev) if par is not None else None
-        st = dict(N=N, Cx=Cx, sp3=sp3, sp=tuple(sp), Cc=Cc, S=S, token=token, callbacks=None,
-                  table=unet.time_bias_table(steps, N) if split is None else split.time_bias_table(unet, steps), scal=self.step_scalar_table().to(dev),
-                  x=torch.empty((N,) + sp3 + (Cx,), dtype=torch.float32, device=dev),
-                  pred_x0=torch.empty((N,) + sp3 + (Cx,), dtype=torch.float32, device=dev),
-                  unet_in=torch.zeros((N,) + sp3 + (pad32(Cx + Cc),), dtype=torch.bfloat16, device=dev),
-                  eps=torch.empty((N,) + sp3 + (pad32(unet.out_channels),), dtype=torch.float32, device=dev),
-                  # cross-attention context [N, L, C] as a STATIC channels-last buffer [N,1,1,L,Cpad]: the captured chain reads it in place
-                  ctx=(CL(torch.zeros((N, 1, 1, ctx_shape[0], pad32(ctx_shape[1])), dtype=torch.bfloat16, device=dev), ctx_shape[1])
-                       if ctx_shape is not None else None),
-                  graph=None, warmed=False)
-        if mask_C:
-            st.update(ip_x0=torch.empty((N,) + sp3 + (Cx,), dtype=torch.float32, device=dev),
-                      ip_mask=torch.empty((N,) + sp3 + (mask_C,), dtype=torch.float32, device=dev),
-                      ip_noise=torch.empty((S, N) + sp3 + (Cx,), dtype=torch.float32, device=dev),
-                      ip_scal=self.q_sample_scalar_table().to(dev))
-        if split is not None:
-            st["split"] = split
-        if logged is not None:
-            st.update(log={S - 1 - index: j for j, index in enumerate(logged)},
-                      log_x=torch.empty((len(logged), N, Cx) + tuple(sp), dtype=torch.float32, device=dev),
-                      log_p0=torch.empty((len(logged), N, Cx) + tuple(sp), dtype=torch.float32, device=dev))
+                st.update(vq=vq[0], scal=torch.cat([st["scal"], st["scal"][:, 2:3]], 1).contiguous())
+            if self.extend_state is not None:
+                self.extend_state(st)
+            self._graphs[key] = st
         if vq is not None:
-            sc = self.step_scalar_table().to(dev)
-            st.update(vq=vq[0], scal=torch.cat([sc, sc[:, 2:3] * vq[1]], 1).contiguous())          # fp32 product sigma_t * temperature
-        self._graphs[key] = st
+            st["scal"][:, 4].copy_(st["scal"][:, 2] * vq[1])          # fp32 product sigma_t * temperature
         return st
-
-    def load_state(self, st, x_T: torch.Tensor, c_concat: Optional[torch.Tensor], context: Optional[torch.Tensor] = None):
-        """x_T (NC..) -> fp32 CL state + bf16 UNet input; conditioning latent -> channels [Cx, Cx+Cc) of the UNet input; context
-        [N, L, C] -> the state's channels-last context buffer."""
-        if context is not None:
-            ops.to_cl(context.permute(0, 2, 1).contiguous().float(), out=st["ctx"].t, c_offset=0, zero_fill=False)
-        st["x"].view((st["N"],) + tuple(x_T.shape[2:]) + (st["Cx"],)).copy_(nc_to_rows(x_T))          # plumbing: layout copy
-        ops.to_cl(x_T, out=st["unet_in"], c_offset=0, zero_fill=False)
-        if c_concat is not None:
-            ops.to_cl(c_concat.float(), out=st["unet_in"], c_offset=st["Cx"], zero_fill=False)
-        if "split" in st:
-            st["split"].bind(st["unet_in"], st["ctx"] if context is not None else None)
-
-    def _eps(self, st, uin, bias, ctx_cl, out, head_ddim=None):
-        """eps of the state's x under the UNet input `uin` (unet_eps: full size, or on crops with a "split" state)."""
-        return unet_eps(self.model.model.diffusion_model, st.get("split"), st["x"], uin, st["Cx"] + st["Cc"], bias, ctx_cl, out, head_ddim)
-
-    def load_inpaint(self, st, x0: torch.Tensor, mask: torch.Tensor, mask_noise_tape=None):
-        """x0 [N, C, *sp] and mask [N, Cm, *sp] (inpaint_operands' views) -> the state's static CL buffers; the S q_sample noises from
-        the tape, or from one device randn [S, N, C, *sp].  Outside any graph: a captured chain reads the buffers in place."""
-        N, Cx, S = st["N"], st["Cx"], st["S"]
-        dev = st["x"].device
-        sp = tuple(x0.shape[2:])
-        nd = len(sp)
-        st["ip_x0"].view((N,) + sp + (Cx,)).copy_(nc_to_rows(x0.to(dev)))              # plumbing: layout copies
-        st["ip_mask"].view((N,) + sp + (mask.shape[1],)).copy_(nc_to_rows(mask.to(dev)))
-        noise = st["ip_noise"].view((S, N) + sp + (Cx,))
-        if mask_noise_tape is not None:
-            for i in range(S):
-                noise[i].copy_(nc_to_rows(mask_noise_tape[i].to(dev).float()))
-        else:
-            noise.copy_(torch.randn((S, N, Cx) + sp, device=dev).permute((0, 1) + tuple(range(3, nd + 3)) + (2,)))
-
-    def _blend(self, st, i):
-        """Inpainting blend before step i's UNet evaluation (ddim.py:144-148): x and the UNet input's channels [0, Cx) <- q_sample(x0,
-        t_i) * mask + (1 - mask) * x.  No-op (no launch) on a mask-free state."""
-        if "ip_x0" not in st:
-            return
-        Cx = st["Cx"]
-        M = st["x"].numel() // Cx
-        ops.inpaint_blend(st["x"].view(M, Cx), st["ip_x0"].view(M, Cx), st["ip_mask"].view(M, -1), st["ip_noise"][i].view(M, Cx),
-                          st["ip_scal"][i], unet_in=st["unet_in"].view(M, -1))
-
-    def _after_step(self, st, i):
-        """What follows sampling step i's update: on a logging state the two `gg_log_rows` copies of x and pred_x0 into their slots
-        (launches like any other, so they are captured with the chain); with callbacks, callback(i) and img_callback(pred_x0, i)."""
-        j = st["log"].get(i) if "log" in st else None
-        Cx = st["Cx"]
-        M = st["x"].numel() // Cx
-        if j is not None:
-            ops.log_rows(st["x"].view(M, Cx), st["N"], st["log_x"][j])
-            ops.log_rows(st["pred_x0"].view(M, Cx), st["N"], st["log_p0"][j])
-        cb = st.get("callbacks")
-        if cb is not None:
-            if cb[0]:
-                cb[0](i)
-            if cb[1]:
-                p0 = torch.empty((st["N"], Cx) + tuple(d for d in st["sp"]), dtype=torch.float32, device=st["x"].device)
-                ops.log_rows(st["pred_x0"].view(M, Cx), st["N"], p0)
-                cb[1](p0, i)
 
     def _update(self, st, eps, scal, noise=None):
         """The DDIM update as its own launch on the state's buffers: gg_ddim_step, or gg_ddim_step_vq on a "vq" state (quantised pred_x0
         and / or a temperature; `scal` is then a row of the five-column table)."""
-        Cx = st["Cx"]
-        M = st["x"].numel() // Cx
+        x, e, p0, uin = cs.rows(st, "x", eps, "pred_x0", "unet_in")
         if "vq" in st:
-            ops.ddim_step_vq(st["x"].view(M, Cx), eps.view(M, -1), scal, st["vq"], noise=noise,
-                             pred_x0_out=st["pred_x0"].view(M, Cx), unet_in=st["unet_in"].view(M, -1))
+            ops.ddim_step_vq(x, e, scal, st["vq"], noise=noise, pred_x0_out=p0, unet_in=uin)
         else:
-            ops.ddim_step(st["x"].view(M, Cx), eps.view(M, -1), scal, noise=noise,
-                          pred_x0_out=st["pred_x0"].view(M, Cx), unet_in=st["unet_in"].view(M, -1))
-
-    def _noise(self, st, i, eta, noise_tape, p=0.0):
-        """Step i's noise as a channels-last tensor (None on a deterministic step), after noise_dropout p (ddim.py:202-203)."""
-        if noise_tape is not None:
-            nt = noise_tape[i].to(st["x"].device).float()
-            if p > 0.0:
-                nt = torch.nn.functional.dropout(nt, p=p)
-            return nc_to_rows(nt).contiguous()
-        if eta != 0.0:
-            noise = torch.randn_like(st["x"])
-            return torch.nn.functional.dropout(noise, p=p) if p > 0.0 else noise
-        return None
+            ops.ddim_step(x, e, scal, noise=noise, pred_x0_out=p0, unet_in=uin)
 
     def _step(self, st, ctx_cl, bias, scal, noise):
         """One reverse step on the state's buffers; `bias` / `scal` are rows of the per-schedule tables (ddim.py:165-205)."""
-        unet = self.model.model.diffusion_model
-        Cx, Cc = st["Cx"], st["Cc"]
-        M = st["x"].numel() // Cx
         # deterministic steps: the update is the head conv's epilogue where the kernel supports it (Cx == 4 on the box kernel)
-        hd = (st["x"].view(M, Cx), scal, st["pred_x0"].view(M, Cx), st["unet_in"].view(M, -1)) \
-            if (noise is None and self.fuse_ddim and Cx == 4 and "vq" not in st and "split" not in st) else None
-        head = self._eps(st, st["unet_in"], bias, ctx_cl, st["eps"], hd)
+        fuse = noise is None and self.head_update_is_ddim and self.fuse_ddim and st["Cx"] == 4 and "vq" not in st and "split" not in st
+        x, p0, uin = cs.rows(st, "x", "pred_x0", "unet_in")
+        head = cs.unet_eps(st, self.model.model.diffusion_model, st["unet_in"], bias, ctx_cl, st["eps"], (x, scal, p0, uin) if fuse else None)
         self.last_step_fused = head is not None and head.fused_ddim
         if not self.last_step_fused:
             self._update(st, st["eps"], scal, noise)
 
-    def _run_steps_cfg(self, st, x_T, cfg, eta, noise_tape, noise_dropout=0.0):
+    def _run_steps_cfg(self, st, cfg, eta, noise_tape, noise_dropout=0.0):
         """Classifier-free guidance (ddim.py:175-180): e = e_u + s (e_c - e_u).  The reference stacks [uncond, cond] into one batch of 2 N;
         every layer of the UNet is per sample, so two evaluations on the same x with the two conditionings give the same two halves.
-        Eager (off the timed path); the update kernel refreshes the conditional UNet input, the unconditional one copies x from it."""
+        Eager (off the timed path); the update kernel refreshes the conditional UNet input, the unconditional one copies x from it.
+        The unconditional UNet input and context are members of the state, made on the first guided call and refilled afterwards: a
+        call leaves no memory behind, and SplitUNet.bind, which keeps crop buffers per UNet input and context it is given, sees two."""
         unet = self.model.model.diffusion_model
         uc_concat, uc_ctx = split_cond(cfg[0], self.model.model.conditioning_key)
         scale = cfg[1]
-        Cx, Cc = st["Cx"], st["Cc"]
-        M = st["x"].numel() // Cx
-        split = st.get("split")
-        if split is None:
-            uin_u = st["unet_in"].clone()
-        else:
-            # patch-wise: SplitUNet.bind keeps crop buffers per UNet input and per context it is given, so the unconditional ones are
-            # members of the state, made on the first guided call and refilled afterwards: a call leaves no memory behind
-            if "cfg_unet_in" not in st:
-                st["cfg_unet_in"] = torch.empty_like(st["unet_in"])
-            uin_u = st["cfg_unet_in"]
-            uin_u.copy_(st["unet_in"])
+        Cx = st["Cx"]
+        if "cfg_unet_in" not in st:
+            st["cfg_unet_in"] = torch.empty_like(st["unet_in"])
+        uin_u = st["cfg_unet_in"]
+        uin_u.copy_(st["unet_in"])
         if uc_concat is not None:
             ops.to_cl(uc_concat.float(), out=uin_u, c_offset=Cx, zero_fill=False)
-        ctx_u = None
+        ctx_u = st["ctx"]
         if uc_ctx is not None:
-            if split is None:
-                ctx_u = CL(torch.zeros_like(st["ctx"].t), st["ctx"].C)
-            else:
-                if "cfg_ctx" not in st:
-                    st["cfg_ctx"] = CL(torch.zeros_like(st["ctx"].t), st["ctx"].C)
-                ctx_u = st["cfg_ctx"]
+            if "cfg_ctx" not in st:
+                st["cfg_ctx"] = CL(torch.zeros_like(st["ctx"].t), st["ctx"].C)
+            ctx_u = st["cfg_ctx"]
             ops.to_cl(uc_ctx.permute(0, 2, 1).contiguous().float(), out=ctx_u.t, c_offset=0, zero_fill=False)
-        elif st["ctx"] is not None:
-            ctx_u = st["ctx"]
         eps_u = torch.empty_like(st["eps"])
-        if split is not None:
-            split.bind(uin_u, ctx_u)
+        if "split" in st:
+            st["split"].bind(uin_u, ctx_u)
         for i in range(st["S"]):
-            noise = self._noise(st, i, eta, noise_tape, noise_dropout)
+            noise = cs.step_noise(st, i, noise_tape, eta != 0.0, noise_dropout)
             if "ip_x0" in st:                   # inpainting: both evaluations see the blended x (ddim.py:144-148 precede :175-180)
-                self._blend(st, i)
+                cs.blend(st, i)
                 uin_u[..., :Cx].copy_(st["unet_in"][..., :Cx])
-            self._eps(st, uin_u, st["table"][i], ctx_u, eps_u)
-            self._eps(st, st["unet_in"], st["table"][i], st["ctx"], st["eps"])
+            cs.unet_eps(st, unet, uin_u, st["table"][i], ctx_u, eps_u)
+            cs.unet_eps(st, unet, st["unet_in"], st["table"][i], st["ctx"], st["eps"])
             ops.lincomb4([eps_u, st["eps"]], [1.0 - scale, scale], 1.0, st["eps"])        # (1 - s) e_u + s e_c
             self._update(st, st["eps"], st["scal"][i], noise)
             uin_u[..., :Cx].copy_(st["unet_in"][..., :Cx])
-            self._after_step(st, i)
+            cs.after_step(st, i)
         self.last_step_fused = False
 
     def chain_graphable(self, st, ctx_cl=None, eta=0.0, noise_tape=None) -> bool:
         return bool(self.use_graph and eta == 0.0 and noise_tape is None and (ctx_cl is None or ctx_cl is st["ctx"]) and st["S"] > 2
                     and st.get("callbacks") is None)
 
-    def chain(self, st, ctx_cl=None):
-        """All S deterministic steps back to back, every step reading ITS rows of the time-bias / scalar tables in place: no
-        per-step copies, no host decisions, so the whole chain (13 k kernel nodes at S = 50) is one capturable launch sequence."""
+    def chain(self, st, ctx_cl=None, eta=0.0, noise_tape=None, noise_dropout=0.0):
+        """All S steps back to back, every step reading ITS rows of the time-bias / scalar tables in place.  Deterministic (the defaults):
+        no per-step copies, no host decisions, so the whole chain (13 k kernel nodes at S = 50) is one capturable launch sequence."""
         for i in range(st["S"]):
-            self._blend(st, i)
-            self._step(st, ctx_cl, st["table"][i], st["scal"][i], None)
-            self._after_step(st, i)
+            noise = cs.step_noise(st, i, noise_tape, eta != 0.0, noise_dropout)
+            cs.blend(st, i)
+            self._step(st, ctx_cl, st["table"][i], st["scal"][i], noise)
+            cs.after_step(st, i)
         st["fused"] = self.last_step_fused
 
     def run_steps(self, st, ctx_cl, eta, noise_tape, noise_dropout=0.0):
-        S = st["S"]
-        if self.chain_graphable(st, ctx_cl, eta, noise_tape):
-            # first call: eager (fills the weight-repack caches); afterwards ONE hipGraph replay per chain
-            ops.replay_captured(st, "graph", lambda: self.chain(st, ctx_cl))
-            self.last_step_fused = st["fused"]          # a replay runs no host code: what the captured steps did
-            return
-        for i in range(S):
-            noise = self._noise(st, i, eta, noise_tape, noise_dropout)
-            self._blend(st, i)
-            self._step(st, ctx_cl, st["table"][i], st["scal"][i], noise)
-            self._after_step(st, i)
+        if not self.chain_graphable(st, ctx_cl, eta, noise_tape):
+            return self.chain(st, ctx_cl, eta, noise_tape, noise_dropout)
+        # first call: eager (fills the weight-repack caches); afterwards ONE hipGraph replay per chain
+        ops.replay_captured(st, "graph", lambda: self.chain(st, ctx_cl))
+        self.last_step_fused = st["fused"]          # a replay runs no host code: what the captured steps did
 
 
 class PLMSSampler(DDIMSampler):
@@ -2054,23 +1783,18 @@ class PLMSSampler(DDIMSampler):
 
     def run_steps(self, st, ctx_cl, eta, noise_tape, noise_dropout=0.0):          # eta = 0: no noise, nothing to drop
         unet = self.model.model.diffusion_model
-        Cx, Cc, S = st["Cx"], st["Cc"], st["S"]
-        M = st["x"].numel() // Cx
-        x, eps, uin = st["x"].view(M, Cx), st["eps"], st["unet_in"].view(M, -1)
+        S, eps = st["S"], st["eps"]
+        x, uin = cs.rows(st, "x", "unet_in")
         old: List[torch.Tensor] = []
         e_prime = torch.empty_like(eps)
-
-        def update(e_cl, scal):
-            self._update(st, e_cl, scal)               # quantize_x0 (plms.py:184-185): gg_ddim_step_vq on a "vq" state
-
         for i in range(S):
-            self._blend(st, i)                 # inpainting (plms.py:147-150): before the first evaluation, so x_keep holds the blended x
-            self._eps(st, st["unet_in"], st["table"][i], ctx_cl, eps)
+            cs.blend(st, i)                    # inpainting (plms.py:147-150): before the first evaluation, so x_keep holds the blended x
+            cs.unet_eps(st, unet, st["unet_in"], st["table"][i], ctx_cl, eps)
             e_t = eps.clone()
             if len(old) == 0:
                 x_keep, uin_keep = x.clone(), uin.clone()
-                update(e_t, st["scal"][i])                                             # provisional x_prev
-                self._eps(st, st["unet_in"], st["table"][min(i + 1, S - 1)], ctx_cl, eps)    # e(x_prev, t_next)
+                self._update(st, e_t, st["scal"][i])                                       # provisional x_prev
+                cs.unet_eps(st, unet, st["unet_in"], st["table"][min(i + 1, S - 1)], ctx_cl, eps)      # e(x_prev, t_next)
                 ops.lincomb4([e_t, eps], [1.0, 1.0], 2.0, e_prime)
                 x.copy_(x_keep); uin.copy_(uin_keep)
             elif len(old) == 1:
@@ -2079,8 +1803,8 @@ class PLMSSampler(DDIMSampler):
                 ops.lincomb4([e_t, old[-1], old[-2]], [23.0, -16.0, 5.0], 12.0, e_prime)
             else:
                 ops.lincomb4([e_t, old[-1], old[-2], old[-3]], [55.0, -59.0, 37.0, -9.0], 24.0, e_prime)
-            update(e_prime, st["scal"][i])
-            self._after_step(st, i)
+            self._update(st, e_prime, st["scal"][i])               # quantize_x0 (plms.py:184-185): gg_ddim_step_vq on a "vq" state
+            cs.after_step(st, i)
             old.append(e_t)
             if len(old) >= 4:
                 old.pop(0)

@@ -1,0 +1,388 @@
+"""Launch-trace recorder for the latent chain: which ops launches and UNet evaluations a sampler call makes, with which operands, and
+what it returns, on the GPU.
+
+The recorder wraps names that a restructuring of the chain leaves alone, in the manner of tests/stale.Launches: the launching functions
+of ops that the samplers call (OPS) and the UNet instance's forward_cl / time_bias_table / context_cl.  It wraps nothing inside the
+sampler modules.  The UNet's own launches are not recorded: one forward_cl call is one entry.  A trace entry holds the name and, under
+the parameter names of the real function (bound through its signature, defaults applied):
+  tensor / CL operands  shape, dtype, strides (0 where the extent is 1), storage offset and a buffer number, assigned by first appearance of the storage address
+                        within the call (within each sampler call, where a case makes two: `renumber`) -- so the trace does not depend
+                        on who allocated what; every operand is kept alive until the call ends, so that no address is handed out twice;
+  everything else       as it was passed (flags, coefficients, extents; the timesteps of a time-bias table as a list).
+Every case makes the same call CALLS times (eager, capture + replay, replay: the ladder of ops.replay_captured); all traces are kept,
+and a replay records nothing of the chain.  The tensors a call returns are kept as SHA-1 digests of their bytes; noise comes from
+tapes, or from torch.manual_seed before each call.
+
+tests/golden/make_golden_chain_traces.py writes the fingerprints (one digest per entry) to tests/golden/chain_launch_traces.json and
+tests/test_chain_trace_gpu.py compares.  A planted defect (DEFECTS) acts inside the recording wrappers, as if the chain had made the
+call so: the same plant works on any version of the samplers."""
+from __future__ import annotations
+
+import hashlib
+import inspect
+import json
+
+import torch
+
+from util import AE_SMALL, LDM_SMALL, seeded
+
+OPS = ("ddim_step", "ddim_step_vq", "ddpm_step", "ddpm_step_x0", "dpm_solver_step", "vq_nearest", "inpaint_blend", "lincomb4", "log_rows",
+       "to_cl", "unfold_cl", "fold_weighted_cl", "capture_graph")
+UNET = ("forward_cl", "time_bias_table", "context_cl")
+DEFECTS = ("blend_after_step", "plms_bias_row", "log_slot")
+CALLS = 3
+N, LAT, T_DDPM, S, S_PLMS, T_ANC = 2, 8, 20, 4, 5, 4
+SEED = 4321
+DTYPES = {torch.bfloat16: "bf16", torch.float32: "f32", torch.float64: "f64", torch.int32: "i32", torch.int64: "i64"}
+LOSS = dict(target="torch.nn.Identity")
+SPLIT = dict(ks=(8, 8), stride=(4, 4), vqf=4, patch_distributed_vq=True, tie_braker=False, clip_max_weight=0.5, clip_min_weight=0.01,
+             clip_max_tie_weight=0.5, clip_min_tie_weight=0.01)
+
+
+# ------------------------------------------------------------------------------------------------ the recorder
+class Recorder:
+    def __init__(self, unet, defect=None):
+        from jointimagegeneration_amd import ops
+        assert defect is None or defect in DEFECTS
+        self.ops, self.unet, self.defect = ops, unet, defect
+        self.begin()
+
+    def begin(self):
+        self.entries, self.buffers, self.keep = [], {}, []
+        self.held_blend, self.forwards, self.last_bias = None, 0, None
+
+    def renumber(self):
+        """Buffer numbers start again: between the sampler calls of a case that makes more than one per call."""
+        self.buffers = {}
+
+    def describe(self, v):
+        if isinstance(v, self.ops.CL):
+            return dict(self.describe(v.t), C=int(v.C))
+        if isinstance(v, torch.Tensor):
+            self.keep.append(v)
+            buf = self.buffers.setdefault(v.untyped_storage().data_ptr(), len(self.buffers))
+            stride = [s if n > 1 else 0 for n, s in zip(v.shape, v.stride())]           # the stride of an extent of 1 addresses nothing
+            return dict(shape=list(v.shape), dtype=DTYPES[v.dtype], stride=stride, offset=int(v.storage_offset()), buf=buf)
+        if isinstance(v, (tuple, list)):
+            return [self.describe(x) for x in v]
+        if v is None or isinstance(v, (bool, int, float, str)):
+            return v
+        raise TypeError(f"chain_trace: no description for an argument of type {type(v).__name__}")
+
+    def record(self, name, args):
+        self.entries.append({"op": name, **{n: self.describe(v) for n, v in args.items()}})
+
+    # ---- wrappers
+    def wrap_op(self, name):
+        real = getattr(self.ops, name)
+        sig = inspect.signature(real)
+
+        def wrapper(*a, **k):
+            if name == "capture_graph":
+                self.entries.append({"op": name})
+                return real(*a, **k)
+            b = sig.bind(*a, **k)
+            b.apply_defaults()
+            args = dict(b.arguments)
+            if name == "log_rows" and self.defect == "log_slot":                # the copy lands one slot further (wrapping inside the buffer)
+                slot = args["slot"]
+                total = slot.untyped_storage().nbytes() // slot.element_size()
+                args["slot"] = slot.as_strided(slot.size(), slot.stride(), (slot.storage_offset() + slot.numel()) % total)
+            if name == "inpaint_blend" and self.defect == "blend_after_step":   # held back until the step's update has been made
+                assert self.held_blend is None
+                self.held_blend = (real, args)
+                return None
+            self.record(name, args)
+            out = real(**args)
+            if name in ("ddim_step", "ddim_step_vq"):
+                self.release_blend()
+            return out
+        return wrapper
+
+    def release_blend(self):
+        if self.held_blend is not None:
+            (real, args), self.held_blend = self.held_blend, None
+            self.record("inpaint_blend", args)
+            real(**args)
+
+    def forward_cl(self, real):
+        def wrapper(x, bias_row, context=None, head_out=None, head_ddim=None, head_post=None):
+            assert head_post is None
+            if self.defect == "plms_bias_row" and self.forwards == 1:          # the second evaluation reads the first one's bias row
+                bias_row = self.last_bias
+            self.forwards, self.last_bias = self.forwards + 1, bias_row
+            self.record("forward_cl", dict(x=x, bias_row=bias_row, context=context, head_out=head_out, head_ddim_given=head_ddim is not None,
+                                           head_ddim=head_ddim))
+            out = real(x, bias_row, context, head_out=head_out, head_ddim=head_ddim)
+            if out.fused_ddim:
+                self.release_blend()
+            return out
+        return wrapper
+
+    def time_bias_table(self, real):
+        def wrapper(timesteps, N):
+            self.entries.append({"op": "time_bias_table", "timesteps": [float(v) for v in timesteps.tolist()], "N": int(N)})
+            return real(timesteps, N)
+        return wrapper
+
+    def context_cl(self, real):
+        def wrapper(context):
+            self.record("context_cl", dict(context=context))
+            return real(context)
+        return wrapper
+
+    def __enter__(self):
+        self.saved = {name: getattr(self.ops, name) for name in OPS}
+        for name in OPS:
+            setattr(self.ops, name, self.wrap_op(name))
+        for name in UNET:                                                       # instance attributes in front of the class's methods
+            setattr(self.unet, name, getattr(self, name)(getattr(self.unet, name)))
+        return self
+
+    def __exit__(self, *exc):
+        for name, real in self.saved.items():
+            setattr(self.ops, name, real)
+        for name in UNET:
+            delattr(self.unet, name)
+        return False
+
+
+def tensors_of(r):
+    """The tensors of a result in a fixed order: tuples and lists in theirs, dicts by key."""
+    if isinstance(r, torch.Tensor):
+        return [r]
+    if isinstance(r, dict):
+        return [t for k in sorted(r) for t in tensors_of(r[k])]
+    if isinstance(r, (tuple, list)):
+        return [t for x in r for t in tensors_of(x)]
+    return []
+
+
+def sha1(t: torch.Tensor) -> str:
+    return hashlib.sha1(t.detach().float().contiguous().cpu().numpy().tobytes()).hexdigest()[:12]
+
+
+# ------------------------------------------------------------------------------------------------ models and operands
+_MODELS = {}
+
+
+def model(kind, dev):
+    """The small LatentDiffusion variants of the sampler tests (UNet LDM_SMALL, 8x8 latents), on T_DDPM timesteps:
+    concat (Cx = 4, Cc = 4, VQ first stage), x0 / clip (the same weights, output read as x_0 / clip_denoised set), split (concat with
+    split_input_params), c3 (Cx = 3, Cc = 3: no fused head), ctx (cross-attention, context 5 x 48), hybrid, ddpm (the pixel-space DDPM)."""
+    if kind in _MODELS:
+        return _MODELS[kind]
+    from jointimagegeneration_amd.config import instantiate_from_config
+    from jointimagegeneration_amd.ldm import LatentDiffusion
+    unet = lambda **kw: dict(target="ldm.modules.diffusionmodules.openaimodel.UNetModel", params=dict(LDM_SMALL, **kw))
+    vq = dict(target="ldm.models.autoencoder.VQModelInterface", params=dict(embed_dim=4, n_embed=64, dims=2, ddconfig=dict(AE_SMALL), lossconfig=LOSS))
+    ae2 = dict(target="ldm.models.autoencoder.AutoencoderKL", params=dict(embed_dim=4, dims=2, ddconfig=dict(AE_SMALL, in_channels=2, out_ch=2), lossconfig=LOSS))
+    ident = dict(target="ldm.modules.encoders.modules.IdentityEncoder")
+    common = dict(linear_start=0.0015, linear_end=0.0195, timesteps=T_DDPM, image_size=LAT, dims=2, first_stage_key="image", num_timesteps_cond=1,
+                  use_ema=False)
+    if kind in ("concat", "x0", "clip", "split"):
+        m = LatentDiffusion(first_stage_config=vq, cond_stage_config=ae2, unet_config=unet(), channels=4, cond_stage_key="segmentation",
+                            parameterization="x0" if kind == "x0" else "eps", **common)
+        m = seeded(m, "ldm_pipe.")
+        if kind == "clip":
+            m.clip_denoised = True
+        if kind == "split":
+            m.split_input_params = dict(SPLIT)
+    elif kind == "c3":
+        m = seeded(LatentDiffusion(first_stage_config="__is_no_first_stage__", cond_stage_config=ident, unet_config=unet(in_channels=6, out_channels=3),
+                                   channels=3, cond_stage_key="mask", conditioning_key="concat", **common), "ldm_c3.")
+    elif kind in ("ctx", "hybrid"):
+        cfg = unet(in_channels=4 if kind == "ctx" else 8, use_spatial_transformer=True, transformer_depth=1, context_dim=48)
+        m = seeded(LatentDiffusion(first_stage_config="__is_no_first_stage__", cond_stage_config=ident, unet_config=cfg, channels=4,
+                                   cond_stage_key="caption", conditioning_key="crossattn" if kind == "ctx" else "hybrid", **common), "ldm_ctx.")
+    elif kind == "ddpm":
+        m = seeded(instantiate_from_config(dict(target="ldm.models.diffusion.ddpm.DDPM",
+                                                params=dict(unet_config=unet(in_channels=4), timesteps=T_ANC, linear_start=0.0015, linear_end=0.0195,
+                                                            image_size=LAT, channels=4, log_every_t=2, use_ema=False))), "ddpm_pix.")
+    else:
+        raise KeyError(kind)
+    _MODELS[kind] = m.to(dev)
+    return _MODELS[kind]
+
+
+_OPERANDS = {}
+
+
+def operands(dev):
+    if not _OPERANDS:
+        g = torch.Generator().manual_seed(77)
+        r = lambda *s: torch.randn(*s, generator=g).to(dev)
+        lat = (N, 4, LAT, LAT)
+        mask1 = torch.ones(N, 1, LAT, LAT)
+        mask1[:, :, 2:6, 3:7] = 0.0
+        mask1[:, :, 0, 0] = 0.25                                                # a soft value
+        maskC = mask1.repeat(1, 4, 1, 1).contiguous()
+        maskC[:, 1, 5:, :2] = 0.0
+        _OPERANDS.update(c=r(*lat), uc=r(*lat), uc2=r(*lat), x_T=r(*lat), x0=r(*lat), mask1=mask1.to(dev), maskC=maskC.to(dev),
+                         tape=[r(*lat) for _ in range(S_PLMS)], qtape=[r(*lat) for _ in range(S_PLMS)],
+                         c3=r(N, 3, LAT, LAT), x_T3=r(N, 3, LAT, LAT), ctx=r(N, 5, 48), uctx=r(N, 5, 48), uctx2=r(N, 5, 48))
+    return _OPERANDS
+
+
+# ------------------------------------------------------------------------------------------------ cases
+def _cases():
+    """name -> build(dev) -> (the model whose UNet is wrapped, run(rec) -> what the call returns).  `run` is called CALLS times, with
+    the recorder."""
+    from jointimagegeneration_amd.dpm_solver import DPMSolverSampler
+    from jointimagegeneration_amd.ldm import DDIMSampler, PLMSSampler
+    cases = {}
+    LATENT = (4, LAT, LAT)
+
+    def sampler_case(name, cls, kind="concat", steps=S, setup=None, cond="c", x_T="x_T", shape=LATENT, make=dict, **kw):
+        def build(dev):
+            m, op = model(kind, dev), operands(dev)
+            s = cls(m, **make())
+            if setup:
+                setup(s)
+            conditioning = cond(op) if callable(cond) else op[cond]
+            args = {k: (v(op) if callable(v) else v) for k, v in kw.items()}
+            return m, lambda rec: s.sample(steps, N, shape, conditioning=conditioning, x_T=op[x_T], verbose=False, **args)
+        assert name not in cases
+        cases[name] = build
+
+    def off(flag):
+        return lambda s: setattr(s, flag, False)
+    ip = lambda mask, tape: dict(mask=lambda op: op[mask], x0=lambda op: op["x0"], **({"mask_noise_tape": lambda op: op["qtape"]} if tape else {}))
+    tape = lambda op: op["tape"]
+
+    sampler_case("ddim-eta0", DDIMSampler)
+    sampler_case("ddim-eta1-tape", DDIMSampler, eta=1.0, noise_tape=tape)
+    sampler_case("ddim-fuse_ddim-off", DDIMSampler, setup=off("fuse_ddim"))
+    sampler_case("ddim-use_graph-off", DDIMSampler, setup=off("use_graph"))
+    sampler_case("ddim-c3-unfused-head", DDIMSampler, kind="c3", cond="c3", x_T="x_T3", shape=(3, LAT, LAT))
+    sampler_case("ddim-context", DDIMSampler, kind="ctx", cond="ctx")
+    sampler_case("ddim-hybrid", DDIMSampler, kind="hybrid", cond=lambda op: dict(c_concat=[op["c"]], c_crossattn=[op["ctx"]]))
+    for mask in ("mask1", "maskC"):
+        for with_tape in (True, False):
+            sampler_case(f"ddim-inpaint-{mask}-{'tape' if with_tape else 'draw'}", DDIMSampler, **ip(mask, with_tape))
+    sampler_case("ddim-quantize_x0", DDIMSampler, quantize_x0=True)
+    sampler_case("ddim-temperature-eta1", DDIMSampler, eta=1.0, noise_tape=tape, temperature=0.7)
+    sampler_case("ddim-noise_dropout", DDIMSampler, eta=1.0, noise_tape=tape, noise_dropout=0.25)
+    sampler_case("ddim-noise_dropout-draw", DDIMSampler, eta=1.0, noise_dropout=0.25)
+    sampler_case("ddim-log_every_t2", DDIMSampler, log_every_t=2)
+    sampler_case("ddim-split", DDIMSampler, kind="split")
+    sampler_case("plms", PLMSSampler, steps=S_PLMS)
+    sampler_case("plms-inpaint", PLMSSampler, steps=S_PLMS, **ip("mask1", True))
+    sampler_case("plms-quantize_x0", PLMSSampler, steps=S_PLMS, quantize_x0=True)
+    sampler_case("plms-log_every_t2", PLMSSampler, steps=S_PLMS, log_every_t=2)
+    sampler_case("dpm-order1", DPMSolverSampler, make=lambda: dict(order=1))
+    sampler_case("dpm-order2", DPMSolverSampler)
+    sampler_case("dpm-clip_denoised", DPMSolverSampler, clip_denoised=True)
+    sampler_case("dpm-x0-model", DPMSolverSampler, kind="x0")
+    sampler_case("dpm-inpaint", DPMSolverSampler, **ip("mask1", True))
+    sampler_case("dpm-guidance", DPMSolverSampler, unconditional_conditioning=lambda op: op["uc"], unconditional_guidance_scale=2.0)
+    sampler_case("dpm-log_every_t2", DPMSolverSampler, log_every_t=2)
+
+    def guided(name, kind, cond, ucs, cls=DDIMSampler):
+        """Classifier-free guidance: one call is two sample() calls on one sampler, with different unconditional inputs."""
+        def build(dev):
+            m, op = model(kind, dev), operands(dev)
+            s = cls(m)
+            return m, lambda rec: [(rec.renumber(), s.sample(S, N, LATENT, conditioning=op[cond], x_T=op["x_T"], verbose=False,
+                                                             unconditional_guidance_scale=3.0, unconditional_conditioning=op[uc]))[1] for uc in ucs]
+        cases[name] = build
+
+    guided("ddim-guidance-twice", "concat", "c", ("uc", "uc2"))
+    guided("ddim-guidance-context-twice", "ctx", "ctx", ("uctx", "uctx2"))
+    guided("ddim-split-guidance", "split", "c", ("uc", "uc2"))
+
+    def callbacks(dev):
+        m, op = model("concat", dev), operands(dev)
+        s = DDIMSampler(m)
+
+        def run(rec):
+            seen, imgs = [], []
+            out = s.sample(S, N, LATENT, conditioning=op["c"], x_T=op["x_T"], verbose=False, callback=seen.append,
+                           img_callback=lambda p, i: (seen.append(-1 - i), imgs.append(p.clone())))
+            assert seen == [v for i in range(S) for v in (i, -1 - i)], seen
+            return out, imgs
+        return m, run
+    cases["ddim-callbacks"] = callbacks
+
+    def ancestral(name, kind="concat", loop="p_sample_loop", **kw):
+        def build(dev):
+            m, op = model(kind, dev), operands(dev)
+            args = {k: (v(op) if callable(v) else v) for k, v in kw.items()}
+            extra = dict(timesteps=T_ANC, return_intermediates=True) if loop == "p_sample_loop" else dict(start_T=T_ANC)
+            return m, lambda rec: getattr(m, loop)(op["c"], (N,) + LATENT, x_T=op["x_T"], verbose=False, **extra, **args)
+        assert name not in cases
+        cases[name] = build
+
+    ancestral("anc-plain")
+    ancestral("anc-tape", noise_tape=tape)
+    ancestral("anc-inpaint-tape", noise_tape=tape, **ip("mask1", True))
+    ancestral("anc-inpaint-draw", **ip("maskC", False))
+    ancestral("anc-quantize_denoised", quantize_denoised=True, noise_tape=tape)
+    ancestral("anc-log_every_t2", log_every_t=2, noise_tape=tape)
+    ancestral("anc-split", kind="split", noise_tape=tape)
+    ancestral("anc-callbacks", noise_tape=tape, callback=lambda op: (lambda t: None), img_callback=lambda op: (lambda x, t: None))
+    prog = dict(loop="progressive_denoising", log_every_t=2)
+    ancestral("prog-temperature-list", temperature=[1.0, 0.9, 0.8, 0.7], noise_tape=tape, **prog)
+    ancestral("prog-noise_dropout", noise_dropout=0.25, **prog)
+    ancestral("prog-x0-model", kind="x0", noise_tape=tape, **prog)
+    ancestral("prog-clip_denoised", kind="clip", noise_tape=tape, **prog)
+    ancestral("prog-clip-quantize", kind="clip", quantize_denoised=True, noise_tape=tape, **prog)
+    ancestral("prog-inpaint-draw", **ip("mask1", False), **prog)
+
+    def ddpm(dev):
+        m, op = model("ddpm", dev), operands(dev)
+        return m, lambda rec: m.p_sample_loop((N,) + LATENT, return_intermediates=True, x_T=op["x_T"], noise_tape=op["tape"])
+    cases["ddpm-p_sample_loop"] = ddpm
+    return cases
+
+
+def case_names():
+    return sorted(_cases())
+
+
+def trace(name: str, dev, defect=None) -> dict:
+    """{"calls": the CALLS entry lists, "results": per call the digests of the returned tensors}."""
+    m, run = _cases()[name](dev)
+    rec = Recorder(m.model.diffusion_model, defect)
+    calls, results = [], []
+    with torch.no_grad(), rec:
+        for _ in range(CALLS):
+            rec.begin()
+            torch.manual_seed(SEED)
+            out = run(rec)
+            rec.release_blend()
+            torch.cuda.synchronize()
+            calls.append(rec.entries)
+            results.append([sha1(t) for t in tensors_of(out)])
+        rec.begin()
+    return {"calls": calls, "results": results}
+
+
+def digest(v) -> str:
+    return hashlib.sha1(json.dumps(v, sort_keys=True, separators=(",", ":")).encode()).hexdigest()[:8]
+
+
+def fingerprint(t: dict) -> dict:
+    """What the fixture keeps: per call `op:digest` of every entry in order (a digest covers the whole entry) and the result digests,
+    each list as one blank-separated string."""
+    return {"calls": [" ".join(f"{e['op']}:{digest(e)}" for e in call) for call in t["calls"]], "results": [" ".join(r) for r in t["results"]]}
+
+
+def compare(got: dict, want: dict):
+    """Differences between a trace and a fixture fingerprint, each named by call and entry, with the entry as it is now."""
+    fp, out = fingerprint(got), []
+    for k in range(CALLS):
+        g, w = fp["calls"][k].split(), want["calls"][k].split()
+        names = lambda es: [e.split(":")[0] for e in es]
+        if names(g) != names(w):
+            i = next((i for i, (a, b) in enumerate(zip(names(g), names(w))) if a != b), min(len(g), len(w)))
+            at = lambda es: names(es)[i] if i < len(es) else "nothing"
+            out.append(f"call {k} entry {i}: the launch sequence differs from here: got {at(g)}, fixture {at(w)} ({len(g)} entries, fixture {len(w)})")
+        else:
+            out += [f"call {k} entry {i} {e['op']}: not the fixture's entry; it is now {json.dumps(e)}"
+                    for i, (e, a, b) in enumerate(zip(got["calls"][k], g, w)) if a != b]
+        g, w = fp["results"][k].split(), want["results"][k].split()
+        if g != w:
+            out.append(f"call {k}: returned tensors {[i for i, (a, b) in enumerate(zip(g, w)) if a != b] if len(g) == len(w) else 'count'} "
+                       f"differ from the fixture's ({len(g)} tensors, fixture {len(w)})")
+    return out

@@ -37,7 +37,7 @@ INVENTORY = [
          "values written through .data (after ops.invalidate_caches)": ["test_ldm_chain_follows_a_data_write_after_invalidate_caches"],
          "ops.FP32": ["test_loss_modules_follow_fp32_validation_entered_and_left"],
          "a freed module's id and storage reused": []}, ["test_harness_reports_a_planted_stale_token"]),
-    row("chain state: time-bias table, step scalars, q_sample scalars, static buffers, chain graph", "DDIMSampler._graphs (PLMS, DPM-Solver alike)",
+    row("chain state (chain.new_state): time-bias table, step scalars, q_sample scalars, static buffers, chain graph", "DDIMSampler._graphs (PLMS, DPM-Solver alike)",
         "ldm.py", {"weights_token(": 1, "replay_captured(": 1},
         "(N, Cx, sp3, Cc, device, ctx_shape) + state_tag + inpaint / vq / log / split entries",
         "(S, ddim_timesteps, ddim_sigmas, weights_token(unet), step / q_sample scalar tables) + the codebook's identity",

@@ -311,3 +311,28 @@ def test_context_reaches_plms_ancestral_guided_and_hybrid_sampling(dev, g, chain
                                                verbose=False, x_T=x_T, dims=2)[0]
     base = hyb(ch, lat)
     assert differs(base, hyb(ch.flip(0).contiguous(), lat)) and differs(base, hyb(ch, lat.flip(0).contiguous()))
+
+
+def test_a_second_guided_call_allocates_nothing_for_the_unconditional_inputs(dev, g, chain_ldm):
+    """Classifier-free guidance on a full-size (not patch-wise) state: the unconditional UNet input and context are members of the
+    state, made on the first guided call and refilled by the second, which leaves no byte behind and follows its new inputs."""
+    from jointimagegeneration_amd.ldm import DDIMSampler
+    tok, x_T = T(g["chain_tokens"]).to(dev), T(g["chain_x_T"]).to(dev)
+    c = chain_ldm.get_learned_conditioning(tok)
+    uc, uc2 = c.flip(0).contiguous(), (c * 0.5).contiguous()
+    s = DDIMSampler(chain_ldm)
+    run = lambda u: s.sample(S=3, batch_size=2, shape=(4, 8, 8), conditioning=c, verbose=False, x_T=x_T, dims=2, unconditional_guidance_scale=3.0,
+                             unconditional_conditioning=u)[0]
+    z = run(uc)
+    assert len(s._graphs) == 1
+    st = next(iter(s._graphs.values()))
+    members = (st["cfg_unet_in"], st["cfg_ctx"].t)
+    torch.cuda.synchronize()
+    before = torch.cuda.memory_allocated()
+    z2 = run(uc)
+    torch.cuda.synchronize()
+    same = torch.equal(z, z2)
+    del z2
+    assert torch.cuda.memory_allocated() == before and same
+    assert st["cfg_unet_in"] is members[0] and st["cfg_ctx"].t is members[1]
+    assert not torch.equal(run(uc2), z) and torch.equal(run(uc), z)                 # refilled: nothing of the other call is left in them

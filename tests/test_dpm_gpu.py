@@ -374,3 +374,26 @@ def test_default_pipeline_is_unchanged_ddim(dev, small):
     assert all("hist" not in st and st["scal"].shape[1] == 4 for st in a.sampler._graphs.values())
     fast = GuideGenPipeline(None, small, ddim_steps=5, sampler="dpmpp_2m")
     assert not torch.equal(fast.sample_ct(labels, 7, 32, 4242), ct_a)
+
+
+def test_the_head_conv_is_never_asked_for_the_ddim_update(dev, small, operands):
+    """fuse_ddim set to True on the solver changes nothing: the head conv's epilogue is DDIM's update, which the class never asks for."""
+    from jointimagegeneration_amd.dpm_solver import DPMSolverSampler
+    from jointimagegeneration_amd.ldm import DDIMSampler
+    unet = small.model.diffusion_model
+    asked = []
+    unet.forward_cl = lambda *a, **k: (asked.append(k.get("head_ddim")), type(unet).forward_cl(unet, *a, **k))[1]
+    try:
+        want, _ = DPMSolverSampler(small).sample(S, N, SHAPE, conditioning=operands["c"], x_T=operands["x_T"], verbose=False)
+        sampler = DPMSolverSampler(small)
+        sampler.fuse_ddim = True
+        for k in range(3):                                                 # eager warm-up, capture + replay, replay
+            z, _ = sampler.sample(S, N, SHAPE, conditioning=operands["c"], x_T=operands["x_T"], verbose=False)
+            assert torch.equal(z, want) and sampler.last_step_fused is False, k
+        assert len(asked) >= 3 * sampler.ddim_timesteps.shape[0] and all(h is None for h in asked)
+        assert DPMSolverSampler.head_update_is_ddim is False and DDIMSampler.head_update_is_ddim is True
+        del asked[:]
+        DDIMSampler(small).sample(S, N, SHAPE, conditioning=operands["c"], x_T=operands["x_T"], verbose=False)
+        assert asked and all(h is not None for h in asked)                 # the wrapper does see DDIM's request
+    finally:
+        del unet.forward_cl

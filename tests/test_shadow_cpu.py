@@ -737,7 +737,7 @@ def test_contract_record_fails_assert_within_bounds():
 
 
 # ------------------------------------------------------------------------------------------------ completeness
-NETWORK_MODULES = ("cond", "lpips", "aeloss", "blocks", "unet", "ldm")
+NETWORK_MODULES = ("cond", "lpips", "aeloss", "blocks", "unet", "ldm", "chain")
 
 
 def ops_calls(source: str):
