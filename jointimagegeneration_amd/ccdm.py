@@ -8,6 +8,7 @@ fixed-shape step is captured in a hipGraph (torch.cuda.CUDAGraph) and replayed w
 """
 from __future__ import annotations
 
+import itertools
 import math
 from typing import Any, Dict, List, Optional, Sequence, Tuple, cast
 
@@ -16,10 +17,11 @@ import torch
 from torch import Tensor, nn
 
 from . import ops
+from .chain import nc_to_rows, rows_to_nc
 from .ops import CL, pad32
 from .unet import create_unet_openai
 
-__all__ = ["DiffusionModel", "DenoisingModel", "build_model", "linear_schedule", "cosine_schedule"]
+__all__ = ["DiffusionModel", "DenoisingModel", "build_model", "linear_schedule", "cosine_schedule", "uniform_x_T"]
 
 
 def linear_schedule(time_steps: int, start=1e-2, end=0.2):
@@ -39,6 +41,12 @@ def cosine_schedule(time_steps: int, s: float = 8e-3):
     return betas, 1 - betas, cumalphas
 
 
+def uniform_x_T(K: int, size: Sequence[int], seeds: Sequence[int], device) -> Tensor:
+    """One uniform categorical x_T (evaluator.py:135-136) per seed, each from its own generator: int32 labels [len(seeds), *size]."""
+    return torch.cat([torch.randint(0, K, (1,) + tuple(size), generator=torch.Generator(device=device).manual_seed(int(s)), device=device,
+                                    dtype=torch.int32) for s in seeds])
+
+
 class CategoricalBCHW:
     """What q_xt_given_x0 / q_xt_given_xtm1 return (the reference's OneHotCategoricalBCHW, one_hot_categorical.py): the distribution
     keep[b] * x + unif[b] / K around a one-hot x (mix [B, 2] = (keep, unif)).  `.probs` is channels-last [B, *sp, K], normalised as torch's Categorical does
@@ -51,7 +59,7 @@ class CategoricalBCHW:
     def probs(self) -> Tensor:
         nd = self.x.ndim
         k, u = (self.mix[:, i].view((-1,) + (1,) * (nd - 1)) for i in (0, 1))
-        p = (k * self.x + u / self.K).permute((0,) + tuple(range(2, nd)) + (1,))
+        p = nc_to_rows(k * self.x + u / self.K)
         return p / p.sum(-1, keepdim=True)
 
     def sample_labels(self, rng_tape: Optional[Tensor] = None, philox_seeds: Optional[Sequence[int]] = None) -> Tensor:
@@ -68,9 +76,7 @@ class CategoricalBCHW:
 
     def sample(self, rng_tape: Optional[Tensor] = None, philox_seeds: Optional[Sequence[int]] = None) -> Tensor:
         """One-hot NC[D]HW sample in x's dtype (index scatter of the kernel's labels: plumbing)."""
-        lab = self.sample_labels(rng_tape, philox_seeds)
-        nd = self.x.ndim
-        return torch.nn.functional.one_hot(lab.long(), self.K).permute((0, nd - 1) + tuple(range(1, nd - 1))).to(self.x.dtype)
+        return rows_to_nc(torch.nn.functional.one_hot(self.sample_labels(rng_tape, philox_seeds).long(), self.K)).to(self.x.dtype)
 
 
 class DiffusionModel(nn.Module):
@@ -147,17 +153,110 @@ class DiffusionModel(nn.Module):
         (one launch per distinct t). Returns the UN-clamped-equivalent normalised posterior (values >= 1e-12)."""
         ops.require_gpu(xt, "theta_post_prob")
         K = self.num_classes
-        nd = xt.ndim
-        perm = (0,) + tuple(range(2, nd)) + (1,)
-        inv = (0, nd - 1) + tuple(range(1, nd - 1))
-        out = torch.empty_like(theta_x0.permute(perm).contiguous())
+        out = torch.empty_like(nc_to_rows(theta_x0).contiguous())
         for b in range(xt.shape[0]):
             sc = self.step_scalars([int(t[b])]).to(xt.device)[0]
-            p0 = theta_x0[b:b + 1].permute(perm).contiguous().float()
+            p0 = nc_to_rows(theta_x0[b:b + 1]).contiguous().float()
             lab = xt[b:b + 1].argmax(dim=1).to(torch.int32).contiguous().view(-1)
             M = lab.numel()
             ops.ccdm_posterior_sample(p0.view(M, K), False, lab, sc, K, draw=False, probs_out=out[b].view(M, K))
-        return out.permute(inv)
+        return rows_to_nc(out)
+
+
+class LabelChain:
+    """The state of one `DenoisingModel.sample_labels` call and the launches made on it: the UNet input `xin` (channels-last; channels
+    [0, K) the one-hot of the int32 labels `lab` [M], then the condition), the head's `logits`, the posterior `probs` [M, K], the per-step
+    tables `table`, `scal`, `kmix`, `rmix`, and the `cur_*` buffers, from which a captured step reads its rows and its Philox offset
+    words in place.  `ladder` holds the step graph of `ops.replay_captured`: it lives, as all of this does, for one call."""
+
+    def __init__(self, model: "DenoisingModel", labels: Tensor, condition: Optional[Tensor], tv: Sequence[int],
+                 seeds: Optional[Sequence[int]], known_f: Optional[Tensor], keep_f: Optional[Tensor], resample: int):
+        dev, unet, diffusion = labels.device, model.unet, model.diffusion
+        self.model, self.K, self.M = model, diffusion.num_classes, labels.numel()
+        self.masked, self.edit, self.bf16 = known_f is not None, known_f is not None or resample > 1, not ops.FP32
+        K, M, N = self.K, self.M, labels.shape[0]
+        sp3 = (1,) * (4 - labels.ndim) + tuple(labels.shape[1:])
+        self.scal = diffusion.step_scalars(tv).to(dev)
+        self.table = unet.time_bias_table(torch.tensor(tv, dtype=torch.float32, device=dev), N)
+        self.xin = torch.zeros((N,) + sp3 + (pad32(unet.in_channels),), dtype=torch.bfloat16 if self.bf16 else torch.float32, device=dev)
+        self.lab = labels.contiguous().view(-1).clone()
+        ops.labels_to_onehot(self.lab, K, self.xin.view(M, -1))       # channels [0,K) one-hot, rest zero
+        if condition is not None:                                     # unet.py:774-775: cat([x, input_condition], 1)
+            ops.to_cl(condition.to(dev), out=self.xin, c_offset=K, zero_fill=False)
+        self.logits = torch.empty((N,) + sp3 + (pad32(K),), dtype=torch.float32, device=dev)
+        self.probs = torch.empty((M, K), dtype=torch.float32, device=dev)
+        self.cur_bias = torch.empty_like(self.table[0])
+        self.cur_scal = torch.empty(2, dtype=torch.float32, device=dev)
+        self.cur_off = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.xcl = CL(self.xin, unet.in_channels)
+        self.seeds = None if seeds is None else ops.philox_seed_tensor(seeds, dev)
+        if self.masked:
+            self.known, self.keep = known_f.to(dev), keep_f.to(dev)
+            self.kmix = diffusion.known_mix(tv).to(dev)
+            self.cur_kmix = torch.empty((N, 2), dtype=torch.float32, device=dev)
+            self.cur_koff = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.rmix = None
+        if resample > 1:
+            self.rmix = diffusion.renoise_mix(tv).to(dev)
+            self.cur_rmix = torch.empty((N, 2), dtype=torch.float32, device=dev)
+            self.cur_roff = torch.zeros(1, dtype=torch.int64, device=dev)
+            self.rkeys = self.keys()
+        self.ladder = dict(warmed=False, graph=None)
+
+    def keys(self) -> Tensor:
+        """gg_ccdm_q_sample draws per sample; the single-key stream (key philox_seed, counter = the row of the batch) is its one-sample case."""
+        return self.seeds if self.seeds is not None else ops.philox_seed_tensor([self.model.philox_seed], self.lab.device)
+
+    def onehot_out(self, final: bool = False) -> Optional[Tensor]:
+        """The launch that changes the labels refreshes the UNet's one-hot input in bf16; `refresh_onehot` does in fp32 validation mode."""
+        return self.xin.view(self.M, -1) if (self.bf16 and not final) else None
+
+    def refresh_onehot(self, final: bool = False) -> None:
+        if not (self.bf16 or final):                                           # fp32 validation mode: an index scatter
+            ops.labels_to_onehot(self.lab, self.K, self.xin.view(self.M, -1))
+
+    def set_step(self, i: int, t: int, j: int) -> None:
+        if j == 0:
+            self.cur_bias.copy_(self.table[i]); self.cur_scal.copy_(self.scal[i])
+            if self.masked:
+                self.cur_kmix.copy_(self.kmix[i])
+            if self.rmix is not None:
+                self.cur_rmix.copy_(self.rmix[i])
+        self.t, self.j = t, j                                         # `renoise` fills its own word, immediately before its launch
+        self.cur_off.fill_(ops.philox_offset_word(t, j, ops.PHILOX_POSTERIOR) if self.edit else t)
+        if self.masked:
+            self.cur_koff.fill_(ops.philox_offset_word(t, j, ops.PHILOX_KNOWN))
+
+    def step(self, draw: bool, E=None, want_probs: bool = False) -> None:
+        m = self.model
+        post = dict(xt=self.lab, scalars=self.cur_scal, K=self.K, E=E, philox_seed=m.philox_seed, philox_offset=self.cur_off, draw=draw,
+                    labels_out=self.lab, onehot_out=self.onehot_out(), philox_seeds=self.seeds)
+        # softmax + posterior + draw as the head conv's epilogue where the kernel can (ops.conv `post`): the fp32 logits (128 B per
+        # voxel) are then never written; steps that return the posterior itself (the last one, traces) take the sampler kernel
+        head = m.unet.forward_cl(self.xcl, self.cur_bias, head_out=self.logits, head_post=post if (self.bf16 and not want_probs) else None)
+        m.last_step_fused = head.fused_post
+        if not head.fused_post:
+            ops.ccdm_posterior_sample(self.logits.view(self.M, -1), True, probs_out=self.probs if want_probs else None, **post)
+            self.refresh_onehot()
+
+    def blend(self, E=None, final: bool = False) -> None:
+        """x_t <- a draw of q(x_t | x_0 = known) where keep != 0, into the labels and the one-hot UNet input (operands (1, 0): known itself)."""
+        ops.ccdm_inpaint_blend(self.lab, self.known, self.keep, self.cur_kmix, self.K, E=E, philox_seed=self.model.philox_seed,
+                               philox_seeds=self.seeds, philox_offset=self.cur_koff, onehot_out=self.onehot_out(final))
+        self.refresh_onehot(final)
+
+    def renoise(self, E=None) -> None:
+        """x_t <- a draw of q(x_t | x_{t-1}) on every voxel, in place."""
+        self.cur_roff.fill_(ops.philox_offset_word(self.t, self.j, ops.PHILOX_RENOISE))
+        mix = self.cur_rmix if (self.seeds is not None or E is not None) else self.cur_rmix[:1]
+        ops.ccdm_q_sample(self.lab, mix, self.K, E=E, philox_seeds=None if E is not None else self.rkeys, philox_offset=self.cur_roff,
+                          labels_out=self.lab, onehot_out=self.onehot_out())
+        self.refresh_onehot()
+
+    def graphed_step(self) -> None:                                   # what `ops.replay_captured` captures
+        if self.masked:
+            self.blend()
+        self.step(True)
 
 
 class DenoisingModel(nn.Module):
@@ -169,6 +268,7 @@ class DenoisingModel(nn.Module):
         self.dataset_file, self.step_T_sample = dataset_file, step_T_sample
         self.philox_seed = 1024           # RNG of the throughput path (counter-based, in-kernel)
         self.use_graph = True
+        self.last_step_fused = False      # whether the last eager step ran as the head conv's epilogue
 
     @property
     def time_steps(self):
@@ -211,12 +311,10 @@ class DenoisingModel(nn.Module):
         labels = x.argmax(dim=1).to(torch.int32).contiguous()                   # x_T one-hot -> labels (plumbing)
         lab, probs = self.sample_labels(labels, condition, init_t, rng_tapes, known=known, keep=keep, resample=resample)
         K = self.diffusion.num_classes
-        nd = x.ndim
-        inv = (0, nd - 1) + tuple(range(1, nd - 1))
         if self.step_T_sample is None or self.step_T_sample == "majority":
-            out = torch.nn.functional.one_hot(lab.long(), K).permute(inv)       # int64 one-hot like max_prob_sample
+            out = rows_to_nc(torch.nn.functional.one_hot(lab.long(), K))        # int64 one-hot like max_prob_sample
         elif self.step_T_sample == "confidence":
-            out = probs.view(*lab.shape, K).permute(inv)
+            out = rows_to_nc(probs.view(*lab.shape, K))
         else:
             raise ValueError(f"step_T_sample={self.step_T_sample}")
         return {"diffusion_out": out}
@@ -264,139 +362,45 @@ class DenoisingModel(nn.Module):
         rng_tapes: per (t, j) the blend tape (with a mask), the posterior tape (t > 1), the re-noise tape (j < R - 1), in that order.
         trace entries: t, j, labels, probs and, with a mask, x_in (the labels after the blend, the UNet's input)."""
         known_f, keep_f = self.check_edit(labels.shape, known, keep, resample)
-        masked = known_f is not None
-        edit = masked or resample > 1
-        dev = labels.device
-        K = self.diffusion.num_classes
-        unet = self.unet
-        N = labels.shape[0]
-        sp = tuple(labels.shape[1:])
-        sp3 = (1,) * (3 - len(sp)) + sp
-        M = labels.numel()
+        if philox_seeds is not None and len(philox_seeds) != labels.shape[0]:
+            raise ValueError(f"sample_labels: {len(philox_seeds)} philox_seeds for a batch of {labels.shape[0]}")
         tv = self.t_values(init_t)
         S = len(tv)
-        scal = self.diffusion.step_scalars(tv).to(dev)
-        table = unet.time_bias_table(torch.tensor(tv, dtype=torch.float32, device=dev), N)
-        cin = unet.in_channels
-        xin = torch.zeros((N,) + sp3 + (pad32(cin),), dtype=torch.float32 if ops.FP32 else torch.bfloat16, device=dev)
-        lab = labels.contiguous().view(-1).clone()
-        ops.labels_to_onehot(lab, K, xin.view(M, -1))                 # channels [0,K) one-hot, rest zero
-        if condition is not None:                                     # unet.py:774-775: cat([x, input_condition], 1)
-            ops.to_cl(condition.to(dev), out=xin, c_offset=K, zero_fill=False)
-        logits = torch.empty((N,) + sp3 + (pad32(K),), dtype=torch.float32, device=dev)
-        probs = torch.empty((M, K), dtype=torch.float32, device=dev)
-        cur_bias = torch.empty_like(table[0])
-        cur_scal = torch.empty(2, dtype=torch.float32, device=dev)
-        cur_off = torch.zeros(1, dtype=torch.int64, device=dev)
-        xcl = CL(xin, cin)
-        seeds = None
-        if philox_seeds is not None:
-            if len(philox_seeds) != N:
-                raise ValueError(f"sample_labels: {len(philox_seeds)} philox_seeds for a batch of {N}")
-            seeds = ops.philox_seed_tensor(philox_seeds, dev)
-
-        def step(draw: bool, E=None, want_probs=False):
-            bf16_in = xin.dtype == torch.bfloat16
-            # softmax + posterior + draw as the head conv's epilogue where the kernel can (ops.conv `post`): the fp32 logits (128 B per
-            # voxel) are then never written; steps that return the posterior itself (the last one, traces) take the sampler kernel
-            post = dict(xt=lab, scalars=cur_scal, K=K, E=E, philox_seed=self.philox_seed, philox_offset=cur_off, draw=draw, labels_out=lab,
-                        onehot_out=xin.view(M, -1), philox_seeds=seeds) if (bf16_in and not want_probs) else None
-            head = unet.forward_cl(xcl, cur_bias, head_out=logits, head_post=post)
-            self.last_step_fused = head.fused_post
-            if head.fused_post:
-                return
-            ops.ccdm_posterior_sample(logits.view(M, -1), True, lab, cur_scal, K, E=E, philox_seed=self.philox_seed,
-                                      philox_offset=cur_off, draw=draw, labels_out=lab,
-                                      probs_out=probs if want_probs else None, onehot_out=xin.view(M, -1) if bf16_in else None,
-                                      philox_seeds=seeds)
-            if not bf16_in:                                           # fp32 validation mode: the one-hot input is refreshed by an index scatter
-                ops.labels_to_onehot(lab, K, xin.view(M, -1))
-
-        bf16_state = xin.dtype == torch.bfloat16
-        if masked:
-            known_f, keep_f = known_f.to(dev), keep_f.to(dev)
-            kmix = self.diffusion.known_mix(tv).to(dev)
-            cur_kmix = torch.empty((N, 2), dtype=torch.float32, device=dev)
-            cur_koff = torch.zeros(1, dtype=torch.int64, device=dev)
-        if resample > 1:
-            rmix = self.diffusion.renoise_mix(tv).to(dev)
-            cur_rmix = torch.empty((N, 2), dtype=torch.float32, device=dev)
-            cur_roff = torch.zeros(1, dtype=torch.int64, device=dev)
-            # gg_ccdm_q_sample draws per sample; the single-key stream (key philox_seed, counter = the row of the batch) is its one-sample case
-            rkeys = seeds if seeds is not None else ops.philox_seed_tensor([self.philox_seed], dev)
-
-        def blend(E=None, final=False):
-            # x_t <- a draw of q(x_t | x_0 = known) where keep != 0, into the labels and the one-hot UNet input (operands (1, 0): known itself)
-            ops.ccdm_inpaint_blend(lab, known_f, keep_f, cur_kmix, K, E=E, philox_seed=self.philox_seed, philox_seeds=seeds,
-                                   philox_offset=cur_koff, onehot_out=xin.view(M, -1) if (bf16_state and not final) else None)
-            if not bf16_state and not final:
-                ops.labels_to_onehot(lab, K, xin.view(M, -1))
-
-        def renoise(E=None):
-            # x_t <- a draw of q(x_t | x_{t-1}) on every voxel, in place
-            mix = cur_rmix if (seeds is not None or E is not None) else cur_rmix[:1]
-            ops.ccdm_q_sample(lab, mix, K, E=E, philox_seeds=None if E is not None else rkeys, philox_offset=cur_roff, labels_out=lab,
-                              onehot_out=xin.view(M, -1) if bf16_state else None)
-            if not bf16_state:
-                ops.labels_to_onehot(lab, K, xin.view(M, -1))
-
-        def masked_step():
-            blend()
-            step(True)
-
+        st = LabelChain(self, labels, condition, tv, philox_seeds, known_f, keep_f, resample)
         if rng_tapes is not None:
             # per (t, j): the blend tape with a mask, the posterior tape of a DRAWING step (t = 1 takes the argmax), the re-noise tape
-            need = sum(resample * (int(masked) + int(t > 1)) + (resample - 1) for t in tv)
+            need = sum(resample * (int(st.masked) + int(t > 1)) + (resample - 1) for t in tv)
             if len(rng_tapes) < need:
-                what = f"{need} drawing steps (t = {tv[0]} .. 2)" if not edit else \
-                    f"{S} steps (t = {tv[0]} .. {tv[-1]}) x {resample} repetitions{' with a mask' if masked else ''}"
+                what = f"{need} drawing steps (t = {tv[0]} .. 2)" if not st.edit else \
+                    f"{S} steps (t = {tv[0]} .. {tv[-1]}) x {resample} repetitions{' with a mask' if st.masked else ''}"
                 raise ValueError(f"sample_labels: {what} need {need} rng tapes, got {len(rng_tapes)}")
+        tapes = itertools.repeat(None) if rng_tapes is None else (tp.to(labels.device).contiguous() for tp in rng_tapes)   # read in draw order
         use_graph = self.use_graph and rng_tapes is None and trace is None and S > 3 and not ops.FP32
-        ladder, ti = dict(warmed=False, graph=None), 0               # lives for this call
-        graphed_step = masked_step if masked else (lambda: step(True))
-
-        def tape():
-            nonlocal ti
-            if rng_tapes is None:
-                return None
-            ti += 1
-            return rng_tapes[ti - 1].to(dev).contiguous()
-
         for i, t in enumerate(tv):
-            cur_bias.copy_(table[i]); cur_scal.copy_(scal[i])
-            if masked:
-                cur_kmix.copy_(kmix[i])
-            if resample > 1:
-                cur_rmix.copy_(rmix[i])
             for j in range(resample):
-                cur_off.fill_(ops.philox_offset_word(t, j, ops.PHILOX_POSTERIOR) if edit else t)
-                if masked:
-                    cur_koff.fill_(ops.philox_offset_word(t, j, ops.PHILOX_KNOWN))
+                st.set_step(i, t, j)
                 last, draw = (i == S - 1 and j == resample - 1), (t > 1)
-                x_in = None
                 if use_graph and draw and not last:
-                    ops.replay_captured(ladder, "graph", graphed_step)   # the fixed-shape step: eager once, captured once (hipGraph)
+                    ops.replay_captured(st.ladder, "graph", st.graphed_step)   # the fixed-shape step: eager once, captured once (hipGraph)
                 else:
-                    if masked:
-                        blend(tape())
-                        if trace is not None:
-                            x_in = lab.clone().view(labels.shape)
-                    step(draw, tape() if draw else None, want_probs=last or trace is not None)
+                    if st.masked:
+                        st.blend(next(tapes))
+                        x_in = st.lab.clone().view(labels.shape) if trace is not None else None
+                    st.step(draw, next(tapes) if draw else None, want_probs=last or trace is not None)
                 if trace is not None:
-                    entry = dict(t=t, j=j, labels=lab.clone().view(labels.shape), probs=probs.clone())
-                    if masked:
+                    entry = dict(t=t, j=j, labels=st.lab.clone().view(labels.shape), probs=st.probs.clone())
+                    if st.masked:
                         entry["x_in"] = x_in
                     trace.append(entry)
                 if j < resample - 1:                                 # between two repetitions, outside the captured step
-                    cur_roff.fill_(ops.philox_offset_word(t, j, ops.PHILOX_RENOISE))
-                    renoise(tape())
-        if masked:
+                    st.renoise(next(tapes))
+        if st.masked:
             # the labels are discrete and kept anatomy must come back unchanged: one more blend with operands (1, 0), whose race has one
             # non-zero class, and the returned posterior rows of the kept voxels are the one-hot of known (an index select: plumbing)
-            cur_kmix.copy_(torch.tensor([1.0, 0.0], dtype=torch.float32, device=dev))
-            blend(final=True)
-            probs = torch.where(keep_f.view(-1, 1) != 0, torch.nn.functional.one_hot(known_f.long(), K).to(probs.dtype), probs)
-        return lab.view(labels.shape), probs
+            st.cur_kmix.copy_(torch.tensor([1.0, 0.0], dtype=torch.float32, device=labels.device))
+            st.blend(final=True)
+            st.probs = torch.where(st.keep.view(-1, 1) != 0, torch.nn.functional.one_hot(st.known.long(), st.K).to(st.probs.dtype), st.probs)
+        return st.lab.view(labels.shape), st.probs
 
 
 def build_model(time_steps: int, schedule: str, schedule_params, input_shapes, cond_encoded_shape, backbone: str,

@@ -45,7 +45,7 @@ import yaml
 from . import distributed as ggd
 from . import metrics
 from . import postprocess
-from .ccdm import build_model
+from .ccdm import build_model, uniform_x_T
 from .encoder import build_feature_cond_encoder
 from .io import load_checkpoint, read_nifti, write_nifti
 from .losses import ccdm_step_losses
@@ -215,15 +215,13 @@ def main(argv=None):
             known, keep = (torch.from_numpy(a).to(dev)[None].expand((S,) + size).contiguous() for a in edits[vid])
             ed = dict(known=known, keep=keep, resample=args.resample)
         if S == 1:
-            g = torch.Generator(device=dev).manual_seed(1024 + vid)
-            x_T = torch.randint(0, K, (1,) + size, generator=g, device=dev, dtype=torch.int32)   # uniform categorical x_T
+            x_T = uniform_x_T(K, size, [1024 + vid], dev)
             model.philox_seed = 1024 + vid
             labels, _ = model.sample_labels(x_T, torch.zeros((1, 1) + size, device=dev), init_t, **ed)
             write_nifti(os.path.join(out_dir, f"pred_{vid:04d}.nii.gz"), labels[0].to(torch.uint8).cpu().numpy())
         else:                                                                         # the S masks of a volume: one batch, S independent chains
             seeds = [1024 + vid * S + j for j in range(S)]
-            x_T = torch.cat([torch.randint(0, K, (1,) + size, generator=torch.Generator(device=dev).manual_seed(sd), device=dev, dtype=torch.int32)
-                             for sd in seeds])
+            x_T = uniform_x_T(K, size, seeds, dev)
             labels, _ = model.sample_labels(x_T, torch.zeros((S, 1) + size, device=dev), init_t, philox_seeds=seeds, **ed)
             host = labels.to(torch.uint8).cpu().numpy()
             for j in range(S):

@@ -24,7 +24,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import ops
-from .ccdm import DenoisingModel, DiffusionModel
+from .ccdm import DenoisingModel, DiffusionModel, uniform_x_T
 from .ldm import DDIMSampler, LatentDiffusion
 from .ops import CL
 from .synth import randomize_parameters
@@ -209,9 +209,7 @@ class GuideGenPipeline:
         (per-sample key of the reverse step), so that it depends on nothing its neighbours hold.  Returns int32 labels [B, D, H, W].
         known / keep / resample: mask editing, as `DenoisingModel.sample_labels` takes them ([B, D, H, W])."""
         dev = self.ccdm.diffusion.betas.device
-        K = self.ccdm.diffusion.num_classes
-        x_T = torch.cat([torch.randint(0, K, (1,) + tuple(size), generator=torch.Generator(device=dev).manual_seed(int(s)), device=dev,
-                                       dtype=torch.int32) for s in seeds])
+        x_T = uniform_x_T(self.ccdm.diffusion.num_classes, size, seeds, dev)
         cond = torch.zeros((len(seeds), 1) + tuple(size), device=dev)
         labels, _ = self.ccdm.sample_labels(x_T, cond, init_t, philox_seeds=[int(s) for s in seeds], known=known, keep=keep, resample=resample)
         return labels

@@ -61,7 +61,7 @@ INVENTORY = [
          "first_stage_model weights": ["test_pipeline_follows_a_stage_weight"],
          "ldm.scale_factor (float, or the scale_by_std buffer)": ["test_pipeline_follows_scale_factor"],
          "the chain state (schedule of ldm)": ["test_pipeline_follows_the_schedule"]}, []),
-    row("CCDM step graph (lives for one sample_labels call)", "a local ladder dict of DenoisingModel.sample_labels", "ccdm.py",
+    row("CCDM step graph (lives for one sample_labels call)", "LabelChain.ladder, the state DenoisingModel.sample_labels builds per call", "ccdm.py",
         {"replay_captured(": 1}, "none: rebuilt per call", "none",
         {"UNet weights": ["test_ccdm_labels_follow_a_unet_weight"], "the diffusion schedule": ["test_ccdm_labels_follow_the_schedule"]}, []),
     row("LPIPS packs", "LPIPS._packs", "lpips.py", {"weights_token(": 1}, "ops.FP32", "(ops.FP32, weights_token(self), identity of shift / scale)",

@@ -30,4 +30,4 @@ for rnd in range(2):
         t30, lab = min((chain(30) for _ in range(2)), key=lambda r: r[0])
         same = "" if ref is None else f"  labels equal to the first run: {bool(torch.equal(ref, lab))}"
         ref = lab if ref is None else ref
-        print(f"fused reverse step {fuse}: {(t30 - t10) / 20 * 1e3:.3f} ms per captured step (last_step_fused {getattr(ccdm, 'last_step_fused', None)}){same}", flush=True)
+        print(f"fused reverse step {fuse}: {(t30 - t10) / 20 * 1e3:.3f} ms per captured step (last_step_fused {ccdm.last_step_fused}){same}", flush=True)
