@@ -498,6 +498,43 @@ int gg_component_filter(const int32_t *labels, const int32_t *root, const int32_
                         int32_t K, const int32_t *keep_largest, const int32_t *min_size, int32_t background, int32_t fill,
                         int32_t *out_labels, uint8_t *kept, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Surface distances of label volumes (gg_surface.hip): the class borders, an exact Euclidean distance transform and the
+ * per-volume reduction that Hausdorff distance, HD95 and the average surface distances are read from (medpy.metric.binary's
+ * definitions, the module the reference's evaluator takes dc / precision / recall from).  The rules of the entries above: labels are
+ * contiguous int32 [B, D, H, W] on the device (M = D * H * W < 2^31, B <= 65535), memory and workspace are the caller's, all work is on
+ * the passed stream, no allocation, no host read-back, no synchronisation: capturable.  No atomics: every output is a fixed function
+ * of the inputs, bit for bit, whatever the order the workgroups run in.  Volumes never mix and rows never wrap.
+ *
+ * gg_label_border: border uint8 [B, M] = 1 where labels[v] lies in [0, K) and some neighbour of v under scipy's
+ *   generate_binary_structure(3, connectivity) -- the offsets in {-1, 0, 1}^3 with 1 <= |dd| + |dh| + |dw| <= connectivity; 1: faces,
+ *   2: and edges, 3: and corners -- carries another label or lies outside the volume; 0 everywhere else.  For every class c at once this
+ *   is m ^ binary_erosion(m, structure, iterations=1, border_value=0) with m = labels == c; an axis of extent 1 makes every voxel of a
+ *   class a border voxel.  1 <= K <= 32, connectivity 1, 2 or 3. */
+int gg_label_border(const int32_t *labels, int32_t B, int32_t D, int32_t H, int32_t W, int32_t K, int32_t connectivity, uint8_t *border,
+                    void *stream);
+/* gg_edt_squared: sq fp64 [B, M], sq[v] = min over the sites u of v's own volume of (sd dd)^2 + (sh dh)^2 + (sw dw)^2, +inf in a volume
+ *   without sites.  A site is a voxel with labels == cls and border != 0; border == NULL makes every voxel of class cls a site (the
+ *   general-purpose form).  sd, sh, sw: finite spacings > 0.  Exact and separable: three passes, along W, H and D, each the lower
+ *   envelope of the parabolas of one line, every line staged whole in LDS, each output scanning outwards from its own position until
+ *   (s k)^2 alone reaches its best value.  Each term is formed as (s * k) * (s * k) and added without contraction, so with unit spacing
+ *   -- or any spacing whose products stay exactly representable -- sq is the integer answer bit for bit.
+ *   No extent D, H or W may exceed 1024, the line length the LDS tile is sized for (8192 fp64 values: at least 8 lines of 1024 side by
+ *   side): a longer one is GG_ERR_UNSUPPORTED, by name.  workspace: gg_edt_squared_workspace_bytes(B, D, H, W) bytes (one fp64 volume
+ *   set, the other side of the passes' ping-pong); 0 for extents outside the supported range. */
+int64_t gg_edt_squared_workspace_bytes(int32_t B, int32_t D, int32_t H, int32_t W);
+int gg_edt_squared(const int32_t *labels, const uint8_t *border, int32_t cls, int32_t B, int32_t D, int32_t H, int32_t W, double sd,
+                   double sh, double sw, double *sq, void *workspace, int64_t workspace_bytes, void *stream);
+/* gg_surface_reduce: over the voxels v of volume b with border_a[v] != 0 and labels_a[v] == cls (border_a == NULL: labels_a[v] == cls),
+ *   dist2 fp64 [B, M] = sq_b[v] there and -1 at every other voxel; stats fp64 [B, 3] = (their count, the sum of sqrt(sq_b) over them, the
+ *   maximum of sq_b over them; (0, 0, -1) when there is none).  Two stages: one workgroup per chunk of 4096 voxels (each thread adds its
+ *   16 voxels in index order, the workgroup combines by a fixed tree), then one workgroup per volume adds the chunks' partials in a fixed
+ *   order; the chunk count is an argument of the second kernel.  Two runs on one input give the same bits.
+ *   workspace: gg_surface_reduce_workspace_bytes(B, M) bytes (three fp64 per chunk). */
+int64_t gg_surface_reduce_workspace_bytes(int32_t B, int64_t M);
+int gg_surface_reduce(const int32_t *labels_a, const uint8_t *border_a, const double *sq_b, int32_t cls, int32_t B, int64_t M, double *dist2,
+                      double *stats, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* Three-view LPIPS of CT volumes (ldm/modules/losses/lpips.py; latentdiffusion/sample_diffusion.py:437-475), gg_lpips.hip: the kernels
  * around the VGG16 convolutions (which are gg_conv_forward / gg_conv_forward_f32 calls).  All three: the caller's stream, no allocation,
  * no synchronisation, capturable.

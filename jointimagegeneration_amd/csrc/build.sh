@@ -16,7 +16,7 @@ stale() {
 }
 OBJS=()
 PIDS=()
-for f in gg_conv gg_conv_halo gg_conv_halo3 gg_conv_box gg_conv_box_spec gg_conv_tiny gg_conv_tile gg_norm gg_attn gg_sampler gg_loss gg_patchgan gg_vq gg_metrics gg_components gg_lpips gg_render gg_fold gg_f32 gg_resample gg_cond gg_ubench; do
+for f in gg_conv gg_conv_halo gg_conv_halo3 gg_conv_box gg_conv_box_spec gg_conv_tiny gg_conv_tile gg_norm gg_attn gg_sampler gg_loss gg_patchgan gg_vq gg_metrics gg_components gg_surface gg_lpips gg_render gg_fold gg_f32 gg_resample gg_cond gg_ubench; do
   if stale $f; then
     echo "hipcc $f.hip"
     EXTRA=""

@@ -28,6 +28,13 @@ metrics.json.  `--largest-component all|a,b,c`, `--min-component V` and `--conne
 single sample at --samples 1 -- into `clean_{vid:04d}.nii.gz` and add a `components` block: per volume and class the components, voxels
 and largest component before and after.  With --gt, `dice_consensus` / `dice_clean` (and their means) score the two new masks.  The
 existing keys and files are untouched (--keep-mask / --keep-classes belong to mask editing, hence the new names).
+
+Surface distances (metrics.surface_distances; medpy.metric.binary's hd / hd95 / asd / assd, the module evaluator.py takes dc, precision
+and recall from): `--gt DIR --surface [--spacing d,h,w] [--surface-connectivity 1|2|3]` adds a `surface` block to metrics.json: the five
+scores per class, their class means and `absent` (the classes missing from the prediction or the ground truth, which have no surface
+distance: null), per volume and averaged over the run; with --samples S a volume's scores are the mean over its S masks.  With the
+cleaning options `hd95_consensus` / `hd95_clean` stand beside `dice_consensus` / `dice_clean`.  --gt alone now also reports `precision`
+and `recall` per class beside Dice.  Without --surface none of the surface kernels is launched.
 """
 from __future__ import annotations
 
@@ -117,6 +124,26 @@ def load_edit(args, vids, size, K: int):
     return out
 
 
+def score_volume(labels: torch.Tensor, gt: torch.Tensor, K: int, ignore, surf):
+    """The scores of one volume's S masks against its ground truth: (confusion matrix, ensemble scores or None, the volume's surface
+    document -- metrics.case_surface -- or None without --surface).  A seam for the tests: main's only scoring call, so that a test
+    without a device can show that no surface op is reached when `surf` is None."""
+    cm, scores = metrics.score_case(labels, gt, K)
+    return cm, scores, (metrics.case_surface(labels, gt, K, surf, ignore) if surf is not None else None)
+
+
+def pack_surface(doc: dict) -> torch.Tensor:
+    """The five [K] rows of a surface document as fp64 bit patterns (int64 [5 K]); None travels as NaN."""
+    rows = [[float("nan") if v is None else v for v in doc[name]] for name in metrics.SURFACE_SCORES]
+    return torch.tensor(rows, dtype=torch.float64).reshape(-1).view(torch.int64)
+
+
+def unpack_surface(bits: torch.Tensor, K: int, classes) -> dict:
+    vals = bits.contiguous().view(torch.float64).reshape(len(metrics.SURFACE_SCORES), K).tolist()
+    rows = {name: [None if v != v else v for v in row] for name, row in zip(metrics.SURFACE_SCORES, vals)}
+    return metrics.mean_surface([rows], classes)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("params_file", nargs="?", default="params_eval.yml")
@@ -136,6 +163,7 @@ def main(argv=None):
     ap.add_argument("--resample", type=int, default=1, help="repetitions of every step of an edited chain (re-noised one step in between)")
     ap.add_argument("--consensus", action="store_true", help="with --samples S > 1: write the per-voxel vote of the S masks and its entropy")
     postprocess.add_cleanup_arguments(ap)
+    metrics.add_surface_arguments(ap)
     args = ap.parse_args(argv)
     if args.resample < 1:
         raise ValueError(f"--resample {args.resample}: at least one repetition per step")
@@ -161,6 +189,11 @@ def main(argv=None):
     clean_opts = postprocess.cleanup_options(args, K)
     if clean_opts is not None and S > 1 and not args.consensus:
         raise ValueError("--largest-component / --min-component clean ONE mask per volume: with --samples S > 1 give --consensus")
+    surf = metrics.surface_options(args)
+    if surf is not None and not args.gt:
+        raise ValueError("--surface needs --gt DIR: surface distances are measured against the ground-truth volumes")
+    if surf is not None and (len(size) != 3 or max(size) > metrics.ops.EDT_MAX_EXTENT):
+        raise ValueError(f"--surface: volume {size} has an extent above {metrics.ops.EDT_MAX_EXTENT}, the longest line of the distance transform")
     if any(t < 1 or t > params["time_steps"] for t in loss_ts):
         raise ValueError(f"--loss-t {args.loss_t}: steps are 1..{params['time_steps']}")
     assert torch.cuda.is_available(), "the GuideGen engine needs an MI355X (no CPU fallback)"
@@ -209,6 +242,9 @@ def main(argv=None):
     # then the [K, K] counts of the consensus and of the cleaned mask against the ground truth
     post_vol = 3 + 8 * K
     post_buf = torch.zeros(post_vol * n_vol + 2 * K * K, dtype=torch.int64, device=dev) if (args.consensus or clean_opts is not None) else None
+    # the surface block travels the same way: per volume the five [K] rows of its scores, then the hd95 rows of the consensus and of the
+    # cleaned mask, all as fp64 bit patterns (NaN: no surface distance)
+    surf_buf = torch.zeros((n_vol, 7 * K), dtype=torch.int64, device=dev) if surf is not None else None
     for vid in vids:                                                                  # volumes are independent units
         ed = {}
         if edits is not None:                                                         # the S masks of a volume share one known / keep pair
@@ -243,6 +279,9 @@ def main(argv=None):
                 if gts is not None:
                     post_buf[post_vol * n_vol:post_vol * n_vol + K * K] += metrics.confusion_matrix(
                         torch.from_numpy(gts[vid]).to(dev), mask, K).reshape(-1)
+                    if surf is not None:
+                        sd = metrics.case_surface(mask[None], torch.from_numpy(gts[vid]).to(dev), K, surf, ignore)
+                        surf_buf[vid, 5 * K:6 * K] = pack_surface(sd)[K:2 * K].to(dev)
             if clean_opts is not None:
                 cleaned, _ = postprocess.clean(mask, K, scores=False, **clean_opts)[:2]
                 tables = torch.stack([postprocess.components(m, K, clean_opts["connectivity"])[2][0] for m in (mask, cleaned)])
@@ -250,9 +289,14 @@ def main(argv=None):
                 write_nifti(os.path.join(out_dir, f"clean_{vid:04d}.nii.gz"), cleaned.to(torch.uint8).cpu().numpy())
                 if gts is not None:
                     post_buf[post_vol * n_vol + K * K:] += metrics.confusion_matrix(torch.from_numpy(gts[vid]).to(dev), cleaned, K).reshape(-1)
+                    if surf is not None:
+                        sd = metrics.case_surface(cleaned[None], torch.from_numpy(gts[vid]).to(dev), K, surf, ignore)
+                        surf_buf[vid, 6 * K:] = pack_surface(sd)[K:2 * K].to(dev)
         if gts is not None:
-            cm, scores = metrics.score_case(labels, torch.from_numpy(gts[vid]).to(dev), K)
+            cm, scores, sd = score_volume(labels, torch.from_numpy(gts[vid]).to(dev), K, ignore, surf)
             score_buf[:K * K] += cm.reshape(-1)
+            if sd is not None:
+                surf_buf[vid, :5 * K] = pack_surface(sd).to(dev)
             if scores is not None:
                 vals = torch.tensor([scores["ged"], scores["diversity_pred"], scores["diversity_gt"], scores["hm_iou"]], dtype=torch.float64)
                 score_buf[K * K + 4 * vid:K * K + 4 * vid + 4] = vals.view(torch.int64).to(dev)
@@ -302,6 +346,11 @@ def main(argv=None):
         if rank == 0 and score_buf is None:
             with open(os.path.join(out_dir, "metrics.json"), "w") as f:
                 json.dump(dict(edit=edit_doc, **post_doc), f, indent=1)
+    surf_host = None
+    if surf_buf is not None:
+        if torch.distributed.is_available() and torch.distributed.is_initialized():
+            torch.distributed.all_reduce(surf_buf)                                    # a volume belongs to one rank, the others hold zeros
+        surf_host = surf_buf.cpu()
     if score_buf is not None:
         if torch.distributed.is_available() and torch.distributed.is_initialized():
             torch.distributed.all_reduce(score_buf)                                   # once, after the sampling loop: off the data path
@@ -319,6 +368,16 @@ def main(argv=None):
             if edit_doc is not None:
                 doc["edit"] = edit_doc
             doc.update(post_doc)
+            if surf_host is not None:
+                classes = doc["dice_classes"]
+                doc["surface"] = metrics.surface_block({v: unpack_surface(surf_host[v, :5 * K], K, classes) for v in range(n_vol)}, K, surf, ignore)
+                for j, (name, on) in enumerate((("consensus", args.consensus), ("clean", clean_opts is not None))):
+                    if on:                                                        # per class the mean over the volumes that have it (NaN: none)
+                        per = surf_host[:, (5 + j) * K:(6 + j) * K].contiguous().view(torch.float64).numpy()
+                        hd95 = [[float(v) for v in per[:, c] if v == v] for c in classes]
+                        doc[f"hd95_{name}"] = [float(np.mean(v)) if v else None for v in hd95]
+                        scored = [v for v in doc[f"hd95_{name}"] if v is not None]
+                        doc[f"mean_hd95_{name}"] = float(np.mean(scored)) if scored else None
             with open(os.path.join(out_dir, "metrics.json"), "w") as f:
                 json.dump(doc, f, indent=1)
             print(f"[rank 0] {metrics.summary_line(doc)} -> {os.path.join(out_dir, 'metrics.json')}", file=sys.stderr)

@@ -1180,6 +1180,93 @@ def component_filter(labels: torch.Tensor, root: torch.Tensor, size: torch.Tenso
     return out, kept
 
 
+# ------------------------------------------------------------------------------------- surface distances (gg_surface.hip)
+EDT_MAX_EXTENT = 1024          # the line length gg_edt_squared's LDS tile is sized for (include/guidegen_hip.h)
+
+
+def _check_border(what: str, labels: torch.Tensor, border: Optional[torch.Tensor]) -> None:
+    if border is None:
+        return
+    require_gpu(border, what)
+    if border.dtype != torch.uint8 or not border.is_contiguous() or border.numel() != labels.numel() or border.device != labels.device:
+        raise ValueError(f"{what}: border must be a contiguous uint8 tensor of {labels.numel()} voxels on {labels.device}, "
+                         f"got {border.dtype} {tuple(border.shape)}")
+
+
+def _check_f64(what: str, name: str, t: torch.Tensor, numel: int, device) -> None:
+    require_gpu(t, what)
+    if t.dtype != torch.float64 or not t.is_contiguous() or t.numel() != numel or t.device != device:
+        raise ValueError(f"{what}: {name} must be a contiguous float64 tensor of {numel} values on {device}, got {t.dtype} {tuple(t.shape)}")
+
+
+def label_border(labels: torch.Tensor, K: int, connectivity: int = 1) -> torch.Tensor:
+    """Class borders (gg_label_border): labels int32 [B, D, H, W] -> uint8 [B, D*H*W], 1 where the label lies in [0, K) and a neighbour
+    under scipy's generate_binary_structure(3, connectivity) carries another label or lies outside the volume."""
+    _labels_i32(labels, "label_border", "labels", 4)
+    _check_classes("label_border", K)
+    if connectivity not in (1, 2, 3):
+        raise ValueError(f"label_border: connectivity {connectivity} is none of 1 (faces), 2 (and edges), 3 (and corners)")
+    B, M = _check_volumes("label_border", labels)
+    D, H, W = (int(v) for v in labels.shape[1:])
+    border = torch.empty((B, M), dtype=torch.uint8, device=labels.device)
+    call("gg_label_border", labels.data_ptr(), B, D, H, W, K, connectivity, border.data_ptr(), _stream())
+    return border
+
+
+def edt_squared(labels: torch.Tensor, border: Optional[torch.Tensor], cls: int, spacing: Sequence[float] = (1.0, 1.0, 1.0),
+                out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Exact squared Euclidean distance transform (gg_edt_squared): labels int32 [B, D, H, W] -> fp64 [B, D*H*W], per voxel the smallest
+    (sd dd)^2 + (sh dh)^2 + (sw dw)^2 to a site of its own volume (+inf where the volume has none).  A site carries class `cls` and, with
+    `border` (uint8, label_border's), a non-zero border flag.  out / workspace: fp64 tensors of B*D*H*W values to reuse."""
+    _labels_i32(labels, "edt_squared", "labels", 4)
+    B, M = _check_volumes("edt_squared", labels)
+    D, H, W = (int(v) for v in labels.shape[1:])
+    if max(D, H, W) > EDT_MAX_EXTENT:
+        raise ValueError(f"edt_squared: volume {D}x{H}x{W} has an extent above {EDT_MAX_EXTENT}, the longest line gg_edt_squared stages")
+    if not isinstance(cls, int) or isinstance(cls, bool):
+        raise ValueError(f"edt_squared: cls={cls!r} must be an integer class")
+    _check_border("edt_squared", labels, border)
+    import math
+    sp = tuple(float(v) for v in spacing)
+    if len(sp) != 3 or not all(math.isfinite(v) and v > 0.0 for v in sp):
+        raise ValueError(f"edt_squared: spacing {tuple(spacing)} must be three finite values > 0 (d, h, w)")
+    if out is None:
+        out = torch.empty((B, M), dtype=torch.float64, device=labels.device)
+    _check_f64("edt_squared", "out", out, B * M, labels.device)
+    nbytes = int(_lib.load().gg_edt_squared_workspace_bytes(B, D, H, W))
+    if workspace is None:
+        workspace = torch.empty(nbytes // 8, dtype=torch.float64, device=labels.device)
+    _check_f64("edt_squared", "workspace", workspace, nbytes // 8, labels.device)
+    call("gg_edt_squared", labels.data_ptr(), _ptr(border), cls, B, D, H, W, sp[0], sp[1], sp[2], out.data_ptr(), workspace.data_ptr(), nbytes,
+         _stream())
+    return out
+
+
+def surface_reduce(labels_a: torch.Tensor, border_a: Optional[torch.Tensor], sq_b: torch.Tensor, cls: int,
+                   out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """gg_surface_reduce: over the voxels of class `cls` of labels_a (int32 [B, ...]) whose border flag is set, (dist2 fp64 [B, M]: sq_b
+    there and -1 elsewhere; stats fp64 [B, 3]: their count, the sum of sqrt(sq_b), the maximum of sq_b).  Deterministic to the bit."""
+    _labels_i32(labels_a, "surface_reduce", "labels")
+    if labels_a.dim() < 2:
+        raise ValueError(f"surface_reduce: labels must be [B, *spatial], got {tuple(labels_a.shape)}")
+    B, M = _check_volumes("surface_reduce", labels_a)
+    if not isinstance(cls, int) or isinstance(cls, bool):
+        raise ValueError(f"surface_reduce: cls={cls!r} must be an integer class")
+    _check_border("surface_reduce", labels_a, border_a)
+    _check_f64("surface_reduce", "sq_b", sq_b, B * M, labels_a.device)
+    if out is None:
+        out = torch.empty((B, M), dtype=torch.float64, device=labels_a.device)
+    _check_f64("surface_reduce", "out", out, B * M, labels_a.device)
+    if out.data_ptr() == sq_b.data_ptr():
+        raise ValueError("surface_reduce: out must not be sq_b's own memory")
+    nbytes = int(_lib.load().gg_surface_reduce_workspace_bytes(B, M))
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=labels_a.device)
+    stats = torch.empty((B, 3), dtype=torch.float64, device=labels_a.device)
+    call("gg_surface_reduce", labels_a.data_ptr(), _ptr(border_a), sq_b.data_ptr(), cls, B, M, out.data_ptr(), stats.data_ptr(), ws.data_ptr(),
+         nbytes, _stream())
+    return out, stats
+
+
 # ----------------------------------------------------------------------------------------------- LPIPS (gg_lpips.hip)
 def volume_views_cl(x: torch.Tensor, view: int, n0: int, n1: int, shift: torch.Tensor, scale: torch.Tensor, out: torch.Tensor) -> CL:
     """Images [n0, n1) of one axis view of an fp32 volume batch x [B, D, H, W] as channels-last rows (gg_volume_views_cl): view 0 =
